@@ -12,6 +12,13 @@ broadcast of the weight blobs at start-up.
         bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N                 # no launcher in the environment: bench.py starts the N ranks itself (same command as above)
     python bench.py --gpus N --host native   # ONE process: the C host (csrc/srt_multi.hip, main.c:544-673's shape) drives N devices
+    python bench.py --gpus 1 --full          # + per-kernel timing pass, roofline / HBM figures, CPU baseline
+    python bench.py --gpus 1 --dump-outputs DIR   # + the last timed step's stems (a fixed sample) as DIR/stems.npy
+
+A plain run does only what the headline needs: set-up, `--warmup` steps, `--steps` timed steps, the result line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds, after the timed steps, a second pass of the same steps with HIP
+events around every launch (`ms_per_step_events`, `kernel_ms`, `layer_kernels`, `roofline`, `nn_stack`, `dsp_stages`, `layer_*`), the
+output checks, and the reference CPU baseline (`cpu_baseline`, unless `--no-cpu-baseline`).
 
 `--gpus N` is binding: the line is printed only when N ranks (or N native workers) on N distinct devices really ran; with fewer devices
 visible the program exits non-zero with a message instead of printing an `n_gpus: 1` line.
@@ -193,13 +200,38 @@ def cpu_baseline(sample_tiles=None):
                       "(naive CPU_GEMM=1 GEMM, no MKL), tiles fanned out over threads as processMT does, one (tile, sub-network) forward per thread" % (ntiles, STEMS, frames, t_stft, t_nn, t_istft, flavour)}
 
 
+def headline(a, rec):
+    """The fields of the line every run prints: the headline figure and what it was measured on."""
+    stems, dt, world = a.stems, rec["dt"], rec["world"]
+    frames_step = rec["frames_step"]                           # frames that actually get a transform (rows - 3: stftFix.c:378)
+    fps = frames_step * world * a.steps / dt
+    return {
+        "metric": "x_realtime (%d-stem separation, 44.1 kHz stereo, PCM->stems resident in HBM); frames_per_s alongside" % stems,
+        "value": fps * HOP / FS, "unit": "x real-time", "frames_per_s": fps,
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": {"f32": "f32", "f16": "f16 products, f32 accumulate (conv only; STFT/iSTFT f32)", "f16x2": "f16x2 split products (exact in f32), f32 accumulate"}[a.precision],
+        "data": "synthetic",
+        "config": {"workload": "%d-stem, %s, batch=%d spectrogram tiles of %dx%d per GPU (%s); "
+                               "%d frames = %.1f s of audio per GPU per step" % (stems, {"f32": "fp32", "f16": "fp16-MFMA conv + fp32 STFT/iSTFT", "f16x2": "fp16 hi+lo MFMA conv + fp32 STFT/iSTFT"}[a.precision],
+                                                                                 a.tiles, T, F,
+                                                                                 "BASELINE configs[4]: 5 stems, fp16 MFMA conv with fp32 STFT/iSTFT" if (stems == 5 and a.precision == "f16")
+                                                                                 else "BASELINE configs[2]" if (stems == 4 and a.precision == "f32") else "BASELINE configs[2]'s batch in a labelled non-headline mode",
+                                                                                 frames_step, frames_step * HOP / FS),
+                   "stems": stems, "tiles_per_gpu": a.tiles, "T": T, "F": F, "parallelism": "tile-sharded x%d, no data-path collective" % world,
+                   "impl": a.impl, "precision": a.precision},
+        "host": rec["host"], "distributed": rec["distributed"],
+    }
+
+
 def make_line(a, rec):
-    """The one JSON line, from a measurement record (measure_ranks on rank 0, or measure_native)."""
+    """The one JSON line, from a measurement record (measure_ranks on rank 0, or measure_native): the headline, and with --full the
+    per-kernel, roofline and CPU-baseline figures."""
+    res = headline(a, rec)
+    if not a.full:
+        return res
     stems, dt, dt_ev, tim, kern, world, rows = a.stems, rec["dt"], rec["dt_ev"], rec["tim"], rec["kern"], rec["world"], rec["rows"]
     nocheck = os.environ.get("SRT_BENCH_NOCHECK") == "1"
-    frames_step = rec["frames_step"]                           # frames that actually get a transform (rows - 3: stftFix.c:378)
-    frames_total = frames_step * world * a.steps
-    fps = frames_total / dt
     per = {}
     for name, ms in tim:
         per.setdefault(name, []).append(ms)
@@ -277,23 +309,9 @@ def make_line(a, rec):
                 break
         except Exception:
             continue
-    step_ms = dt / a.steps * 1e3
-    res = {
-        "metric": "x_realtime (%d-stem separation, 44.1 kHz stereo, PCM->stems resident in HBM); frames_per_s alongside" % stems,
-        "value": fps * HOP / FS, "unit": "x real-time", "frames_per_s": fps,
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": step_ms, "ms_per_step_events": dt_ev / a.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": {"f32": "f32", "f16": "f16 products, f32 accumulate (conv only; STFT/iSTFT f32)", "f16x2": "f16x2 split products (exact in f32), f32 accumulate"}[a.precision],
-        "data": "synthetic",
-        "config": {"workload": "%d-stem, %s, batch=%d spectrogram tiles of %dx%d per GPU (%s); "
-                               "%d frames = %.1f s of audio per GPU per step" % (stems, {"f32": "fp32", "f16": "fp16-MFMA conv + fp32 STFT/iSTFT", "f16x2": "fp16 hi+lo MFMA conv + fp32 STFT/iSTFT"}[a.precision],
-                                                                                 a.tiles, T, F,
-                                                                                 "BASELINE configs[4]: 5 stems, fp16 MFMA conv with fp32 STFT/iSTFT" if (stems == 5 and a.precision == "f16")
-                                                                                 else "BASELINE configs[2]" if (stems == 4 and a.precision == "f32") else "BASELINE configs[2]'s batch in a labelled non-headline mode",
-                                                                                 frames_step, frames_step * HOP / FS),
-                   "stems": stems, "tiles_per_gpu": a.tiles, "T": T, "F": F, "parallelism": "tile-sharded x%d, no data-path collective" % world,
-                   "impl": a.impl, "precision": a.precision},
-        "host": rec["host"], "distributed": rec["distributed"],
+    step_ms = res["ms_per_step"]
+    res.update({
+        "ms_per_step_events": dt_ev / a.steps * 1e3,
         "roofline": {"bound": "mfma", "kernel": dom, "achieved": dom_tflops, "peak": dom_peak, "unit": "TFLOP/s",
                      "frac": dom_tflops / dom_peak, "traffic": traffic,
                      "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE*2 + WRITE_SIZE, %s)" % pmc_file,
@@ -333,7 +351,7 @@ def make_line(a, rec):
                                 for k in avg if k in LAYER_FLOP},
         # every layer against the HBM roofline too (algorithmic bytes at this mode's element sizes / kernel time / 8 TB/s)
         "layer_hbm_frac": {k: round(layer_bytes(k, prec, act16, stems, masks16) * inst / (avg[k] * 1e-3) / (PEAK_HBM_TBS * 1e12), 4) for k in avg if k in LAYER_FLOP},
-    }
+    })
     rf = res["roofline"]
     if rf["hbm"]["frac"] > rf["frac"]:
         # the dominant kernel is nearer the HBM roofline than the MFMA one (the fp16-MFMA mode is HBM-bound): report THAT as the
@@ -353,6 +371,20 @@ def make_line(a, rec):
         except Exception as ex:                          # the baseline must never take the GPU number down with it
             res["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": 0, "kind": "reference", "sample": "failed: %r" % (ex,)}
     return res
+
+
+DUMP_SAMPLES = 1 << 20          # per stem and channel: 4 stems x 2 x 2^20 float32 = 32 MB (40 MB at five stems)
+
+
+def dump_outputs(out_dir, out):
+    """What the timed path returned in its last step: the stems (stems x 2 channels x samples, float32) as out_dir/stems.npy.  The whole
+    array is ~0.5 GB, so the file holds the same 2^20 seeded sample positions of every (stem, channel) row, in ascending order."""
+    import torch
+    n = out.shape[-1]
+    idx = np.sort(np.random.default_rng(20240).choice(n, min(n, DUMP_SAMPLES), replace=False))
+    sample = out.index_select(out.dim() - 1, torch.from_numpy(idx).to(out.device)).cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "stems.npy"), sample)
 
 
 def flush_c_stdio():
@@ -469,23 +501,28 @@ def measure_ranks(a, stems):
         eng.separate(L, R, out)
     sync()
     dt = time.perf_counter() - t0
-    # per-kernel durations: a second, separately timed pass of the same K steps with HIP events around every launch on the
-    # engine's own stream (what `roofline` and `kernel_ms` are computed from; its wall time is reported as ms_per_step_events)
-    eng.set_timing(True)
-    t1 = time.perf_counter()
-    for _ in range(a.steps):
-        eng.separate(L, R, out)
-    sync()
-    dt_ev = time.perf_counter() - t1
-    tim = eng.get_timing()
-    kern = eng.get_timing_kernels()                           # [(launch name, kernel symbol the engine actually launched)]
-    eng.set_timing(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out)
+    dt_ev, tim, kern = None, [], []
+    if a.full:
+        # per-kernel durations: a second, separately timed pass of the same K steps with HIP events around every launch on the
+        # engine's own stream (what `roofline` and `kernel_ms` are computed from; its wall time is reported as ms_per_step_events)
+        eng.set_timing(True)
+        t1 = time.perf_counter()
+        for _ in range(a.steps):
+            eng.separate(L, R, out)
+        sync()
+        dt_ev = time.perf_counter() - t1
+        tim = eng.get_timing()
+        kern = eng.get_timing_kernels()                       # [(launch name, kernel symbol the engine actually launched)]
+        eng.set_timing(False)
     if dist_on:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    nocheck = os.environ.get("SRT_BENCH_NOCHECK") == "1"       # timing-ablation builds (scripts/gpu_tune.sh): wrong results by construction
-    assert nocheck or torch.isfinite(out).all()
+    if a.full:
+        nocheck = os.environ.get("SRT_BENCH_NOCHECK") == "1"   # timing-ablation builds (scripts/gpu_tune.sh): wrong results by construction
+        assert nocheck or torch.isfinite(out).all()
     rec = None
     if rank == 0:
         rec = {"dt": dt, "dt_ev": dt_ev, "tim": tim, "kern": kern, "world": world, "rows": rows, "frames_step": int(eng.L.srtStftFrames(n)),
@@ -560,7 +597,12 @@ def main():
     ap.add_argument("--host", default="ranks", choices=["ranks", "native"],
                     help="ranks (default): one process per GPU over torch.distributed (bench.py starts them itself when no launcher did).  "
                          "native: one process, the C multi-device host (srtMulti*), one worker thread per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel timing pass and report the roofline / HBM figures, check the outputs, "
+                         "and time the reference CPU baseline (off by default: a plain run prints the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the stems the last timed step computed (rank 0; a fixed seeded sample, float32) as DIR/stems.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--stem-modes", default=None, help="per stem: 1 = ELU/ELU (the 4-stem model), 0 = LeakyReLU/ReLU; measurement aid")
     ap.add_argument("--cpu-tiles", type=int, default=0)
     ap.add_argument("--rendezvous-only", action="store_true", help=argparse.SUPPRESS)     # tests: launcher + world join, no GPU work
@@ -573,6 +615,8 @@ def main():
     a.stem_modes = a.stem_modes or "1" * a.stems
     if len(a.stem_modes) != a.stems:
         raise SystemExit("bench.py: --stem-modes needs %d digits" % a.stems)
+    if a.dump_outputs and (a.host == "native" or a.config == "c4"):
+        raise SystemExit("bench.py: --dump-outputs needs the per-process host and --config c3")
     ensure_world(a, sys.argv[1:])
     if a.rendezvous_only:
         return rendezvous_only(a)

@@ -10,7 +10,7 @@ TAG=${1:-abl_c8}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 export SPLEETERRT_LIB=$PWD/spleeterrt_amd/libspleeterrt_amd_tuning.so
 for a in ${2:-0 3 4 8 16 12}; do
-  SRT_TUNE_C8=$a timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --precision f16 --stems 5 > $OUT/bench_$a.json 2>> $OUT/bench.err
+  SRT_TUNE_C8=$a timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --precision f16 --stems 5 > $OUT/bench_$a.json 2>> $OUT/bench.err
   python - <<PY
 import json
 try:

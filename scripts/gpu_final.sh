@@ -8,10 +8,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ( time timeout 1100 python -m pytest tests -m gpu -q --durations=8 ) > $OUT/pytest.log 2>&1
 tail -5 $OUT/pytest.log
-timeout 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json
 for prec in f16 f16x2; do
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --precision $prec > $OUT/bench_$prec.json 2>> $OUT/bench.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --precision $prec > $OUT/bench_$prec.json 2>> $OUT/bench.err
 done
 timeout 300 python scripts/stream_c4.py --repeats 3 --out $OUT/c4.json > $OUT/c4.log 2>&1
 tail -c 400 $OUT/c4.log

@@ -8,7 +8,7 @@ for lib in "$@"; do
   lab=$(basename $lib .so)
   if [ "$lib" = default ]; then envs="SRT_AB=0"; else envs="SPLEETERRT_LIB=$lib"; fi
   for rep in 1 2; do
-    env $envs timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline $ARGS > $OUT/bench_${lab}_$rep.json 2>> $OUT/bench.err
+    env $envs timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $ARGS > $OUT/bench_${lab}_$rep.json 2>> $OUT/bench.err
     python - <<PY
 import json
 try:

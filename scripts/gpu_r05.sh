@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 line() {   # label, env assignment (may be empty), extra bench args
-  env $2 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline $3 > "$OUT/bench_$1.json" 2>> $OUT/bench.err
+  env $2 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $3 > "$OUT/bench_$1.json" 2>> $OUT/bench.err
   python - <<PY
 import json
 try:
@@ -23,7 +23,7 @@ for st in "$@"; do
     tests) ( time timeout 3000 python -m pytest tests -m gpu -q -x --durations=15 ) > $OUT/pytest.log 2>&1; tail -30 $OUT/pytest.log ;;
     dsp) ( time timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --durations=8 -k "stft or istft or separate_end_to_end or minimum_length or chunked_stream or full_size_batch" ) > $OUT/dsp.log 2>&1; tail -25 $OUT/dsp.log ;;
     quick) ( time timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -x --durations=8 -k "odd_geometries or winograd_decoder_layers or up6_streamed or forward_layers or stft_matches or istft_roundtrip or separate_end_to_end or shipped_launch" ) > $OUT/quick.log 2>&1; tail -15 $OUT/quick.log ;;
-    bench) timeout 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+    bench) timeout 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
     benchq) line default "" "" ;;
     ab:*) IFS=';' read -ra SETS <<< "${st#ab:}"; for t in "${SETS[@]}"; do line "$t" "$t" ""; done ;;
     prof) timeout 900 bash scripts/profile_gpu.sh $TAG > $OUT/profile.log 2>&1; tail -3 $OUT/profile.log ;;

@@ -11,7 +11,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 line() {   # label, env assignment (may be empty), extra bench args
-  env $2 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline $3 > "$OUT/bench_$1.json" 2>> $OUT/bench.err
+  env $2 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $3 > "$OUT/bench_$1.json" 2>> $OUT/bench.err
   python - <<PY
 import json
 try:
@@ -25,7 +25,7 @@ for st in "$@"; do
     tests) ( time timeout 3000 python -m pytest tests -m gpu -q -x --durations=15 ) > $OUT/pytest.log 2>&1; tail -30 $OUT/pytest.log ;;
     quick) ( time timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -x --durations=8 -k "odd_geometries or winograd_decoder_layers or up6_streamed or forward_layers or stft_matches or istft_roundtrip or separate_end_to_end or shipped_launch" ) > $OUT/quick.log 2>&1; tail -15 $OUT/quick.log ;;
     k:*) ( time timeout 1500 python -m pytest tests -m gpu -q -x --durations=8 -k "${st#k:}" ) > $OUT/k.log 2>&1; tail -15 $OUT/k.log ;;
-    bench) timeout 400 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+    bench) timeout 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
     benchq) line default "" "" ;;
     c5) line c5_f16 "" "--precision f16 --stems 5 --steps 20 --warmup 5" ;;
     f16) line f16 "" "--precision f16 --steps 20 --warmup 5" ;;

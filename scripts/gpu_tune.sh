@@ -14,7 +14,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 run() {   # label, env assignment (may be empty)
-  env $2 timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --precision $PREC > "$OUT/bench_$1.json" 2>> $OUT/bench.err
+  env $2 timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --precision $PREC > "$OUT/bench_$1.json" 2>> $OUT/bench.err
   python - <<PY
 import json
 try:

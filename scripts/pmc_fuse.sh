@@ -9,7 +9,7 @@ for mode in "f32 4" "f16 5"; do
   set -- $mode; PREC=$1; STEMS=$2
   for fuse in 0 1; do
     export SPLEETERRT_FUSE_HEAD=$fuse
-    B1="python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --precision $PREC --stems $STEMS"
+    B1="python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --precision $PREC --stems $STEMS"
     D=$OUT/${PREC}_fuse$fuse
     rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT --kernel-trace --output-format csv -d $D/sq -o p -- $B1 > /dev/null 2> $D.sq.err
     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $D/mix -o p -- $B1 > /dev/null 2> $D.mix.err

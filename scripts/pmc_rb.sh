@@ -5,7 +5,7 @@ export SPLEETERRT_LIB=$R/spleeterrt_amd/libspleeterrt_amd_tuning.so SRT_BENCH_NO
 cd /tmp
 for t in default encrb=1 decrb=0; do
   if [ $t = default ]; then unset SRT_TUNE; else export SRT_TUNE=$t; fi
-  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS --kernel-trace --output-format csv -d $OUT/pmc_$t -o p -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$t.err
+  rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS --kernel-trace --output-format csv -d $OUT/pmc_$t -o p -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$t.err
   python - <<PY
 import csv, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.defaultdict(set)

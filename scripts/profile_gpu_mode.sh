@@ -11,8 +11,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 ARGS="--no-cpu-baseline --precision $PREC --stems $STEMS"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python $R/bench.py --steps 5 --warmup 2 $ARGS > $OUT/bench_under_trace.json 2> $OUT/trace.err
-B1="python $R/bench.py --steps 1 --warmup 1 $ARGS"
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python $R/bench.py --full --steps 5 --warmup 2 $ARGS > $OUT/bench_under_trace.json 2> $OUT/trace.err
+B1="python $R/bench.py --full --steps 1 --warmup 1 $ARGS"
 MOPS=SQ_INSTS_VALU_MFMA_MOPS_F16
 [ "$PREC" = f32 ] && MOPS=SQ_INSTS_VALU_MFMA_MOPS_F32
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES $MOPS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \

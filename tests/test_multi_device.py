@@ -73,7 +73,7 @@ def test_native_host_bench_line_equals_the_per_process_line():
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k, None)
-        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "8", "--warmup", "3", "--no-cpu-baseline"] + extra, cwd=ROOT, env=env,
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "8", "--warmup", "3", "--full", "--no-cpu-baseline"] + extra, cwd=ROOT, env=env,
                            capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         assert r.stdout.strip().splitlines()[-1].startswith("{"), r.stdout[-600:]      # the JSON line is the LAST thing on stdout (librccl's banner is flushed before it)

@@ -1,11 +1,15 @@
 """CPU tests (no GPU): the oracle is pinned (a) against the committed golden vectors generated from the real
-reference build, and (b) against that build itself when oracle/_ref is present (build container and GPU box)."""
+reference build, and (b) against that build itself when oracle/_ref is present (build container and GPU box); where it is not, (b) checks
+against samples of the same reference outputs stored in tests/golden/reference_checks.npz.  Refresh that file where oracle/_ref is
+built with  SRT_RECORD_REF_CHECKS=1 python -m pytest tests/test_oracle.py"""
 import os
 
 import numpy as np
 import pytest
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "reference_vectors.npz")
+REF_CHECKS = os.path.join(os.path.dirname(__file__), "golden", "reference_checks.npz")
+_recorded = {}                     # samples of the live reference outputs these tests compared against (SRT_RECORD_REF_CHECKS=1 stores them)
 
 
 def _stats(a):
@@ -121,47 +125,76 @@ def test_tail_tile_and_mask_rules(oracle, coeffs):
     assert ratio.max() <= 1.0 + 1e-6                                 # masks live in [0,1]
 
 
-# ------------------------------------------------------------------ against the real reference build, when present
-def _need_ref(oracle, flavour="exe"):
-    if oracle.ref_path(flavour) is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
+# ------------------------------------------------------------------ against the real reference build (or the samples stored from it)
+@pytest.fixture(scope="module", autouse=True)
+def _record_ref_checks():
+    yield
+    if os.environ.get("SRT_RECORD_REF_CHECKS") == "1":
+        np.savez_compressed(REF_CHECKS, **_recorded)
+
+
+def _stored(key):
+    return np.load(REF_CHECKS)[key]
+
+
+def _sample(a, step):
+    return np.ascontiguousarray(np.asarray(a).ravel()[::step])
+
+
+def _vs_ref_net(oracle, key, got, flavour, live, tol, step):
+    """got against the reference network's output for the same input: the real build's whole output where oracle/_ref is built (live()),
+    otherwise every step-th element of it as stored from that build."""
+    if oracle.ref_path(flavour) is not None:
+        yr = live()
+        assert np.abs(got - yr).max() <= tol
+        _recorded[key] = _sample(yr, step)
+    else:
+        assert np.abs(_sample(got, step) - _stored(key)).max() <= tol
+
+
+def _ref_net(oracle, coeff, F, T, mode, flavour, x):
+    def live():
+        net = oracle.RefNet(coeff, F, T, mode, flavour)
+        yr = net(x)
+        net.close()
+        return yr
+    return live
 
 
 def test_oracle_vs_reference_forward(oracle, coeffs):
-    _need_ref(oracle)
     x = _mag(oracle, 1, 64, 512, 31)[0]
     for flavour, variant, tol in (("vst", oracle.VARIANT_VST, 0.0), ("exe", oracle.VARIANT_EXE, 2.5e-7)):
         for stem, mode in ((2, 0), (3, 1)):
-            net = oracle.RefNet(coeffs(stem), 512, 64, mode, flavour)
-            yr = net(x)
-            net.close()
-            assert np.abs(oracle.forward(coeffs(stem), x, mode, variant) - yr).max() <= tol
+            _vs_ref_net(oracle, "fwd_64x512_%s_stem%d" % (flavour, stem), oracle.forward(coeffs(stem), x, mode, variant), flavour,
+                        _ref_net(oracle, coeffs(stem), 512, 64, mode, flavour, x), tol, 7)
 
 
 @pytest.mark.parametrize("T,F", [(256, 1024), (512, 1024), (256, 1536), (256, 2048)])
 def test_oracle_vs_reference_forward_at_shipped_tile_sizes(oracle, coeffs, T, F):
     """The restatement pinned against the real reference network at the tile sizes the GPU tests check it at: BASELINE's 256 x 1024, the CLI's
     default 512 x 1024 (main.c:701-702), the plugin's 256 x 1536 (PluginProcessor.cpp:124) and the CLI's widest, 2048 bins (main.c:745-748)."""
-    _need_ref(oracle)
     x = _mag(oracle, 1, T, F, 31 + T + F)[0]
     for flavour, variant, tol, stem, mode in (("vst", oracle.VARIANT_VST, 0.0, 3, 1), ("exe", oracle.VARIANT_EXE, 2.5e-7, 2, 0)):
-        net = oracle.RefNet(coeffs(stem), F, T, mode, flavour)
-        yr = net(x)
-        net.close()
-        assert np.abs(oracle.forward(coeffs(stem), x, mode, variant) - yr).max() <= tol
+        _vs_ref_net(oracle, "fwd_%dx%d_%s" % (T, F, flavour), oracle.forward(coeffs(stem), x, mode, variant), flavour,
+                    _ref_net(oracle, coeffs(stem), F, T, mode, flavour, x), tol, 61)
 
 
 def test_oracle_vs_reference_stft(oracle):
-    _need_ref(oracle)
     n = 4096 * 4 + 8192
     L, R = oracle.synth_audio(n, 12345, True)
+    re, im = oracle.stft(L, R)
+    if oracle.ref_path("exe") is None:              # no reference build here: the samples stored from it (and its peaks)
+        peak = float(_stored("stft_re_peak"))
+        assert np.abs(_sample(re, 3) - _stored("stft_re")).max() <= 1e-6 * peak and np.abs(_sample(im, 3) - _stored("stft_im")).max() <= 1e-6 * peak
+        assert np.abs(_sample(oracle.istft(re, im), 3) - _stored("istft")).max() <= 1e-6 * float(_stored("istft_peak"))
+        return
     st = oracle.RefSTFT(1)
     rre, rim = st.stft(L, R)
-    re, im = oracle.stft(L, R)
     peak = np.abs(rre).max()
     assert np.abs(re - rre).max() <= 1e-6 * peak and np.abs(im - rim).max() <= 1e-6 * peak
     ro = st.istft(rre, rim)
     assert np.abs(oracle.istft(re, im) - ro).max() <= 1e-6 * np.abs(ro).max()
+    _recorded.update(stft_re=_sample(rre, 3), stft_im=_sample(rim, 3), stft_re_peak=np.array(peak), istft=_sample(ro, 3), istft_peak=np.array(np.abs(ro).max()))
     # property the reference implies but never checks: multi-threaded stft == single-threaded, bitwise (SURVEY §4)
     st3 = oracle.RefSTFT(3)
     r3, i3 = st3.stft(L, R)
@@ -190,26 +223,32 @@ def test_cli_flow_restatement_vs_reference_linked_harness(oracle, tmp_path, stem
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     ref = os.path.join(root, "host", "offline_ref")
-    if oracle.ref_path("exe") is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
-    if not os.path.exists(ref):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(root, "host"), "offline_ref"])
+    live = oracle.ref_path("exe") is not None       # else: the samples stored from the reference build's output files
+    if live and not os.path.exists(ref):            # (linking the harness needs the reference's headers: where they are absent, the stored samples)
+        live = subprocess.call(["make", "-s", "-C", os.path.join(root, "host"), "offline_ref"]) == 0
     T, F, n = 64, 512, 44100 + 321
     h0, h1 = oracle.synth_coeff_fp16(1), oracle.synth_coeff_fp16(0)          # container order: net[0] drum, net[1] vocal
-    np.concatenate([h0, h1]).tofile(tmp_path / "w.f16")
     L, R = oracle.synth_audio(n, 321, True)
-    np.stack([L, R], 1).astype(np.float32).tofile(tmp_path / "in.f32")
-    subprocess.check_call([ref, str(T), str(F), str(stems), str(tmp_path / "w.f16"), str(tmp_path / "in.f32"), str(tmp_path / "o")])
+    if live:
+        np.concatenate([h0, h1]).tofile(tmp_path / "w.f16")
+        np.stack([L, R], 1).astype(np.float32).tofile(tmp_path / "in.f32")
+        subprocess.check_call([ref, str(T), str(F), str(stems), str(tmp_path / "w.f16"), str(tmp_path / "in.f32"), str(tmp_path / "o")])
     final = 4096 * ((n + 4095) // 4096) + 8192
     pL, pR = np.zeros(final, np.float32), np.zeros(final, np.float32)
     pL[4096:4096 + n], pR[4096:4096 + n] = L, R
     got = oracle.cli_separate(oracle.fp16_expand(h0), oracle.fp16_expand(h1), pL, pR, F, T, stems, oracle.VARIANT_EXE, 0.1)
     names = ["Vocal", "Accompaniment"] if stems == 2 else ["Drum", "Vocal", "Accompaniment"]
     for k, nm in enumerate(names):
-        r = np.fromfile(tmp_path / ("o_%s.f32" % nm), np.float32).reshape(-1, 2)
         a = got[k][:, 4096:4096 + n].T
+        key = "cli%d_%s" % (stems, nm)
+        if not live:
+            a = _sample(a, 7)
+            assert np.abs(a - _stored(key)).max() <= 2e-6 * max(float(_stored(key + "_peak")), 1e-3), "%s: %g" % (nm, np.abs(a - _stored(key)).max())
+            continue
+        r = np.fromfile(tmp_path / ("o_%s.f32" % nm), np.float32).reshape(-1, 2)
         assert a.shape == r.shape
         assert np.abs(a - r).max() <= 2e-6 * max(np.abs(r).max(), 1e-3), "%s: %g" % (nm, np.abs(a - r).max())
+        _recorded.update({key: _sample(r, 7), key + "_peak": np.array(np.abs(r).max())})
 
 
 def test_oracle_fp16_expand_every_pattern(oracle):

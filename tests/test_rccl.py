@@ -41,7 +41,7 @@ def _launch(args, distributed):
 
 
 def test_bench_line_under_a_world_of_one_nccl_group():
-    args = ["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "3", "--no-cpu-baseline"]
+    args = ["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "3", "--full", "--no-cpu-baseline"]
     best = None
     for _ in range(3):
         plain = _launch(args, False)
@@ -65,7 +65,7 @@ def test_bench_line_under_a_world_of_one_nccl_group():
 def test_bench_fp16_modes_report_honest_rooflines(precision):
     """the fp16-MFMA bench lines price their kernels against the fp16 MFMA peak (2.5 PFLOP/s dense) and the HBM roofline,
     and no fraction anywhere in the line exceeds 1 (bench.py asserts it too; an earlier version divided fp16 work by the fp32 peak: frac 2.11)."""
-    d = _launch(["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "3", "--no-cpu-baseline", "--precision", precision], False)
+    d = _launch(["bench.py", "--gpus", "1", "--steps", "6", "--warmup", "3", "--full", "--no-cpu-baseline", "--precision", precision], False)
     rf = d["roofline"]
     assert d["config"]["precision"] == precision and ("_f16<" in rf["kernel"] or "_c8<" in rf["kernel"]), rf["kernel"]      # csrc/srt_nn3.hip / the C8 forms of csrc/srt_nn5.hip
     assert 0.0 < rf["frac"] <= 1.0 and 0.0 < rf["hbm"]["frac"] <= 1.0 and 0.0 < rf["step"]["frac"] <= 1.0 and 0.0 < rf["step"]["hbm"]["frac"] <= 1.0
