@@ -80,8 +80,12 @@ struct HostStaging {
 // hipGraph replay of the launch sequences a low-latency caller repeats with the same arguments (srtSetGraphMode): the real-time
 // plugin runs srtForward on the same two mask buffers for ever, the tile API on one pair of buffers.  A sequence is captured
 // the first time its argument tuple is seen and replayed afterwards: one host call instead of ~25 launches on the audio thread.
-struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns; };
-struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; };
+// `layout`: the switches that change which kernels and tensor layouts a forward records (SPLEETERRT_C8, C8L1, D1F16, M16; read per call), so a flipped
+// switch captures a new graph instead of replaying the old layout.
+struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, layout; };
+// c8 / c8_l1 / masks16: what the captured forward left in last_c8 / last_c8_l1 / last_masks16 - a replay runs no host code, so run_graphed puts them back
+// (srtCopyTensor reads the taps by them; an eager call in between may have changed them)
+struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; bool c8, c8_l1, masks16; };
 #define SRT_GRAPH_SLOTS 4
 
 // Every entry point that allocates or launches runs on the device the engine was created on, whatever the caller's
@@ -405,6 +409,15 @@ static void ensure_ws(srt_engine* e, size_t instances)
     else { e->ws = nullptr; (void)hipGetLastError(); }
 }
 
+// GraphKey::layout: one bit per layout switch the forward reads per call, set where the switch is on (unset or not "0")
+static int graph_layout_switches()
+{
+    static const char* const names[] = { "SPLEETERRT_C8", "SPLEETERRT_C8L1", "SPLEETERRT_D1F16", "SPLEETERRT_M16" };
+    int bits = 0;
+    for (int i = 0; i < 4; ++i) { const char* v = getenv(names[i]); if (!(v && v[0] == '0')) bits |= 1 << i; }
+    return bits;
+}
+
 // Run `issue` (a function that only enqueues work on e->stream) through the graph cache when graph mode is on.  `valid` says
 // whether the arguments passed the entry point's checks: an invalid call is issued eagerly (it fails with its own error code and
 // nothing is captured).  Graph mode is switched off for good only when the capture / instantiate API itself fails - a user error
@@ -418,6 +431,7 @@ static int run_graphed(srt_engine* e, const GraphKey& key, bool valid, F&& issue
         if (g.exec && !memcmp(&g.key, &key, sizeof key)) {
             g.used = ++e->gclock;
             HIPCHK(hipGraphLaunch(g.exec, e->stream));
+            e->last_c8 = g.c8; e->last_c8_l1 = g.c8_l1; e->last_masks16 = g.masks16;
             return 0;
         }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -448,6 +462,7 @@ static int run_graphed(srt_engine* e, const GraphKey& key, bool valid, F&& issue
     if (v->exec) hipGraphExecDestroy(v->exec);
     if (v->graph) hipGraphDestroy(v->graph);
     v->key = key; v->graph = graph; v->exec = exec; v->used = ++e->gclock;
+    v->c8 = e->last_c8; v->c8_l1 = e->last_c8_l1; v->masks16 = e->last_masks16;
     HIPCHK(hipGraphLaunch(exec, e->stream));
     return 0;
 }
@@ -689,7 +704,7 @@ int srtForward(srt_engine* e, const float* d_mag, int ntiles, float* d_masks)
     if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
     if (valid && cap == hipStreamCaptureStatusNone) ensure_ws(e, (size_t)e->cfg.n_stems * ntiles);
     GraphKey k; memset(&k, 0, sizeof k);
-    k.kind = 1; k.p0 = d_mag; k.p2 = d_masks; k.ntiles = ntiles; k.ns = e->cfg.n_stems;
+    k.kind = 1; k.p0 = d_mag; k.p2 = d_masks; k.ntiles = ntiles; k.ns = e->cfg.n_stems; k.layout = graph_layout_switches();
     const int rc = run_graphed(e, k, valid, [&]() { return forward_range(e, d_mag, ntiles, d_masks, 0, e->cfg.n_stems); });
     if (!rc) e->last_ntiles = ntiles;
     return rc;
@@ -817,7 +832,7 @@ int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, s
     if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
     if (valid && cap == hipStreamCaptureStatusNone) ensure_ws(e, (size_t)e->cfg.n_stems * ntiles);
     GraphKey k; memset(&k, 0, sizeof k);
-    k.kind = 2; k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows;
+    k.kind = 2; k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.layout = graph_layout_switches();
     const int rc = run_graphed(e, k, valid, [&]() { return separate_issue(e, d_L, d_R, n, frames, rows, d_out); });
     if (!rc) e->last_ntiles = (int)ntiles;
     return rc;
@@ -1132,7 +1147,8 @@ int srtCopyTensor(srt_engine* e, const char* name, int stem, int tile, float* h_
         // "actN" is no longer stored: the next encoder layer applies act(bn(convN)) while staging.  Materialise it for the tap.
         const LayerOff& L = e->lo.down[idx];
         const float* c = e->coeff_all + (size_t)stem * SRT_COEFF_STRIDE;
-        HIPCHK(hipMalloc((void**)&tmp, per * sizeof(float)));
+        const hipError_t em = hipMalloc((void**)&tmp, per * sizeof(float));
+        if (em != hipSuccess) { if (planar) hipFree(planar); return fail(-2, "HIP error: %s", hipGetErrorString(em)); }
         if (srt_launch_bn_act(src, halves_in, tmp, c + L.bn + L.cout, c + L.bn, L.cout, per / L.cout, e->cfg.stem_mode[stem] ? SRT_ACT_ELU : SRT_ACT_LEAKY, e->cfg.variant, e->stream)) { hipFree(tmp); if (planar) hipFree(planar); return fail(-2, "bn-act launch failed"); }
         src = tmp;
     } else if (halves_in) {
