@@ -16,9 +16,16 @@
  *   mono input duplicated to both channels              main.c:768-769
  *   stems <= 2 -> <name>_Vocal.wav, <name>_Accompaniment.wav; else + <name>_Drum.wav      main.c:812-843, 894-965
  *   outputs are IEEE-float32 stereo 44.1 kHz RIFF/WAVE, <name> = basename of the input INCLUDING its extension
+ *   input at another rate converted to 44.1 kHz first  main.c:264-271 (JamesDSPOfflineResampling), on the GPU (srtResample*):
+ *   opt-in with $SPLEETERRT_RESAMPLE:
+ *     unset / 0  only 44.1 kHz input is accepted (other rates are refused before anything else happens)
+ *     1          the reference's behaviour: 8000..384000 Hz input is converted to 44.1 kHz, the flow runs on
+ *                srtResampleLength(frames, rate, 44100) frames (main.c:266) and the stems are written at 44.1 kHz
+ *     source     as 1, then every stem is converted back to the input's rate and written with the input's frame count
+ *   The rate is checked before the weights are read; the conversion runs after that, on the first device.
  *
- * Out of scope here (SURVEY §2.1 #9,#11,#12): FLAC/MP3 decoding and the sample-rate converter — the input must be a
- * 44.1 kHz RIFF/WAVE file (PCM 8/16/24/32-bit or float32, 1 or 2 channels).  The reference embeds its weights
+ * Out of scope here (SURVEY §2.1 #9,#11,#12): FLAC/MP3 decoding — the input must be a RIFF/WAVE file (PCM 8/16/24/32-bit
+ * or float32, 1 or 2 channels).  The reference embeds its weights
  * (model.c, absent from the public tree); here the fp16 container `spleeterQuantized` (spleeter.h:59-62) is read from
  * the 6th argument or $SPLEETERRT_WEIGHTS.
  */
@@ -94,12 +101,12 @@ static size_t read_wav(const char *path, float **pcm, unsigned *channels, unsign
     }
 }
 
-/* planar (with the 4096-sample pre-shift undone) -> float32 stereo RIFF/WAVE */
-static int write_wav(const char *path, const float *L, const float *R, size_t frames)
+/* planar (the caller has undone the 4096-sample pre-shift) -> float32 stereo RIFF/WAVE at `rate` Hz */
+static int write_wav(const char *path, const float *L, const float *R, size_t frames, uint32_t rate)
 {
     FILE *f = fopen(path, "wb");
     if (!f) { fprintf(stderr, "cannot write %s\n", path); return -1; }
-    const uint32_t data = (uint32_t)(frames * 8), rate = 44100;
+    const uint32_t data = (uint32_t)(frames * 8);
     unsigned char h[58];
     memcpy(h, "RIFF", 4); memcpy(h + 8, "WAVEfmt ", 8); memcpy(h + 38, "fact", 4); memcpy(h + 50, "data", 4);
 #define PUT32(o, v) do { uint32_t v_ = (v); h[o] = v_ & 255; h[o + 1] = (v_ >> 8) & 255; h[o + 2] = (v_ >> 16) & 255; h[o + 3] = (v_ >> 24) & 255; } while (0)
@@ -109,7 +116,7 @@ static int write_wav(const char *path, const float *L, const float *R, size_t fr
     fwrite(h, 1, sizeof h, f);
     float *il = (float *)malloc((frames ? frames : 1) * 8);
     if (!il) { fprintf(stderr, "out of host memory writing %s\n", path); fclose(f); return -1; }
-    for (size_t i = 0; i < frames; ++i) { il[2 * i] = L[i + FFT]; il[2 * i + 1] = R[i + FFT]; }       /* channel_joinFloat(..., preshift 4096), main.c:806 */
+    for (size_t i = 0; i < frames; ++i) { il[2 * i] = L[i]; il[2 * i + 1] = R[i]; }
     const size_t w = fwrite(il, 8, frames, f);
     free(il);
     fclose(f);
@@ -137,17 +144,25 @@ int main(int argc, char **argv)
     const char *wpath = argc > 6 ? argv[6] : getenv("SPLEETERRT_WEIGHTS");
     if (!wpath) { fprintf(stderr, "no weights: pass the fp16 container (spleeterQuantized) as the 6th argument or in $SPLEETERRT_WEIGHTS\n"); return -1; }
 
+    /* $SPLEETERRT_RESAMPLE: 0 = 44.1 kHz input only, 1 = convert to 44.1 kHz (main.c:264-271), source = 1 + stems back at the input's rate */
+    const char *rs = getenv("SPLEETERRT_RESAMPLE");
+    int resample = 0;
+    if (rs && *rs && strcmp(rs, "0")) {
+        if (!strcmp(rs, "1")) resample = 1;
+        else if (!strcmp(rs, "source")) resample = 2;
+        else { fprintf(stderr, "SPLEETERRT_RESAMPLE=%s: expected 0, 1 or source\n", rs); return -1; }
+    }
+
     float *pcm = 0; unsigned channels = 0, rate = 0;
     const size_t nframes = read_wav(argv[5], &pcm, &channels, &rate);
     if (!nframes) return -1;
-    if (rate != 44100) { fprintf(stderr, "%s: %u Hz — only 44.1 kHz input is accepted (the resampler is outside this harness)\n", argv[5], rate); return -1; }
+    if (rate != 44100 && !resample) { fprintf(stderr, "%s: %u Hz — only 44.1 kHz input is accepted (set SPLEETERRT_RESAMPLE=1 to convert it on the GPU)\n", argv[5], rate); return -1; }
+    if (rate != 44100 && (rate < 8000 || rate > 384000)) { fprintf(stderr, "%s: %u Hz — the converter takes 8000..384000 Hz\n", argv[5], rate); return -1; }
+    const int convert = rate != 44100;
+    const size_t n44 = convert ? srtResampleLength(nframes, (int)rate, 44100) : nframes;       /* main.c:266 */
+    const size_t nout = resample == 2 ? nframes : n44;                                          /* frames of every output file */
     /* the outputs are float32 stereo RIFF files: 8 bytes per frame under a 32-bit chunk size (main.c writes the same container) */
-    if ((uint64_t)nframes * 8u + 58u > 0xFFFFFFFFull) { fprintf(stderr, "%s: %zu frames do not fit a float32 stereo RIFF/WAVE output (4 GiB limit); split the input\n", argv[5], nframes); return -1; }
-    const size_t readcount = (nframes + FFT - 1) / FFT, finalSize = FFT * readcount + 2 * FFT;
-    float *inL = (float *)calloc(finalSize, sizeof(float)), *inR = (float *)calloc(finalSize, sizeof(float));
-    if (!inL || !inR) { fprintf(stderr, "out of host memory (%zu samples per channel)\n", finalSize); return -1; }
-    for (size_t i = 0; i < nframes; ++i) { inL[FFT + i] = pcm[i * channels]; inR[FFT + i] = pcm[i * channels + (channels - 1)]; }
-    free(pcm);
+    if ((uint64_t)nout * 8u + 58u > 0xFFFFFFFFull) { fprintf(stderr, "%s: %zu output frames do not fit a float32 stereo RIFF/WAVE output (4 GiB limit); split the input\n", argv[5], nout); return -1; }
 
     const size_t nhalf = srtCoeffBytes() / 4;
     uint16_t *halfs = (uint16_t *)malloc(2 * nhalf * sizeof(uint16_t));
@@ -155,6 +170,26 @@ int main(int argc, char **argv)
     if (!halfs) { fprintf(stderr, "out of host memory\n"); return -1; }
     if (!wf || fread(halfs, sizeof(uint16_t), 2 * nhalf, wf) != 2 * nhalf) { fprintf(stderr, "cannot read %zu halves from %s\n", 2 * nhalf, wpath); return -1; }
     fclose(wf);
+
+    const size_t readcount = (n44 + FFT - 1) / FFT, finalSize = FFT * readcount + 2 * FFT;
+    float *inL = (float *)calloc(finalSize, sizeof(float)), *inR = (float *)calloc(finalSize, sizeof(float));
+    if (!inL || !inR) { fprintf(stderr, "out of host memory (%zu samples per channel)\n", finalSize); return -1; }
+    if (convert) {
+        /* planar copy of the input, converted on the device straight into the pre-shifted buffers (mono: one channel, duplicated after) */
+        float *pl = (float *)malloc(nframes * sizeof(float)), *pr = channels == 2 ? (float *)malloc(nframes * sizeof(float)) : pl;
+        if (!pl || !pr) { fprintf(stderr, "out of host memory (%zu input frames)\n", nframes); return -1; }
+        for (size_t i = 0; i < nframes; ++i) { pl[i] = pcm[i * channels]; pr[i] = pcm[i * channels + (channels - 1)]; }
+        srt_resampler *r = 0;
+        const double tr = now();
+        if (srtResamplerCreate((int)rate, 44100, 0, 0, 0, 0, &r) || srtResampleHost(r, pl, pr, nframes, inL + FFT, inR + FFT)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+        srtResamplerDestroy(r);
+        printf("Resampling %u Hz -> 44100 Hz on the GPU takes %1.14lf sec (%zu -> %zu frames)\n", rate, now() - tr, nframes, n44);
+        if (pr != pl) free(pr);
+        free(pl);
+    } else {
+        for (size_t i = 0; i < nframes; ++i) { inL[FFT + i] = pcm[i * channels]; inR[FFT + i] = pcm[i * channels + (channels - 1)]; }
+    }
+    free(pcm);
     printf("Audio & model file loading takes: %1.14lf sec\n", now() - t0);
 
     const size_t rows = srtStftRows(finalSize), len = srtIstftLength(rows);
@@ -210,13 +245,28 @@ int main(int argc, char **argv)
 
     static const char *names2[] = { "Vocal", "Accompaniment" }, *names3[] = { "Drum", "Vocal", "Accompaniment" };
     const char **names = stems == 2 ? names2 : names3;
+    srt_resampler *back = 0;                                           /* SPLEETERRT_RESAMPLE=source: stems back to the input's rate */
+    float *bl = 0, *br = 0;
+    if (resample == 2 && convert) {
+        const size_t nb = srtResampleLength(n44, 44100, (int)rate), cap = nb > nframes ? nb : nframes;
+        bl = (float *)calloc(cap, sizeof(float)); br = (float *)calloc(cap, sizeof(float));
+        if (!bl || !br) { fprintf(stderr, "out of host memory (%zu frames)\n", cap); return -1; }
+        if (srtResamplerCreate(44100, (int)rate, 0, 0, 0, 0, &back)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+    }
     for (int k = 0; k < stems; ++k) {
         char path[4096];
         t0 = now();
         snprintf(path, sizeof path, "%s_%s.wav", base_name(argv[5]), names[k]);
-        if (write_wav(path, out + (size_t)(2 * k) * len, out + (size_t)(2 * k + 1) * len, nframes)) return -1;
+        const float *L = out + (size_t)(2 * k) * len + FFT, *R = out + (size_t)(2 * k + 1) * len + FFT;   /* channel_joinFloat(..., preshift 4096), main.c:806 */
+        if (back) {                                                    /* the stem's 44.1 kHz frames [0, n44), zero outside */
+            if (srtResampleHost(back, L, R, n44, bl, br)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+            L = bl; R = br;
+        }
+        if (write_wav(path, L, R, nout, back ? rate : 44100)) return -1;
         printf("Saving file -> %s takes %1.14lf sec\n", path, now() - t0);
     }
+    if (back) srtResamplerDestroy(back);
+    free(bl); free(br);
     free(out); free(inL); free(inR);
     return 0;
 }

@@ -166,6 +166,28 @@ SRT_API int  srtMultiBenchResident(srt_multi *m, int tiles, int steps, int warmu
 /* (with seconds_events != NULL the per-launch timing window of engine 0 stays OPEN after the call so that srtGetTiming / srtGetTimingKernels on
  * srtMultiEngine(m, 0) can read the K event-timed passes; the caller closes it with srtSetTiming(engine, 0)) */
 
+/* ---- sample-rate conversion: the reference program converts every input to 44.1 kHz before separating (Executable/main.c:264-271,
+ * JamesDSPOfflineResampling -> libsamplerate's src_simple, the sinc converter of libsamplerate/src_sinc.c:366-512, with the 22 438-point
+ * table main.c:133-208 rebuilds at start-up, read with index_inc = 491).  The same arithmetic on the GPU, with the phase of output frame n
+ * kept exactly (n * fs_in / fs_out in 64-bit integers) and every frame computed, the last one included.  Planar stereo fp32. */
+typedef struct srt_resampler srt_resampler;
+/* frames main.c:266 allocates: ceil(n_in * (fs_out / (double)fs_in)); pure arithmetic, no device */
+SRT_API size_t srtResampleLength(size_t n_in, int fs_in, int fs_out);
+/* current device, like srtCreate.  h_table NULL = built-in filter, else a half filter of table_len floats
+ * sampled at index_inc points per input sample (the reference's: 22438, 491).  Rates 8000..384000 Hz.
+ * Arguments are checked before any HIP call. */
+SRT_API int  srtResamplerCreate(int fs_in, int fs_out, const float *h_table, int table_len, int index_inc,
+                                void *stream, srt_resampler **out);
+SRT_API int  srtResamplerDestroy(srt_resampler *r);
+/* device-resident, asynchronous on the resampler's stream, capturable (no host sync):
+ * output frames [out0, out0 + n_out) of the converted stream of the n_in input frames in d_L / d_R
+ * (d_R may equal d_L: mono; d_Ro may then equal d_Lo).  A frame's value depends on its index only: any split of a range gives the same bits. */
+SRT_API int  srtResample(srt_resampler *r, const float *d_L, const float *d_R, size_t n_in,
+                         size_t out0, size_t n_out, float *d_Lo, float *d_Ro);
+/* host buffers, synchronous, the whole stream: h_Lo / h_Ro hold srtResampleLength(n_in, fs_in, fs_out) frames */
+SRT_API int  srtResampleHost(srt_resampler *r, const float *h_L, const float *h_R, size_t n_in,
+                             float *h_Lo, float *h_Ro);
+
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6" */
 SRT_API int  srtSetTiming(srt_engine *e, int enable);                    /* record HIP events around every launch of the next calls */

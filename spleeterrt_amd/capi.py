@@ -85,6 +85,13 @@ def load_library():
     L.srtMultiEngine.argtypes = [vp, C.c_int]
     L.srtMultiEngine.restype = vp
     L.srtMultiBenchResident.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    # sample-rate converter (csrc/srt_resample.hip)
+    L.srtResampleLength.restype = C.c_size_t
+    L.srtResampleLength.argtypes = [C.c_size_t, C.c_int, C.c_int]
+    L.srtResamplerCreate.argtypes = [C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
+    L.srtResamplerDestroy.argtypes = [vp]
+    L.srtResample.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_size_t, C.c_size_t, f32p, f32p]
+    L.srtResampleHost.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
     _lib = L
     return L
 
@@ -320,3 +327,74 @@ class Engine:
         n = self._chk(self.L.srtGetTimingKernels(self.h, buf, len(buf)))
         ks = buf.value.decode().split(";")[:n]
         return [(name, k) for (name, _), k in zip(tim, ks)]
+
+
+class Resampler:
+    """Sample-rate conversion fs_in -> fs_out on the current device (srtResampler*, include/spleeterrt_amd.h): the reference program's
+    libsamplerate sinc converter (main.c:264-271) on planar stereo fp32.  table=None: the built-in filter; otherwise a half filter in
+    libsamplerate's layout (table_len floats, index_inc points per input sample), e.g. the reference's 22 438-point table."""
+
+    def __init__(self, fs_in, fs_out, table=None, index_inc=491, stream=None):
+        import numpy as np
+        self.L = load_library()
+        self.fs_in, self.fs_out = int(fs_in), int(fs_out)
+        self._table = None if table is None else np.ascontiguousarray(table, np.float32)
+        import torch
+        if stream is None and torch.cuda.is_available():
+            stream = torch.cuda.current_stream()
+        self.stream = stream
+        sp = None if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+        h = C.c_void_p()
+        tp = None if self._table is None else C.c_void_p(self._table.ctypes.data)
+        self._chk(self.L.srtResamplerCreate(self.fs_in, self.fs_out, tp, 0 if self._table is None else self._table.size, int(index_inc), sp, C.byref(h)))
+        self.h = h
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (self.L.srtLastError().decode(), rc))
+        return rc
+
+    def length(self, n):
+        """output frames of an n-frame input: ceil(n * (fs_out / fs_in)), as main.c:266"""
+        return self.L.srtResampleLength(int(n), self.fs_in, self.fs_out)
+
+    def resample(self, L, R, out0=0, n_out=None, Lo=None, Ro=None):
+        """CUDA float32 tensors [n] -> (Lo, Ro): output frames [out0, out0 + n_out) (default: all of them).  R may be L (mono)."""
+        import torch
+        assert L.is_cuda and L.dtype == torch.float32 and R.is_cuda and R.dtype == torch.float32 and L.numel() == R.numel()
+        mono = R is L
+        L = L.contiguous()
+        R = L if mono else R.contiguous()
+        n = L.numel()
+        if n_out is None:
+            n_out = max(self.length(n) - out0, 0)
+        if Lo is None:
+            Lo = torch.empty(n_out, device=L.device, dtype=torch.float32)
+        if Ro is None:
+            Ro = torch.empty(n_out, device=L.device, dtype=torch.float32)
+        self._chk(self.L.srtResample(self.h, _ptr(L), _ptr(R), n, int(out0), int(n_out), _ptr(Lo), _ptr(Ro)))
+        return Lo, Ro
+
+    def resample_host(self, L, R):
+        """numpy float32 [n] x2 -> (Lo, Ro) numpy, the whole stream (synchronous)"""
+        import numpy as np
+        mono = R is L
+        L = np.ascontiguousarray(L, np.float32)
+        R = L if mono else np.ascontiguousarray(R, np.float32)
+        assert L.size == R.size
+        m = self.length(L.size)
+        Lo, Ro = np.empty(m, np.float32), np.empty(m, np.float32)
+        self._chk(self.L.srtResampleHost(self.h, C.c_void_p(L.ctypes.data), C.c_void_p(R.ctypes.data), L.size,
+                                         C.c_void_p(Lo.ctypes.data), C.c_void_p(Ro.ctypes.data)))
+        return Lo, Ro
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.srtResamplerDestroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,271 @@
+// srt_resample.hip — band-limited sample-rate conversion of planar stereo fp32 PCM in HBM (srtResampler*, include/spleeterrt_amd.h).
+//
+// The arithmetic is libsamplerate's sinc converter as the reference program runs it (Executable/main.c:264-271 -> src_simple ->
+// libsamplerate/src_sinc.c:366-512, sinc_stereo_vari_process / calc_output_stereo), restated with an exact rational phase:
+//   output frame n sits at input position n * fs_in / fs_out = i + frac   (64-bit integers; frac = ((n fs_in) mod fs_out) / fs_out)
+//   float_increment = index_inc * min(r, 1), increment = lrint(float_increment * 4096) (12 fraction bits), start = lrint(frac * float_increment * 4096)
+//   left half:  taps x[i - k] at filter index start + k increment        (k >= 0, index <= (table_len - 2) << 12)
+//   right half: taps x[i + 1 + j] at filter index increment - start + j increment   (index > 0, same bound)
+//   weight = c[f >> 12] + (f & 4095) / 4096 * (c[(f >> 12) + 1] - c[f >> 12]),   y = min(r, 1) * sum(weight * x),  x = 0 outside [0, n_in)
+// The weights of a frame depend only on its phase n mod Q (Q = fs_out / gcd), so srt_resample_bank_kernel evaluates them once per
+// resampler into a bank [T/4][Q][4] (T taps per frame, window starting at i - LO); srt_resample_kernel then stages each block's input
+// window in LDS and runs the T-tap dot products in fp32 (fixed order, explicit FMAs).  A frame's value depends on its absolute index only:
+// any partition of the output range gives the same bits.  When the bank would exceed SRT_RS_BANK_BYTES the kernel evaluates the same
+// weight function per tap instead (ONFLY = true): same floats, same FMA order, same bits.
+#include "srt_internal.h"
+#include "../../include/spleeterrt_amd.h"
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <new>
+#include <vector>
+
+#define SRT_RS_BANK_BYTES (8u << 20)     // per-phase weight bank limit: every common rate pair fits (96 k -> 44.1 k: 147 phases x 200 taps = 118 KB)
+#define SRT_RS_LDS_BYTES  (64u << 10)    // input window staged per workgroup
+#define SRT_RS_MIN_RATE 8000
+#define SRT_RS_MAX_RATE 384000
+
+struct SrtRsGeom {
+    long long P, Q;          // fs_in / g, fs_out / g
+    long long inc, maxIdx;   // increment, (table_len - 2) << 12
+    int LO, T4;              // window = input frames [i - LO, i - LO + T4); T4 = taps padded to a multiple of 4 (zero weights)
+    double fi, scale;        // float_increment, float_increment / index_inc
+};
+
+struct SrtRsArgs {
+    SrtRsGeom g;
+    const float* table; const float4* bank;
+    const float* L; const float* R; long long nIn;
+    float* Lo; float* Ro;
+    long long out0, outEnd;  // frames [out0, outEnd); Lo[0] holds frame out0
+    int B, opt;              // frames per workgroup, frames per thread (B = blockDim.x * opt)
+    long long stepI, stepR, stepM;   // blockDim.x frames further: i += stepI (+1 on carry), (n P) mod Q += stepR, n mod Q += stepM
+};
+
+// start of the filter for phase m = n mod Q  (src_sinc.c:468: double_to_fp(input_index * float_increment))
+__device__ __host__ inline long long rs_start(const SrtRsGeom& g, long long m)
+{
+    const double frac = (double)((m * g.P) % g.Q) / (double)g.Q;
+    return (long long)rint(frac * g.fi * 4096.0);
+}
+
+// weight of window tap t (input frame i - LO + t) for a frame whose filter starts at `start`; zero where the reference takes no tap
+__device__ inline float rs_weight(const SrtRsGeom& g, const float* __restrict__ table, long long start, int t)
+{
+#pragma clang fp contract(off)
+    const long long u = (long long)t - g.LO;
+    long long f;
+    if (u <= 0) f = start - u * g.inc;                          // left half, src_sinc.c:375-394
+    else { f = g.inc - start + (u - 1) * g.inc; if (f <= 0) return 0.0f; }   // right half, :397-412 (filter index 0 excluded)
+    if (f > g.maxIdx) return 0.0f;
+    const long long k = f >> 12;
+    const double fr = (double)(f & 4095) * (1.0 / 4096.0);
+    const double c0 = table[k], c1 = table[k + 1];
+    const double w = c0 + fr * (c1 - c0);
+    return (float)(g.scale * w);
+}
+
+__global__ __launch_bounds__(256) void srt_resample_bank_kernel(SrtRsGeom g, const float* __restrict__ table, float* __restrict__ bank)
+{
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x, n = g.Q * g.T4;
+    if (e >= n) return;
+    const long long q4 = g.Q * 4, m = (e % q4) >> 2;
+    const int t = (int)(e / q4) * 4 + (int)(e & 3);
+    bank[e] = rs_weight(g, table, rs_start(g, m), t);
+}
+
+template <bool ONFLY>
+__global__ __launch_bounds__(256) void srt_resample_kernel(SrtRsArgs a)
+{
+    extern __shared__ float2 win[];
+    const SrtRsGeom& g = a.g;
+    const long long n0 = a.out0 + (long long)blockIdx.x * a.B;
+    const long long nEnd = min(n0 + (long long)a.B, a.outEnd);
+    const long long i0 = n0 * g.P / g.Q, s0 = i0 - g.LO;
+    const int W = (int)((nEnd - 1) * g.P / g.Q - i0) + g.T4;   // <= floor((B - 1) P / Q) + 1 + T4 frames: the host sized the LDS for that
+    for (int j = threadIdx.x; j < W; j += blockDim.x) {
+        const long long s = s0 + j;
+        float2 v = make_float2(0.0f, 0.0f);
+        if (s >= 0 && s < a.nIn) { v.x = a.L[s]; v.y = a.R[s]; }
+        win[j] = v;
+    }
+    __syncthreads();
+    long long n = n0 + threadIdx.x;
+    if (n >= nEnd) return;
+    long long pos = n * g.P, i = pos / g.Q, r = pos - i * g.Q, m = n % g.Q;
+    for (int k = 0; k < a.opt && n < nEnd; ++k) {
+        const float2* x = win + (i - i0);
+        float l0 = 0.0f, r0 = 0.0f, l1 = 0.0f, r1 = 0.0f;
+        if (ONFLY) {
+            const long long start = rs_start(g, m);
+            for (int t = 0; t < g.T4; t += 4) {
+                const float w0 = rs_weight(g, a.table, start, t), w1 = rs_weight(g, a.table, start, t + 1);
+                const float w2 = rs_weight(g, a.table, start, t + 2), w3 = rs_weight(g, a.table, start, t + 3);
+                const float2 x0 = x[t], x1 = x[t + 1], x2 = x[t + 2], x3 = x[t + 3];
+                l0 = fmaf(w0, x0.x, l0); r0 = fmaf(w0, x0.y, r0); l1 = fmaf(w1, x1.x, l1); r1 = fmaf(w1, x1.y, r1);
+                l0 = fmaf(w2, x2.x, l0); r0 = fmaf(w2, x2.y, r0); l1 = fmaf(w3, x3.x, l1); r1 = fmaf(w3, x3.y, r1);
+            }
+        } else {
+            const float4* wp = a.bank + m;
+#pragma unroll 4
+            for (int t = 0; t < g.T4; t += 4) {
+                const float4 w = wp[(long long)(t >> 2) * g.Q];
+                const float2 x0 = x[t], x1 = x[t + 1], x2 = x[t + 2], x3 = x[t + 3];
+                l0 = fmaf(w.x, x0.x, l0); r0 = fmaf(w.x, x0.y, r0); l1 = fmaf(w.y, x1.x, l1); r1 = fmaf(w.y, x1.y, r1);
+                l0 = fmaf(w.z, x2.x, l0); r0 = fmaf(w.z, x2.y, r0); l1 = fmaf(w.w, x3.x, l1); r1 = fmaf(w.w, x3.y, r1);
+            }
+        }
+        const long long o = n - a.out0;
+        a.Lo[o] = l0 + l1;
+        if (a.Ro != a.Lo) a.Ro[o] = r0 + r1;
+        n += blockDim.x; i += a.stepI; r += a.stepR; m += a.stepM;
+        if (r >= g.Q) { r -= g.Q; ++i; }
+        if (m >= g.Q) m -= g.Q;
+    }
+}
+
+struct srt_resampler {
+    int fs_in, fs_out, device, onfly;
+    SrtRsGeom g;
+    int B, threads;
+    size_t ldsBytes;
+    hipStream_t stream;
+    float* d_table; float* d_bank;
+};
+
+static int rs_fail(int code, const char* fmt, const char* detail = "") { return srt_set_error(code, fmt, detail); }
+static long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
+
+// built-in half filter in the reference's layout (index_inc = 491, 22 438 points): a Kaiser-windowed sinc (beta 12) with its cutoff at
+// 0.918 of the lower rate's Nyquist frequency, the window reaching its edge at the table's last point.  Project's own design: passband
+// flat to 2e-5 dB up to 17 kHz and stopband below -115 dB from 22.5 kHz at 48 k -> 44.1 k (tests/test_resample.py).
+static void builtin_table(std::vector<float>& c)
+{
+    const int n = 22438, inc = 491;
+    const double fc = 0.918, beta = 12.0, half = (n - 1) / (double)inc, PI = 3.141592653589793;
+    auto i0 = [](double x) { double s = 1.0, term = 1.0; for (int k = 1; k < 200; ++k) { term *= (x / (2.0 * k)) * (x / (2.0 * k)); s += term; if (term < 1e-18 * s) break; } return s; };
+    const double norm = 1.0 / i0(beta);
+    c.resize(n);
+    for (int k = 0; k < n; ++k) {
+        const double t = k / (double)inc, q = t / half, a = fc * t;
+        const double sinc = k == 0 ? 1.0 : sin(PI * a) / (PI * a);
+        c[k] = (float)(fc * sinc * i0(beta * sqrt(q < 1.0 ? 1.0 - q * q : 0.0)) * norm);
+    }
+}
+
+size_t srtResampleLength(size_t n_in, int fs_in, int fs_out)
+{
+    if (fs_in <= 0 || fs_out <= 0) return 0;
+    return (size_t)ceil((double)n_in * (fs_out / (double)fs_in));      // main.c:266
+}
+
+int srtResamplerCreate(int fs_in, int fs_out, const float* h_table, int table_len, int index_inc, void* stream, srt_resampler** out)
+{
+    if (!out) return rs_fail(-1, "srtResamplerCreate: null output pointer");
+    *out = nullptr;
+    if (fs_in < SRT_RS_MIN_RATE || fs_in > SRT_RS_MAX_RATE || fs_out < SRT_RS_MIN_RATE || fs_out > SRT_RS_MAX_RATE)
+        return rs_fail(-1, "srtResamplerCreate: sample rates must lie in 8000..384000 Hz");
+    if (h_table && table_len < 2) return rs_fail(-1, "srtResamplerCreate: table_len must be at least 2");
+    if (h_table && index_inc < 1) return rs_fail(-1, "srtResamplerCreate: index_inc must be at least 1");
+    if (h_table && table_len > (1 << 24)) return rs_fail(-1, "srtResamplerCreate: table_len above 2^24");
+    std::vector<float> tab;
+    if (!h_table) { builtin_table(tab); table_len = (int)tab.size(); index_inc = 491; }
+    SrtRsGeom g;
+    const long long gc = gcd_ll(fs_in, fs_out);
+    g.P = fs_in / gc; g.Q = fs_out / gc;
+    const double r = fs_out / (double)fs_in;
+    g.fi = index_inc * (r < 1.0 ? r : 1.0);
+    g.scale = g.fi / index_inc;
+    g.inc = (long long)rint(g.fi * 4096.0);
+    g.maxIdx = (long long)(table_len - 2) << 12;
+    if (g.inc < 1) return rs_fail(-1, "srtResamplerCreate: index_inc * min(fs_out / fs_in, 1) rounds to a zero filter increment");
+    const long long half = g.maxIdx / g.inc, taps = 2 * half + 2;
+    g.LO = (int)half;
+    g.T4 = (int)((taps + 3) / 4 * 4);
+    // workgroup size: the most frames whose input window fits the LDS budget
+    int B = 1024;
+    auto window = [&](int b) { return (size_t)(((long long)(b - 1) * g.P) / g.Q + 1 + g.T4) * sizeof(float2); };
+    while (B > 64 && window(B) > SRT_RS_LDS_BYTES) B >>= 1;
+    if (window(B) > SRT_RS_LDS_BYTES) return rs_fail(-1, "srtResamplerCreate: filter too long for this rate pair (input window above 64 KiB)");
+    const size_t bankBytes = (size_t)g.Q * g.T4 * sizeof(float);
+    const char* of = getenv("SPLEETERRT_RESAMPLE_ONFLY");               // measurement / test aid: skip the bank (the results are the same bits)
+    const int onfly = bankBytes > SRT_RS_BANK_BYTES || (of && of[0] == '1');
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return rs_fail(-3, "srtResamplerCreate: no HIP device (this library has no CPU path)");
+    srt_resampler* s = new (std::nothrow) srt_resampler();
+    if (!s) return rs_fail(-2, "srtResamplerCreate: out of host memory");
+    s->fs_in = fs_in; s->fs_out = fs_out; s->g = g; s->onfly = onfly; s->B = B; s->threads = B < 256 ? B : 256; s->ldsBytes = window(B);
+    s->stream = (hipStream_t)stream; s->d_table = nullptr; s->d_bank = nullptr;
+    const float* src = h_table ? h_table : tab.data();
+    hipError_t e = hipGetDevice(&s->device);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_table, (size_t)table_len * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_table, src, (size_t)table_len * sizeof(float), hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess && !onfly) e = hipMalloc((void**)&s->d_bank, bankBytes);
+    if (e == hipSuccess && !onfly) {
+        const long long n = g.Q * g.T4;
+        SRT_LAUNCH(srt_resample_bank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, g, s->d_table, s->d_bank);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);          // the host table may go away after the call
+    if (e != hipSuccess) { srtResamplerDestroy(s); return rs_fail(-2, "srtResamplerCreate: HIP error: %s", hipGetErrorString(e)); }
+    *out = s;
+    return 0;
+}
+
+int srtResamplerDestroy(srt_resampler* s)
+{
+    if (!s) return 0;
+    if (s->stream) hipStreamSynchronize(s->stream);
+    else hipDeviceSynchronize();
+    if (s->d_table) hipFree(s->d_table);
+    if (s->d_bank) hipFree(s->d_bank);
+    delete s;
+    return 0;
+}
+
+int srtResample(srt_resampler* s, const float* d_L, const float* d_R, size_t n_in, size_t out0, size_t n_out, float* d_Lo, float* d_Ro)
+{
+    if (!s) return rs_fail(-1, "srtResample: null resampler");
+    if (n_out == 0) return 0;
+    if (!d_L || !d_R || !d_Lo || !d_Ro) return rs_fail(-1, "srtResample: null buffer");
+    if (d_Lo == d_Ro && d_L != d_R) return rs_fail(-1, "srtResample: d_Lo == d_Ro needs mono input (d_L == d_R)");
+    const unsigned long long nb = (n_out + s->B - 1) / s->B;
+    if (nb > 0x7fffffffull || out0 + n_out > (size_t)1 << 44) return rs_fail(-1, "srtResample: output range too large");
+    SrtRsArgs a;
+    a.g = s->g; a.table = s->d_table; a.bank = (const float4*)s->d_bank;
+    a.L = d_L; a.R = d_R; a.nIn = (long long)n_in; a.Lo = d_Lo; a.Ro = d_Ro;
+    a.out0 = (long long)out0; a.outEnd = (long long)(out0 + n_out);
+    a.B = s->B; a.opt = s->B / s->threads;
+    const long long adv = (long long)s->threads * s->g.P;
+    a.stepI = adv / s->g.Q; a.stepR = adv % s->g.Q; a.stepM = s->threads % s->g.Q;
+    if (s->onfly) SRT_LAUNCH(srt_resample_kernel<true>, dim3((unsigned)nb), dim3(s->threads), s->ldsBytes, s->stream, a);
+    else SRT_LAUNCH(srt_resample_kernel<false>, dim3((unsigned)nb), dim3(s->threads), s->ldsBytes, s->stream, a);
+    if (srt_launch_status()) return rs_fail(-2, "srtResample: kernel launch failed%s", "");
+    return 0;
+}
+
+int srtResampleHost(srt_resampler* s, const float* h_L, const float* h_R, size_t n_in, float* h_Lo, float* h_Ro)
+{
+    if (!s) return rs_fail(-1, "srtResampleHost: null resampler");
+    if (!h_L || !h_R || !h_Lo || !h_Ro) return rs_fail(-1, "srtResampleHost: null buffer");
+    const size_t n_out = srtResampleLength(n_in, s->fs_in, s->fs_out);
+    if (n_out == 0) return 0;
+    const bool mono = h_L == h_R;
+    float *dIn = nullptr, *dOut = nullptr;
+    const size_t inF = mono ? n_in : 2 * n_in;
+    hipError_t e = hipMalloc((void**)&dIn, inF * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&dOut, 2 * n_out * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(dIn, h_L, n_in * sizeof(float), hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess && !mono) e = hipMemcpyAsync(dIn + n_in, h_R, n_in * sizeof(float), hipMemcpyHostToDevice, s->stream);
+    int rc = 0;
+    if (e == hipSuccess) rc = srtResample(s, dIn, mono ? dIn : dIn + n_in, n_in, 0, n_out, dOut, dOut + n_out);
+    if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(h_Lo, dOut, n_out * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(h_Ro, dOut + n_out, n_out * sizeof(float), hipMemcpyDeviceToHost, s->stream);
+    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(s->stream);
+    if (dIn) hipFree(dIn);
+    if (dOut) hipFree(dOut);
+    if (rc) return rc;
+    if (e != hipSuccess) return rs_fail(-2, "srtResampleHost: HIP error: %s", hipGetErrorString(e));
+    return 0;
+}
