@@ -132,6 +132,22 @@ SRT_API int  srtPrepareForward(srt_engine *e, const float *d_mag, int ntiles, fl
 /* free the grow-only device staging of the host-buffer entry points (srtSeparateHostStream*, srtSeparateCliHost); the next such call re-allocates */
 SRT_API int  srtReleaseStaging(srt_engine *e);
 
+/* ---- multichannel Wiener filter: official Spleeter's `separate --mwf` post-processing, norbert.wiener(v, x, n) with its defaults (soft-mask start,
+ * eps = 2^-23), over the stereo image - a stem's left output can draw on the mixture's right channel.  v_{j,c} = mask * |x_c| in band (x = 4096 * spectrum, the
+ * networks' scale); n EM iterations, each with a 2x2 spatial covariance R_j per (stem, bin) summed over EVERY row of the call, then W_j = v_j R_j C^-1
+ * applied to x.  Bins >= F keep the engine's rule (oob_weight * spectrum).  On the GPU: one statistics pass + one finalize per iteration (fixed-order
+ * sums, no atomics: bit-reproducible, also under graph replay), one filter pass, one inverse transform per stem.
+ * srtSetWiener: 0 = off (the default; nothing changes), 1..3 = iterations (Spleeter's default is 1).  Allocates its workspace for max_tiles tiles now
+ * (call it before capturing).  -1 with ratio_mask set or iterations outside 0..3.  While it is on, srtSeparate / srtSeparateEx apply it (srtSeparateEx:
+ * the statistics window is the call's own `rows`, so a tile range of a longer stream is filtered with its own covariance), in the fp16 mode too (the
+ * masks then stay fp32).  Refused with -1 because the statistics span the whole signal: srtSeparateHostStream* (chunks), srtSeparateCli* (no stem
+ * axis either) and srtMultiSeparate* (ranges per device).  In graph mode the iteration count is part of the captured call's key. */
+SRT_API int  srtSetWiener(srt_engine *e, int iterations);
+/* the filter + inverse transform for a caller-given spectrum [2][rows][2052] (srtStft layout) and fp32 masks [n_stems][ntiles][2][T][F] of all stems,
+ * `iterations` 1..3 whatever srtSetWiener says; d_out as srtIstft.  srtCopyTensor(e, "wiener_cov", stem, iteration, h, 5F + 1) then returns R_j of
+ * that iteration of the last filtered call as [F][4] (R00, R11, Re R01, Im R01), the weight sums sum_t v_j [F] (spectrum units) and a [1]. */
+SRT_API int  srtIstftWiener(srt_engine *e, const float *d_spec, size_t rows, const float *d_masks, int iterations, float *d_out);
+
 /* ---- one node, several devices: the reference CLI's tile-range fan-out (Executable/main.c:544-673, `processMT`: spawnNthreads workers, each with
  * its own network instance and a contiguous tile range, one shared read-only weight blob) with a GPU where the reference has a CPU thread.
  * One engine per entry of `devices` (an index may repeat: several engines on one GPU), one host thread per engine while a call runs; weights are
@@ -189,7 +205,8 @@ SRT_API int  srtResampleHost(srt_resampler *r, const float *h_L, const float *h_
                              float *h_Lo, float *h_Ro);
 
 /* debug / measurement */
-SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6" */
+SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";
+                                                                                                                   "wiener_cov": tile = iteration (see srtIstftWiener) */
 SRT_API int  srtSetTiming(srt_engine *e, int enable);                    /* record HIP events around every launch of the next calls */
 SRT_API int  srtGetTiming(srt_engine *e, char *names, size_t names_bytes, float *ms, int max_entries); /* returns count; syncs the stream */
 /* which kernel ran each of those launches (same order), ';'-separated, named as rocprofv3 names kernels ("srt_dec_wino<4, 16, 1, 0>"):

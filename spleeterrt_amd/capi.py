@@ -53,6 +53,8 @@ def load_library():
     L.srtForward.argtypes = [vp, f32p, C.c_int, f32p]
     L.srtForwardStems.argtypes = [vp, f32p, C.c_int, f32p, C.c_int, C.c_int]
     L.srtRatioMask.argtypes = [vp, f32p, C.c_int]
+    L.srtSetWiener.argtypes = [vp, C.c_int]
+    L.srtIstftWiener.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_int, f32p]
     L.srtSeparateCli.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.srtSeparateCliHost.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.srtSeparateHostStream.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp]
@@ -104,7 +106,7 @@ class Engine:
     """One engine per (device, stream): nstems sub-networks evaluated over batches of T x F spectrogram tiles."""
 
     def __init__(self, F=1024, T=256, stem_modes=(1, 1, 1, 1), oob_weights=None, variant=VARIANT_EXE, max_tiles=1,
-                 impl=IMPL_MFMA, device=None, precision=PREC_F32, ratio_mask=False, batch_invariant=False):
+                 impl=IMPL_MFMA, device=None, precision=PREC_F32, ratio_mask=False, batch_invariant=False, wiener=0):
         import torch
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: spleeterrt_amd has no CPU path")
@@ -125,6 +127,9 @@ class Engine:
         h = C.c_void_p()
         self._chk(self.L.srtCreate(C.byref(cfg), C.c_void_p(self.stream.cuda_stream), C.byref(h)))
         self.h = h
+        self.wiener = 0
+        if wiener:
+            self.set_wiener(wiener)
 
     def _chk(self, rc):
         if rc < 0:
@@ -189,6 +194,27 @@ class Engine:
         assert masks.is_contiguous() and masks.shape[0] == self.S
         self._chk(self.L.srtRatioMask(self.h, _ptr(masks), masks.shape[1]))
         return masks
+
+    def set_wiener(self, iterations):
+        """multichannel Wiener filter (Spleeter's --mwf) inside separate / separate_ex: 0 = off, 1..3 EM iterations (srtSetWiener)"""
+        self._chk(self.L.srtSetWiener(self.h, int(iterations)))
+        self.wiener = int(iterations)
+
+    def istft_wiener(self, spec, masks, iterations=1):
+        """spec [2,rows,2052,2], fp32 masks [S,ntiles,2,T,F] -> Wiener-filtered stems [S,2,rows*1024+3072] (srtIstftWiener)"""
+        t = self.torch
+        rows = spec.shape[1]
+        assert masks.is_cuda and masks.dtype == t.float32 and masks.is_contiguous() and masks.shape[0] == self.S
+        out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
+        self._chk(self.L.srtIstftWiener(self.h, _ptr(spec.contiguous()), rows, _ptr(masks), int(iterations), _ptr(out)))
+        return out
+
+    def wiener_cov(self, stem, iteration):
+        """(R [F,4] = R00, R11, Re R01, Im R01; weight sums [F]; a) of one stem and iteration of the last filtered call"""
+        import numpy as np
+        a = np.empty(5 * self.F + 1, np.float32)
+        self._chk(self.L.srtCopyTensor(self.h, b"wiener_cov", stem, iteration, C.c_void_p(a.ctypes.data), a.size))
+        return a[:4 * self.F].reshape(self.F, 4), a[4 * self.F:5 * self.F], float(a[5 * self.F])
 
     def stft(self, L, R, want_mag=True):
         """planar PCM -> (spec [2,rows,2052,2], mag [ntiles,2,T,F] or None)"""

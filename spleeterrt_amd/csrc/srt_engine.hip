@@ -82,7 +82,7 @@ struct HostStaging {
 // the first time its argument tuple is seen and replayed afterwards: one host call instead of ~25 launches on the audio thread.
 // `layout`: the switches that change which kernels and tensor layouts a forward records (SPLEETERRT_C8, C8L1, D1F16, M16; read per call), so a flipped
 // switch captures a new graph instead of replaying the old layout.
-struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, layout; };
+struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, layout, wiener; };
 // c8 / c8_l1 / masks16: what the captured forward left in last_c8 / last_c8_l1 / last_masks16 - a replay runs no host code, so run_graphed puts them back
 // (srtCopyTensor reads the taps by them; an eager call in between may have changed them)
 struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; bool c8, c8_l1, masks16; };
@@ -131,6 +131,12 @@ struct srt_engine {
     float2* spec; float2* spec2; float* mag; float* masks; float* frames;   // spec2: residual spectrum of the CLI chain (on first use)
     size_t rows_cap, frames_rows;
     int last_ntiles;
+    // multichannel Wiener filter (srt_wiener.hip, srtSetWiener): allocated for max_tiles when it is switched on (or by the first srtIstftWiener)
+    int wiener;                                        // EM iterations applied by srtSeparate / srtSeparateEx, 0: off
+    int wiener_last;                                   // iterations of the last filtered call: the R tables srtCopyTensor("wiener_cov") can return
+    float* wslab;                                      // statistics partials + block maxima
+    float* wtab;                                       // R tables, weight sums, a
+    float2* wspec;                                     // filtered spectra [n_stems][2][rows][SRT_SPEC_LD]
     // timing
     bool timing; std::vector<TimingEntry> tlog;
 };
@@ -196,7 +202,7 @@ static void free_all(srt_engine* e)
     for (int i = 0; i < 6; ++i) { if (e->wino_u[i]) hipFree(e->wino_u[i]); if (e->wino_e[i]) hipFree(e->wino_e[i]); if (e->act32[i]) hipFree(e->act32[i]); }
     for (int i = 0; i < 6; ++i) { if (e->wpack_down[i]) hipFree(e->wpack_down[i]); if (e->wpack_up[i]) hipFree(e->wpack_up[i]); }
     for (int i = 0; i < 6; ++i) { if (e->raw[i]) hipFree(e->raw[i]); if (e->up[i]) hipFree(e->up[i]); if (i < 5 && e->act16buf[i]) hipFree(e->act16buf[i]); }
-    void* misc[] = { e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->frames };
+    void* misc[] = { e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->frames, e->wslab, e->wtab, e->wspec };
     for (void* m : misc) if (m) hipFree(m);
     for (auto& t : e->tlog) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
 }
@@ -223,6 +229,7 @@ int srtCreate(const srt_config* cfg, void* stream, srt_engine** out)
     memset(e->have_coeff, 0, sizeof e->have_coeff);
     memset(e->raw, 0, sizeof e->raw); memset(e->up, 0, sizeof e->up); memset(e->act16buf, 0, sizeof e->act16buf);
     e->preWin = e->postWin = nullptr; e->twiddle = nullptr; e->spec = nullptr; e->spec2 = nullptr; e->mag = e->masks = e->frames = nullptr;
+    e->wiener = e->wiener_last = 0; e->wslab = e->wtab = nullptr; e->wspec = nullptr;
     e->cfg = *cfg;
     { const char* bi = getenv("SPLEETERRT_BATCH_INVARIANT"); if (bi && bi[0] == '1') e->cfg.batch_invariant = 1; }
     e->stream = (hipStream_t)stream; e->lo = make_layout(); e->timing = false; e->last_ntiles = cfg->max_tiles;
@@ -801,6 +808,80 @@ static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const fl
     return 0;
 }
 
+// ---- multichannel Wiener filter (srt_wiener.hip)
+static int istft_one(srt_engine* e, const float2* spec, size_t rows, const float* mask_stem, float oob, float* d_dst, const char* tag);
+static size_t wiener_slab_floats(const srt_engine* e) { return (size_t)SRT_WIENER_MAX_CHUNKS * e->cfg.n_stems * 4 * e->cfg.F + (size_t)SRT_WIENER_MAX_CHUNKS * SRT_WIENER_BINBLK; }
+static size_t wiener_tab_floats(const srt_engine* e) { return (size_t)SRT_WIENER_MAX_ITERS * e->cfg.n_stems * e->cfg.F * 5 + 4; }
+
+// the statistics slab, the R tables and the S filtered spectra for max_tiles tiles - allocated once (srtSetWiener, or the first srtIstftWiener), never
+// inside a capture, kept until srtDestroy (a captured graph holds these addresses)
+static int ensure_wiener_ws(srt_engine* e)
+{
+    if (e->wslab && e->wtab && e->wspec) return 0;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
+    if (cap != hipStreamCaptureStatusNone) return fail(-1, "Wiener filter: workspace not allocated (call srtSetWiener before capturing)");
+    SrtSetupLock setup;
+    if (!e->wslab) HIPCHK(hipMalloc((void**)&e->wslab, wiener_slab_floats(e) * sizeof(float)));
+    if (!e->wtab) {
+        HIPCHK(hipMalloc((void**)&e->wtab, wiener_tab_floats(e) * sizeof(float)));
+        HIPCHK(hipMemset(e->wtab, 0, wiener_tab_floats(e) * sizeof(float)));
+    }
+    if (!e->wspec) HIPCHK(hipMalloc((void**)&e->wspec, (size_t)e->cfg.n_stems * 2 * e->rows_cap * SRT_SPEC_LD * sizeof(float2)));
+    return 0;
+}
+
+// statistics passes (one stats + one finalize launch per iteration), the filter, then one inverse transform per stem on its filtered spectrum
+// (no masks: all-ones in band; bins >= F get oob_weight as with masks).  The statistics window is exactly the `rows` rows of this call.
+static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, int iters, float* d_out)
+{
+    const int T = e->cfg.T, S = e->cfg.n_stems, F = e->cfg.F;
+    SrtWienerParams w; memset(&w, 0, sizeof w);
+    w.spec = (const float2*)d_spec; w.spec_ch_stride = rows * SRT_SPEC_LD; w.rows = (int)rows;
+    w.masks = d_masks; w.nstems = S; w.ntiles = (int)((rows + T - 1) / T); w.T = T; w.F = F;
+    int nch = (int)((rows + 15) / 16); if (nch > SRT_WIENER_MAX_CHUNKS) nch = SRT_WIENER_MAX_CHUNKS;
+    w.rpc = (int)((rows + nch - 1) / nch); w.nchunks = (int)((rows + w.rpc - 1) / w.rpc);
+    w.slab = e->wslab; w.slab_max = e->wslab + (size_t)SRT_WIENER_MAX_CHUNKS * S * 4 * F;
+    w.rtab = e->wtab; w.wsum = e->wtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4; w.scal = w.wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F;
+    w.out = e->wspec; w.out_stem = 2 * rows * SRT_SPEC_LD;
+    for (int pass = 1; pass <= iters; ++pass) {
+        { TimerScope ts(e, "wiener_stats"); if (srt_launch_wiener_stats(w, pass, e->stream)) return fail(-2, "Wiener statistics launch failed"); }
+        { TimerScope ts(e, "wiener_cov"); if (srt_launch_wiener_finalize(w, pass, e->stream)) return fail(-2, "Wiener finalize launch failed"); }
+    }
+    { TimerScope ts(e, "wiener_filter"); if (srt_launch_wiener_filter(w, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
+    e->wiener_last = iters;
+    const size_t len = srtIstftLength(rows);
+    for (int j = 0; j < S; ++j) {
+        const int rc = istft_one(e, e->wspec + (size_t)j * w.out_stem, rows, nullptr, e->cfg.oob_weight[j], d_out + (size_t)j * 2 * len, "istft");
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, int iterations, float* d_out)
+{
+    if (!e || !d_spec || !d_masks || !d_out) return fail(-1, "srtIstftWiener: null argument");
+    DeviceScope ds(e->device);
+    if (iterations < 1 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtIstftWiener: iterations must be 1..3");
+    if (rows < 1 || (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstftWiener: need 1 <= rows <= max_tiles * T");
+    const int rc = ensure_wiener_ws(e);
+    if (rc) return rc;
+    return wiener_issue(e, d_spec, rows, d_masks, iterations, d_out);
+}
+
+int srtSetWiener(srt_engine* e, int iterations)
+{
+    if (!e) return fail(-1, "srtSetWiener: null engine");
+    if (iterations < 0 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtSetWiener: iterations must be 0 (off) or 1..3");
+    if (iterations && e->cfg.ratio_mask) return fail(-1, "srtSetWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
+    DeviceScope ds(e->device);
+    if (iterations) { const int rc = ensure_wiener_ws(e); if (rc) return rc; }
+    e->wiener = iterations;
+    return 0;
+}
+
+int srt_engine_wiener(const srt_engine* e) { return e->wiener; }
+
 static int separate_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
 {
     const int T = e->cfg.T;
@@ -810,10 +891,11 @@ static int separate_issue(srt_engine* e, const float* d_L, const float* d_R, siz
     // fp16 mode: the masks between the head and the inverse transform - the engine's own buffer, never seen by a caller - are halves where both kernels take them
     // (srt_head_rows_kernel<.., true> / srt_istft_ola3_kernel<.., true>: F <= 1024, no ratio mask, head launches of >= 1024 workgroups; SPLEETERRT_M16=0: floats, for A/B runs)
     const char* m16v = getenv("SPLEETERRT_M16");
-    e->masks16_req = e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && e->cfg.F <= 1024 && !(m16v && m16v[0] == '0');
+    e->masks16_req = e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && !e->wiener && e->cfg.F <= 1024 && !(m16v && m16v[0] == '0');
     rc = forward_range(e, e->mag, (int)ntiles, e->masks, 0, e->cfg.n_stems);
     e->masks16_req = false;
     if (rc) return rc;
+    if (e->wiener) return wiener_issue(e, (const float*)e->spec, rows, e->masks, e->wiener, d_out);     // (fp32 masks: masks16_req is off while the filter is on)
     // ratio_mask: normalised across the stems inside the inverse kernel's prologue (srt_ratio_of, srt_dsp.hip) - e->masks keeps the raw sigmoid masks
     return istft_issue(e, (const float*)e->spec, rows, e->masks, d_out, e->cfg.ratio_mask != 0, e->last_masks16);
 }
@@ -832,9 +914,10 @@ int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, s
     if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
     if (valid && cap == hipStreamCaptureStatusNone) ensure_ws(e, (size_t)e->cfg.n_stems * ntiles);
     GraphKey k; memset(&k, 0, sizeof k);
-    k.kind = 2; k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.layout = graph_layout_switches();
+    k.kind = 2; k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.layout = graph_layout_switches(); k.wiener = e->wiener;
     const int rc = run_graphed(e, k, valid, [&]() { return separate_issue(e, d_L, d_R, n, frames, rows, d_out); });
     if (!rc) e->last_ntiles = (int)ntiles;
+    if (!rc && e->wiener) e->wiener_last = e->wiener;                       // (a replay runs no host code)
     return rc;
 }
 
@@ -915,6 +998,7 @@ static int cli_check(srt_engine* e, int stems)
     if (stems != 2 && stems != 3) return fail(-1, "srtSeparateCli: stems must be 2 or 3");
     if (e->cfg.n_stems < 2) return fail(-1, "srtSeparateCli: the engine needs sub-networks 0 (drum) and 1 (vocal)");
     if (e->cfg.ratio_mask) return fail(-1, "srtSeparateCli: ratio_mask does not apply to the CLI flows (the sub-networks see different inputs)");
+    if (e->wiener) return fail(-1, "srtSeparateCli: the Wiener filter does not apply to the CLI flows (the sub-networks see different inputs, and its statistics span the whole signal)");
     return 0;
 }
 
@@ -1024,6 +1108,7 @@ static int host_stream(srt_engine* e, const float* h_L, const float* h_R, size_t
 {
     if (!e || !h_L || !h_R || !h_out) return fail(-1, "srtSeparateHostStream: null argument");
     if (rows < 1 || frames > rows) return fail(-1, "srtSeparateHostStream: need 1 <= frames <= rows");
+    if (e->wiener) return fail(-1, "srtSeparateHostStream: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)");
     DeviceScope ds(e->device);
     const int S = cli_stems ? cli_stems : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;
     const size_t chunk_rows = (size_t)e->cfg.max_tiles * T, tail = SRT_FFT - SRT_HOP;
@@ -1116,6 +1201,18 @@ int srtCopyTensor(srt_engine* e, const char* name, int stem, int tile, float* h_
     if (!e || !name || !h_dst) return fail(-1, "srtCopyTensor: null argument");
     DeviceScope ds(e->device);
     if (!name[0]) return fail(-1, "srtCopyTensor: empty tensor name");
+    if (!strcmp(name, "wiener_cov")) {                                       // R_j of iteration `tile` [F][4], its weight sums [F], a [1]
+        const int S = e->cfg.n_stems, F = e->cfg.F, it = tile;
+        if (!e->wtab || stem < 0 || stem >= S || it < 1 || it > e->wiener_last) return fail(-1, "srtCopyTensor: wiener_cov needs a stem and 1 <= iteration <= the iterations of the last filtered call");
+        if ((size_t)5 * F + 1 > max_floats) return fail(-1, "srtCopyTensor: destination too small");
+        const size_t o = (size_t)(it - 1) * S * F + (size_t)stem * F;
+        const float* wsum = e->wtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipMemcpy(h_dst, e->wtab + o * 4, (size_t)F * 4 * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_dst + 4 * F, wsum + o, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_dst + 5 * F, wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F, sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
     if (stem < 0 || stem >= e->cfg.n_stems || tile < 0 || tile >= e->last_ntiles) return fail(-1, "srtCopyTensor: stem / tile outside the last forward batch");
     const int idx = name[strlen(name) - 1] - '1';
     const float* base = nullptr; size_t per = 0; bool derived = false;

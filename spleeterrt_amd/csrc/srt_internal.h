@@ -188,6 +188,30 @@ int srt_launch_carry(float* out, size_t plane_len, int nplanes, size_t tail, flo
 // cross-stem ratio mask, in place on [nstems][count]: m_s <- (m_s^2 + eps/S) / (sum_j m_j^2 + eps)
 int srt_launch_ratio_mask(float* masks, int nstems, size_t count, hipStream_t s);
 
+// multichannel Wiener filter (srt_wiener.hip; norbert.wiener(v, x, n) as official Spleeter's --mwf runs it), in spectrum units: every x of the
+// specification is 4096 * spec, which moves the scale into the epsilon terms (see the kernel file's header).
+#define SRT_WIENER_MAX_ITERS 3
+#define SRT_WIENER_MAX_CHUNKS 256    // row chunks of the statistics pass: partial sums per chunk, summed in chunk order by the finalize kernel
+#define SRT_WIENER_BINBLK 9          // 256-bin blocks that cover bins 0..2048 (the first pass also takes max |x| over all of them)
+struct SrtWienerParams {
+    const float2* spec; size_t spec_ch_stride;   // [2][rows][SRT_SPEC_LD]
+    int rows;
+    const float* masks;                          // fp32 [nstems][ntiles][2][T][F], ntiles = ceil(rows / T)
+    int nstems, ntiles, T, F;
+    int nchunks, rpc;                            // row chunks of the statistics pass and rows per chunk
+    float* slab;                                 // [SRT_WIENER_MAX_CHUNKS][nstems][4][F] per-chunk partial sums
+    float* slab_max;                             // [SRT_WIENER_MAX_CHUNKS][SRT_WIENER_BINBLK] per-block max |spec|
+    float* rtab;                                 // [SRT_WIENER_MAX_ITERS][nstems][F][4]: R_j (R00, R11, Re R01, Im R01)
+    float* wsum;                                 // [SRT_WIENER_MAX_ITERS][nstems][F]: sum over rows of v_j, spectrum units
+    float* scal;                                 // [0]: norbert's a = max(1, max |x| / 10)
+    float2* out; size_t out_stem;                // filter: stem j's spectrum at out + j * out_stem, [2][rows][SRT_SPEC_LD]
+};
+int srt_launch_wiener_stats(const SrtWienerParams& p, int pass, hipStream_t s);      // pass 1..n: statistics of the estimates after pass - 1 iterations
+int srt_launch_wiener_finalize(const SrtWienerParams& p, int pass, hipStream_t s);   // R tables of that pass (and a, pass 1)
+int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s);    // W_j x after `iters` iterations for every stem; bins >= F copied
+struct srt_engine;
+int srt_engine_wiener(const srt_engine* e);                                             // iterations switched on (srtSetWiener), 0: off
+
 // streaming (srt_dsp.hip kernels, srt_stream.hip host logic): one hop = 1 forward + 4 masked inverse FFTs + 50 % OLA
 struct SrtStreamHop {
     const float* ring;        // [2][4096] device copy of the input ring buffer

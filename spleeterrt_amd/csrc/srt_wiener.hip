@@ -1,0 +1,213 @@
+// srt_wiener.hip — multichannel Wiener filter over a whole call (srtSetWiener / srtIstftWiener, include/spleeterrt_amd.h).
+//
+// What official Spleeter runs for `spleeter separate --mwf`: norbert.wiener(v, x, iterations = n, use_softmask = True, eps = 2^-23), with
+//   x_c = 4096 spec_c, v_{j,c} = m_{j,c} |x_c| (bins < F), soft-mask start y_j = v_j / (eps + sum_i v_i) x, a = max(1, max |x| / 10), then n EM
+//   iterations on y^ = y / a: v_j = (|y^_L|^2 + |y^_R|^2) / 2, R_j = sum_t y^ y^H / (eps + sum_t v_j), C = sum_j v_j R_j + sqrt(eps) I,
+//   y^_j <- v_j R_j C^-1 x^; the stem's spectrum is a y^_j / 4096.
+// Everything here runs in spectrum units (s = x / 4096).  The algebra is scale free except for the epsilon terms, which take the scale:
+//   soft mask: v / (eps / 4096 + sum v) s;   R_j = sum_t y y^H / (eps al^2 + sum_t v_j);   C = sum_j v_j R_j + sqrt(eps) al^2 I,   al = a / 4096,
+// and W_j s is already the output spectrum (the a of the normalisation cancels against the final a y^).
+//
+// Kernels (no atomics anywhere: every sum has one fixed order, so a call is bit-reproducible run to run and under graph replay):
+//   srt_wiener_stats_kernel     pass p of n: grid (256-bin blocks, row chunks); a thread owns one bin and walks the chunk's rows, re-evaluating the
+//                               chain (soft mask + p - 1 iterations) from the spectrum, the masks and the earlier R tables, and keeps the four sums
+//                               |y_L|^2, |y_R|^2, Re / Im y_L y_R* per stem in registers; one store per (chunk, stem, sum, bin) into the slab.
+//                               Pass 1 also takes max |s| over bins 0..2048 (per-block maximum: exact, order free).
+//   srt_wiener_finalize_kernel  one thread per (stem, bin): adds the chunks' partials in chunk order, divides by the regularised weight sum, writes R.
+//                               Pass 1 reduces the block maxima into a first.
+//   srt_wiener_filter_kernel    the chain through all n iterations per (row, bin), writing every stem's filtered spectrum (bins >= F: the input
+//                               spectrum, to which the inverse transform applies oob_weight as for masks).
+// The 2 x 2 inverse is the closed form with det C = c00 c11 - |c01|^2 (real); C >= sqrt(eps) al^2 I keeps it away from zero, as in norbert.
+#include "srt_internal.h"
+#include <math.h>
+
+#define W_EPS      1.1920928955078125e-07f        // 2^-23: fp32 machine epsilon, norbert's default for complex64
+#define W_SQRT_EPS 3.4526698300124393e-04f        // 2^-11.5
+#define W_EPS_SOFT 2.9103830456733704e-11f        // 2^-35 = eps / 4096: the soft mask's epsilon in spectrum units
+#define W_FILTER_ROWS 16                          // rows per workgroup of the filter
+
+// soft-mask start: y_j = v_j / (eps + sum_i v_i) s per channel; m points at stem 0's mask value of this (row, bin), stems sstride apart, R channel + tf
+__device__ __forceinline__ void w_start(float2 (&yl)[SRT_MAX_STEMS], float2 (&yr)[SRT_MAX_STEMS], float2 sL, float2 sR,
+                                        const float* __restrict__ m, size_t sstride, size_t tf, int S)
+{
+    const float aL = hypotf(sL.x, sL.y), aR = hypotf(sR.x, sR.y);
+    float vl[SRT_MAX_STEMS], vr[SRT_MAX_STEMS], suml = 0.0f, sumr = 0.0f;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        vl[j] = 0.0f; vr[j] = 0.0f;
+        if (j < S) { vl[j] = m[j * sstride] * aL; vr[j] = m[j * sstride + tf] * aR; suml += vl[j]; sumr += vr[j]; }
+    }
+    const float il = 1.0f / (W_EPS_SOFT + suml), ir = 1.0f / (W_EPS_SOFT + sumr);
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        const float gl = vl[j] * il, gr = vr[j] * ir;
+        yl[j] = make_float2(gl * sL.x, gl * sL.y);
+        yr[j] = make_float2(gr * sR.x, gr * sR.y);
+    }
+}
+
+// one EM iteration at (row, bin): R points at stem 0's entry of this bin in the iteration's table, stems F apart; delta = sqrt(eps) al^2
+__device__ __forceinline__ void w_iter(float2 (&yl)[SRT_MAX_STEMS], float2 (&yr)[SRT_MAX_STEMS], float2 sL, float2 sR,
+                                       const float4* __restrict__ R, int F, float delta, int S)
+{
+    float v[SRT_MAX_STEMS];
+    float c00 = delta, c11 = delta, c01r = 0.0f, c01i = 0.0f;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        v[j] = 0.5f * (yl[j].x * yl[j].x + yl[j].y * yl[j].y + yr[j].x * yr[j].x + yr[j].y * yr[j].y);
+        if (j < S) {
+            const float4 r = R[(size_t)j * F];
+            c00 += v[j] * r.x; c11 += v[j] * r.y; c01r += v[j] * r.z; c01i += v[j] * r.w;
+        }
+    }
+    const float id = 1.0f / (c00 * c11 - (c01r * c01r + c01i * c01i));
+    // z = C^-1 s with C^-1 = [c11, -c01; -conj(c01), c00] / det
+    const float2 zL = make_float2((c11 * sL.x - (c01r * sR.x - c01i * sR.y)) * id, (c11 * sL.y - (c01r * sR.y + c01i * sR.x)) * id);
+    const float2 zR = make_float2((c00 * sR.x - (c01r * sL.x + c01i * sL.y)) * id, (c00 * sR.y - (c01r * sL.y - c01i * sL.x)) * id);
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        if (j < S) {
+            const float4 r = R[(size_t)j * F];                 // y_j = v_j R_j z: R = [R00, R01; conj(R01), R11]
+            const float2 a = make_float2(r.x * zL.x + (r.z * zR.x - r.w * zR.y), r.x * zL.y + (r.z * zR.y + r.w * zR.x));
+            const float2 b = make_float2((r.z * zL.x + r.w * zL.y) + r.y * zR.x, (r.z * zL.y - r.w * zL.x) + r.y * zR.y);
+            yl[j] = make_float2(v[j] * a.x, v[j] * a.y);
+            yr[j] = make_float2(v[j] * b.x, v[j] * b.y);
+        }
+    }
+}
+
+__device__ __forceinline__ float w_block_max(float x, float* red)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
+    __syncthreads();
+    x = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    return x;
+}
+
+__global__ void __launch_bounds__(256) srt_wiener_stats_kernel(const SrtWienerParams p, int pass)
+{
+    __shared__ float red[4];
+    const int k = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, S = p.nstems;
+    const int r0 = c * p.rpc, r1 = min(r0 + p.rpc, p.rows);
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const float al = (pass > 1 ? p.scal[0] : 1.0f) * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F, anyb = k < SRT_HALF;
+    const float2* sLp = p.spec + (anyb ? k : 0);
+    const float2* sRp = sLp + p.spec_ch_stride;
+    float acc[SRT_MAX_STEMS][4];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
+    float mx = 0.0f;
+    if (anyb) {
+        for (int t = r0; t < r1; ++t) {
+            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD];
+            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y)));
+            if (!inb) continue;
+            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;
+            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+            w_start(yl, yr, sL, sR, m, sstride, tf, S);
+            for (int i = 0; i < pass - 1; ++i)
+                w_iter(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y;
+                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y;
+                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      // y_L conj(y_R)
+                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y;
+            }
+        }
+    }
+    if (inb) {
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k] = acc[j][q];
+    }
+    if (pass == 1) {                                             // (block-uniform branch: every thread reaches the barriers)
+        mx = w_block_max(mx, red);
+        if (threadIdx.x == 0) p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] = mx;
+    }
+}
+
+__global__ void __launch_bounds__(256) srt_wiener_finalize_kernel(const SrtWienerParams p, int pass)
+{
+    __shared__ float red[4];
+    const int S = p.nstems;
+    float a;
+    if (pass == 1) {                                             // every block reduces the same maxima: the same a everywhere
+        float mx = 0.0f;
+        for (int i = threadIdx.x; i < p.nchunks * SRT_WIENER_BINBLK; i += 256) mx = fmaxf(mx, p.slab_max[i]);
+        mx = w_block_max(mx, red);
+        a = fmaxf(1.0f, mx * 4096.0f / 10.0f);
+        if (blockIdx.x == 0 && threadIdx.x == 0) p.scal[0] = a;
+    } else a = p.scal[0];
+    const int idx = blockIdx.x * 256 + threadIdx.x;              // j * F + k
+    if (idx >= S * p.F) return;
+    const int j = idx / p.F, k = idx - j * p.F;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    for (int c = 0; c < p.nchunks; ++c) {                        // chunk order: the same sums every call
+        const float* q = p.slab + (((size_t)c * S + j) * 4) * p.F + k;
+        s0 += q[0]; s1 += q[p.F]; s2 += q[2 * (size_t)p.F]; s3 += q[3 * (size_t)p.F];
+    }
+    const float al = a * (1.0f / 4096.0f);
+    const float w = 0.5f * (s0 + s1);
+    const float inv = 1.0f / (W_EPS * al * al + w);
+    const size_t o = (size_t)(pass - 1) * S * p.F + idx;
+    reinterpret_cast<float4*>(p.rtab)[o] = make_float4(s0 * inv, s1 * inv, s2 * inv, s3 * inv);
+    p.wsum[o] = w;
+}
+
+__global__ void __launch_bounds__(256) srt_wiener_filter_kernel(const SrtWienerParams p, int iters)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x, S = p.nstems;
+    if (k >= SRT_HALF) return;
+    const int r0 = blockIdx.y * W_FILTER_ROWS, r1 = min(r0 + W_FILTER_ROWS, p.rows);
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf, och = p.out_stem / 2;
+    const float al = p.scal[0] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F;
+    for (int t = r0; t < r1; ++t) {
+        const size_t o = (size_t)t * SRT_SPEC_LD + k;
+        const float2 sL = p.spec[o], sR = p.spec[p.spec_ch_stride + o];
+        if (!inb) {                                              // bins >= F: the input spectrum (oob_weight is applied by the inverse transform)
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j)
+                if (j < S) { p.out[j * p.out_stem + o] = sL; p.out[j * p.out_stem + och + o] = sR; }
+            continue;
+        }
+        const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;
+        float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+        w_start(yl, yr, sL, sR, m, sstride, tf, S);
+        for (int i = 0; i < iters; ++i)
+            w_iter(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S) { p.out[j * p.out_stem + o] = yl[j]; p.out[j * p.out_stem + och + o] = yr[j]; }
+    }
+}
+
+int srt_launch_wiener_stats(const SrtWienerParams& p, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || p.nchunks < 1 || p.nchunks > SRT_WIENER_MAX_CHUNKS || p.nstems < 1 || p.nstems > SRT_MAX_STEMS ||
+        p.F < 1 || p.F > SRT_HALF - 1 || (size_t)p.nchunks * p.rpc < (size_t)p.rows || (size_t)p.ntiles * p.T < (size_t)p.rows) return -1;
+    const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
+    SRT_LAUNCH(srt_wiener_stats_kernel, dim3(bx, p.nchunks), dim3(256), 0, s, p, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_finalize(const SrtWienerParams& p, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS) return -1;
+    SRT_LAUNCH(srt_wiener_finalize_kernel, dim3((p.nstems * p.F + 255) / 256), dim3(256), 0, s, p, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s)
+{
+    if (iters < 1 || iters > SRT_WIENER_MAX_ITERS || p.rows < 1 || (size_t)p.ntiles * p.T < (size_t)p.rows || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD) return -1;
+    SRT_LAUNCH(srt_wiener_filter_kernel, dim3(SRT_WIENER_BINBLK, (p.rows + W_FILTER_ROWS - 1) / W_FILTER_ROWS), dim3(256), 0, s, p, iters);
+    return srt_launch_status();
+}

@@ -61,12 +61,20 @@ def rank_span(n, T, rank=0, world=1):
     return Span(t0, t1, s0, ns, max(0, min(frames - row0, row1 - row0)), max(0, row1 - row0), s0)
 
 
+def _refuse_wiener(engine, world):
+    """The Wiener filter's statistics span the whole signal: ranks would each filter their range with its own covariance."""
+    if world > 1 and getattr(engine, "wiener", 0):
+        raise ValueError("the Wiener filter's statistics span the whole signal: a rank's share (world = %d) would get its own covariance; "
+                         "set_wiener(0) or run one rank" % world)
+
+
 def separate_host_range(engine, L, R, rank=0, world=1, out=None, pinned=False):
     """This rank's share of a HOST-resident stream (numpy / pinned arrays of the whole stream, or anything sliceable):
     one srtSeparateHostStream call over its tile range — chunks of engine.max_tiles tiles, H2D / compute / D2H overlapped
     on three HIP streams, chunk overlaps carried on the device.  Returns (span, stems [S,2,rows*1024+3072]) or
     (span, None) when the rank has no tiles.  The reference's counterpart is one tile-range worker of processMT
     (Executable/main.c:544-673); there is no exchange with other ranks."""
+    _refuse_wiener(engine, world)
     sp = rank_span(len(L), engine.T, rank, world)
     if sp.rows == 0:
         return sp, None
@@ -82,6 +90,7 @@ def total_output_length(n):
 def separate_stream(engine, L, R, rank=0, world=1):
     """Run this rank's chunks.  `engine` needs .T, .max_tiles and .separate_ex(L, R, frames, rows) -> [S,2,rows*1024+3072]
     (spleeterrt_amd.Engine on a GPU; tests substitute a CPU stand-in).  Returns [(out_offset, array)]."""
+    _refuse_wiener(engine, world)
     parts = []
     for c in plan(len(L), engine.T, engine.max_tiles, rank, world):
         o = engine.separate_ex(L[c.sample0:c.sample0 + c.nsamples], R[c.sample0:c.sample0 + c.nsamples], c.frames, c.rows)
