@@ -99,6 +99,19 @@ SRT_API int  srtSeparate(srt_engine *e, const float *d_L, const float *d_R, size
 SRT_API int  srtStftEx(srt_engine *e, const float *d_L, const float *d_R, size_t n, size_t frames, size_t rows, float *d_spec, float *d_mag);
 SRT_API int  srtSeparateEx(srt_engine *e, const float *d_L, const float *d_R, size_t n, size_t frames, size_t rows, float *d_out);
 
+/* Many independent tracks in one packed batch.  Track k of a batch occupies the packed tiles [tile0[k], tile0[k] + ceil(srtStftRows(n[k]) / T)).
+ * srtBatchPlan is pure host arithmetic (no device, like srtRankSpan): tile0 may be NULL; *total_tiles = the sum.  -1 for ntracks < 1, T < 1 or any n[k] < 4096.
+ * srtSeparateBatch: K whole tracks (srtSeparate geometry each) in one launch sequence - one batched STFT, one srtForward over the packed tiles, one batched
+ * inverse transform - with each track's stems equal to what srtSeparate gives for it alone (bit for bit with batch_invariant; ratio_mask and the fp16
+ * mode's half masks as in srtSeparate).  d_L, d_R, n, d_out: host arrays of ntracks entries (device pointers); d_out[k]: [n_stems][2][srtIstftLength(srtStftRows(n[k]))].
+ * The track table is uploaded in stream order into engine memory, so the host arrays may be reused once the call returns; the call does not wait for the GPU
+ * (it only waits for the table upload it issued four calls earlier).  It always launches eagerly, also in graph mode, and is refused inside a stream capture.
+ * -1, with nothing launched, for ntracks < 1, a null array or entry, any n[k] < 4096, more than max_tiles packed tiles, or the Wiener filter on (its
+ * statistics would have to be per track).  srtCopyTensor afterwards addresses the packed tiles: tile = tile0[k] + the tile within track k. */
+SRT_API int  srtBatchPlan(const size_t *n, int ntracks, int T, size_t *tile0, size_t *total_tiles);
+SRT_API int  srtSeparateBatch(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
+                              const size_t *n, float *const *d_out);
+
 /* A long HOST-resident stream through one GPU: cut into chunks of max_tiles tiles, upload / compute / download overlapped on
  * three HIP streams with double buffers, chunk overlaps (3072 samples) added on the device.  Geometry as srtSeparateEx.
  * h_out: [n_stems][2][srtIstftLength(rows)].  Synchronous; replaces main()'s whole-file stft -> processMT -> istft
@@ -206,7 +219,8 @@ SRT_API int  srtResampleHost(srt_resampler *r, const float *h_L, const float *h_
 
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";
-                                                                                                                   "wiener_cov": tile = iteration (see srtIstftWiener) */
+                                                                                                                   "wiener_cov": tile = iteration (see srtIstftWiener);
+                                                                                                                   after srtSeparateBatch: packed tile indices */
 SRT_API int  srtSetTiming(srt_engine *e, int enable);                    /* record HIP events around every launch of the next calls */
 SRT_API int  srtGetTiming(srt_engine *e, char *names, size_t names_bytes, float *ms, int max_entries); /* returns count; syncs the stream */
 /* which kernel ran each of those launches (same order), ';'-separated, named as rocprofv3 names kernels ("srt_dec_wino<4, 16, 1, 0>"):

@@ -68,6 +68,8 @@ def load_library():
     L.srtStftEx.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_size_t, C.c_size_t, f32p, f32p]
     L.srtSeparateEx.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_size_t, C.c_size_t, f32p]
     L.srtCopyTensor.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, vp, C.c_size_t]
+    L.srtBatchPlan.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.srtSeparateBatch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
     L.srtSetGraphMode.argtypes = [vp, C.c_int]
     L.srtPrepareForward.argtypes = [vp, f32p, C.c_int, f32p]
     L.srtReleaseStaging.argtypes = [vp]
@@ -244,6 +246,27 @@ class Engine:
             out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
         self._chk(self.L.srtSeparate(self.h, _ptr(L), _ptr(R), n, _ptr(out)))
         return out
+
+    def separate_batch(self, tracks, outs=None):
+        """many independent tracks: [(L, R)] CUDA float32 tensors -> [stems [S,2,rows_k*1024+3072]], each equal to separate(L, R) of that track.
+        The list is cut in order into calls of at most max_tiles packed tiles (stream.pack_tracks); one srtSeparateBatch per call."""
+        from . import stream
+        t = self.torch
+        ns = [L.numel() for L, _ in tracks]
+        for L, R in tracks:
+            assert L.is_cuda and R.is_cuda and L.dtype == t.float32 and R.dtype == t.float32 and R.numel() == L.numel()
+        if outs is None:
+            outs = [t.empty((self.S, 2, self.L.srtIstftLength(self.L.srtStftRows(n))), device=self.device, dtype=t.float32) for n in ns]
+        assert len(outs) == len(tracks)
+        for o, n in zip(outs, ns):
+            assert o.is_cuda and o.is_contiguous() and o.numel() >= self.S * 2 * self.L.srtIstftLength(self.L.srtStftRows(n))
+        src = [(L.contiguous(), R.contiguous()) for L, R in tracks]      # (kept alive until the calls are issued; the stream orders any reuse)
+        for g in stream.pack_tracks(ns, self.T, self.max_tiles):
+            k = len(g.tracks)
+            P = C.c_void_p * k
+            self._chk(self.L.srtSeparateBatch(self.h, k, P(*[src[i][0].data_ptr() for i in g.tracks]), P(*[src[i][1].data_ptr() for i in g.tracks]),
+                                              (C.c_size_t * k)(*[ns[i] for i in g.tracks]), P(*[outs[i].data_ptr() for i in g.tracks])))
+        return outs
 
     def separate_cli(self, L, R, stems):
         """the offline CLI's flow (main.c:776-798 / 845-928): -> [stems,2,len] = (Vocal, Accompaniment) or (Drum, Vocal, Accompaniment)"""

@@ -211,13 +211,16 @@ __device__ __forceinline__ float srt_ratio_of(float own, const float* __restrict
 
 #pragma clang fp contract(fast)
 
-template <bool RATIO = false>
-__global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftParams p, int G)
+// What a workgroup of the inverse kernels reads and writes of ONE signal: the whole call's signal (srt_istft_ola_kernel / srt_istft_ola3_kernel),
+// or one track of a packed batch (srt_istft_batch_kernel: spectrum and masks offset to the track's first packed row / tile, its own frames and output).
+// Everything else (stem count and stride, T, F, oob weights, tables) comes from the launch's SrtIstftParams.
+struct IstftView { const float2* spec; const float* masks; float* out; size_t out_len; int frames; };
+__device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { IstftView v = { p.spec, p.masks, p.out, p.out_len, p.frames }; return v; }
+
+#define ISTFT_OLA_LDS_F2 (2 * FFT_SMEM_F2 + FFT_TWB_F2)   // two staging / exchange buffers + the pass-2 twiddles (one LDS object)
+template <bool RATIO>
+__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem)
 {
-    // 1-D launch in XCD order, stem fastest: the nstems workgroups that walk the SAME run of frames sit next to each other on
-    // one XCD, so the spectrum rows the first of them pulls from HBM are L2 hits for the others (each stem re-read them before).
-    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
-    __shared__ cf s_mem[2 * FFT_SMEM_F2 + FFT_TWB_F2];   // two staging / exchange buffers + the pass-2 twiddles (one LDS object)
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
     cf* sy = s_mem + FFT_SMEM_F2;                        // this frame's exchange 1; the roles swap every frame
     cf* s_twb = s_mem + 2 * FFT_SMEM_F2;
@@ -225,12 +228,12 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
     cf twa[15];
     fft_load_twiddles_pp(twa, s_twb, p.tab.twiddle, tid);
     const size_t tf = (size_t)p.T * p.F;
-    const int nseg = p.frames + 3;
+    const int nseg = w.frames + 3;
     const int s0 = run * G, s1 = min(s0 + G, nseg);
     const float oob = p.oob[stem];                                           // bins >= F: "unaffectedWeight" (main.c:486-493)
-    const cf* spec = reinterpret_cast<const cf*>(p.spec);
-    float* oL = p.out + (size_t)(stem * 2 + 0) * p.out_len;
-    float* oR = p.out + (size_t)(stem * 2 + 1) * p.out_len;
+    const cf* spec = reinterpret_cast<const cf*>(w.spec);
+    float* oL = w.out + (size_t)(stem * 2 + 0) * w.out_len;
+    float* oR = w.out + (size_t)(stem * 2 + 1) * w.out_len;
 
     cf acc[4][4];                                       // [segment slot][j] = (R, L) pairs: one packed fma per output sample pair
 #pragma unroll
@@ -244,12 +247,12 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
     float gl[9], gr[9];
     // fetch only ISSUES loads (no value depends on them until the next iteration): without masks the two mask rows
     // are read from a harmless table instead of branching on the pointer
-    const bool has_mask = p.masks != nullptr;
-    auto fetch = [&](int f) {                                               // 0 <= f < p.frames
+    const bool has_mask = w.masks != nullptr;
+    auto fetch = [&](int f) {                                               // 0 <= f < w.frames
         const int tile = f / p.T, t = f % p.T;
         const cf* specL = spec + (size_t)f * SRT_SPEC_LD;
         const cf* specR = specL + p.spec_ch_stride;
-        const float* mL = has_mask ? p.masks + ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F : p.tab.postWin;
+        const float* mL = has_mask ? w.masks + ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F : p.tab.postWin;
         const float* mR = has_mask ? mL + tf : p.tab.postWin;
 #pragma unroll
         for (int j = 0; j < 9; ++j) {
@@ -262,7 +265,7 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
 #pragma unroll
     for (int k2 = 0; k2 < 16; ++k2) pw[k2] = p.tab.postWin[tid + 256 * k2];
     const int f0 = max(s0 - 3, 0);                      // frames before 0 do not exist: the window simply starts empty
-    if (f0 < p.frames) fetch(f0);
+    if (f0 < w.frames) fetch(f0);
     // Segment f is complete once frame f has been added, but it is WRITTEN in iteration f + 1, right before that iteration requests the rows of
     // frame f + 2: vmcnt counts loads and stores in one queue, so the wait for a frame's rows also waits for every store issued before them -
     // stores issued just ahead of the wait (the end of the previous iteration, where this code stood in rounds 1-2) cost their full
@@ -278,13 +281,13 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
         }
     };
     for (int f = f0; f < s1; ++f) {
-        if (f < p.frames) {                             // workgroup-uniform; false only for the last three segments of the stream
+        if (f < w.frames) {                             // workgroup-uniform; false only for the last three segments of the stream
             // staging into sx: its last readers (exchange 1 of the previous frame, when it was `sy`) all passed that frame's
             // second barrier; the first barrier below also orders the twiddle table written before the loop
             if constexpr (RATIO) {
                 if (has_mask && p.ratio) {               // normalise this frame's mask values across the stems (they arrived with the spectrum rows)
                     const int tile = f / p.T, t = f % p.T;
-                    const float* r0 = p.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
+                    const float* r0 = w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) {
                         const int km = min(min(tid + 256 * j, 2048), p.F - 1);
@@ -314,7 +317,7 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
             for (int n2 = 0; n2 < 16; ++n2) v[n2] = sx[tid + 256 * n2];
             __builtin_amdgcn_s_waitcnt(0x0F70);          // all of this frame's rows have arrived (also the ones only lane 0 uses): nothing below waits on the stores
             if (f > f0) emit_and_slide(f - 1);
-            fetch(min(f + 1, p.frames - 1));            // the staging registers are free again: next frame's rows fly under this FFT
+            fetch(min(f + 1, w.frames - 1));            // the staging registers are free again: next frame's rows fly under this FFT
             // exchange 1 in sy (free: its previous contents, the previous frame's exchange 2, were read before the barrier above),
             // exchange 2 back in sx (every thread has read its staged values before the transform's first barrier)
             fft4096_pp(v, sy, sx, twa, s_twb, tid);
@@ -326,6 +329,16 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
         } else if (f > f0) emit_and_slide(f - 1);
     }
     if (s1 > f0) emit_and_slide(s1 - 1);                // the last segment of the run
+}
+
+template <bool RATIO = false>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftParams p, int G)
+{
+    // 1-D launch in XCD order, stem fastest: the nstems workgroups that walk the SAME run of frames sit next to each other on
+    // one XCD, so the spectrum rows the first of them pulls from HBM are L2 hits for the others (each stem re-read them before).
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<RATIO>(p, istft_view(p), stem, run, G, s_mem);
 }
 
 
@@ -380,13 +393,18 @@ __device__ __forceinline__ void fft4096_1b(cf (&v)[16], cf* x, const cf w1, cons
     fft16(v);
 }
 
-__global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p, int fpb)
+// The signal a workgroup of the forward kernels transforms: the whole call's (srt_stft_kernel), or one track of a packed batch (srt_stft_batch_kernel:
+// its own PCM and frame counts, spectrum and magnitudes offset to its first packed row / tile).
+struct StftView { const float* L; const float* R; size_t nsamples; int frames_computed, rows_total; float2* spec; float* mag; };
+__device__ __forceinline__ StftView stft_view(const SrtStftParams& p) { StftView v = { p.L, p.R, p.nsamples, p.frames_computed, p.rows_total, p.spec, p.mag }; return v; }
+
+// frames [blk * fpb, (blk + 1) * fpb) of the view (rows past rows_total are not this call's)
+__device__ __forceinline__ void stft_run(const SrtStftParams& p, const StftView& w, int blk, int fpb, cf* s_mem)
 {
-    __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
     cf* sx = s_mem;
     cf* mir = s_mem + FFT_SMEM_F2;
     cf* s_twb = mir + FFT_MIR_F2;
-    const int tid = threadIdx.x, blk = blockIdx.x;
+    const int tid = threadIdx.x;
     const cf w1 = reinterpret_cast<const cf*>(p.tab.twiddle)[tid];
     if (tid < FFT_TWB_F2) s_twb[tid] = reinterpret_cast<const cf*>(p.tab.twiddle)[(16 * (tid & 15) * (tid / 16 + 1)) & 4095];
     float nxtL[16], nxtR[16];
@@ -398,8 +416,8 @@ __global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p,
 #pragma unroll
         for (int n2 = 0; n2 < 16; ++n2) {
             const int n = tid + 256 * n2;
-            const size_t q = pos + n < p.nsamples ? pos + n : 0;
-            nxtL[n2] = p.L[q]; nxtR[n2] = p.R[q];
+            const size_t q = pos + n < w.nsamples ? pos + n : 0;
+            nxtL[n2] = w.L[q]; nxtR[n2] = w.R[q];
         }
     };
     // Consecutive frames share three of their four hops, and thread tid's samples tid + 256 n2 of frame f + 1 are its samples n2 + 4 of frame f: the staging
@@ -412,30 +430,30 @@ __global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p,
 #pragma unroll
         for (int n2 = 12; n2 < 16; ++n2) {
             const int n = tid + 256 * n2;
-            const size_t q = pos + n < p.nsamples ? pos + n : 0;
-            nxtL[n2] = p.L[q]; nxtR[n2] = p.R[q];
+            const size_t q = pos + n < w.nsamples ? pos + n : 0;
+            nxtL[n2] = w.L[q]; nxtR[n2] = w.R[q];
         }
     };
-    const int flast = max(p.frames_computed, 1) - 1;
+    const int flast = max(w.frames_computed, 1) - 1;
     fetch(min((int)(blk * fpb), flast));
     __syncthreads();                                     // the pass-2 twiddles are in LDS
     for (int fi = 0; fi < fpb; ++fi) {
         const int f = blk * fpb + fi;
-        if (f >= p.rows_total) break;
+        if (f >= w.rows_total) break;
         const int tile = f / p.T, t = f % p.T;
-        float* magL = p.mag ? p.mag + ((size_t)(tile * 2 + 0) * p.T + t) * p.F : nullptr;
-        float* magR = p.mag ? p.mag + ((size_t)(tile * 2 + 1) * p.T + t) * p.F : nullptr;
-        cf* specL = reinterpret_cast<cf*>(p.spec) + (size_t)f * SRT_SPEC_LD;
+        float* magL = w.mag ? w.mag + ((size_t)(tile * 2 + 0) * p.T + t) * p.F : nullptr;
+        float* magR = w.mag ? w.mag + ((size_t)(tile * 2 + 1) * p.T + t) * p.F : nullptr;
+        cf* specL = reinterpret_cast<cf*>(w.spec) + (size_t)f * SRT_SPEC_LD;
         cf* specR = specL + p.spec_ch_stride;
-        if (f >= p.frames_computed) {                    // rows the reference leaves calloc'ed (stftFix.c:368-371)
+        if (f >= w.frames_computed) {                    // rows the reference leaves calloc'ed (stftFix.c:368-371)
             for (int k = tid; k < SRT_SPEC_LD; k += 256) { specL[k] = f2(0.f, 0.f); specR[k] = f2(0.f, 0.f); }
-            if (p.mag) for (int k = tid; k < p.F; k += 256) { magL[k] = 0.f; magR[k] = 0.f; }
+            if (w.mag) for (int k = tid; k < p.F; k += 256) { magL[k] = 0.f; magR[k] = 0.f; }
             continue;
         }
         cf v[16];
 #pragma unroll
         for (int n2 = 0; n2 < 16; ++n2) {
-            const bool ok = (size_t)f * SRT_HOP + tid + 256 * n2 < p.nsamples;   // tail frame is zero padded (stftFix.c:460-472)
+            const bool ok = (size_t)f * SRT_HOP + tid + 256 * n2 < w.nsamples;   // tail frame is zero padded (stftFix.c:460-472)
             v[n2] = f2(nxtL[n2], nxtR[n2]) * (ok ? aw[n2] : 0.f);
         }
         if (f + 1 <= flast) fetch_slide(f + 1);          // the next frame's new hop flies under this transform (past the last frame nothing is needed)
@@ -452,7 +470,7 @@ __global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p,
             const int k = tid + 256 * j;
             const cf zk = v[FFT16_AT(j)], zm = mir[(7 - j) * 256 + 256 - tid];
             const cf sl = split_l(zk, zm), sr = split_r(zk, zm);
-            if (p.mag && k < p.F) {
+            if (w.mag && k < p.F) {
                 magL[k] = hypotf(sl.x, sl.y) * 4096.0f;              // main.c:468-469
                 magR[k] = hypotf(sr.x, sr.y) * 4096.0f;
             }
@@ -463,18 +481,23 @@ __global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p,
             const cf sl = tid == 0 ? split_l(z2048, z2048) : f2(0.f, 0.f), sr = tid == 0 ? split_r(z2048, z2048) : f2(0.f, 0.f);
             specL[2048 + tid] = sl;
             specR[2048 + tid] = sr;
-            if (p.mag && tid == 0 && 2048 < p.F) { magL[2048] = hypotf(sl.x, sl.y) * 4096.0f; magR[2048] = hypotf(sr.x, sr.y) * 4096.0f; }
+            if (w.mag && tid == 0 && 2048 < p.F) { magL[2048] = hypotf(sl.x, sl.y) * 4096.0f; magR[2048] = hypotf(sr.x, sr.y) * 4096.0f; }
         }
     }
 }
 
+__global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p, int fpb)
+{
+    __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
+    stft_run(p, stft_view(p), blockIdx.x, fpb, s_mem);
+}
+
 // NM: mask rows cover bins < F <= 256 NM, so only the first NM of a thread's eight bins can carry a mask value (F = 1024: 4 prefetch registers per channel instead of 8)
 // M16: the masks are halves (the engine's own mask buffer in the fp16 mode, written by srt_head_rows_kernel<.., true>; never with RATIO)
-template <int NM, bool RATIO = false, bool M16 = false>
-__global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(const SrtIstftParams p, int G)
+#define ISTFT_OLA3_LDS_F2 (FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2)
+template <int NM, bool RATIO, bool M16>
+__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem)
 {
-    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;       // stem fastest: the stems of a run share the spectrum rows in L2
-    __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
     cf* sx = s_mem;
     cf* mir = s_mem + FFT_SMEM_F2;
     cf* s_twb = mir + FFT_MIR_F2;
@@ -482,12 +505,12 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
     const cf w1 = reinterpret_cast<const cf*>(p.tab.twiddle)[tid];
     if (tid < FFT_TWB_F2) s_twb[tid] = reinterpret_cast<const cf*>(p.tab.twiddle)[(16 * (tid & 15) * (tid / 16 + 1)) & 4095];
     const size_t tf = (size_t)p.T * p.F;
-    const int nseg = p.frames + 3;
+    const int nseg = w.frames + 3;
     const int s0 = run * G, s1 = min(s0 + G, nseg);
     const float oob = p.oob[stem];                                           // bins >= F: "unaffectedWeight" (main.c:486-493)
-    const cf* spec = reinterpret_cast<const cf*>(p.spec);
-    float* oL = p.out + (size_t)(stem * 2 + 0) * p.out_len;
-    float* oR = p.out + (size_t)(stem * 2 + 1) * p.out_len;
+    const cf* spec = reinterpret_cast<const cf*>(w.spec);
+    float* oL = w.out + (size_t)(stem * 2 + 0) * w.out_len;
+    float* oR = w.out + (size_t)(stem * 2 + 1) * w.out_len;
     cf acc[4][4];                                       // [segment slot][j] = (R, L) pairs
 #pragma unroll
     for (int h = 0; h < 4; ++h)
@@ -496,15 +519,15 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
     cf sl[8], sr[8];
     float gl[NM], gr[NM];
     cf sl8, sr8;                                        // bin 2048 (only thread 0 uses it; the address is uniform)
-    const bool has_mask = p.masks != nullptr;
-    auto fetch = [&](int f) {                                               // 0 <= f < p.frames
+    const bool has_mask = w.masks != nullptr;
+    auto fetch = [&](int f) {                                               // 0 <= f < w.frames
         const int tile = f / p.T, t = f % p.T;
         const cf* specL = spec + (size_t)f * SRT_SPEC_LD;
         const cf* specR = specL + p.spec_ch_stride;
         const size_t mo = ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F;
-        const float* mL = has_mask ? p.masks + mo : p.tab.postWin;
+        const float* mL = has_mask ? w.masks + mo : p.tab.postWin;
         const float* mR = has_mask ? mL + tf : p.tab.postWin;
-        const _Float16* hL = reinterpret_cast<const _Float16*>(p.masks) + mo;                   // (M16: the launcher checks that masks are given)
+        const _Float16* hL = reinterpret_cast<const _Float16*>(w.masks) + mo;                   // (M16: the launcher checks that masks are given)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int k = tid + 256 * j;
@@ -529,7 +552,7 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
     constexpr float SIN_PI8[16] = { 0.0f, 0.38268343236508977173f, 0.70710678118654752440f, 0.92387953251128675613f, 1.0f, 0.92387953251128675613f, 0.70710678118654752440f, 0.38268343236508977173f,
                                     0.0f, -0.38268343236508977173f, -0.70710678118654752440f, -0.92387953251128675613f, -1.0f, -0.92387953251128675613f, -0.70710678118654752440f, -0.38268343236508977173f };
     const int f0 = max(s0 - 3, 0);
-    if (f0 < p.frames) fetch(f0);
+    if (f0 < w.frames) fetch(f0);
     __syncthreads();                                     // the pass-2 twiddles are in LDS
     auto emit_and_slide = [&](int seg) {
         if (seg >= s0) {
@@ -542,14 +565,14 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
         }
     };
     for (int f = f0; f < s1; ++f) {
-        if (f < p.frames) {
+        if (f < w.frames) {
             // G = F'_L + i F'_R, F' = re - i im, Hermitian-extended; kept swapped (im, re): inverse-by-forward trick.  Bins k = tid + 256 j < 2048 are this
             // thread's own transform inputs n2 = j; their partners 4096 - k go through `mir` to thread 256 - tid (slot 15 - j).
             cf v[16];
             if constexpr (RATIO) {
                 if (has_mask && p.ratio) {               // (see srt_ratio_of; the extra loads are why this instantiation is built for two workgroups per CU)
                     const int tile = f / p.T, t = f % p.T;
-                    const float* r0 = p.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
+                    const float* r0 = w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
 #pragma unroll
                     for (int j = 0; j < NM; ++j) {
                         const int km = min(tid + 256 * j, p.F - 1);
@@ -574,7 +597,7 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);          // all of this frame's rows have arrived: nothing below waits on the stores
             if (f > f0) emit_and_slide(f - 1);
-            fetch(min(f + 1, p.frames - 1));             // next frame's rows fly under this transform
+            fetch(min(f + 1, w.frames - 1));             // next frame's rows fly under this transform
             __syncthreads();                             // the mirror values are visible; every thread is past the previous frame's exchange 2
 #pragma unroll
             for (int n2 = 8; n2 < 16; ++n2) v[n2] = mir[(15 - n2) * 256 + 256 - tid];
@@ -589,6 +612,14 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
         } else if (f > f0) emit_and_slide(f - 1);
     }
     if (s1 > f0) emit_and_slide(s1 - 1);
+}
+
+template <int NM, bool RATIO = false, bool M16 = false>
+__global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(const SrtIstftParams p, int G)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;       // stem fastest: the stems of a run share the spectrum rows in L2
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, RATIO, M16>(p, istft_view(p), stem, run, G, s_mem);
 }
 
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s)
@@ -631,6 +662,133 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s)
     } else if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_kernel<false>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
     else if (p.masks16) SRT_LAUNCH((srt_istft_ola3_kernel<4, false, true>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
     else SRT_LAUNCH((srt_istft_ola3_kernel<4>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
+    return srt_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------- packed batch of tracks (srtSeparateBatch)
+// K independent tracks share one launch of each transform.  Track k owns the packed tiles [tile0, tile0 + ntiles) of the engine's buffers (spectrum rows from
+// tile0 * T); a run of workgroups belongs to one track (the table's wg_stft / wg_istft: prefix sums of the per-track workgroup counts), and each workgroup runs
+// the single-signal kernels' body on its track's view - the same frames, the same arithmetic, the same accumulation order per output sample (the inverse starts
+// every run with the 3-frame warm-up from zero, so its bits do not depend on the run length G either).
+
+// the track of workgroup (or run) `wg`: the last k with first(k) <= wg.  wg is workgroup-uniform, so every probe is a uniform (scalar) load.
+template <bool ISTFT>
+__device__ __forceinline__ int srt_batch_track(const SrtBatchTrack* __restrict__ t, int ntracks, int wg)
+{
+    int lo = 0, hi = ntracks - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((ISTFT ? t[mid].wg_istft : t[mid].wg_stft) <= wg) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// p: the packed buffers (spec, spec_ch_stride, mag: never null here), T, F, tables; the PCM and frame counts come from the table
+__global__ void __launch_bounds__(256, 3) srt_stft_batch_kernel(const SrtStftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int fpb)
+{
+    __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
+    const SrtBatchTrack tk = tracks[srt_batch_track<false>(tracks, ntracks, blockIdx.x)];
+    const int blk = blockIdx.x - tk.wg_stft;
+    float* mag = p.mag + (size_t)tk.tile0 * 2 * p.T * p.F;
+    const StftView w = { tk.L, tk.R, tk.n, tk.frames, tk.rows, p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD, mag };
+    stft_run(p, w, blk, fpb, s_mem);
+    // Magnitude rows from the track's last row to its tile boundary are zero (what srtStftEx's memset leaves there: the network reads whole tiles).  They are
+    // shared out over the track's workgroups, after their transforms (a store queued ahead of the frame loop would hold up its first load wait).
+    const int nwg = (tk.rows + fpb - 1) / fpb, pad = tk.ntiles * p.T - tk.rows;
+    const int fb = tk.rows + (int)((long)(blk + 1) * pad / nwg);
+    for (int f = tk.rows + (int)((long)blk * pad / nwg); f < fb; ++f) {
+        const int tile = f / p.T, t = f % p.T;
+        float* magL = mag + ((size_t)(tile * 2 + 0) * p.T + t) * p.F;
+        float* magR = magL + (size_t)p.T * p.F;
+        for (int k = threadIdx.x; k < p.F; k += 256) { magL[k] = 0.f; magR[k] = 0.f; }
+    }
+}
+
+// OLA3: the three-per-CU form (F <= 1024), otherwise the two-per-CU table-window form; RATIO / M16 as srt_istft_ola3_kernel.  p.ntiles = the packed tile count
+// (the stem stride of the masks), p.spec / p.masks: the packed buffers; frames, output and its length per track.
+template <bool OLA3, bool RATIO, bool M16>
+__global__ void __launch_bounds__(256, OLA3 && !RATIO ? 3 : 2) srt_istft_batch_kernel(const SrtIstftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int G)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;       // stem fastest, as in the single-signal kernels
+    __shared__ cf s_mem[OLA3 ? ISTFT_OLA3_LDS_F2 : ISTFT_OLA_LDS_F2];
+    const SrtBatchTrack tk = tracks[srt_batch_track<true>(tracks, ntracks, run)];
+    const size_t mo = (size_t)tk.tile0 * 2 * p.T * p.F;                     // the track's first mask element (halves for M16)
+    IstftView w;
+    w.spec = p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD;
+    w.masks = !p.masks ? nullptr : M16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(p.masks) + mo) : p.masks + mo;
+    w.out = tk.out; w.out_len = tk.out_len; w.frames = tk.rows;
+    if constexpr (OLA3) istft_ola3_run<4, RATIO, M16>(p, w, stem, run - tk.wg_istft, G, s_mem);
+    else istft_ola_run<RATIO>(p, w, stem, run - tk.wg_istft, G, s_mem);
+}
+
+// smallest q >= q0 with count(q) <= limit (count falls as q grows); q0 when even qmax does not get there
+template <class C>
+static int srt_batch_step(int q0, int qmax, long limit, C&& count)
+{
+    if (count(q0) <= limit || qmax <= q0 || count(qmax) > limit) return q0;
+    int lo = q0, hi = qmax;                                                 // count(lo) > limit >= count(hi)
+    while (hi - lo > 1) { const int mid = lo + (hi - lo) / 2; if (count(mid) <= limit) hi = mid; else lo = mid; }
+    return hi;
+}
+
+// The two grids of a batch, with the single-signal launchers' rules applied to the totals: frames per STFT workgroup from the row total (srt_launch_stft; the
+// magnitude rows that pad each track to whole tiles are zeroed by the track's workgroups on the side), the inverse's run length from the total segment count
+// (srt_launch_istft).  Rounding per track can add up to one workgroup per track, so
+// the step is raised until the grid again fits the rounds the totals call for.  Fills every track's wg_stft / wg_istft.
+int srt_batch_geometry(SrtBatchTrack* t, int ntracks, int T, int F, int nstems, SrtBatchGrid* g)
+{
+    if (ntracks < 1 || nstems < 1) return -1;
+    long rows = 0, nseg = 0;
+    int max_rows = 1, max_seg = 1;
+    for (int k = 0; k < ntracks; ++k) {
+        rows += t[k].rows; nseg += t[k].rows + 3;
+        max_rows = max(max_rows, t[k].rows); max_seg = max(max_seg, t[k].rows + 3);
+    }
+    auto stft_blocks = [&](int q) { long b = 0; for (int k = 0; k < ntracks; ++k) b += (t[k].rows + q - 1) / q; return b; };
+    int fpb = rows >= 4096 ? STFT_FPB : (rows >= 1024 ? 2 : 1);
+    if (rows >= 4096) {
+        constexpr int cap = 24;
+        const long slots = 768, rounds = (rows + slots * cap - 1) / (slots * cap);
+        fpb = (int)((rows + slots * rounds - 1) / (slots * rounds));
+        fpb = srt_batch_step(fpb, max_rows, slots * rounds, stft_blocks);
+    }
+    const int target = F > 1024 ? 1024 : 768;
+    const int max_runs = target / nstems > 0 ? target / nstems : 1;
+    auto runs = [&](int q) { long r = 0; for (int k = 0; k < ntracks; ++k) r += (t[k].rows + 3 + q - 1) / q; return r; };
+    int G = (int)((nseg + max_runs - 1) / max_runs);
+    const int gmin = nseg * nstems >= 4096 ? 13 : 5;
+    if (G < gmin) G = gmin;
+    G = srt_batch_step(G, max_seg, max_runs, runs);
+    long wb = 0, wr = 0;
+    for (int k = 0; k < ntracks; ++k) {
+        t[k].wg_stft = (int)wb; t[k].wg_istft = (int)wr;
+        wb += (t[k].rows + fpb - 1) / fpb;
+        wr += (t[k].rows + 3 + G - 1) / G;
+    }
+    if (wb > (1l << 30) || wr * nstems > (1l << 30)) return -1;
+    g->fpb = fpb; g->stft_blocks = (int)wb; g->G = G; g->istft_runs = (int)wr;
+    return 0;
+}
+
+int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s)
+{
+    if (!p.mag || g.stft_blocks <= 0) return -1;
+    SRT_LAUNCH(srt_stft_batch_kernel, dim3(g.stft_blocks), dim3(256), 0, s, p, d_tracks, ntracks, g.fpb);
+    return srt_launch_status();
+}
+
+// the same form per geometry as srt_launch_istft
+int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s)
+{
+    if (g.istft_runs <= 0) return -1;
+    if (p.masks16 && (!p.masks || p.F > 1024 || (p.ratio && p.nstems > 1))) return -1;
+    const dim3 grid(g.istft_runs * p.nstems);
+    if (p.ratio && p.masks && p.nstems > 1) {
+        if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_kernel<false, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+        else SRT_LAUNCH((srt_istft_batch_kernel<true, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+    } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_kernel<false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+    else if (p.masks16) SRT_LAUNCH((srt_istft_batch_kernel<true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+    else SRT_LAUNCH((srt_istft_batch_kernel<true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     return srt_launch_status();
 }
 

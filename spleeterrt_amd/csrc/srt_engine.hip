@@ -82,6 +82,7 @@ struct HostStaging {
 // the first time its argument tuple is seen and replayed afterwards: one host call instead of ~25 launches on the audio thread.
 // `layout`: the switches that change which kernels and tensor layouts a forward records (SPLEETERRT_C8, C8L1, D1F16, M16; read per call), so a flipped
 // switch captures a new graph instead of replaying the old layout.
+#define SRT_BATCH_SLOTS 4
 struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, layout, wiener; };
 // c8 / c8_l1 / masks16: what the captured forward left in last_c8 / last_c8_l1 / last_masks16 - a replay runs no host code, so run_graphed puts them back
 // (srtCopyTensor reads the taps by them; an eager call in between may have changed them)
@@ -137,6 +138,10 @@ struct srt_engine {
     float* wslab;                                      // statistics partials + block maxima
     float* wtab;                                       // R tables, weight sums, a
     float2* wspec;                                     // filtered spectra [n_stems][2][rows][SRT_SPEC_LD]
+    // packed batches of tracks (srtSeparateBatch): the device track table (max_tiles rows: every track takes at least one tile) and a ring of pinned
+    // host slots it is uploaded from, each reused only after the copy from it issued SRT_BATCH_SLOTS calls earlier has completed (bev)
+    SrtBatchTrack* btab; SrtBatchTrack* bpin;
+    hipEvent_t bev[SRT_BATCH_SLOTS]; bool bused[SRT_BATCH_SLOTS]; int bslot;
     // timing
     bool timing; std::vector<TimingEntry> tlog;
 };
@@ -202,8 +207,10 @@ static void free_all(srt_engine* e)
     for (int i = 0; i < 6; ++i) { if (e->wino_u[i]) hipFree(e->wino_u[i]); if (e->wino_e[i]) hipFree(e->wino_e[i]); if (e->act32[i]) hipFree(e->act32[i]); }
     for (int i = 0; i < 6; ++i) { if (e->wpack_down[i]) hipFree(e->wpack_down[i]); if (e->wpack_up[i]) hipFree(e->wpack_up[i]); }
     for (int i = 0; i < 6; ++i) { if (e->raw[i]) hipFree(e->raw[i]); if (e->up[i]) hipFree(e->up[i]); if (i < 5 && e->act16buf[i]) hipFree(e->act16buf[i]); }
-    void* misc[] = { e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->frames, e->wslab, e->wtab, e->wspec };
+    void* misc[] = { e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->frames, e->wslab, e->wtab, e->wspec, e->btab };
     for (void* m : misc) if (m) hipFree(m);
+    if (e->bpin) hipHostFree(e->bpin);
+    for (hipEvent_t ev : e->bev) if (ev) hipEventDestroy(ev);
     for (auto& t : e->tlog) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
 }
 
@@ -230,6 +237,7 @@ int srtCreate(const srt_config* cfg, void* stream, srt_engine** out)
     memset(e->raw, 0, sizeof e->raw); memset(e->up, 0, sizeof e->up); memset(e->act16buf, 0, sizeof e->act16buf);
     e->preWin = e->postWin = nullptr; e->twiddle = nullptr; e->spec = nullptr; e->spec2 = nullptr; e->mag = e->masks = e->frames = nullptr;
     e->wiener = e->wiener_last = 0; e->wslab = e->wtab = nullptr; e->wspec = nullptr;
+    e->btab = e->bpin = nullptr; memset(e->bev, 0, sizeof e->bev); memset(e->bused, 0, sizeof e->bused); e->bslot = 0;
     e->cfg = *cfg;
     { const char* bi = getenv("SPLEETERRT_BATCH_INVARIANT"); if (bi && bi[0] == '1') e->cfg.batch_invariant = 1; }
     e->stream = (hipStream_t)stream; e->lo = make_layout(); e->timing = false; e->last_ntiles = cfg->max_tiles;
@@ -1091,6 +1099,99 @@ int srtSeparate(srt_engine* e, const float* d_L, const float* d_R, size_t n, flo
 {
     if (n < SRT_FFT) return fail(-1, "srtSeparate: need at least 4096 samples");
     return srtSeparateEx(e, d_L, d_R, n, srtStftFrames(n), srtStftRows(n), d_out);
+}
+
+// ---- packed batch of independent tracks (srt_dsp.hip: srt_stft_batch_kernel / srt_istft_batch_kernel)
+int srtBatchPlan(const size_t* n, int ntracks, int T, size_t* tile0, size_t* total_tiles)
+{
+    if (!n || !total_tiles || ntracks < 1 || T < 1) return fail(-1, "srtBatchPlan: need ntracks >= 1, T >= 1, n and total_tiles");
+    for (int k = 0; k < ntracks; ++k) if (n[k] < SRT_FFT) return fail(-1, "srtBatchPlan: every track needs at least 4096 samples");
+    size_t t = 0;
+    for (int k = 0; k < ntracks; ++k) {
+        if (tile0) tile0[k] = t;
+        t += (srtStftRows(n[k]) + T - 1) / T;
+    }
+    *total_tiles = t;
+    return 0;
+}
+
+// the device track table and the pinned upload slots, allocated on the first batch call and kept until srtDestroy
+static int ensure_batch(srt_engine* e)
+{
+    if (e->btab && e->bpin && e->bev[SRT_BATCH_SLOTS - 1]) return 0;
+    SrtSetupLock setup;
+    const size_t cap = (size_t)e->cfg.max_tiles;
+    if (!e->btab) HIPCHK(hipMalloc((void**)&e->btab, cap * sizeof(SrtBatchTrack)));
+    if (!e->bpin) HIPCHK(hipHostMalloc((void**)&e->bpin, SRT_BATCH_SLOTS * cap * sizeof(SrtBatchTrack), hipHostMallocDefault));
+    for (hipEvent_t& ev : e->bev) if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    return 0;
+}
+
+int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
+{
+    if (!e) return fail(-1, "srtSeparateBatch: null engine");
+    DeviceScope ds(e->device);
+    if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "srtSeparateBatch: need ntracks >= 1 and the four track arrays");
+    char what[48];
+    for (int k = 0; k < ntracks; ++k) {
+        snprintf(what, sizeof what, "%d", k);
+        if (!d_L[k] || !d_R[k] || !d_out[k]) return fail(-1, "srtSeparateBatch: null pointer in track %s", what);
+        if (n[k] < SRT_FFT) return fail(-1, "srtSeparateBatch: track %s has fewer than 4096 samples", what);
+    }
+    if (e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
+    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
+    size_t total = 0;
+    if (srtBatchPlan(n, ntracks, T, nullptr, &total)) return -1;
+    if (total > (size_t)e->cfg.max_tiles) {
+        snprintf(what, sizeof what, "%zu", total);
+        return fail(-1, "srtSeparateBatch: the tracks take %s tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", what);
+    }
+    for (int s = 0; s < S; ++s) if (!e->have_coeff[s]) return fail(-5, "srtSeparateBatch: weights not set for every stem");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
+    if (cap != hipStreamCaptureStatusNone) return fail(-1, "srtSeparateBatch: not capturable (the track table is uploaded per call): call it outside stream capture");
+    int rc = ensure_batch(e);
+    if (rc) return rc;
+    // the table goes up in stream order from a pinned slot; the slot's previous copy (SRT_BATCH_SLOTS calls ago) must have left it first
+    const int slot = e->bslot;
+    if (e->bused[slot]) HIPCHK(hipEventSynchronize(e->bev[slot]));
+    SrtBatchTrack* h = e->bpin + (size_t)slot * e->cfg.max_tiles;
+    size_t tile0 = 0;
+    for (int k = 0; k < ntracks; ++k) {
+        SrtBatchTrack& t = h[k];
+        t.L = d_L[k]; t.R = d_R[k]; t.n = n[k];
+        t.frames = (int)srtStftFrames(n[k]); t.rows = (int)srtStftRows(n[k]);
+        t.tile0 = (int)tile0; t.ntiles = (t.rows + T - 1) / T; tile0 += t.ntiles;
+        t.out = d_out[k]; t.out_len = srtIstftLength(t.rows);
+    }
+    SrtBatchGrid g;
+    if (srt_batch_geometry(h, ntracks, T, F, S, &g)) return fail(-1, "srtSeparateBatch: batch geometry out of range");
+    HIPCHK(hipMemcpyAsync(e->btab, h, (size_t)ntracks * sizeof(SrtBatchTrack), hipMemcpyHostToDevice, e->stream));
+    HIPCHK(hipEventRecord(e->bev[slot], e->stream));
+    e->bused[slot] = true; e->bslot = (slot + 1) % SRT_BATCH_SLOTS;
+    const size_t ch_stride = total * T * SRT_SPEC_LD;          // the packed spectrum: [2][total * T][SRT_SPEC_LD]
+    {
+        SrtStftParams p; memset(&p, 0, sizeof p);
+        p.spec = e->spec; p.spec_ch_stride = ch_stride; p.mag = e->mag;
+        p.rows_total = (int)(total * T); p.T = T; p.F = F; p.tab = tables_of(e);
+        TimerScope ts(e, "stft_batch");
+        if (srt_launch_stft_batch(p, e->btab, ntracks, g, e->stream)) return fail(-2, "batched stft launch failed");
+    }
+    // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue
+    const char* m16v = getenv("SPLEETERRT_M16");
+    e->masks16_req = e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && e->cfg.F <= 1024 && !(m16v && m16v[0] == '0');
+    rc = forward_range(e, e->mag, (int)total, e->masks, 0, S);
+    e->masks16_req = false;
+    if (rc) return rc;
+    SrtIstftParams q; memset(&q, 0, sizeof q);
+    q.spec = e->spec; q.spec_ch_stride = ch_stride; q.frames = (int)(total * T);
+    q.masks = e->masks; q.masks16 = e->last_masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)total; q.T = T; q.F = F;
+    for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
+    q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
+    q.tab = tables_of(e);
+    TimerScope ts(e, "istft_batch");
+    if (srt_launch_istft_batch(q, e->btab, ntracks, g, e->stream)) return fail(-2, "batched istft launch failed");
+    return 0;
 }
 
 // Long host-resident stream through one GPU: the stream is cut into chunks of max_tiles tiles (tiles are independent,

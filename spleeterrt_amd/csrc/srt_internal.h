@@ -171,6 +171,19 @@ struct SrtIstftParams {
 };
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s);
 int srt_launch_istft(const SrtIstftParams& p, hipStream_t s);
+// packed batch of independent tracks (srtSeparateBatch): one row of the device-resident track table per track
+struct SrtBatchTrack {
+    const float* L; const float* R; size_t n;    // the track's PCM, n >= 4096 samples
+    float* out; size_t out_len;                  // its stems [nstems][2][out_len], out_len = rows * 1024 + 3072
+    int frames, rows;                            // srtStftFrames(n), srtStftRows(n)
+    int tile0, ntiles;                           // packed tiles [tile0, tile0 + ntiles) = ceil(rows / T) (spectrum rows from tile0 * T)
+    int wg_stft, wg_istft;                       // the track's first workgroup of the batched STFT / first run of the batched inverse (srt_batch_geometry)
+};
+struct SrtBatchGrid { int fpb, stft_blocks, G, istft_runs; };
+int srt_batch_geometry(SrtBatchTrack* t, int ntracks, int T, int F, int nstems, SrtBatchGrid* g);       // host: fills wg_stft / wg_istft
+// p as srt_launch_stft / srt_launch_istft on the packed buffers (mag required; p.ntiles = the packed tile count); the per-track fields are taken from d_tracks
+int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s);
+int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s);
 
 // residual chain of the offline CLI (main.c:845-866): res = spec - spec*mask (bins >= F: spec - spec*oob), |res|*4096 -> mag
 struct SrtResidualParams {

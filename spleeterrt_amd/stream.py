@@ -61,6 +61,31 @@ def rank_span(n, T, rank=0, world=1):
     return Span(t0, t1, s0, ns, max(0, min(frames - row0, row1 - row0)), max(0, row1 - row0), s0)
 
 
+BatchGroup = namedtuple("BatchGroup", "tracks tile0 ntiles")
+
+
+def pack_tracks(ns, T, max_tiles):
+    """Greedy grouping, in order, of independent tracks of ns[k] samples into srtSeparateBatch calls of at most max_tiles packed
+    tiles: a call takes tracks until the next one would not fit.  Track k takes ceil(stft_rows(ns[k]) / T) tiles, packed from
+    tile0.  Returns [BatchGroup(tracks = indices into ns, tile0 = each track's first tile in its call, ntiles = the call's total)]."""
+    groups, cur, tile0, used = [], [], [], 0
+    for k, n in enumerate(ns):
+        if n < FFT:
+            raise ValueError("track %d: %d samples, at least %d needed" % (k, n, FFT))
+        nt = (stft_rows(n) + T - 1) // T
+        if nt > max_tiles:
+            raise ValueError("track %d alone takes %d tiles, more than max_tiles = %d: separate it with the chunked paths" % (k, nt, max_tiles))
+        if used + nt > max_tiles:
+            groups.append(BatchGroup(cur, tile0, used))
+            cur, tile0, used = [], [], 0
+        cur.append(k)
+        tile0.append(used)
+        used += nt
+    if cur:
+        groups.append(BatchGroup(cur, tile0, used))
+    return groups
+
+
 def _refuse_wiener(engine, world):
     """The Wiener filter's statistics span the whole signal: ranks would each filter their range with its own covariance."""
     if world > 1 and getattr(engine, "wiener", 0):
