@@ -2,7 +2,7 @@
  * Spleeter4Stems.h — drop-in for the reference's real-time streaming surface (VST/Source/Spleeter4Stems.h:67-69),
  * the API the JUCE plugin calls from the host's audio callback (VST/Source/PluginProcessor.cpp:115-182).
  *
- * Same three symbols, argument meaning and timing as the reference:
+ * Same three symbols, argument meaning and timing as the reference (plus the live mode, Spleeter4StemsInitLive / Spleeter4StemsLatency below):
  *   - Spleeter4Stems is caller-allocated (`malloc(sizeof(Spleeter4Stems))`, PluginProcessor.cpp:123); here its body is
  *     opaque storage that holds the engine handle (the reference's members were never part of the calling contract);
  *   - coeffProvider[k] points at 39 290 900 bytes of spleeterCoeff for stem k = drum, bass, accompaniment, vocal
@@ -59,6 +59,13 @@ typedef struct
 S4S_API void Spleeter4StemsInit(Spleeter4Stems *msr, int initSpectralBinLimit, int initTimeStep, void *coeffProvider[4]);
 S4S_API void Spleeter4StemsFree(Spleeter4Stems *msr);
 S4S_API void Spleeter4StemsProcessSamples(Spleeter4Stems *msr, const float *inLeft, const float *inRight, int inSampleCount, float **components);
+/* Low-latency live mode (not in the reference): the networks run every hopsPerRun hops (1..timeStep) on the newest timeStep
+   frames, and a frame is synthesised with `lookahead` (0..timeStep-hopsPerRun) frames of future context, so the delay is
+   (lookahead + 2*hopsPerRun) hops + 1024 samples.  Spleeter4StemsInit is Spleeter4StemsInitLive(msr, F, T, coeffProvider, T, 0).
+   Out-of-range arguments are reported like any other Init failure (the instance is muted).  Free / ProcessSamples as above. */
+S4S_API void Spleeter4StemsInitLive(Spleeter4Stems *msr, int initSpectralBinLimit, int initTimeStep, void *coeffProvider[4], int hopsPerRun, int lookahead);
+/* the delay in samples for a host that passes 1024-sample blocks (for AudioProcessor::setLatencySamples); 0 for a NULL instance */
+S4S_API int Spleeter4StemsLatency(const Spleeter4Stems *msr);
 #ifdef __cplusplus
 }
 #endif

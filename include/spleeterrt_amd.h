@@ -217,6 +217,25 @@ SRT_API int  srtResample(srt_resampler *r, const float *d_L, const float *d_R, s
 SRT_API int  srtResampleHost(srt_resampler *r, const float *h_L, const float *h_R, size_t n_in,
                              float *h_Lo, float *h_Ro);
 
+/* ---- live separation with a sliding network window: the real-time surface of Spleeter4Stems.h with a short delay.  The networks run
+ * every hops_per_run = K hops (1 <= K <= T) on the window of the newest T frames; frame g takes its mask from the run whose window holds it at row
+ * T-1-(h_r-g) with h_r-g in [L, L+K-1], L = lookahead (0 <= L <= T-K frames of future context), and is synthesised D = L + 2K hops after it was
+ * analysed.  K = T, L = 0 with the plugin's config is exactly Spleeter4Stems.  Frames near the window's right edge see less future context, so
+ * separation quality falls as L approaches 0.
+ * srtLiveCreate: current device; cfg honours F, T, n_stems, stem_mode, oob_weight, variant, impl, precision, ratio_mask, batch_invariant; max_tiles
+ * must be 1; h_coeff: n_stems spleeterCoeff blobs (copied).  Every argument is checked before any HIP call (-1 with srtLastError() text).  Init does
+ * all allocation, graph capture and the pre-warm of the hop path; the Wiener filter is never on.
+ * srtLiveProcess: n samples per channel in, up to n samples written to each of the 2*n_stems planar outputs (stem-major L/R pairs), with the
+ * reference's accounting (Spleeter4StemsProcessSamples): one 1024-sample segment per completed hop, a two-segment queue, the queue emitting from the
+ * call that completes the first hop and never more than the call's n.  Returns the count written (0..n), negative on a bad argument.  Never
+ * allocates or captures; after a device failure (reported once) the stream emits silence with the same accounting.
+ * srtLiveLatency: (L + 2K) * 1024 + 1024 samples, the delay for a caller that passes 1024-sample blocks; the first D hops are silence. */
+typedef struct srt_live srt_live;
+SRT_API int  srtLiveCreate(const srt_config *cfg, int hops_per_run, int lookahead, const void *const *h_coeff, srt_live **out);
+SRT_API int  srtLiveProcess(srt_live *s, const float *inL, const float *inR, int n, float *const *out);
+SRT_API int  srtLiveLatency(const srt_live *s);
+SRT_API void srtLiveDestroy(srt_live *s);
+
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";
                                                                                                                    "wiener_cov": tile = iteration (see srtIstftWiener);

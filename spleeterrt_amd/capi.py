@@ -89,6 +89,12 @@ def load_library():
     L.srtMultiEngine.argtypes = [vp, C.c_int]
     L.srtMultiEngine.restype = vp
     L.srtMultiBenchResident.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    # live separation with a sliding network window (csrc/srt_stream.hip)
+    L.srtLiveCreate.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.srtLiveProcess.argtypes = [vp, vp, vp, C.c_int, C.POINTER(vp)]
+    L.srtLiveLatency.argtypes = [vp]
+    L.srtLiveDestroy.argtypes = [vp]
+    L.srtLiveDestroy.restype = None
     # sample-rate converter (csrc/srt_resample.hip)
     L.srtResampleLength.restype = C.c_size_t
     L.srtResampleLength.argtypes = [C.c_size_t, C.c_int, C.c_int]
@@ -376,6 +382,83 @@ class Engine:
         n = self._chk(self.L.srtGetTimingKernels(self.h, buf, len(buf)))
         ks = buf.value.decode().split(";")[:n]
         return [(name, k) for (name, _), k in zip(tim, ks)]
+
+
+def live_latency(hops_per_run, lookahead):
+    """srtLiveLatency's arithmetic: the delay in samples of a live stream fed 1024-sample blocks, (L + 2K) * 1024 + 1024"""
+    return (int(lookahead) + 2 * int(hops_per_run)) * 1024 + 1024
+
+
+class Live:
+    """Live separation with a sliding network window (srtLive*, include/spleeterrt_amd.h) on the current device: the networks
+    run every hops_per_run hops on the newest T frames, with `lookahead` frames of future context per frame.  hops_per_run = T, lookahead = 0 with
+    the plugin's config (VST, stem modes 1, oob 0.25 / 0 / 0.25 / 0.25) is Spleeter4Stems.  coeffs: one float32 spleeterCoeff blob per stem."""
+
+    def __init__(self, F, T, stem_modes, oob_weights, variant, precision, hops_per_run, lookahead, coeffs, impl=IMPL_MFMA,
+                 ratio_mask=False, batch_invariant=False, max_tiles=1):
+        import numpy as np
+        self.L = load_library()
+        self.S, self.F, self.T = len(stem_modes), F, T
+        self.hops_per_run, self.lookahead = int(hops_per_run), int(lookahead)
+        cfg = _Config()
+        cfg.F, cfg.T, cfg.n_stems, cfg.variant, cfg.max_tiles, cfg.impl = F, T, self.S, variant, max_tiles, impl
+        cfg.precision, cfg.ratio_mask, cfg.batch_invariant = precision, int(bool(ratio_mask)), int(bool(batch_invariant))
+        for i, m in enumerate(stem_modes):
+            cfg.stem_mode[i] = int(m)
+            cfg.oob_weight[i] = float(oob_weights[i])
+        blobs = [None if c is None else np.ascontiguousarray(c, np.float32) for c in coeffs]
+        for b in blobs:
+            assert b is None or b.size == COEFF_FLOATS
+        ptrs = (C.c_void_p * max(len(blobs), 1))(*[None if b is None else b.ctypes.data for b in blobs])
+        h = C.c_void_p()
+        self._chk(self.L.srtLiveCreate(C.byref(cfg), self.hops_per_run, self.lookahead, ptrs, C.byref(h)))
+        self.h = h
+
+    def _chk(self, rc):
+        if rc < 0:
+            raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (self.L.srtLastError().decode(), rc))
+        return rc
+
+    @property
+    def latency(self):
+        """samples between an input sample and its separated output for 1024-sample calls (srtLiveLatency)"""
+        return self._chk(self.L.srtLiveLatency(self.h))
+
+    def process(self, L, R, chunks=(1024,)):
+        """Feed planar float32 L, R in calls of the sizes in `chunks` (cycled).  Returns (written [2S][m], timeline [2S][n]): the concatenation of what
+        the calls wrote (the counts srtLiveProcess returned) and the same samples placed where each call's output starts in the caller's buffers
+        (zero where nothing was written), the form tests/test_stream.py's _run builds for the plugin."""
+        import numpy as np
+        L = np.ascontiguousarray(L, np.float32)
+        R = np.ascontiguousarray(R, np.float32)
+        n = L.size
+        assert R.size == n
+        nc = 2 * self.S
+        timeline = np.zeros((nc, n), np.float32)
+        pieces = []
+        pos = i = 0
+        P = C.c_void_p * nc
+        while pos < n:
+            c = min(int(chunks[i % len(chunks)]), n - pos)
+            i += 1
+            w = self._chk(self.L.srtLiveProcess(self.h, C.c_void_p(L.ctypes.data + 4 * pos), C.c_void_p(R.ctypes.data + 4 * pos), c,
+                                                P(*[timeline[j].ctypes.data + 4 * pos for j in range(nc)])))
+            if w:
+                pieces.append((pos, w))
+            pos += c
+        written = np.concatenate([timeline[:, p:p + w] for p, w in pieces], axis=1) if pieces else np.zeros((nc, 0), np.float32)
+        return written, timeline
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.srtLiveDestroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Resampler:

@@ -903,6 +903,67 @@ int srt_launch_ratio_mask(float* masks, int nstems, size_t count, hipStream_t s)
 }
 
 // ------------------------------------------------------------------------------------------- streaming hop
+// Inverse of the DELAYED frame for stem st: masked spectrum -> time frame -> synthesis window on the last 2048 samples ->
+// 50 % overlap-add with the kept half -> output segment interleaved by 2*nstems (Spleeter4Stems.c:64-101,272-320).
+// srt_live_inverse_kernel runs it for every config but the plugin's.  The plugin's config (4 stems, oob 0.25 / 0 / 0.25 / 0.25) keeps
+// srt_stream_inverse_kernel below unchanged: under fp contract(fast) the compiler fuses the mask products into FMAs differently once the
+// body is shared or the weight is an argument (measured: 1-ulp differences on most output samples at 256 x 1536, with no source form
+// found that reproduces the fixed kernel's choice), and the plugin's output must stay bit-identical.
+__device__ __forceinline__ void srt_stream_inverse_body(const SrtStreamHop& p, int st, cf* s_tw, cf* s_x)
+{
+    const int tid = threadIdx.x;
+    fft_load_twiddles(s_tw, p.twiddle, tid);
+    const cf* specL = reinterpret_cast<const cf*>(p.specRow);
+    const cf* specR = reinterpret_cast<const cf*>(p.specRow) + p.specChStride;
+    const float* mL = p.maskRow + st * p.maskStemStride;
+    const float* mR = mL + p.maskChStride;
+    const float oob = p.oob[st];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const int k = tid + 256 * j;
+        if (k <= 2048) {
+            const cf sl = specL[k], sr = specR[k];
+            float gl = oob, gr = oob;
+            if (k < p.F) { gl = mL[k]; gr = mR[k]; }
+            const float reL = sl.x * gl, imL = sl.y * gl, reR = sr.x * gr, imR = sr.y * gr;
+            if (k == 0) s_x[0] = f2(reR, reL);
+            else if (k == 2048) s_x[2048] = f2(reR - imR, reL - imL);
+            else {
+                s_x[k] = f2(reR - imL, reL + imR);
+                s_x[4096 - k] = f2(reR + imL, reL - imR);
+            }
+        }
+    }
+    __syncthreads();
+    cf v[16];
+#pragma unroll
+    for (int n2 = 0; n2 < 16; ++n2) v[n2] = s_x[tid + 256 * n2];
+    __syncthreads();
+    fft4096(v, s_x, s_tw, tid);
+    float* ovL = p.overlap + (size_t)(2 * st) * 1024;
+    float* ovR = ovL + 1024;
+    const int os = 2 * p.nstems;
+    // thread holds samples tid + 256*k2; only the last 2048 are synthesised.  k2 = 8..11 -> output, 12..15 -> kept half.
+#pragma unroll
+    for (int k2 = 8; k2 < 12; ++k2) {
+        const int i = tid + 256 * (k2 - 8);                                   // 0..1023
+        const float w0 = p.synthesisWnd[i], w1 = p.synthesisWnd[i + 1024];
+        const cf y0 = v[FFT16_AT(k2)], y1 = v[FFT16_AT(k2 + 4)];
+        p.out[(size_t)i * os + 2 * st + 0] = ovL[i] + y0.y * w0;             // mOverlapStage2dash + timeDomainOut (:313-315)
+        p.out[(size_t)i * os + 2 * st + 1] = ovR[i] + y0.x * w0;
+        ovL[i] = y1.y * w1;                                                   // :317-318
+        ovR[i] = y1.x * w1;
+    }
+}
+
+// one workgroup per stem (blockIdx.x = stem < p.nstems)
+__global__ void __launch_bounds__(256) srt_live_inverse_kernel(const SrtStreamHop p)
+{
+    __shared__ cf s_tw[FFT_TW_F2];
+    __shared__ cf s_x[FFT_SMEM_F2];
+    srt_stream_inverse_body(p, blockIdx.x, s_tw, s_x);
+}
+
 // Inverse of the DELAYED frame for one stem (blockIdx.x = stem): masked spectrum -> time frame -> synthesis window on the
 // last 2048 samples -> 50 % overlap-add with the kept half -> interleaved-by-8 output segment (Spleeter4Stems.c:64-101,272-320).
 __global__ void __launch_bounds__(256) srt_stream_inverse_kernel(const SrtStreamHop p)
@@ -994,8 +1055,33 @@ __global__ void __launch_bounds__(256) srt_stream_forward_kernel(const SrtStream
 
 int srt_launch_stream_hop(const SrtStreamHop& p, hipStream_t s)
 {
-    SRT_LAUNCH(srt_stream_inverse_kernel, dim3(4), dim3(256), 0, s, p);     // reads the delayed row ...
+    if (p.nstems < 1 || p.nstems > SRT_MAX_STEMS) return -1;
+    const bool plugin = p.nstems == 4 && p.oob[0] == 0.25f && p.oob[1] == 0.0f && p.oob[2] == 0.25f && p.oob[3] == 0.25f;
+    if (plugin) SRT_LAUNCH(srt_stream_inverse_kernel, dim3(4), dim3(256), 0, s, p);           // reads the delayed row ...
+    else SRT_LAUNCH(srt_live_inverse_kernel, dim3(p.nstems), dim3(256), 0, s, p);
     if (hipGetLastError() != hipSuccess) return -1;
     SRT_LAUNCH(srt_stream_forward_kernel, dim3(1), dim3(256), 0, s, p);     // ... before the current frame overwrites it
+    return srt_launch_status();
+}
+
+// Live window gather (srt_stream.hip): the magnitude ring holds frame g in row g mod T of each channel; the network wants the
+// window's oldest frame in row 0.  dst[c][i][:] = ring[c][(i + rot) mod T][:], one workgroup per (row, 512 columns), 16-byte
+// loads and stores.  rot = 0 is a plain copy (the plugin's geometry, where every window starts at a multiple of T).
+__global__ void __launch_bounds__(128) srt_live_gather_kernel(const float4* __restrict__ ring, float4* __restrict__ dst, int T, int F4, int rot)
+{
+    const int f = blockIdx.x * 128 + threadIdx.x;
+    if (f >= F4) return;
+    const int row = blockIdx.y, c = row >= T ? 1 : 0, i = row - c * T;
+    int src = i + rot;
+    if (src >= T) src -= T;
+    dst[(size_t)row * F4 + f] = ring[((size_t)c * T + src) * F4 + f];
+}
+
+int srt_launch_live_gather(const float* ring, float* dst, int T, int F, int rot, hipStream_t s)
+{
+    if (T < 1 || F < 4 || F % 4 || rot < 0 || rot >= T) return -1;
+    const int F4 = F / 4;
+    SRT_LAUNCH(srt_live_gather_kernel, dim3((F4 + 127) / 128, 2 * T), dim3(128), 0, s,
+               reinterpret_cast<const float4*>(ring), reinterpret_cast<float4*>(dst), T, F4, rot);
     return srt_launch_status();
 }

@@ -214,13 +214,19 @@ static void free_all(srt_engine* e)
     for (auto& t : e->tlog) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
 }
 
+int srt_check_config(const srt_config* cfg, const char* who)
+{
+    if (cfg->F < 64 || cfg->F > 2048 || cfg->F % 64 || cfg->T < 64 || cfg->T % 64)
+        return srt_set_error(-1, "%s: F and T must be multiples of 64 (F <= 2048)", who);     // spleeter.c:113-119 floor-divides by 64
+    if (cfg->n_stems < 1 || cfg->n_stems > SRT_MAX_STEMS || cfg->max_tiles < 1) return srt_set_error(-1, "%s: bad n_stems / max_tiles", who);
+    return 0;
+}
+
 int srtCreate(const srt_config* cfg, void* stream, srt_engine** out)
 {
     if (!cfg || !out) return fail(-1, "srtCreate: null argument");
     SrtSetupLock setup;
-    if (cfg->F < 64 || cfg->F > 2048 || cfg->F % 64 || cfg->T < 64 || cfg->T % 64)
-        return fail(-1, "srtCreate: F and T must be multiples of 64 (F <= 2048)");     // spleeter.c:113-119 floor-divides by 64
-    if (cfg->n_stems < 1 || cfg->n_stems > SRT_MAX_STEMS || cfg->max_tiles < 1) return fail(-1, "srtCreate: bad n_stems / max_tiles");
+    if (const int rc = srt_check_config(cfg, "srtCreate")) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-3, "srtCreate: no HIP device (this library has no CPU path)");
     srt_engine* e = new srt_engine();

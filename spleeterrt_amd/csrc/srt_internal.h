@@ -225,7 +225,7 @@ int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s)
 struct srt_engine;
 int srt_engine_wiener(const srt_engine* e);                                             // iterations switched on (srtSetWiener), 0: off
 
-// streaming (srt_dsp.hip kernels, srt_stream.hip host logic): one hop = 1 forward + 4 masked inverse FFTs + 50 % OLA
+// streaming (srt_dsp.hip kernels, srt_stream.hip host logic): one hop = 1 forward + n_stems masked inverse FFTs + 50 % OLA
 struct SrtStreamHop {
     const float* ring;        // [2][4096] device copy of the input ring buffer
     int inPos;                // ring read origin (Spleeter4Stems.c:262)
@@ -236,11 +236,18 @@ struct SrtStreamHop {
     const float* maskRow;     // stem s, channel c at maskRow + s*maskStemStride + c*maskChStride
     size_t maskStemStride, maskChStride;
     int F;
-    float* overlap;           // [8][1024]
-    float* out;               // [1024][8] interleaved segment
+    int nstems;               // stems inverted per hop (one workgroup each), 1..SRT_MAX_STEMS
+    float oob[SRT_MAX_STEMS]; // per stem: weight of bins F..2048 (the plugin: 0.25, 0, 0.25, 0.25)
+    float* overlap;           // [2*nstems][1024]
+    float* out;               // [1024][2*nstems] interleaved segment
     const float* analysisWnd; const float* synthesisWnd; const float2* twiddle;
 };
 int srt_launch_stream_hop(const SrtStreamHop& p, hipStream_t s);
+// Live window gather: dst[c][i] = ring[c][(i + rot) mod T] for the [2][T][F] magnitude ring (rows of F floats, F % 4 == 0)
+int srt_launch_live_gather(const float* ring, float* dst, int T, int F, int rot, hipStream_t s);
+struct srt_config;
+// srtCreate's argument checks (no HIP call): 0, or the negative code with srtLastError() set and `who` naming the caller
+int srt_check_config(const srt_config* cfg, const char* who);
 
 // ---- multi-device host driver (srt_multi.hip) over the engine (srt_engine.hip)
 struct srt_engine;
