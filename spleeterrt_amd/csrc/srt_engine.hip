@@ -77,16 +77,24 @@ struct HostStaging {
     bool ready;
 };
 
+// What the last forward left behind, for the calls that come after it (srtCopyTensor's taps, the inverse transform of srtSeparate).  forward_range and
+// wiener_issue write it; a graph replay runs no host code, so the slot keeps the record its capture left and run_graphed puts it back.
+struct ForwardRecord {
+    int ntiles;                        // instance stride of the activation buffers = tiles of that forward
+    bool c8, c8_l1, masks16;           // raw2..6 / act2..5 / up1..4 are channel-interleaved by eight (srt_nn5.hip); conv1 / act1 too; the engine's OWN mask buffer holds halves
+    unsigned up6_fused; int up6_s0; SrtConvParams up6_params;     // bit s: stem s ran up6 + head in one pass (no up6 plane stored) - srtCopyTensor("up6") re-launches up6 alone from that launch's stem range and parameters
+    int wiener_last;                   // iterations of the last filtered call: the R tables srtCopyTensor("wiener_cov") can return
+};
+
 // hipGraph replay of the launch sequences a low-latency caller repeats with the same arguments (srtSetGraphMode): the real-time
 // plugin runs srtForward on the same two mask buffers for ever, the tile API on one pair of buffers.  A sequence is captured
 // the first time its argument tuple is seen and replayed afterwards: one host call instead of ~25 launches on the audio thread.
-// `layout`: the switches that change which kernels and tensor layouts a forward records (SPLEETERRT_C8, C8L1, D1F16, M16; read per call), so a flipped
-// switch captures a new graph instead of replaying the old layout.
+// `sw`: the run-time switches of the call (SrtSwitches, srt_internal.h) - all of them decide what a forward records, so a flipped switch captures a new
+// graph instead of replaying the old form.  Keys are zeroed before they are filled and compared with memcmp.
 #define SRT_BATCH_SLOTS 4
-struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, layout, wiener; };
-// c8 / c8_l1 / masks16: what the captured forward left in last_c8 / last_c8_l1 / last_masks16 - a replay runs no host code, so run_graphed puts them back
-// (srtCopyTensor reads the taps by them; an eager call in between may have changed them)
-struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; bool c8, c8_l1, masks16; };
+struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; };
+// left: e->last as the capture left it (an eager call in between may have changed it)
+struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; ForwardRecord left; };
 #define SRT_GRAPH_SLOTS 4
 
 // Every entry point that allocates or launches runs on the device the engine was created on, whatever the caller's
@@ -100,50 +108,45 @@ struct DeviceScope {
 };
 
 struct srt_engine {
-    srt_config cfg;
-    int device;
-    hipStream_t stream;
-    HostStaging hs;
-    Layout lo;
-    float* coeff_all;                                  // [n_stems][SRT_COEFF_STRIDE]
-    float* wpack_down[6]; float* wpack_up[6];          // per layer: [n_stems][Cin*25*CP]
-    size_t wpack_down_stem[6], wpack_up_stem[6];
-    uint16_t* wpack16_down[6]; uint16_t* wpack16_up[6];  // fp16-MFMA packs [n_stems][Cin/16][25][2][CP][8] (precision != F32 only)
-    size_t wpack16_down_stem[6], wpack16_up_stem[6];
-    float* wpack2_d1;                                  // down1 stem-stacked [2][25][CP2], repacked per launch group (tiny)
-    float* wpack2_u5;                                  // up5 class-stacked [n_stems][64][15][32]
-    float* wino_u[6]; size_t wino_u_stem[6];           // Winograd-transformed decoder weights (srt_nn4.hip), layers in srt_wino_mask() only
-    float* wino_e[6]; size_t wino_e_stem[6];           // the same for the encoder layers that can run in Winograd form (down3..down6)
-    float* act32[6];                                   // fp32 act(BN(raw_i)) copies, i = 2..4: the inputs of those layers (written by their producers)
-    bool   have_coeff[SRT_MAX_STEMS];
-    float* raw[6]; float* up[6];
-    size_t raw_tile[6], up_tile[6];                    // elements per instance
-    float* act16buf[5];                                // fp16-storage mode only: act(bn(raw_i)) as halves, written by the producer
-    bool act16;                                        // raw[0..5] and up[0..4] hold IEEE halves (precision F16 on a supported geometry)
-    uint16_t* wpack16cs_u5;                            // act16 only: up5's class-stacked fp16 weights [n_stems][4][15][2][32][8] (srt_nn5.hip)
-    SrtConvParams up6_params; int up6_s0; unsigned up6_stale;          // the last forward ran up6 + head in one pass (no up6 plane stored): srtCopyTensor("up6") re-launches up6 alone from these
-    bool last_c8_l1;                                   // ... and conv1 / act1 too (down1 ran on its streamed kernels)
-    bool masks16_req, last_masks16;                    // srtSeparate in the fp16 mode: the engine's OWN mask buffer may hold halves (asked for by separate_issue / what the last forward did)
-    bool last_c8;                                      // the last forward stored raw2..6 / act2..5 / up1..4 channel-interleaved by eight (srt_nn5.hip): srtCopyTensor's view
-    float* ws; size_t ws_floats;                       // split-K partial sums of small-batch launches (allocated on the first one)
-    int graph_mode; unsigned long gclock; GraphSlot gslots[SRT_GRAPH_SLOTS];
+    srt_config cfg{};
+    int device = 0;
+    hipStream_t stream = nullptr;
+    HostStaging hs{};
+    Layout lo{};
+    float* coeff_all = nullptr;                        // [n_stems][SRT_COEFF_STRIDE]
+    float* wpack_down[6] = {}; float* wpack_up[6] = {};  // per layer: [n_stems][Cin*25*CP]
+    size_t wpack_down_stem[6] = {}, wpack_up_stem[6] = {};
+    uint16_t* wpack16_down[6] = {}; uint16_t* wpack16_up[6] = {};  // fp16-MFMA packs [n_stems][Cin/16][25][2][CP][8] (precision != F32 only)
+    size_t wpack16_down_stem[6] = {}, wpack16_up_stem[6] = {};
+    float* wpack2_d1 = nullptr;                        // down1 stem-stacked [2][25][CP2], repacked per launch group (tiny)
+    float* wpack2_u5 = nullptr;                        // up5 class-stacked [n_stems][64][15][32]
+    float* wino_u[6] = {}; size_t wino_u_stem[6] = {};   // Winograd-transformed decoder weights (srt_nn4.hip), layers in srt_wino_mask() only
+    float* wino_e[6] = {}; size_t wino_e_stem[6] = {};   // the same for the encoder layers that can run in Winograd form (down3..down6)
+    float* act32[6] = {};                              // fp32 act(BN(raw_i)) copies, i = 2..4: the inputs of those layers (written by their producers)
+    bool   have_coeff[SRT_MAX_STEMS] = {};
+    float* raw[6] = {}; float* up[6] = {};
+    size_t raw_tile[6] = {}, up_tile[6] = {};          // elements per instance
+    float* act16buf[5] = {};                           // fp16-storage mode only: act(bn(raw_i)) as halves, written by the producer
+    bool act16 = false;                                // raw[0..5] and up[0..4] hold IEEE halves (precision F16 on a supported geometry)
+    uint16_t* wpack16cs_u5 = nullptr;                  // act16 only: up5's class-stacked fp16 weights [n_stems][4][15][2][32][8] (srt_nn5.hip)
+    ForwardRecord last{};                              // what the last forward left (ntiles starts at max_tiles: srtCreate)
+    float* ws = nullptr; size_t ws_floats = 0;         // split-K partial sums of small-batch launches (allocated on the first one)
+    int graph_mode = 0; unsigned long gclock = 0; GraphSlot gslots[SRT_GRAPH_SLOTS] = {};
     // DSP
-    float *preWin, *postWin; float2* twiddle;
-    float2* spec; float2* spec2; float* mag; float* masks; float* frames;   // spec2: residual spectrum of the CLI chain (on first use)
-    size_t rows_cap, frames_rows;
-    int last_ntiles;
+    float *preWin = nullptr, *postWin = nullptr; float2* twiddle = nullptr;
+    float2* spec = nullptr; float2* spec2 = nullptr; float* mag = nullptr; float* masks = nullptr;   // spec2: residual spectrum of the CLI chain (on first use)
+    size_t rows_cap = 0;
     // multichannel Wiener filter (srt_wiener.hip, srtSetWiener): allocated for max_tiles when it is switched on (or by the first srtIstftWiener)
-    int wiener;                                        // EM iterations applied by srtSeparate / srtSeparateEx, 0: off
-    int wiener_last;                                   // iterations of the last filtered call: the R tables srtCopyTensor("wiener_cov") can return
-    float* wslab;                                      // statistics partials + block maxima
-    float* wtab;                                       // R tables, weight sums, a
-    float2* wspec;                                     // filtered spectra [n_stems][2][rows][SRT_SPEC_LD]
+    int wiener = 0;                                    // EM iterations applied by srtSeparate / srtSeparateEx, 0: off
+    float* wslab = nullptr;                            // statistics partials + block maxima
+    float* wtab = nullptr;                             // R tables, weight sums, a
+    float2* wspec = nullptr;                           // filtered spectra [n_stems][2][rows][SRT_SPEC_LD]
     // packed batches of tracks (srtSeparateBatch): the device track table (max_tiles rows: every track takes at least one tile) and a ring of pinned
     // host slots it is uploaded from, each reused only after the copy from it issued SRT_BATCH_SLOTS calls earlier has completed (bev)
-    SrtBatchTrack* btab; SrtBatchTrack* bpin;
-    hipEvent_t bev[SRT_BATCH_SLOTS]; bool bused[SRT_BATCH_SLOTS]; int bslot;
+    SrtBatchTrack* btab = nullptr; SrtBatchTrack* bpin = nullptr;
+    hipEvent_t bev[SRT_BATCH_SLOTS] = {}; bool bused[SRT_BATCH_SLOTS] = {}; int bslot = 0;
     // timing
-    bool timing; std::vector<TimingEntry> tlog;
+    bool timing = false; std::vector<TimingEntry> tlog;
 };
 
 const char* srtLastError(void) { return g_err; }
@@ -198,16 +201,11 @@ static void free_all(srt_engine* e)
 {
     free_graphs(e);
     free_staging(e);
-    if (e->coeff_all) hipFree(e->coeff_all);
-    for (int i = 0; i < 6; ++i) { if (e->wpack16_down[i]) hipFree(e->wpack16_down[i]); if (e->wpack16_up[i]) hipFree(e->wpack16_up[i]); }
-    if (e->ws) hipFree(e->ws);
-    if (e->wpack2_d1) hipFree(e->wpack2_d1);
-    if (e->wpack2_u5) hipFree(e->wpack2_u5);
-    if (e->wpack16cs_u5) hipFree(e->wpack16cs_u5);
-    for (int i = 0; i < 6; ++i) { if (e->wino_u[i]) hipFree(e->wino_u[i]); if (e->wino_e[i]) hipFree(e->wino_e[i]); if (e->act32[i]) hipFree(e->act32[i]); }
-    for (int i = 0; i < 6; ++i) { if (e->wpack_down[i]) hipFree(e->wpack_down[i]); if (e->wpack_up[i]) hipFree(e->wpack_up[i]); }
-    for (int i = 0; i < 6; ++i) { if (e->raw[i]) hipFree(e->raw[i]); if (e->up[i]) hipFree(e->up[i]); if (i < 5 && e->act16buf[i]) hipFree(e->act16buf[i]); }
-    void* misc[] = { e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->frames, e->wslab, e->wtab, e->wspec, e->btab };
+    for (int i = 0; i < 6; ++i) {
+        void* layer[] = { e->wpack16_down[i], e->wpack16_up[i], e->wino_u[i], e->wino_e[i], e->act32[i], e->wpack_down[i], e->wpack_up[i], e->raw[i], e->up[i], i < 5 ? e->act16buf[i] : nullptr };
+        for (void* m : layer) if (m) hipFree(m);
+    }
+    void* misc[] = { e->coeff_all, e->ws, e->wpack2_d1, e->wpack2_u5, e->wpack16cs_u5, e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->wslab, e->wtab, e->wspec, e->btab };
     for (void* m : misc) if (m) hipFree(m);
     if (e->bpin) hipHostFree(e->bpin);
     for (hipEvent_t ev : e->bev) if (ev) hipEventDestroy(ev);
@@ -230,23 +228,10 @@ int srtCreate(const srt_config* cfg, void* stream, srt_engine** out)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-3, "srtCreate: no HIP device (this library has no CPU path)");
     srt_engine* e = new srt_engine();
-    memset(&e->hs, 0, sizeof e->hs);
-    e->ws = nullptr; e->ws_floats = 0;
-    e->graph_mode = 0; e->gclock = 0; memset(e->gslots, 0, sizeof e->gslots);
     if (hipGetDevice(&e->device) != hipSuccess) { delete e; return fail(-3, "srtCreate: no current HIP device"); }
-    memset(e->wpack16_down, 0, sizeof e->wpack16_down); memset(e->wpack16_up, 0, sizeof e->wpack16_up);
-    memset(e->wino_u, 0, sizeof e->wino_u); memset(e->wino_u_stem, 0, sizeof e->wino_u_stem);
-    memset(e->wino_e, 0, sizeof e->wino_e); memset(e->wino_e_stem, 0, sizeof e->wino_e_stem); memset(e->act32, 0, sizeof e->act32);
-    e->wpack16cs_u5 = nullptr; e->last_c8 = false; e->last_c8_l1 = false; e->masks16_req = e->last_masks16 = false; e->up6_stale = 0; e->up6_s0 = 0;
-    e->coeff_all = nullptr; e->wpack2_d1 = e->wpack2_u5 = nullptr; memset(e->wpack_down, 0, sizeof e->wpack_down); memset(e->wpack_up, 0, sizeof e->wpack_up);
-    memset(e->have_coeff, 0, sizeof e->have_coeff);
-    memset(e->raw, 0, sizeof e->raw); memset(e->up, 0, sizeof e->up); memset(e->act16buf, 0, sizeof e->act16buf);
-    e->preWin = e->postWin = nullptr; e->twiddle = nullptr; e->spec = nullptr; e->spec2 = nullptr; e->mag = e->masks = e->frames = nullptr;
-    e->wiener = e->wiener_last = 0; e->wslab = e->wtab = nullptr; e->wspec = nullptr;
-    e->btab = e->bpin = nullptr; memset(e->bev, 0, sizeof e->bev); memset(e->bused, 0, sizeof e->bused); e->bslot = 0;
     e->cfg = *cfg;
     { const char* bi = getenv("SPLEETERRT_BATCH_INVARIANT"); if (bi && bi[0] == '1') e->cfg.batch_invariant = 1; }
-    e->stream = (hipStream_t)stream; e->lo = make_layout(); e->timing = false; e->last_ntiles = cfg->max_tiles;
+    e->stream = (hipStream_t)stream; e->lo = make_layout(); e->last.ntiles = cfg->max_tiles;
     if (e->lo.total != SRT_COEFF_FLOATS) { delete e; return fail(-4, "internal: weight layout size mismatch"); }
     const size_t S = cfg->n_stems, NT = cfg->max_tiles, HW = (size_t)cfg->T * cfg->F;
 #define EALLOC(ptr, nfloats) do { if (hipMalloc((void**)&(ptr), (nfloats) * sizeof(float)) != hipSuccess) { free_all(e); delete e; return fail(-2, "srtCreate: hipMalloc failed"); } } while (0)
@@ -299,7 +284,6 @@ int srtCreate(const srt_config* cfg, void* stream, srt_engine** out)
     EALLOC(e->spec, 2 * 2 * e->rows_cap * SRT_SPEC_LD);
     EALLOC(e->mag, NT * 2 * HW);
     EALLOC(e->masks, S * NT * 2 * HW);
-    e->frames_rows = 0;                                 // windowed-frame scratch is allocated on first use (ensure_frames)
 #undef EALLOC
     // tables: same formulas and float rounding as InitSTFT (stftFix.c:302-313)
     std::vector<float> pre(SRT_FFT), post(SRT_FFT), tw(2 * SRT_FFT), sig(1026);
@@ -430,13 +414,13 @@ static void ensure_ws(srt_engine* e, size_t instances)
     else { e->ws = nullptr; (void)hipGetLastError(); }
 }
 
-// GraphKey::layout: one bit per layout switch the forward reads per call, set where the switch is on (unset or not "0")
-static int graph_layout_switches()
+SrtSwitches srt_read_switches()
 {
-    static const char* const names[] = { "SPLEETERRT_C8", "SPLEETERRT_C8L1", "SPLEETERRT_D1F16", "SPLEETERRT_M16" };
-    int bits = 0;
-    for (int i = 0; i < 4; ++i) { const char* v = getenv(names[i]); if (!(v && v[0] == '0')) bits |= 1 << i; }
-    return bits;
+    SrtSwitches sw;
+#define SRT_SW_READ(field, name, dflt, rule) { const char* v = getenv(name); sw.field = SRT_SW_##rule == SRT_SW_FLAG ? !(v && v[0] == '0') : (SRT_SW_##rule == SRT_SW_INT_NONEMPTY ? v && v[0] : v != nullptr) ? atoi(v) : dflt; }
+    SRT_SWITCH_TABLE(SRT_SW_READ)
+#undef SRT_SW_READ
+    return sw;
 }
 
 // Run `issue` (a function that only enqueues work on e->stream) through the graph cache when graph mode is on.  `valid` says
@@ -452,7 +436,9 @@ static int run_graphed(srt_engine* e, const GraphKey& key, bool valid, F&& issue
         if (g.exec && !memcmp(&g.key, &key, sizeof key)) {
             g.used = ++e->gclock;
             HIPCHK(hipGraphLaunch(g.exec, e->stream));
-            e->last_c8 = g.c8; e->last_c8_l1 = g.c8_l1; e->last_masks16 = g.masks16;
+            const int tables = e->last.wiener_last;
+            e->last = g.left;
+            if (!key.wiener) e->last.wiener_last = tables;                  // a sequence without the filter leaves the R tables of an earlier call as they are
             return 0;
         }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -483,14 +469,229 @@ static int run_graphed(srt_engine* e, const GraphKey& key, bool valid, F&& issue
     if (v->exec) hipGraphExecDestroy(v->exec);
     if (v->graph) hipGraphDestroy(v->graph);
     v->key = key; v->graph = graph; v->exec = exec; v->used = ++e->gclock;
-    v->c8 = e->last_c8; v->c8_l1 = e->last_c8_l1; v->masks16 = e->last_masks16;
+    v->left = e->last;
     HIPCHK(hipGraphLaunch(exec, e->stream));
     return 0;
 }
 
+static bool stream_capturing(const srt_engine* e) { hipStreamCaptureStatus cap = hipStreamCaptureStatusNone; if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap); return cap != hipStreamCaptureStatusNone; }
+
+// Graph-mode preamble of srtForward / srtSeparateEx: completes `valid` with the weights, allocates the split-K workspace (never inside a capture) and
+// starts the key - zeroed, the call kind and the switches; the caller adds its arguments.  Returns `valid`.
+static bool graph_prepare(srt_engine* e, bool valid, size_t ntiles, int kind, const SrtSwitches& sw, GraphKey* k)
+{
+    for (int s = 0; s < e->cfg.n_stems; ++s) valid = valid && e->have_coeff[s];
+    if (valid && !stream_capturing(e)) ensure_ws(e, (size_t)e->cfg.n_stems * ntiles);
+    memset(k, 0, sizeof *k);
+    k->kind = kind; k->sw = sw;
+    return valid;
+}
+
+// first element of (stem, tile) in an all-stem activation buffer of a forward over ntiles tiles (stem stride = ntiles instances of `per` elements);
+// the elements are halves or floats as the engine stores activations (eoff) unless f32 says floats (up6's plane, the fp32 copies, the masks)
+static inline float* stem_at(const srt_engine* e, float* buf, size_t per, int ntiles, int stem, bool f32 = false, int tile = 0) { const size_t el = ((size_t)stem * ntiles + tile) * per; return f32 ? buf + el : eoff(e, buf, el); }
+
+// One forward_range call: its stem range and tiles and the kernel-choice flags that follow from the launch size.
+struct ForwardPlan {
+    int ntiles, s0, ns;
+    // few: at most 16 instances keep the direct kernels and (small: when the workspace exists) cut the deep layers' K loops into slices; larger launches run up1..up5 and
+    // down3..down6 in Winograd form.  batch_invariant: never few (ws stays null) - the Winograd-form layers wherever the geometry fits, the same bits for a tile in any batch.
+    bool few, small;
+    // c8: fp16 storage, launches above 16 instances - the tensors between down2 and up5 are channel-interleaved by eight, the layers run on the DMA-fed kernels of srt_nn5.hip;
+    // c8_l1: ... and down1's two outputs (raw1: up6's skip input, act1: down2's input) where down1 runs on its streamed kernels.  (sw.c8 / sw.c8l1 = 0: planar, for A/B runs)
+    bool c8, c8_l1;
+    unsigned elu_mask;          // all stems go in one launch per layer; the activation pair is per stem (spleeter.c:130-139) and travels as a bit mask
+    const float* cbase;         // the first stem's coefficient blob
+};
+
+// what the two layer kinds set alike: channels, batch, the stems' weights, the split-K workspace of small launches
+static SrtConvParams layer_params(const srt_engine* e, const ForwardPlan& f, const LayerOff& L, float* wpack, size_t wpack_stem, int act)
+{
+    SrtConvParams p; memset(&p, 0, sizeof p);
+    p.Cin = L.cin; p.Cout = L.cout; p.ntiles = f.ntiles; p.nstems = f.ns;
+    p.wraw = f.cbase + L.w; p.bias = f.cbase + L.b; p.coeff_stem = SRT_COEFF_STRIDE;
+    p.wpack = wpack + (size_t)f.s0 * wpack_stem; p.wpack_stem = wpack_stem; p.CP = L.cp;
+    p.act = act; p.elu_mask = f.elu_mask; p.variant = e->cfg.variant;
+    if (f.small) { p.ws = e->ws; p.ws_floats = e->ws_floats; }
+    return p;
+}
+
+static SrtConvParams encoder_params(const srt_engine* e, const ForwardPlan& f, int i, const float* d_mag)
+{
+    const LayerOff& L = e->lo.down[i];
+    const int nt = f.ntiles;
+    SrtConvParams p = layer_params(e, f, L, e->wpack_down[i], e->wpack_down_stem[i], SRT_ACT_LEAKY);
+    p.H = e->cfg.T >> i; p.W = e->cfg.F >> i; p.CA = L.cin;
+    if (i == 0) { p.srcA = d_mag; p.srcA_stem = 0; p.srcA_tile = 2 * (size_t)e->cfg.T * e->cfg.F; }     // every stem reads the same magnitudes
+    else {
+        // the previous layer's conv + bias; its batch-norm + activation (spleeter.c:188) is applied by this layer while staging
+        const LayerOff& P = e->lo.down[i - 1];
+        p.srcA_stem = (size_t)nt * e->raw_tile[i - 1]; p.srcA_tile = e->raw_tile[i - 1];
+        if (e->act16) {            // fp16 storage: the producer wrote act(bn(raw)) as a second fp16 tensor (see srt_enc_f16)
+            p.srcA = stem_at(e, e->act16buf[i - 1], e->raw_tile[i - 1], nt, f.s0);
+            p.in16 = 1;
+        } else {
+            p.srcA = stem_at(e, e->raw[i - 1], e->raw_tile[i - 1], nt, f.s0);
+            p.inShift = f.cbase + P.bn; p.inScale = f.cbase + P.bn + P.cout;
+        }
+    }
+    p.srcB = p.srcA;
+    p.outRaw = stem_at(e, e->raw[i], e->raw_tile[i], nt, f.s0);
+    p.out16 = e->act16;
+    if (e->act16 && i < 5) {
+        p.outAct = stem_at(e, e->act16buf[i], e->raw_tile[i], nt, f.s0);
+        p.bnShift = f.cbase + L.bn; p.bnScale = f.cbase + L.bn + L.cout;
+    }
+    p.out_stem = (size_t)nt * e->raw_tile[i]; p.out_tile = e->raw_tile[i];
+    if (i == 0) p.c8out = f.c8_l1;
+    return p;
+}
+
+static SrtConvParams decoder_params(const srt_engine* e, const ForwardPlan& f, int i)
+{
+    const LayerOff& L = e->lo.up[i];
+    const int nt = f.ntiles, sk = 5 - i;                                        // skip tensor = raw[5-i]; up1 consumes conv6 alone
+    SrtConvParams p = layer_params(e, f, L, e->wpack_up[i], e->wpack_up_stem[i], SRT_ACT_RELU);
+    p.H = e->cfg.T >> (6 - i); p.W = e->cfg.F >> (6 - i);
+    p.srcA = stem_at(e, e->raw[sk], e->raw_tile[sk], nt, f.s0); p.srcA_stem = (size_t)nt * e->raw_tile[sk]; p.srcA_tile = e->raw_tile[sk];
+    if (i == 0) { p.CA = L.cin; p.srcB = p.srcA; p.srcB_stem = p.srcA_stem; p.srcB_tile = p.srcA_tile; }
+    else {
+        p.CA = L.cin / 2;
+        p.srcB = stem_at(e, e->up[i - 1], e->up_tile[i - 1], nt, f.s0); p.srcB_stem = (size_t)nt * e->up_tile[i - 1]; p.srcB_tile = e->up_tile[i - 1];
+    }
+    p.in16 = e->act16; p.out16 = e->act16 && i < 5;
+    p.c8srcB = f.c8 && i == 5;                                                  // up6 reads up5's C8 output
+    p.c8srcA = f.c8_l1 && i == 5;                                               // ... and down1's raw tensor, its skip input, where that is C8 too
+    p.bnShift = f.cbase + L.bn; p.bnScale = f.cbase + L.bn + L.cout;
+    p.outAct = stem_at(e, e->up[i], e->up_tile[i], nt, f.s0, i == 5);           // up6's output (the head's input) stays fp32
+    p.out_stem = (size_t)nt * e->up_tile[i]; p.out_tile = e->up_tile[i];
+    if (i == 4) { p.wpack2 = e->wpack2_u5 + (size_t)f.s0 * 64 * 15 * 32; p.wpack2_stem = 64 * 15 * 32; p.CP2 = 32; }
+    return p;
+}
+
+// Encoder layer i (spleeter.c:182-238) on the first kernel of the chain that covers it (launchers return 1 = not covered).
+// act_ready: act32[i-1] holds act(BN(raw_{i-1})) of this batch - carried from layer to layer.
+static int launch_encoder_layer(srt_engine* e, const SrtSwitches& sw, const ForwardPlan& f, int i, SrtConvParams p, bool& act_ready)
+{
+    const LayerOff& L = e->lo.down[i];
+    const int nt = f.ntiles;
+    // down1's own forms come first: on the fp16 MFMA, every stem of the call (up to six) in ONE launch (fp16 mode, C8 outputs: srt_down1_f16_kernel;
+    // sw.d1f16 = 0: the fp32-MFMA streamed kernels below, for A/B runs and the parity test)
+    if (i == 0 && f.c8_l1 && e->cfg.precision == SRT_PREC_F16 && p.nstems <= 6 && !f.small && sw.d1f16) {
+        p.stack = p.nstems;
+        TimerScope tg(e, "down1");
+        const int rg = srt_launch_down1_f16(p, e->stream);
+        if (rg == 0) return 0;
+        if (rg != 1) return fail(-2, "encoder launch failed");
+        p.stack = 0;
+    }
+    if (i == 0 && e->cfg.impl == SRT_IMPL_MFMA) {
+        // stem-stacked M: all stems of the group share the input.  More than four sub-networks (BASELINE configs[4]: five): the streamed down1 kernel stacks at
+        // most 4 x 16 rows, so the first whole groups of four go out here, each as its own stacked launch; the remainder (1..4 stems) follows the common chain
+        while (p.nstems > 4) {
+            SrtConvParams q = p;
+            q.nstems = 4; q.stack = 4; q.CP2 = 64; q.wpack2 = e->wpack2_d1; q.wpack2_stem = 0;
+            if (srt_launch_pack_stemstack(q.wraw, SRT_COEFF_STRIDE, 4, e->wpack2_d1, L.cin, L.cout, q.CP2, e->stream)) return fail(-2, "pack launch failed");
+            { TimerScope tg(e, "down1"); const int rg = srt_launch_enc2(q, sw, e->stream);
+              if (rg == 1) return fail(-4, "internal: stem-stacked down1 group not covered by its launcher");
+              if (rg) return fail(-2, "encoder launch failed"); }
+            p.nstems -= 4; p.elu_mask >>= 4;
+            p.wpack += 4 * p.wpack_stem;                                 // (the per-stem packs advance with the group too - the remainder launch's fallbacks read them)
+            p.wraw += 4 * (size_t)SRT_COEFF_STRIDE; p.bias += 4 * (size_t)SRT_COEFF_STRIDE;
+            if (p.bnShift) { p.bnShift += 4 * (size_t)SRT_COEFF_STRIDE; p.bnScale += 4 * (size_t)SRT_COEFF_STRIDE; }
+            p.outRaw = eoff(e, p.outRaw, 4 * p.out_stem);
+            if (p.outAct) p.outAct = eoff(e, p.outAct, 4 * p.out_stem);
+        }
+        p.stack = p.nstems; p.CP2 = (p.nstems * 16 + 63) / 64 * 64; p.wpack2 = e->wpack2_d1; p.wpack2_stem = 0;
+        if (srt_launch_pack_stemstack(p.wraw, SRT_COEFF_STRIDE, p.nstems, e->wpack2_d1, L.cin, L.cout, p.CP2, e->stream)) return fail(-2, "pack launch failed");
+    }
+    // Winograd form (down3..down6 of launches above 16 instances): reads the act(BN(raw)) copy of its input, writes raw + its own copy when
+    // the next layer runs here too.  The first such layer's input copy is written by the direct layer in front (producer_copy); only when that layer
+    // ran on a kernel without the second output does a batched bn+act pass over its raw tensor make the copy here.
+    const bool ewino = !f.few && e->wino_e[i] && !e->act16;
+    if (ewino) {
+        float* copy = stem_at(e, e->act32[i - 1], e->raw_tile[i - 1], nt, f.s0, true);
+        if (!act_ready) {
+            const LayerOff& P = e->lo.down[i - 1];
+            TimerScope ta(e, "actcopy");
+            if (srt_launch_bn_act_batch(stem_at(e, e->raw[i - 1], e->raw_tile[i - 1], nt, f.s0, true), copy, f.cbase + P.bn + P.cout, f.cbase + P.bn, SRT_COEFF_STRIDE,
+                                        f.ns, nt, P.cout, e->raw_tile[i - 1] / P.cout, SRT_ACT_LEAKY, f.elu_mask, e->cfg.variant, e->stream)) return fail(-2, "bn-act launch failed");
+        }
+        p.srcA = copy; p.srcB = p.srcA;
+        p.inScale = p.inShift = nullptr;
+    }
+    act_ready = ewino && i + 1 < 6 && e->wino_e[i + 1] != nullptr;          // this layer writes the next one's input copy
+    // a direct layer in front of the first Winograd-form one writes that copy itself (srt_enc_mfma2, second fp32 output): one more store per
+    // element instead of a pass that reads the tensor back.  Only the plain MFMA kernel does that (not the split-K one of small batches).
+    const bool next_wino = !f.few && i > 0 && i + 1 < 6 && e->wino_e[i + 1] && e->act32[i] && !e->act16;
+    const bool producer_copy = !ewino && next_wino && e->cfg.impl == SRT_IMPL_MFMA && !f.small && srt_enc_producer_copy();
+    if (act_ready || producer_copy) {
+        p.outAct = stem_at(e, e->act32[i], e->raw_tile[i], nt, f.s0, true);
+        p.bnShift = f.cbase + L.bn; p.bnScale = f.cbase + L.bn + L.cout;
+    }
+    TimerScope ts(e, ("down" + std::to_string(i + 1)).c_str());
+    int rc = 1;
+    if (ewino) {
+        rc = srt_launch_enc_wino(p, e->wino_e[i] + (size_t)f.s0 * e->wino_e_stem[i], e->wino_e_stem[i], e->stream);
+        if (rc == 1) return fail(-4, "internal: Winograd encoder layer not covered by its launcher");
+    }
+    if (rc == 1 && e->cfg.impl == SRT_IMPL_MFMA && e->wpack16_down[i]) {
+        p.wpack16 = e->wpack16_down[i] + (size_t)f.s0 * e->wpack16_down_stem[i]; p.wpack16_stem = e->wpack16_down_stem[i];
+        p.nsplit = e->cfg.precision == SRT_PREC_F16X2 ? 2 : 1;
+        if (f.c8 && (i >= 2 || f.c8_l1)) {                                  // C8 in, C8 out (srt_nn5.hip); down2 when down1 wrote its act copy C8
+            rc = srt_launch_enc_c8(p, sw, e->stream);
+            if (rc == 1) return fail(-4, "internal: C8 activation layout but no C8 kernel for an encoder layer");
+        } else {
+            p.c8out = f.c8 && i == 1;                                       // down2: planar input (down1's act copy), C8 outputs
+#ifdef SRT_TUNING
+            // timing experiment (wrong results): down2 on the C8 kernel as if its input were C8 - what moving down1's act copy to C8 would buy
+            static const bool d2c8 = []() { const char* v = getenv("SRT_TUNE_D2C8"); return v && v[0] == '1'; }();
+            if (d2c8 && p.c8out) rc = srt_launch_enc_c8(p, sw, e->stream); else
+#endif
+            rc = srt_launch_enc_f16(p, e->stream);
+        }
+    }
+    if (e->act16 && i > 0 && rc == 1) return fail(-4, "internal: fp16 activation storage but no fp16 kernel for an encoder layer");
+    if (rc == 1 && e->cfg.impl == SRT_IMPL_MFMA) { rc = srt_launch_enc2(p, sw, e->stream); if (rc == 0 && producer_copy) act_ready = true; }
+    if (rc < 0) return fail(-2, "encoder launch failed");
+    if (rc == 1 && srt_launch_enc(p, e->cfg.impl, e->stream)) return fail(-2, "encoder launch failed");
+    return 0;
+}
+
+// Decoder layer i (spleeter.c:239-294), the same protocol.  up6 runs together with the head where that form is covered: head_done.
+static int launch_decoder_layer(srt_engine* e, const SrtSwitches& sw, const ForwardPlan& f, int i, SrtConvParams p, const SrtHeadParams& head, bool& head_done)
+{
+    TimerScope ts(e, ("up" + std::to_string(i + 1)).c_str());
+    int rc = 1;
+    if (e->cfg.impl == SRT_IMPL_MFMA && e->wpack16_up[i]) {
+        p.wpack16 = e->wpack16_up[i] + (size_t)f.s0 * e->wpack16_up_stem[i]; p.wpack16_stem = e->wpack16_up_stem[i];
+        p.nsplit = e->cfg.precision == SRT_PREC_F16X2 ? 2 : 1;
+        if (f.c8 && i < 5) {                                                // C8 in, C8 out (up5: class-stacked weights)
+            p.wpack16cs = e->wpack16cs_u5 + (size_t)f.s0 * SRT_W16CS_U5; p.wpack16cs_stem = SRT_W16CS_U5;
+            rc = srt_launch_dec_c8(p, sw, e->stream);
+            if (rc == 1) return fail(-4, "internal: C8 activation layout but no C8 kernel for a decoder layer");
+        } else rc = srt_launch_dec_f16(p, e->stream);
+    }
+    if (i == 5) {                                                           // up6 + head in one pass where covered (srt_up6_head_kernel); the plane is then not stored
+        const unsigned bits = ((1u << f.ns) - 1u) << f.s0;
+        e->last.up6_fused &= ~bits;
+        if (e->cfg.impl == SRT_IMPL_MFMA && !e->graph_mode) {               // (graphs are for launches far below this form's threshold; lifting the gate changes what they record)
+            rc = srt_launch_up6_head(p, head, sw, e->stream);
+            if (rc == 0) { head_done = true; e->last.up6_fused |= bits; e->last.up6_params = p; e->last.up6_s0 = f.s0; }
+        }
+    }
+    if (e->act16 && i < 5 && rc == 1) return fail(-4, "internal: fp16 activation storage but no fp16 kernel for a decoder layer");
+    if (rc == 1 && e->wino_u[i] && (!f.few || srt_wino_force())) rc = srt_launch_dec_wino(p, e->wino_u[i] + (size_t)f.s0 * e->wino_u_stem[i], e->wino_u_stem[i], e->stream);
+    if (rc == 1 && e->cfg.impl == SRT_IMPL_MFMA) rc = srt_launch_dec2(p, e->stream);
+    if (rc < 0) return fail(-2, "decoder launch failed");
+    if (rc == 1 && srt_launch_dec(p, e->cfg.impl, e->stream)) return fail(-2, "decoder launch failed");
+    return 0;
+}
+
 // Sub-networks [s0, s0+ns) on ntiles tiles.  Buffers keep their all-stem layout (stem stride = ntiles instances), so a
-// later call for other stems of the same batch lands beside this one's results.
-static int forward_range(srt_engine* e, const float* d_mag, int ntiles, float* d_masks, int s0, int ns)
+// later call for other stems of the same batch lands beside this one's results.  masks16_req: the masks may leave as halves
+// (honoured only for the engine's own mask buffer and where the head kernel takes it; e->last.masks16 says what happened).
+static int forward_range(srt_engine* e, const SrtSwitches& sw, const float* d_mag, int ntiles, float* d_masks, int s0, int ns, bool masks16_req = false)
 {
     if (!e || !d_mag || !d_masks) return fail(-1, "srtForward: null argument");
     DeviceScope ds(e->device);
@@ -499,217 +700,33 @@ static int forward_range(srt_engine* e, const float* d_mag, int ntiles, float* d
     if (s0 < 0 || ns < 1 || s0 + ns > S) return fail(-1, "srtForward: stem range outside the engine's sub-networks");
     for (int s = s0; s < s0 + ns; ++s) if (!e->have_coeff[s]) return fail(-5, "srtForward: weights not set for every stem");
     const size_t HW = (size_t)T * F;
-    e->last_ntiles = ntiles;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
-    if (cap == hipStreamCaptureStatusNone) ensure_ws(e, (size_t)ns * ntiles);      // (no allocation inside a capture: callers pre-allocate)
-    // Kernel choice by launch size: at most 16 instances keep the direct kernels and (when the workspace exists) cut the deep layers' K loops
-    // into slices; larger launches run up1..up5 and down3..down6 in Winograd form.  batch_invariant: never split-K (ws stays null) and the
-    // Winograd-form layers whenever the layer geometry fits, whatever the batch - the same bits for a tile in any batch.
-    const bool few = (size_t)ns * ntiles <= 16 && !e->cfg.batch_invariant;
-    const bool small = few && e->ws;
-    // fp16 storage, launches above 16 instances: the tensors between down2 and up5 are kept channel-interleaved by eight and the layers run on the DMA-fed
-    // kernels of srt_nn5.hip (SPLEETERRT_C8=0: the planar kernels of srt_nn3.hip everywhere, for A/B runs)
-    const char* c8v = getenv("SPLEETERRT_C8");                                     // (read per forward: parity tests compare the two layouts inside one process)
-    const bool c8_env = !(c8v && c8v[0] == '0');
-    const bool c8 = e->act16 && !few && c8_env;
-    // ... and down1's two outputs (raw1: up6's skip input, act1: down2's input) where down1 runs on its streamed kernels (SPLEETERRT_C8L1=0: planar, for A/B runs)
-    const char* c8l1v = getenv("SPLEETERRT_C8L1");
-    const bool c8_l1 = c8 && !(c8l1v && c8l1v[0] == '0') && e->cfg.impl == SRT_IMPL_MFMA && srt_down1_c8_ok(T, F, ntiles, (size_t)ntiles * e->raw_tile[0]);
-    e->last_c8 = c8; e->last_c8_l1 = c8_l1; e->last_masks16 = false;
-    {
-        // all stems go in one launch per layer; the activation pair is per stem (spleeter.c:130-139) and travels as a bit mask
-        unsigned elu_mask = 0;
-        for (int s = 0; s < ns; ++s) if (e->cfg.stem_mode[s0 + s]) elu_mask |= 1u << s;
-        const int actE = SRT_ACT_LEAKY, actD = SRT_ACT_RELU;
-        const float* cbase = e->coeff_all + (size_t)s0 * SRT_COEFF_STRIDE;
-        char nm[32];
-        bool act_ready = false;                                                 // act32[i-1] holds act(BN(raw_{i-1})) of this batch
-        for (int i = 0; i < 6; ++i) {                                           // encoder (spleeter.c:182-238)
-            const LayerOff& L = e->lo.down[i];
-            SrtConvParams p; memset(&p, 0, sizeof p);
-            p.Cin = L.cin; p.Cout = L.cout; p.H = T >> i; p.W = F >> i; p.CA = L.cin; p.ntiles = ntiles; p.nstems = ns;
-            if (i == 0) { p.srcA = d_mag; p.srcA_stem = 0; p.srcA_tile = 2 * HW; }                 // every stem reads the same magnitudes
-            else {
-                // the previous layer's conv + bias; its batch-norm + activation (spleeter.c:188) is applied by this layer while staging
-                const LayerOff& P = e->lo.down[i - 1];
-                p.srcA_stem = (size_t)ntiles * e->raw_tile[i - 1]; p.srcA_tile = e->raw_tile[i - 1];
-                if (e->act16) {            // fp16 storage: the producer wrote act(bn(raw)) as a second fp16 tensor (see srt_enc_f16)
-                    p.srcA = eoff(e, e->act16buf[i - 1], (size_t)s0 * ntiles * e->raw_tile[i - 1]);
-                    p.in16 = 1;
-                } else {
-                    p.srcA = e->raw[i - 1] + (size_t)s0 * ntiles * e->raw_tile[i - 1];
-                    p.inShift = cbase + P.bn; p.inScale = cbase + P.bn + P.cout;
-                }
-            }
-            p.srcB = p.srcA;
-            p.wraw = cbase + L.w; p.bias = cbase + L.b;
-            p.coeff_stem = SRT_COEFF_STRIDE;
-            p.wpack = e->wpack_down[i] + (size_t)s0 * e->wpack_down_stem[i]; p.wpack_stem = e->wpack_down_stem[i];
-            p.CP = L.cp;
-            p.outRaw = eoff(e, e->raw[i], (size_t)s0 * ntiles * e->raw_tile[i]);
-            p.out16 = e->act16;
-            if (e->act16 && i < 5) {
-                p.outAct = eoff(e, e->act16buf[i], (size_t)s0 * ntiles * e->raw_tile[i]);
-                p.bnShift = cbase + L.bn; p.bnScale = cbase + L.bn + L.cout;
-            }
-            p.out_stem = (size_t)ntiles * e->raw_tile[i]; p.out_tile = e->raw_tile[i];
-            p.act = actE; p.elu_mask = elu_mask; p.variant = e->cfg.variant;
-            if (small) { p.ws = e->ws; p.ws_floats = e->ws_floats; }
-            if (i == 0) p.c8out = c8_l1;
-            // fp16 mode, C8 outputs: down1's products on the fp16 MFMA too, every stem of the call (up to six) in ONE launch (srt_down1_f16_kernel;
-            // SPLEETERRT_D1F16=0: the fp32-MFMA streamed kernels below, read per forward for A/B runs and the parity test)
-            if (i == 0 && c8_l1 && e->cfg.precision == SRT_PREC_F16 && p.nstems <= 6 && !small) {
-                const char* dv = getenv("SPLEETERRT_D1F16");
-                if (!(dv && dv[0] == '0')) {
-                    p.stack = p.nstems;
-                    TimerScope tg(e, "down1");
-                    const int rg = srt_launch_down1_f16(p, e->stream);
-                    if (rg == 0) continue;
-                    if (rg != 1) return fail(-2, "encoder launch failed");
-                    p.stack = 0;
-                }
-            }
-            if (i == 0 && e->cfg.impl == SRT_IMPL_MFMA) {                    // stem-stacked M: all stems of the group share the input
-                // more than four sub-networks (BASELINE configs[4]: five): the streamed down1 kernel stacks at most 4 x 16 rows, so the first whole groups of
-                // four go out here, each as its own stacked launch; the remainder (1..4 stems) follows the common path below
-                while (p.nstems > 4) {
-                    SrtConvParams q = p;
-                    q.nstems = 4; q.stack = 4; q.CP2 = 64; q.wpack2 = e->wpack2_d1; q.wpack2_stem = 0;
-                    if (srt_launch_pack_stemstack(q.wraw, SRT_COEFF_STRIDE, 4, e->wpack2_d1, L.cin, L.cout, q.CP2, e->stream)) return fail(-2, "pack launch failed");
-                    { TimerScope tg(e, "down1"); const int rg = srt_launch_enc2(q, e->stream);
-                      if (rg == 1) return fail(-4, "internal: stem-stacked down1 group not covered by its launcher");
-                      if (rg) return fail(-2, "encoder launch failed"); }
-                    p.nstems -= 4; p.elu_mask >>= 4;
-                    p.wpack += 4 * p.wpack_stem;                                 // (the per-stem packs advance with the group too - the remainder launch's fallbacks read them)
-                    p.wraw += 4 * (size_t)SRT_COEFF_STRIDE; p.bias += 4 * (size_t)SRT_COEFF_STRIDE;
-                    if (p.bnShift) { p.bnShift += 4 * (size_t)SRT_COEFF_STRIDE; p.bnScale += 4 * (size_t)SRT_COEFF_STRIDE; }
-                    p.outRaw = eoff(e, p.outRaw, 4 * p.out_stem);
-                    if (p.outAct) p.outAct = eoff(e, p.outAct, 4 * p.out_stem);
-                }
-                p.stack = p.nstems; p.CP2 = (p.nstems * 16 + 63) / 64 * 64; p.wpack2 = e->wpack2_d1; p.wpack2_stem = 0;
-                if (srt_launch_pack_stemstack(p.wraw, SRT_COEFF_STRIDE, p.nstems, e->wpack2_d1, L.cin, L.cout, p.CP2, e->stream)) return fail(-2, "pack launch failed");
-            }
-            // Winograd form (down3..down6 of launches above 16 instances): reads the act(BN(raw)) copy of its input, writes raw + its own copy when
-            // the next layer runs here too.  The first such layer's input copy is written by the direct layer in front (below); only when that layer
-            // ran on a kernel without the second output does a batched bn+act pass over its raw tensor make the copy here.
-            const bool ewino = !few && e->wino_e[i] && !e->act16;
-            if (ewino) {
-                if (!act_ready) {
-                    const LayerOff& P = e->lo.down[i - 1];
-                    TimerScope ta(e, "actcopy");
-                    if (srt_launch_bn_act_batch(e->raw[i - 1] + (size_t)s0 * ntiles * e->raw_tile[i - 1], e->act32[i - 1] + (size_t)s0 * ntiles * e->raw_tile[i - 1],
-                                                cbase + P.bn + P.cout, cbase + P.bn, SRT_COEFF_STRIDE, ns, ntiles, P.cout, e->raw_tile[i - 1] / P.cout,
-                                                actE, elu_mask, e->cfg.variant, e->stream)) return fail(-2, "bn-act launch failed");
-                }
-                p.srcA = e->act32[i - 1] + (size_t)s0 * ntiles * e->raw_tile[i - 1]; p.srcB = p.srcA;
-                p.inScale = p.inShift = nullptr;
-                act_ready = i + 1 < 6 && e->wino_e[i + 1] != nullptr;       // this layer writes the next one's input copy
-                if (act_ready) {
-                    p.outAct = e->act32[i] + (size_t)s0 * ntiles * e->raw_tile[i];
-                    p.bnShift = cbase + L.bn; p.bnScale = cbase + L.bn + L.cout;
-                }
-            } else act_ready = false;
-            // a direct layer in front of the first Winograd-form one writes that copy itself (srt_enc_mfma2, second fp32 output): one more store per
-            // element instead of a pass that reads the tensor back.  Only the plain MFMA kernel does that (not the split-K one of small batches).
-            const bool next_wino = !few && i > 0 && i + 1 < 6 && e->wino_e[i + 1] && e->act32[i] && !e->act16;
-            bool producer_copy = false;
-            if (!ewino && next_wino && e->cfg.impl == SRT_IMPL_MFMA && !small && srt_enc_producer_copy()) {
-                p.outAct = e->act32[i] + (size_t)s0 * ntiles * e->raw_tile[i];
-                p.bnShift = cbase + L.bn; p.bnScale = cbase + L.bn + L.cout;
-                producer_copy = true;
-            }
-            snprintf(nm, sizeof nm, "down%d", i + 1);
-            TimerScope ts(e, nm);
-            int rc2 = 1;
-            if (ewino) {
-                rc2 = srt_launch_enc_wino(p, e->wino_e[i] + (size_t)s0 * e->wino_e_stem[i], e->wino_e_stem[i], e->stream);
-                if (rc2 == 1) return fail(-4, "internal: Winograd encoder layer not covered by its launcher");
-            }
-            if (rc2 == 1 && e->cfg.impl == SRT_IMPL_MFMA && e->wpack16_down[i]) {
-                p.wpack16 = e->wpack16_down[i] + (size_t)s0 * e->wpack16_down_stem[i]; p.wpack16_stem = e->wpack16_down_stem[i];
-                p.nsplit = e->cfg.precision == SRT_PREC_F16X2 ? 2 : 1;
-                if (c8 && (i >= 2 || c8_l1)) {                                  // C8 in, C8 out (srt_nn5.hip); down2 when down1 wrote its act copy C8
-                    rc2 = srt_launch_enc_c8(p, e->stream);
-                    if (rc2 == 1) return fail(-4, "internal: C8 activation layout but no C8 kernel for an encoder layer");
-                } else {
-                    p.c8out = c8 && i == 1;                                     // down2: planar input (down1's act copy), C8 outputs
-#ifdef SRT_TUNING
-                    // timing experiment (wrong results): down2 on the C8 kernel as if its input were C8 - what moving down1's act copy to C8 would buy
-                    static const bool d2c8 = []() { const char* v = getenv("SRT_TUNE_D2C8"); return v && v[0] == '1'; }();
-                    if (d2c8 && p.c8out) rc2 = srt_launch_enc_c8(p, e->stream); else
-#endif
-                    rc2 = srt_launch_enc_f16(p, e->stream);
-                }
-            }
-            if (e->act16 && i > 0 && rc2 == 1) return fail(-4, "internal: fp16 activation storage but no fp16 kernel for an encoder layer");
-            if (rc2 == 1 && e->cfg.impl == SRT_IMPL_MFMA) { rc2 = srt_launch_enc2(p, e->stream); if (rc2 == 0 && producer_copy) act_ready = true; }
-            if (rc2 < 0) return fail(-2, "encoder launch failed");
-            if (rc2 == 1 && srt_launch_enc(p, e->cfg.impl, e->stream)) return fail(-2, "encoder launch failed");
-        }
-        SrtHeadParams head; memset(&head, 0, sizeof head);                     // head (spleeter.c:295-300)
-        head.H = T; head.W = F; head.ntiles = ntiles; head.nstems = ns;
-        head.src = e->up[5] + (size_t)s0 * ntiles * e->up_tile[5]; head.src_stem = (size_t)ntiles * e->up_tile[5]; head.src_tile = e->up_tile[5];
-        head.w = cbase + e->lo.head_w; head.bias = cbase + e->lo.head_b; head.coeff_stem = SRT_COEFF_STRIDE;
-        head.out = d_masks + (size_t)s0 * ntiles * 2 * HW; head.out_stem = (size_t)ntiles * 2 * HW; head.out_tile = 2 * HW;
-        head.variant = e->cfg.variant;
-        head.out16 = e->masks16_req && d_masks == e->masks && srt_head_out16_ok(head);
-        e->last_masks16 = head.out16 != 0;
-        bool head_done = false;
-        for (int i = 0; i < 6; ++i) {                                           // decoder (spleeter.c:239-294)
-            const LayerOff& L = e->lo.up[i];
-            SrtConvParams p; memset(&p, 0, sizeof p);
-            p.Cin = L.cin; p.Cout = L.cout; p.H = T >> (6 - i); p.W = F >> (6 - i); p.ntiles = ntiles; p.nstems = ns;
-            const int sk = 5 - i;                                               // skip tensor = raw[5-i]; up1 consumes conv6 alone
-            p.srcA = eoff(e, e->raw[sk], (size_t)s0 * ntiles * e->raw_tile[sk]); p.srcA_stem = (size_t)ntiles * e->raw_tile[sk]; p.srcA_tile = e->raw_tile[sk];
-            if (i == 0) { p.CA = L.cin; p.srcB = p.srcA; p.srcB_stem = p.srcA_stem; p.srcB_tile = p.srcA_tile; }
-            else {
-                p.CA = L.cin / 2;
-                p.srcB = eoff(e, e->up[i - 1], (size_t)s0 * ntiles * e->up_tile[i - 1]); p.srcB_stem = (size_t)ntiles * e->up_tile[i - 1]; p.srcB_tile = e->up_tile[i - 1];
-            }
-            p.in16 = e->act16; p.out16 = e->act16 && i < 5;
-            p.c8srcB = c8 && i == 5;                                            // up6 reads up5's C8 output
-            p.c8srcA = c8_l1 && i == 5;                                         // ... and down1's raw tensor, its skip input, where that is C8 too
-            p.wraw = cbase + L.w; p.bias = cbase + L.b; p.bnShift = cbase + L.bn; p.bnScale = cbase + L.bn + L.cout;
-            p.coeff_stem = SRT_COEFF_STRIDE;
-            p.wpack = e->wpack_up[i] + (size_t)s0 * e->wpack_up_stem[i]; p.wpack_stem = e->wpack_up_stem[i];
-            p.CP = L.cp;
-            p.outRaw = nullptr;
-            p.outAct = i < 5 ? eoff(e, e->up[i], (size_t)s0 * ntiles * e->up_tile[i]) : e->up[i] + (size_t)s0 * ntiles * e->up_tile[i];
-            p.out_stem = (size_t)ntiles * e->up_tile[i]; p.out_tile = e->up_tile[i];
-            p.act = actD; p.elu_mask = elu_mask; p.variant = e->cfg.variant;
-            if (small) { p.ws = e->ws; p.ws_floats = e->ws_floats; }
-            if (i == 4) { p.wpack2 = e->wpack2_u5 + (size_t)s0 * 64 * 15 * 32; p.wpack2_stem = 64 * 15 * 32; p.CP2 = 32; }
-            snprintf(nm, sizeof nm, "up%d", i + 1);
-            TimerScope ts(e, nm);
-            int rc2 = 1;
-            if (e->cfg.impl == SRT_IMPL_MFMA && e->wpack16_up[i]) {
-                p.wpack16 = e->wpack16_up[i] + (size_t)s0 * e->wpack16_up_stem[i]; p.wpack16_stem = e->wpack16_up_stem[i];
-                p.nsplit = e->cfg.precision == SRT_PREC_F16X2 ? 2 : 1;
-                if (c8 && i < 5) {                                              // C8 in, C8 out (up5: class-stacked weights)
-                    p.wpack16cs = e->wpack16cs_u5 + (size_t)s0 * SRT_W16CS_U5; p.wpack16cs_stem = SRT_W16CS_U5;
-                    rc2 = srt_launch_dec_c8(p, e->stream);
-                    if (rc2 == 1) return fail(-4, "internal: C8 activation layout but no C8 kernel for a decoder layer");
-                } else rc2 = srt_launch_dec_f16(p, e->stream);
-            }
-            if (i == 5) {                                                       // up6 + head in one pass where covered (srt_up6_head_kernel); the plane is then not stored
-                const unsigned bits = ((1u << ns) - 1u) << s0;
-                e->up6_stale &= ~bits;
-                if (e->cfg.impl == SRT_IMPL_MFMA && !e->graph_mode) {              // (graph replays would not maintain up6_stale; graphs are for launches far below this form's threshold)
-                    rc2 = srt_launch_up6_head(p, head, e->stream);
-                    if (rc2 == 0) { head_done = true; e->up6_stale |= bits; e->up6_params = p; e->up6_s0 = s0; }
-                }
-            }
-            if (e->act16 && i < 5 && rc2 == 1) return fail(-4, "internal: fp16 activation storage but no fp16 kernel for a decoder layer");
-            if (rc2 == 1 && e->wino_u[i] && (!few || srt_wino_force())) rc2 = srt_launch_dec_wino(p, e->wino_u[i] + (size_t)s0 * e->wino_u_stem[i], e->wino_u_stem[i], e->stream);
-            if (rc2 == 1 && e->cfg.impl == SRT_IMPL_MFMA) rc2 = srt_launch_dec2(p, e->stream);
-            if (rc2 < 0) return fail(-2, "decoder launch failed");
-            if (rc2 == 1 && srt_launch_dec(p, e->cfg.impl, e->stream)) return fail(-2, "decoder launch failed");
-        }
-        if (!head_done) {
-            TimerScope ts(e, "up7");
-            if (srt_launch_head(head, e->stream)) return fail(-2, "head launch failed");
-        }
+    if (!stream_capturing(e)) ensure_ws(e, (size_t)ns * ntiles);                // (no allocation inside a capture: callers pre-allocate)
+    ForwardPlan f;
+    f.ntiles = ntiles; f.s0 = s0; f.ns = ns; f.elu_mask = 0;
+    f.few = (size_t)ns * ntiles <= 16 && !e->cfg.batch_invariant;
+    f.small = f.few && e->ws;
+    f.c8 = e->act16 && !f.few && sw.c8;
+    f.c8_l1 = f.c8 && sw.c8l1 && e->cfg.impl == SRT_IMPL_MFMA && srt_down1_c8_ok(T, F, ntiles, (size_t)ntiles * e->raw_tile[0], sw);
+    for (int s = 0; s < ns; ++s) if (e->cfg.stem_mode[s0 + s]) f.elu_mask |= 1u << s;
+    f.cbase = e->coeff_all + (size_t)s0 * SRT_COEFF_STRIDE;
+    e->last.ntiles = ntiles; e->last.c8 = f.c8; e->last.c8_l1 = f.c8_l1; e->last.masks16 = false;
+    bool act_ready = false;
+    for (int i = 0; i < 6; ++i)
+        if (const int rc = launch_encoder_layer(e, sw, f, i, encoder_params(e, f, i, d_mag), act_ready)) return rc;
+    SrtHeadParams head; memset(&head, 0, sizeof head);                         // head (spleeter.c:295-300)
+    head.H = T; head.W = F; head.ntiles = ntiles; head.nstems = ns;
+    head.src = stem_at(e, e->up[5], e->up_tile[5], ntiles, s0, true); head.src_stem = (size_t)ntiles * e->up_tile[5]; head.src_tile = e->up_tile[5];
+    head.w = f.cbase + e->lo.head_w; head.bias = f.cbase + e->lo.head_b; head.coeff_stem = SRT_COEFF_STRIDE;
+    head.out = stem_at(e, d_masks, 2 * HW, ntiles, s0, true); head.out_stem = (size_t)ntiles * 2 * HW; head.out_tile = 2 * HW;
+    head.variant = e->cfg.variant;
+    head.out16 = masks16_req && d_masks == e->masks && srt_head_out16_ok(head);
+    e->last.masks16 = head.out16 != 0;
+    bool head_done = false;
+    for (int i = 0; i < 6; ++i)
+        if (const int rc = launch_decoder_layer(e, sw, f, i, decoder_params(e, f, i), head, head_done)) return rc;
+    if (!head_done) {
+        TimerScope ts(e, "up7");
+        if (srt_launch_head(head, e->stream)) return fail(-2, "head launch failed");
     }
     return 0;
 }
@@ -717,18 +734,13 @@ static int forward_range(srt_engine* e, const float* d_mag, int ntiles, float* d
 int srtForward(srt_engine* e, const float* d_mag, int ntiles, float* d_masks)
 {
     if (!e) return fail(-1, "srtForward: null argument");
-    if (!e->graph_mode) return forward_range(e, d_mag, ntiles, d_masks, 0, e->cfg.n_stems);
+    const SrtSwitches sw = srt_read_switches();
+    if (!e->graph_mode) return forward_range(e, sw, d_mag, ntiles, d_masks, 0, e->cfg.n_stems);
     DeviceScope ds(e->device);
-    bool valid = d_mag && d_masks && ntiles >= 1 && ntiles <= e->cfg.max_tiles;
-    for (int s = 0; s < e->cfg.n_stems; ++s) valid = valid && e->have_coeff[s];
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
-    if (valid && cap == hipStreamCaptureStatusNone) ensure_ws(e, (size_t)e->cfg.n_stems * ntiles);
-    GraphKey k; memset(&k, 0, sizeof k);
-    k.kind = 1; k.p0 = d_mag; k.p2 = d_masks; k.ntiles = ntiles; k.ns = e->cfg.n_stems; k.layout = graph_layout_switches();
-    const int rc = run_graphed(e, k, valid, [&]() { return forward_range(e, d_mag, ntiles, d_masks, 0, e->cfg.n_stems); });
-    if (!rc) e->last_ntiles = ntiles;
-    return rc;
+    GraphKey k;
+    const bool valid = graph_prepare(e, d_mag && d_masks && ntiles >= 1 && ntiles <= e->cfg.max_tiles, ntiles, 1, sw, &k);
+    k.p0 = d_mag; k.p2 = d_masks; k.ntiles = ntiles; k.ns = e->cfg.n_stems;
+    return run_graphed(e, k, valid, [&]() { return forward_range(e, sw, d_mag, ntiles, d_masks, 0, e->cfg.n_stems); });
 }
 
 int srtPrepareForward(srt_engine* e, const float* d_mag, int ntiles, float* d_masks)
@@ -755,7 +767,7 @@ int srtReleaseStaging(srt_engine* e)
 int srtForwardStems(srt_engine* e, const float* d_mag, int ntiles, float* d_masks, int stem0, int nstems)
 {
     if (!e) return fail(-1, "srtForward: null argument");
-    return forward_range(e, d_mag, ntiles, d_masks, stem0, nstems);
+    return forward_range(e, srt_read_switches(), d_mag, ntiles, d_masks, stem0, nstems);
 }
 
 int srtRatioMask(srt_engine* e, float* d_masks, int ntiles)
@@ -799,31 +811,35 @@ int srtStft(srt_engine* e, const float* d_L, const float* d_R, size_t n, float* 
     return srtStftEx(e, d_L, d_R, n, srtStftFrames(n), srtStftRows(n), d_spec, d_mag);
 }
 
-static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out, bool ratio, bool masks16 = false);
-// (the public entry applies the masks as they are given: srtRatioMask is its caller's business)
-int srtIstft(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out) { return istft_issue(e, d_spec, rows, d_masks, d_out, false); }
-static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out, bool ratio, bool masks16)
+// inverse transform of `nstems` stems of one spectrum under their masks (nullptr: all-ones) into [nstems][2][srtIstftLength(rows)]; oob: per stem, the weight of bins >= F
+static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out)
 {
-    if (!e || !d_spec || !d_out) return fail(-1, "srtIstft: null argument");
     DeviceScope ds(e->device);
-    if (rows < 1) return fail(-1, "srtIstft: no rows");
     const int T = e->cfg.T;
-    if (d_masks && (rows + T - 1) / T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstft: rows exceed max_tiles * T");
     SrtIstftParams p; memset(&p, 0, sizeof p);
-    p.spec = (const float2*)d_spec; p.spec_ch_stride = rows * SRT_SPEC_LD;
-    p.frames = (int)rows; p.masks = d_masks; p.nstems = e->cfg.n_stems; p.ntiles = (int)((rows + T - 1) / T);
+    p.spec = spec; p.spec_ch_stride = rows * SRT_SPEC_LD;
+    p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = (int)((rows + T - 1) / T);
     p.T = T; p.F = e->cfg.F;
-    for (int s = 0; s < SRT_MAX_STEMS; ++s) p.oob[s] = e->cfg.oob_weight[s];
-    p.ratio = ratio ? 1 : 0;
-    p.masks16 = masks16 ? 1 : 0;
+    for (int s = 0; s < nstems; ++s) p.oob[s] = oob[s];
+    p.ratio = ratio ? 1 : 0; p.masks16 = masks16 ? 1 : 0;
     p.frames_out = nullptr; p.out = d_out; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
     TimerScope ts(e, "istft");
     if (srt_launch_istft(p, e->stream)) return fail(-2, "istft launch failed");
     return 0;
 }
+// ONE stem's mask (or none) into a [2][len] destination
+static int istft_one(srt_engine* e, const float2* spec, size_t rows, const float* mask_stem, float oob, float* d_dst) { return istft_launch(e, spec, rows, mask_stem, 1, &oob, false, false, d_dst); }
+static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out, bool ratio, bool masks16 = false)
+{
+    if (!e || !d_spec || !d_out) return fail(-1, "srtIstft: null argument");
+    if (rows < 1) return fail(-1, "srtIstft: no rows");
+    if (d_masks && (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstft: rows exceed max_tiles * T");
+    return istft_launch(e, (const float2*)d_spec, rows, d_masks, e->cfg.n_stems, e->cfg.oob_weight, ratio, masks16, d_out);
+}
+// (the public entry applies the masks as they are given: srtRatioMask is its caller's business)
+int srtIstft(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out) { return istft_issue(e, d_spec, rows, d_masks, d_out, false); }
 
 // ---- multichannel Wiener filter (srt_wiener.hip)
-static int istft_one(srt_engine* e, const float2* spec, size_t rows, const float* mask_stem, float oob, float* d_dst, const char* tag);
 static size_t wiener_slab_floats(const srt_engine* e) { return (size_t)SRT_WIENER_MAX_CHUNKS * e->cfg.n_stems * 4 * e->cfg.F + (size_t)SRT_WIENER_MAX_CHUNKS * SRT_WIENER_BINBLK; }
 static size_t wiener_tab_floats(const srt_engine* e) { return (size_t)SRT_WIENER_MAX_ITERS * e->cfg.n_stems * e->cfg.F * 5 + 4; }
 
@@ -832,9 +848,7 @@ static size_t wiener_tab_floats(const srt_engine* e) { return (size_t)SRT_WIENER
 static int ensure_wiener_ws(srt_engine* e)
 {
     if (e->wslab && e->wtab && e->wspec) return 0;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
-    if (cap != hipStreamCaptureStatusNone) return fail(-1, "Wiener filter: workspace not allocated (call srtSetWiener before capturing)");
+    if (stream_capturing(e)) return fail(-1, "Wiener filter: workspace not allocated (call srtSetWiener before capturing)");
     SrtSetupLock setup;
     if (!e->wslab) HIPCHK(hipMalloc((void**)&e->wslab, wiener_slab_floats(e) * sizeof(float)));
     if (!e->wtab) {
@@ -863,10 +877,10 @@ static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const f
         { TimerScope ts(e, "wiener_cov"); if (srt_launch_wiener_finalize(w, pass, e->stream)) return fail(-2, "Wiener finalize launch failed"); }
     }
     { TimerScope ts(e, "wiener_filter"); if (srt_launch_wiener_filter(w, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
-    e->wiener_last = iters;
+    e->last.wiener_last = iters;
     const size_t len = srtIstftLength(rows);
     for (int j = 0; j < S; ++j) {
-        const int rc = istft_one(e, e->wspec + (size_t)j * w.out_stem, rows, nullptr, e->cfg.oob_weight[j], d_out + (size_t)j * 2 * len, "istft");
+        const int rc = istft_one(e, e->wspec + (size_t)j * w.out_stem, rows, nullptr, e->cfg.oob_weight[j], d_out + (size_t)j * 2 * len);
         if (rc) return rc;
     }
     return 0;
@@ -896,22 +910,22 @@ int srtSetWiener(srt_engine* e, int iterations)
 
 int srt_engine_wiener(const srt_engine* e) { return e->wiener; }
 
-static int separate_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
+// fp16 mode: the masks between the head and the inverse transform - the engine's own buffer, never seen by a caller - are halves where both kernels take them
+// (srt_head_rows_kernel<.., true> / srt_istft_ola3_kernel<.., true>: F <= 1024, no ratio mask, no Wiener filter (fp32 masks), head launches of >= 1024
+// workgroups: srt_head_out16_ok; sw.m16 = 0: floats, for A/B runs)
+static bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw) { return e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && !e->wiener && e->cfg.F <= 1024 && sw.m16; }
+
+static int separate_issue(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
 {
     const int T = e->cfg.T;
     const size_t ntiles = (rows + T - 1) / T;
     int rc = srtStftEx(e, d_L, d_R, n, frames, rows, (float*)e->spec, e->mag);
     if (rc) return rc;
-    // fp16 mode: the masks between the head and the inverse transform - the engine's own buffer, never seen by a caller - are halves where both kernels take them
-    // (srt_head_rows_kernel<.., true> / srt_istft_ola3_kernel<.., true>: F <= 1024, no ratio mask, head launches of >= 1024 workgroups; SPLEETERRT_M16=0: floats, for A/B runs)
-    const char* m16v = getenv("SPLEETERRT_M16");
-    e->masks16_req = e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && !e->wiener && e->cfg.F <= 1024 && !(m16v && m16v[0] == '0');
-    rc = forward_range(e, e->mag, (int)ntiles, e->masks, 0, e->cfg.n_stems);
-    e->masks16_req = false;
+    rc = forward_range(e, sw, e->mag, (int)ntiles, e->masks, 0, e->cfg.n_stems, masks16_wanted(e, sw));
     if (rc) return rc;
-    if (e->wiener) return wiener_issue(e, (const float*)e->spec, rows, e->masks, e->wiener, d_out);     // (fp32 masks: masks16_req is off while the filter is on)
+    if (e->wiener) return wiener_issue(e, (const float*)e->spec, rows, e->masks, e->wiener, d_out);
     // ratio_mask: normalised across the stems inside the inverse kernel's prologue (srt_ratio_of, srt_dsp.hip) - e->masks keeps the raw sigmoid masks
-    return istft_issue(e, (const float*)e->spec, rows, e->masks, d_out, e->cfg.ratio_mask != 0, e->last_masks16);
+    return istft_issue(e, (const float*)e->spec, rows, e->masks, d_out, e->cfg.ratio_mask != 0, e->last.masks16);
 }
 
 int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
@@ -920,19 +934,13 @@ int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, s
     const int T = e->cfg.T;
     const size_t ntiles = (rows + T - 1) / T;
     if (rows < 1 || ntiles > (size_t)e->cfg.max_tiles) return fail(-1, "srtSeparate: signal longer than max_tiles * T frames");
-    if (!e->graph_mode) return separate_issue(e, d_L, d_R, n, frames, rows, d_out);
+    const SrtSwitches sw = srt_read_switches();
+    if (!e->graph_mode) return separate_issue(e, sw, d_L, d_R, n, frames, rows, d_out);
     DeviceScope ds(e->device);
-    bool valid = d_L && d_R && d_out && frames <= rows;
-    for (int s = 0; s < e->cfg.n_stems; ++s) valid = valid && e->have_coeff[s];
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
-    if (valid && cap == hipStreamCaptureStatusNone) ensure_ws(e, (size_t)e->cfg.n_stems * ntiles);
-    GraphKey k; memset(&k, 0, sizeof k);
-    k.kind = 2; k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.layout = graph_layout_switches(); k.wiener = e->wiener;
-    const int rc = run_graphed(e, k, valid, [&]() { return separate_issue(e, d_L, d_R, n, frames, rows, d_out); });
-    if (!rc) e->last_ntiles = (int)ntiles;
-    if (!rc && e->wiener) e->wiener_last = e->wiener;                       // (a replay runs no host code)
-    return rc;
+    GraphKey k;
+    const bool valid = graph_prepare(e, d_L && d_R && d_out && frames <= rows, ntiles, 2, sw, &k);
+    k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.wiener = e->wiener;
+    return run_graphed(e, k, valid, [&]() { return separate_issue(e, sw, d_L, d_R, n, frames, rows, d_out); });
 }
 
 int srtSetGraphMode(srt_engine* e, int enable)
@@ -941,21 +949,6 @@ int srtSetGraphMode(srt_engine* e, int enable)
     DeviceScope ds(e->device);
     if (!enable) { hipStreamSynchronize(e->stream); free_graphs(e); }
     e->graph_mode = enable != 0;
-    return 0;
-}
-
-// iSTFT of one spectrum under ONE stem's mask (or none) into a [2][len] destination
-static int istft_one(srt_engine* e, const float2* spec, size_t rows, const float* mask_stem, float oob, float* d_dst, const char* tag)
-{
-    DeviceScope ds(e->device);
-    const int T = e->cfg.T;
-    SrtIstftParams p; memset(&p, 0, sizeof p);
-    p.spec = spec; p.spec_ch_stride = rows * SRT_SPEC_LD;
-    p.frames = (int)rows; p.masks = mask_stem; p.nstems = 1; p.ntiles = (int)((rows + T - 1) / T);
-    p.T = T; p.F = e->cfg.F; p.oob[0] = oob;
-    p.frames_out = nullptr; p.out = d_dst; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
-    TimerScope ts(e, tag);
-    if (srt_launch_istft(p, e->stream)) return fail(-2, "istft launch failed");
     return 0;
 }
 
@@ -984,16 +977,17 @@ static int cli_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n
     const size_t HW2 = 2 * (size_t)T * e->cfg.F;
     float* mask0 = e->masks;                                  // stem stride of this batch = ntiles instances
     float* mask1 = e->masks + ntiles * HW2;
+    const SrtSwitches sw = srt_read_switches();
     int rc = srtStftEx(e, d_L, d_R, n, frames, rows, (float*)e->spec, e->mag);
     if (rc) return rc;
     if (stems == 2) {
-        if ((rc = forward_range(e, e->mag, (int)ntiles, e->masks, 1, 1))) return rc;
-        if ((rc = istft_one(e, e->spec, rows, mask1, e->cfg.oob_weight[1], d_out, "istft"))) return rc;
+        if ((rc = forward_range(e, sw, e->mag, (int)ntiles, e->masks, 1, 1))) return rc;
+        if ((rc = istft_one(e, e->spec, rows, mask1, e->cfg.oob_weight[1], d_out))) return rc;
         return residual_now ? cli_time_residual(e, d_L, d_R, n, stems, d_out, len) : 0;
     }
     if (!e->spec2) HIPCHK(hipMalloc((void**)&e->spec2, (size_t)2 * e->rows_cap * SRT_SPEC_LD * sizeof(float2)));
-    if ((rc = forward_range(e, e->mag, (int)ntiles, e->masks, 0, 1))) return rc;
-    if ((rc = istft_one(e, e->spec, rows, mask0, e->cfg.oob_weight[0], d_out, "istft"))) return rc;                 // Drum
+    if ((rc = forward_range(e, sw, e->mag, (int)ntiles, e->masks, 0, 1))) return rc;
+    if ((rc = istft_one(e, e->spec, rows, mask0, e->cfg.oob_weight[0], d_out))) return rc;                 // Drum
     {
         SrtResidualParams r; memset(&r, 0, sizeof r);
         r.spec = e->spec; r.res = e->spec2; r.spec_ch_stride = rows * SRT_SPEC_LD; r.rows = (int)rows; r.T = T; r.F = e->cfg.F;
@@ -1001,9 +995,9 @@ static int cli_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n
         TimerScope ts(e, "residual");
         if (srt_launch_residual(r, e->stream)) return fail(-2, "residual launch failed");
     }
-    if ((rc = istft_one(e, e->spec2, rows, nullptr, 1.0f, d_out + 4 * len, "istft"))) return rc;                      // accompaniment + vocal
-    if ((rc = forward_range(e, e->mag, (int)ntiles, e->masks, 1, 1))) return rc;
-    if ((rc = istft_one(e, e->spec2, rows, mask1, e->cfg.oob_weight[1], d_out + 2 * len, "istft"))) return rc;       // Vocal
+    if ((rc = istft_one(e, e->spec2, rows, nullptr, 1.0f, d_out + 4 * len))) return rc;                      // accompaniment + vocal
+    if ((rc = forward_range(e, sw, e->mag, (int)ntiles, e->masks, 1, 1))) return rc;
+    if ((rc = istft_one(e, e->spec2, rows, mask1, e->cfg.oob_weight[1], d_out + 2 * len))) return rc;       // Vocal
     return residual_now ? cli_time_residual(e, d_L, d_R, n, stems, d_out, len) : 0;
 }
 
@@ -1138,6 +1132,7 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
     if (!e) return fail(-1, "srtSeparateBatch: null engine");
     DeviceScope ds(e->device);
     if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "srtSeparateBatch: need ntracks >= 1 and the four track arrays");
+    const SrtSwitches sw = srt_read_switches();
     char what[48];
     for (int k = 0; k < ntracks; ++k) {
         snprintf(what, sizeof what, "%d", k);
@@ -1153,9 +1148,7 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
         return fail(-1, "srtSeparateBatch: the tracks take %s tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", what);
     }
     for (int s = 0; s < S; ++s) if (!e->have_coeff[s]) return fail(-5, "srtSeparateBatch: weights not set for every stem");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (e->stream) (void)hipStreamIsCapturing(e->stream, &cap);
-    if (cap != hipStreamCaptureStatusNone) return fail(-1, "srtSeparateBatch: not capturable (the track table is uploaded per call): call it outside stream capture");
+    if (stream_capturing(e)) return fail(-1, "srtSeparateBatch: not capturable (the track table is uploaded per call): call it outside stream capture");
     int rc = ensure_batch(e);
     if (rc) return rc;
     // the table goes up in stream order from a pinned slot; the slot's previous copy (SRT_BATCH_SLOTS calls ago) must have left it first
@@ -1184,14 +1177,11 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
         if (srt_launch_stft_batch(p, e->btab, ntracks, g, e->stream)) return fail(-2, "batched stft launch failed");
     }
     // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue
-    const char* m16v = getenv("SPLEETERRT_M16");
-    e->masks16_req = e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && e->cfg.F <= 1024 && !(m16v && m16v[0] == '0');
-    rc = forward_range(e, e->mag, (int)total, e->masks, 0, S);
-    e->masks16_req = false;
+    rc = forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, masks16_wanted(e, sw));
     if (rc) return rc;
     SrtIstftParams q; memset(&q, 0, sizeof q);
     q.spec = e->spec; q.spec_ch_stride = ch_stride; q.frames = (int)(total * T);
-    q.masks = e->masks; q.masks16 = e->last_masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)total; q.T = T; q.F = F;
+    q.masks = e->masks; q.masks16 = e->last.masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)total; q.T = T; q.F = F;
     for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
     q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
     q.tab = tables_of(e);
@@ -1310,7 +1300,7 @@ int srtCopyTensor(srt_engine* e, const char* name, int stem, int tile, float* h_
     if (!name[0]) return fail(-1, "srtCopyTensor: empty tensor name");
     if (!strcmp(name, "wiener_cov")) {                                       // R_j of iteration `tile` [F][4], its weight sums [F], a [1]
         const int S = e->cfg.n_stems, F = e->cfg.F, it = tile;
-        if (!e->wtab || stem < 0 || stem >= S || it < 1 || it > e->wiener_last) return fail(-1, "srtCopyTensor: wiener_cov needs a stem and 1 <= iteration <= the iterations of the last filtered call");
+        if (!e->wtab || stem < 0 || stem >= S || it < 1 || it > e->last.wiener_last) return fail(-1, "srtCopyTensor: wiener_cov needs a stem and 1 <= iteration <= the iterations of the last filtered call");
         if ((size_t)5 * F + 1 > max_floats) return fail(-1, "srtCopyTensor: destination too small");
         const size_t o = (size_t)(it - 1) * S * F + (size_t)stem * F;
         const float* wsum = e->wtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4;
@@ -1320,51 +1310,45 @@ int srtCopyTensor(srt_engine* e, const char* name, int stem, int tile, float* h_
         HIPCHK(hipMemcpy(h_dst + 5 * F, wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F, sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
-    if (stem < 0 || stem >= e->cfg.n_stems || tile < 0 || tile >= e->last_ntiles) return fail(-1, "srtCopyTensor: stem / tile outside the last forward batch");
+    const ForwardRecord& last = e->last;
+    if (stem < 0 || stem >= e->cfg.n_stems || tile < 0 || tile >= last.ntiles) return fail(-1, "srtCopyTensor: stem / tile outside the last forward batch");
     const int idx = name[strlen(name) - 1] - '1';
-    const float* base = nullptr; size_t per = 0; bool derived = false;
+    float* base = nullptr; size_t per = 0; bool derived = false;
     if (!strncmp(name, "conv", 4) && idx >= 0 && idx < 6) { base = e->raw[idx]; per = e->raw_tile[idx]; }
     else if (!strncmp(name, "act", 3) && idx >= 0 && idx < 5) { base = e->raw[idx]; per = e->raw_tile[idx]; derived = true; }
     else if (!strncmp(name, "up", 2) && idx >= 0 && idx < 6) { base = e->up[idx]; per = e->up_tile[idx]; }
     else return fail(-1, "srtCopyTensor: unknown tensor %s", name);
     if (per > max_floats) return fail(-1, "srtCopyTensor: destination too small");
-    // instance stride = ntiles of the last srtForward call
-    if (name[0] == 'u' && idx == 5 && ((e->up6_stale >> stem) & 1u)) {       // the fused launch kept the plane in LDS: materialise the tap with the plain up6 kernel
-        if (stem < e->up6_s0 || stem >= e->up6_s0 + e->up6_params.nstems) return fail(-1, "srtCopyTensor: up6 of this stem was not stored by the fused up6 + head launch of an earlier stem range");
-        if (srt_launch_dec(e->up6_params, e->cfg.impl, e->stream)) return fail(-2, "up6 launch failed");
+    if (name[0] == 'u' && idx == 5 && ((last.up6_fused >> stem) & 1u)) {     // the fused launch kept the plane in LDS: materialise the tap with the plain up6 kernel
+        if (stem < last.up6_s0 || stem >= last.up6_s0 + last.up6_params.nstems) return fail(-1, "srtCopyTensor: up6 of this stem was not stored by the fused up6 + head launch of an earlier stem range");
+        if (srt_launch_dec(last.up6_params, e->cfg.impl, e->stream)) return fail(-2, "up6 launch failed");
     }
     const bool halves = e->act16 && !(name[0] == 'u' && idx == 5);           // up6 (the head's input) is always fp32
-    const float* src = halves ? eoff(e, const_cast<float*>(base), ((size_t)stem * e->last_ntiles + tile) * per) : base + ((size_t)stem * e->last_ntiles + tile) * per;
-    float* tmp = nullptr;
+    const float* src = stem_at(e, base, per, last.ntiles, stem, !halves, tile);     // instance stride = ntiles of the last forward
+    struct DeviceTemp { float* p = nullptr; ~DeviceTemp() { if (p) hipFree(p); } } buf;     // the tap's two conversion stages [2][per], freed on every exit
     // raw2..raw6 (and the act taps derived from them) and up1..up5 of a large fp16-storage batch are channel-interleaved by eight (srt_nn5.hip): the tap
     // is returned planar, like every other
-    const bool c8 = halves && e->last_c8 && ((name[0] == 'u') ? idx <= 4 : (idx >= 1 || e->last_c8_l1));
-    float* planar = nullptr;
+    const bool c8 = halves && last.c8 && ((name[0] == 'u') ? idx <= 4 : (idx >= 1 || last.c8_l1));
+    const bool halves_in = halves && !c8;
+    if (c8 || derived || halves_in) HIPCHK(hipMalloc((void**)&buf.p, 2 * per * sizeof(float)));
+    float* const planar = buf.p; float* const tmp = buf.p + per;
     if (c8) {
         const int C = name[0] == 'u' ? DEC_CH[idx][1] : ENC_CH[idx][1];
-        HIPCHK(hipMalloc((void**)&planar, per * sizeof(float)));
-        if (srt_launch_c8_to_float(src, planar, C, per / C, e->stream)) { hipFree(planar); return fail(-2, "conversion launch failed"); }
+        if (srt_launch_c8_to_float(src, planar, C, per / C, e->stream)) return fail(-2, "conversion launch failed");
         src = planar;
     }
-    const bool halves_in = halves && !c8;
     if (derived) {
         // "actN" is no longer stored: the next encoder layer applies act(bn(convN)) while staging.  Materialise it for the tap.
         const LayerOff& L = e->lo.down[idx];
         const float* c = e->coeff_all + (size_t)stem * SRT_COEFF_STRIDE;
-        const hipError_t em = hipMalloc((void**)&tmp, per * sizeof(float));
-        if (em != hipSuccess) { if (planar) hipFree(planar); return fail(-2, "HIP error: %s", hipGetErrorString(em)); }
-        if (srt_launch_bn_act(src, halves_in, tmp, c + L.bn + L.cout, c + L.bn, L.cout, per / L.cout, e->cfg.stem_mode[stem] ? SRT_ACT_ELU : SRT_ACT_LEAKY, e->cfg.variant, e->stream)) { hipFree(tmp); if (planar) hipFree(planar); return fail(-2, "bn-act launch failed"); }
+        if (srt_launch_bn_act(src, halves_in, tmp, c + L.bn + L.cout, c + L.bn, L.cout, per / L.cout, e->cfg.stem_mode[stem] ? SRT_ACT_ELU : SRT_ACT_LEAKY, e->cfg.variant, e->stream)) return fail(-2, "bn-act launch failed");
         src = tmp;
     } else if (halves_in) {
-        HIPCHK(hipMalloc((void**)&tmp, per * sizeof(float)));
-        if (srt_launch_half_to_float(src, tmp, per, e->stream)) { hipFree(tmp); return fail(-2, "conversion launch failed"); }
+        if (srt_launch_half_to_float(src, tmp, per, e->stream)) return fail(-2, "conversion launch failed");
         src = tmp;
     }
-    hipError_t er = hipStreamSynchronize(e->stream);
-    if (er == hipSuccess) er = hipMemcpy(h_dst, src, per * sizeof(float), hipMemcpyDeviceToHost);
-    if (tmp) hipFree(tmp);
-    if (planar) hipFree(planar);
-    HIPCHK(er);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    HIPCHK(hipMemcpy(h_dst, src, per * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
 }
 

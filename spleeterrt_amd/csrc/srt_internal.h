@@ -26,6 +26,28 @@ struct SrtSetupLock { SrtSetupLock(); ~SrtSetupLock(); };
 
 enum { SRT_ACT_LEAKY = 0, SRT_ACT_RELU = 1, SRT_ACT_ELU = 2 };
 
+// Run-time switches of a forward (A/B runs and the parity tests, which flip them inside one process; INTEGRATION.md mirrors this table).  Every entry point
+// that issues a forward reads them ONCE (srt_read_switches, srt_engine.hip: the only place these names reach getenv) and hands the struct down to forward_range
+// and the launchers that consult it.  The graph cache keys on the whole struct: a flipped switch captures a new graph instead of replaying the old form.
+// Rules - FLAG: 1 unless the value starts with '0';  INT: atoi of the value when the variable is set;  INT_NONEMPTY: atoi of a non-empty value;  else the
+// default.  Every field is an int (no padding: keys that hold the struct are compared with memcmp).     X(field, environment name, default, rule)
+#define SRT_SWITCH_TABLE(X) \
+    X(c8,        "SPLEETERRT_C8",        1,  FLAG)          /* fp16 storage, > 16 instances: down2..up5 channel-interleaved by eight (srt_nn5.hip); 0: planar (srt_nn3.hip) */ \
+    X(c8l1,      "SPLEETERRT_C8L1",      1,  FLAG)          /* ... and down1's two outputs where it runs on its streamed kernels; 0: planar */ \
+    X(d1f16,     "SPLEETERRT_D1F16",     1,  FLAG)          /* fp16 mode, C8 outputs: down1 on the fp16 MFMA, all stems in one launch; 0: the fp32-MFMA streamed kernels */ \
+    X(m16,       "SPLEETERRT_M16",       1,  FLAG)          /* fp16 mode: srtSeparate's own masks as halves (masks16_wanted); 0: floats */ \
+    X(d1s2,      "SPLEETERRT_D1S2",      1,  FLAG)          /* down1 of one or two stems on the two-wave streamed kernel; 0: the tiled kernel (and no C8 down1: srt_down1_c8_ok) */ \
+    X(fuse_head, "SPLEETERRT_FUSE_HEAD", -1, INT_NONEMPTY)  /* up6 + head in one pass: 0 never, 1 wherever covered, -1 (unset): where it measured faster */ \
+    X(c8_wgs,    "SPLEETERRT_C8_WGS",    0,  INT)           /* workgroups per C8 launch, overrides the table and the measurement; 0: those */ \
+    X(c8_nr2,    "SPLEETERRT_C8_NR2",    1,  INT)           /* bit 0: two sub-tiles per wave in up2..up4; 0: one everywhere */ \
+    X(c8_wres,   "SPLEETERRT_C8_WRES",   1,  INT)           /* the weight slab stays in LDS where a unit is one K chunk; 0: moved every step */ \
+    X(c8_tune,   "SPLEETERRT_C8_TUNE",   1,  INT)           /* the first launch of a C8 layer shape measures its workgroup count; 0: table values, 2: and print the choice */
+enum { SRT_SW_FLAG, SRT_SW_INT, SRT_SW_INT_NONEMPTY };
+#define SRT_SW_FIELD(field, name, dflt, rule) int field;
+struct SrtSwitches { SRT_SWITCH_TABLE(SRT_SW_FIELD) };
+#undef SRT_SW_FIELD
+SrtSwitches srt_read_switches();
+
 // Every kernel launch of the library goes through SRT_LAUNCH: besides launching, it notes WHICH kernel (host stub pointer + the
 // launch expression's text) the calling thread launched first since srt_kernel_note_reset().  The engine's per-launch timers keep
 // that with each entry, so srtGetTimingKernels() reports the kernel that actually ran a layer (the dispatch depends on batch
@@ -105,15 +127,15 @@ int  srt_head_out16_ok(const SrtHeadParams& p);      // the launch runs on srt_h
 int  srt_launch_enc(const SrtConvParams& p, int impl, hipStream_t s);
 int  srt_launch_dec(const SrtConvParams& p, int impl, hipStream_t s);
 int  srt_launch_head(const SrtHeadParams& p, hipStream_t s);
-int  srt_launch_up6_head(const SrtConvParams& p, const SrtHeadParams& h, hipStream_t s);   // both layers in one pass; 1: not covered / switched off
+int  srt_launch_up6_head(const SrtConvParams& p, const SrtHeadParams& h, const SrtSwitches& sw, hipStream_t s);   // both layers in one pass; 1: not covered / switched off
 int  srt_launch_bn_act(const float* raw, int raw16, float* out, const float* scale, const float* shift, int C, size_t hw, int kind, int variant, hipStream_t s);
 int  srt_launch_half_to_float(const void* src, float* dst, size_t n, hipStream_t s);
 int  srt_launch_pack_enc(const float* w, float* wp, int Cin, int Cout, int CP, hipStream_t s);
 int  srt_launch_pack_dec(const float* w, float* wp, int Cin, int Cout, int CP, hipStream_t s);
 // v2 kernels (srt_nn2.hip): return 1 when the layer geometry is not covered (caller falls back to the v1 kernels)
-int  srt_launch_enc2(const SrtConvParams& p, hipStream_t s);
+int  srt_launch_enc2(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s);
 int  srt_launch_down1_f16(const SrtConvParams& p, hipStream_t s);   // fp16 mode, C8 outputs: down1 on the fp16 MFMA, p.stack = 1..6 stems in one launch (1: not covered)
-int  srt_down1_c8_ok(int H, int W, int ntiles, size_t out_stem);   // fp16 storage: down1 of this batch runs on the streamed kernels, which can write raw1 / act1 C8
+int  srt_down1_c8_ok(int H, int W, int ntiles, size_t out_stem, const SrtSwitches& sw);   // fp16 storage: down1 of this batch runs on the streamed kernels, which can write raw1 / act1 C8
 int  srt_launch_dec2(const SrtConvParams& p, hipStream_t s);
 int  srt_launch_pack_stemstack(const float* coeff_w0, size_t coeff_stem, int nstems, float* wp2, int Cin, int Cout, int CP2, hipStream_t s);
 int  srt_launch_pack_classstack(const float* w, float* wp2, int Cin, int Cout, hipStream_t s);
@@ -122,8 +144,8 @@ int  srt_launch_enc_f16(const SrtConvParams& p, hipStream_t s);
 int  srt_launch_dec_f16(const SrtConvParams& p, hipStream_t s);
 int  srt_launch_pack16(const float* w, uint16_t* wp16, int Cin, int Cout, int CP, int dec, hipStream_t s);
 // C8-form fp16 kernels (srt_nn5.hip): return 1 when the layer is not covered
-int  srt_launch_enc_c8(const SrtConvParams& p, hipStream_t s);
-int  srt_launch_dec_c8(const SrtConvParams& p, hipStream_t s);
+int  srt_launch_enc_c8(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s);
+int  srt_launch_dec_c8(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s);
 int  srt_launch_pack16_classstack(const float* w, uint16_t* wp, int Cin, int Cout, hipStream_t s);
 int  srt_launch_c8_to_float(const void* src, float* dst, int C, size_t hw, hipStream_t s);
 int  srt_launch_count_not_fp16(const float* w, size_t n, unsigned* d_count, hipStream_t s);   // weights the fp16 pack would round (SRT_PREC_F16X2 guard)

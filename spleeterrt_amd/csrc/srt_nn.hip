@@ -1309,11 +1309,10 @@ int srt_launch_dec(const SrtConvParams& p, int impl, hipStream_t s)
 }
 
 // up6 + head in one pass (srt_up6_head_kernel).  Returns 1 when the launch is not covered or the form is switched off: the caller then launches the two layers
-// separately.  SPLEETERRT_FUSE_HEAD: 0 never, 1 whenever covered, unset: where it measured faster.
-int srt_launch_up6_head(const SrtConvParams& p, const SrtHeadParams& h, hipStream_t s)
+// separately.  sw.fuse_head (SPLEETERRT_FUSE_HEAD): 0 never, 1 whenever covered, unset: where it measured faster.
+int srt_launch_up6_head(const SrtConvParams& p, const SrtHeadParams& h, const SrtSwitches& sw, hipStream_t s)
 {
-    const char* fv = getenv("SPLEETERRT_FUSE_HEAD");                          // (read per launch: the parity tests switch it inside one process)
-    const int mode = fv && fv[0] ? atoi(fv) : -1;
+    const int mode = sw.fuse_head;
     if (mode == 0 || (mode < 0 && !SRT_FUSE_HEAD_DEFAULT(p.in16))) return 1;
     if (p.Cout != 1 || p.Cin != 32 || p.CA != 16 || p.out16 || h.out16 || !p.srcA || !p.srcB || (p.H & 1) || p.W % (p.in16 ? 8 : 4)) return 1;
     // up5's output in C8 (large fp16-storage batches, srt_nn5.hip): not covered.  A BC8 instantiation of this kernel (the same three edits as in srt_up6_stream_kernel) was

@@ -1325,15 +1325,14 @@ static int launch_dec16(const SrtConvParams& p, hipStream_t s)
 
 // fp16 storage: can down1 of a T x F batch of ntiles tiles write its outputs C8, whatever the number of stems?  Only the streamed forms do (four-wave: groups of three
 // or four stems, two-wave: one or two), so this is their launch condition (see srt_launch_enc2) - H, W = the layer's INPUT size.
-int srt_down1_c8_ok(int H, int W, int ntiles, size_t out_stem)
+int srt_down1_c8_ok(int H, int W, int ntiles, size_t out_stem, const SrtSwitches& sw)
 {
-    const char* dv = getenv("SPLEETERRT_D1S2");
     const int Ho = H / 2, Wo = W / 2;
-    return SRT_DOWN1_STREAM_DEFAULT && !(dv && dv[0] == '0') && W % 4 == 0 && Wo % 64 == 0 && Ho % 8 == 0 && (long)(Wo / 64) * ntiles >= 384 &&
+    return SRT_DOWN1_STREAM_DEFAULT && sw.d1s2 && W % 4 == 0 && Wo % 64 == 0 && Ho % 8 == 0 && (long)(Wo / 64) * ntiles >= 384 &&
            (size_t)4 * out_stem < ((size_t)1 << 32) && (size_t)8 * H * W < 0x7fffffffu;
 }
 
-int srt_launch_enc2(const SrtConvParams& p, hipStream_t s)
+int srt_launch_enc2(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s)
 {
     if (p.W % 4) return 1;
     const int Wo = p.W / 2;
@@ -1343,9 +1342,8 @@ int srt_launch_enc2(const SrtConvParams& p, hipStream_t s)
             // one M tile (one or two stems), batches that give every CU four two-wave column workgroups: the streamed form with NW = 2, each column cut into two runs
             const int Ho = p.H / 2;
             const bool h16 = p.out16 && p.outAct && p.bnScale && p.bnShift;
-            const char* dv = getenv("SPLEETERRT_D1S2");                        // (=0: the tiled kernel - A/B runs and the parity test, which switches it inside one process)
-            const bool d1s2 = !(dv && dv[0] == '0');
-            if (d1s2 && SRT_DOWN1_STREAM_DEFAULT && p.CP2 >= 64 && (!p.out16 || h16) && !p.ws && Wo % 64 == 0 && Ho % 8 == 0 && (long)(Wo / 64) * p.ntiles * 2 >= 768 &&
+            // (sw.d1s2 = 0: the tiled kernel - A/B runs and the parity test, which switches it inside one process)
+            if (sw.d1s2 && SRT_DOWN1_STREAM_DEFAULT && p.CP2 >= 64 && (!p.out16 || h16) && !p.ws && Wo % 64 == 0 && Ho % 8 == 0 && (long)(Wo / 64) * p.ntiles * 2 >= 768 &&
                 (size_t)p.stack * p.out_stem < ((size_t)1 << 32) && (size_t)8 * p.H * p.W < 0x7fffffffu) {
                 SrtConvParams q = p;
                 q.rowsplit = 2;

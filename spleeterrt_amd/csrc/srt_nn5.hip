@@ -725,14 +725,10 @@ __global__ void __launch_bounds__(512, WPE) srt_dec_c8(const SrtConvParams p, in
 static int c8_abl() { const char* t = getenv("SRT_TUNE_C8"); return t ? atoi(t) : 0; }
 #define C8_ABL_CASES(X) X(3) X(4) X(8) X(16) X(12) X(32)
 #endif
-static int c8_env(const char* name, int dflt)
-{
-    const char* t = getenv(name);
-    return t ? atoi(t) : dflt;
-}
 // Two decoder workgroups per CU (WPE = 4) measured EQUAL to one (round 6, same box, 5 stems: step 5.006 vs 4.997 ms; up3 0.301 vs 0.322, up5 0.499 vs 0.514, the rest
 // within 2 % either way): the second barrier domain does not buy the overlap the ablation matrix prices.  Tuning library only (SRT_TUNE_C8WPE=4).
 #ifdef SRT_TUNING
+static int c8_env(const char* name, int dflt) { const char* t = getenv(name); return t ? atoi(t) : dflt; }
 static bool c8_wpe4() { static const bool v = c8_env("SRT_TUNE_C8WPE", 1) == 4; return v; }
 #endif
 // Workgroups per launch (each walks its run of units as one stream of K steps).  Measured per layer at 64 tiles x 5 stems (round 6, SPLEETERRT_C8_WGS = 512 .. 4096 on one
@@ -741,7 +737,7 @@ static bool c8_wpe4() { static const bool v = c8_env("SRT_TUNE_C8WPE", 1) == 4; 
 // the class-stacked up5 1280.  SPLEETERRT_C8_WGS=<n> overrides them all (the sweep).
 // None of that transfers from five stems to four (there 1024 is as good as anything for most layers and 512 the best for some): what decides is how the runs fall
 // on the 256 CUs.  So the choice is MEASURED: the first launch of a layer shape times the candidates (c8_tuned below) and the process keeps the winner.
-static int c8_target_wgs(int dflt) { const int v = c8_env("SPLEETERRT_C8_WGS", 0); return v > 0 ? v : dflt; }
+static int c8_target_wgs(const SrtSwitches& sw, int dflt) { return sw.c8_wgs > 0 ? sw.c8_wgs : dflt; }
 // The loader-wave form (LW = 1) measured SLOWER on every layer but down5 / down6 (round 6, same box: 5-stem step 5.26 vs 5.09 ms; up4 0.434 vs 0.385): with one
 // computing wave per SIMD the MFMA stream loses more to its own LDS-read latency than the other waves lose to the DMA issue.  It is compiled into the tuning
 // library only (SRT_TUNE_C8LW=1); the product instantiates LW = 0.
@@ -760,24 +756,24 @@ static int c8_tpw(int nunits, int pairs, int target)
 }
 
 // target: workgroups per launch to aim for; 0 = SPLEETERRT_C8_WGS or the layer's table value
-static int enc_c8_launch(const SrtConvParams& p, hipStream_t s, int target)
+static int enc_c8_launch(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s, int target)
 {
     if (!p.wpack16 || p.Cin % 16 || p.Cout % 32 || !p.in16 || !p.out16 || p.nsplit == 2 || p.inScale) return 1;
     const int Ho = p.H / 2, Wo = p.W / 2, pairs = (p.Cout / 32) * p.nstems;
     if (Wo > 16) {
         constexpr int TH = 8, TW = 32, NI = 1;
-        if (target <= 0) target = c8_target_wgs(p.Cin <= 64 ? 768 : 1536);
+        if (target <= 0) target = c8_target_wgs(sw, p.Cin <= 64 ? 768 : 1536);
         const int nunits = ((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH) * ((p.ntiles + NI - 1) / NI), tpw = c8_tpw(nunits, pairs, target);
         const dim3 grid((unsigned)(((nunits + tpw - 1) / tpw) * pairs));
 #ifdef SRT_TUNING
 #define C8_ENC_CASE(A) if (c8_abl() == A) { SRT_LAUNCH((srt_enc_c8<32, 8, 1, 0, A>), grid, dim3(512), 0, s, p, tpw); return srt_launch_status(); }
         C8_ABL_CASES(C8_ENC_CASE)
 #endif
-        const int tpwf = tpw | (c8_env("SPLEETERRT_C8_WRES", 1) != 0 ? 0x10000 : 0);         // (=0: the weight slab is moved every step even when a unit is one K chunk - A/B runs)
+        const int tpwf = tpw | (sw.c8_wres != 0 ? 0x10000 : 0);         // (=0: the weight slab is moved every step even when a unit is one K chunk - A/B runs)
         C8_LW(SRT_LAUNCH((srt_enc_c8<32, 8, 1, 1>), grid, dim3(512), 0, s, p, tpwf), SRT_LAUNCH((srt_enc_c8<32, 8, 1, 0>), grid, dim3(512), 0, s, p, tpwf));
     } else {
         constexpr int TH = 4, TW = 16, NI = 4;
-        if (target <= 0) target = c8_target_wgs(1536);
+        if (target <= 0) target = c8_target_wgs(sw, 1536);
         const int nunits = ((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH) * ((p.ntiles + NI - 1) / NI), tpw = c8_tpw(nunits, pairs, target);
         const dim3 grid((unsigned)(((nunits + tpw - 1) / tpw) * pairs));
         C8_LW(SRT_LAUNCH((srt_enc_c8<16, 2, 4, 1>), grid, dim3(512), 0, s, p, tpw), SRT_LAUNCH((srt_enc_c8<16, 2, 4, 0>), grid, dim3(512), 0, s, p, tpw));
@@ -785,7 +781,7 @@ static int enc_c8_launch(const SrtConvParams& p, hipStream_t s, int target)
     return srt_launch_status();
 }
 
-static int dec_c8_launch(const SrtConvParams& p, hipStream_t s, int target)
+static int dec_c8_launch(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s, int target)
 {
     const bool cs = p.Cout == 16;
     if (p.Cin % 16 || p.CA % 16 || !p.in16 || !p.out16 || p.nsplit == 2 || (cs ? !p.wpack16cs : (!p.wpack16 || p.Cout % 32 != 0))) return 1;
@@ -793,7 +789,7 @@ static int dec_c8_launch(const SrtConvParams& p, hipStream_t s, int target)
     const int pairs = (cs ? 1 : p.Cout / 32) * p.nstems;
     if (p.W > 16) {
         constexpr int TH = 8, TW = 32, NI = 1;
-        if (target <= 0) target = c8_target_wgs(cs ? 1280 : 1536);
+        if (target <= 0) target = c8_target_wgs(sw, cs ? 1280 : 1536);
         const int nunits = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * ((p.ntiles + NI - 1) / NI), tpw = c8_tpw(nunits, pairs, target);
         const dim3 grid((unsigned)(((nunits + tpw - 1) / tpw) * pairs));
 #ifdef SRT_TUNING
@@ -810,7 +806,7 @@ static int dec_c8_launch(const SrtConvParams& p, hipStream_t s, int target)
         // Two sub-tiles per wave (NRW = 2: units of 16 x 32 input pixels), round 6, same box, 5 stems: up3 0.327 -> 0.297 ms, up4 0.380 -> 0.346, up2 (one tile row per
         // instance) 0.297 -> 0.297.  The class-stacked up5 measured SLOWER in this form (0.445 -> 0.487: its 15 KiB slab is the smaller part of a step and the unit's
         // epilogue doubles), so it keeps one sub-tile per wave; its NRW = 2 instantiation is in the tuning library (SPLEETERRT_C8_NR2=3).  =0: one sub-tile everywhere (A/B runs).
-        const int nr2 = c8_env("SPLEETERRT_C8_NR2", 1);
+        const int nr2 = sw.c8_nr2;
 #ifndef SRT_TUNING
         const bool cs2 = false;
 #else
@@ -829,7 +825,7 @@ static int dec_c8_launch(const SrtConvParams& p, hipStream_t s, int target)
         else C8_LW(SRT_LAUNCH((srt_dec_c8<32, 8, 1, 3, false, 1>), grid, dim3(512), 0, s, p, tpw), SRT_LAUNCH((srt_dec_c8<32, 8, 1, 3, false, 0>), grid, dim3(512), 0, s, p, tpw));
     } else {
         constexpr int TH = 4, TW = 16, NI = 4;
-        if (target <= 0) target = c8_target_wgs(1024);
+        if (target <= 0) target = c8_target_wgs(sw, 1024);
         const int nunits = ((p.W + TW - 1) / TW) * ((p.H + TH - 1) / TH) * ((p.ntiles + NI - 1) / NI), tpw = c8_tpw(nunits, pairs, target);
         const dim3 grid((unsigned)(((nunits + tpw - 1) / tpw) * pairs));
 #ifdef SRT_TUNING
@@ -856,17 +852,17 @@ struct C8Key {
 };
 static std::map<C8Key, int> g_c8_best;
 static std::mutex g_c8_mu;
-static int c8_tuned(int kind, const SrtConvParams& p, hipStream_t s)
+static int c8_tuned(int kind, const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s)
 {
-    auto go = [&](int target) { return kind ? dec_c8_launch(p, s, target) : enc_c8_launch(p, s, target); };
+    auto go = [&](int target) { return kind ? dec_c8_launch(p, sw, s, target) : enc_c8_launch(p, sw, s, target); };
     // The bandwidth-heavy full-resolution layers (down2, down3, the class-stacked up5) are NOT measured: timed back to back on warm inputs they rank the candidates
     // differently from how they run behind their producer in a step (round 6, 4 stems: the isolated winner was 8 % / 4 % / 3 % slower in the step); they keep table values
     // that are within 2 % of the best at both four and five stems (768 / 768 / 1280).
     const bool measured = kind ? p.Cout != 16 : p.Cin >= 64;
-    if (!measured || c8_env("SPLEETERRT_C8_WGS", 0) > 0 || c8_env("SPLEETERRT_C8_TUNE", 1) == 0) return go(0);
+    if (!measured || sw.c8_wgs > 0 || sw.c8_tune == 0) return go(0);
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const C8Key key = {{ kind, p.Cin, p.Cout, p.H, p.W, p.ntiles, p.nstems, (p.outAct && p.bnScale) ? 1 : 0, c8_env("SPLEETERRT_C8_NR2", 1) * 2 + (c8_env("SPLEETERRT_C8_WRES", 1) != 0), dev }};
+    const C8Key key = {{ kind, p.Cin, p.Cout, p.H, p.W, p.ntiles, p.nstems, (p.outAct && p.bnScale) ? 1 : 0, sw.c8_nr2 * 2 + (sw.c8_wres != 0), dev }};
     {
         std::lock_guard<std::mutex> lk(g_c8_mu);
         const auto it = g_c8_best.find(key);
@@ -896,8 +892,8 @@ static int c8_tuned(int kind, const SrtConvParams& p, hipStream_t s)
         std::lock_guard<std::mutex> lk(g_c8_mu);
         g_c8_best[key] = best;                                   // (0 if the timing failed: the table value from now on)
     }
-    if (c8_env("SPLEETERRT_C8_TUNE", 1) >= 2) fprintf(stderr, "[spleeterrt_amd] C8 %s Cin %d Cout %d %dx%d x%d x%d: %d workgroups (%.3f ms)\n", kind ? "dec" : "enc", p.Cin, p.Cout, p.H, p.W, p.ntiles, p.nstems, best, best_ms);
+    if (sw.c8_tune >= 2) fprintf(stderr, "[spleeterrt_amd] C8 %s Cin %d Cout %d %dx%d x%d x%d: %d workgroups (%.3f ms)\n", kind ? "dec" : "enc", p.Cin, p.Cout, p.H, p.W, p.ntiles, p.nstems, best, best_ms);
     return 0;                                                    // (the layer's outputs are in place: every candidate wrote the same values)
 }
-int srt_launch_enc_c8(const SrtConvParams& p, hipStream_t s) { return c8_tuned(0, p, s); }
-int srt_launch_dec_c8(const SrtConvParams& p, hipStream_t s) { return c8_tuned(1, p, s); }
+int srt_launch_enc_c8(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s) { return c8_tuned(0, p, sw, s); }
+int srt_launch_dec_c8(const SrtConvParams& p, const SrtSwitches& sw, hipStream_t s) { return c8_tuned(1, p, sw, s); }

@@ -287,3 +287,64 @@ def test_c8_kernels_store_count_matches_their_vmcnt_wait(tmp_path):
                 if nr == 2:
                     assert dpw + 2 * nst in waits, (mangled, waits)    # ... or of both
         assert len([l for l in body if l.startswith("buffer_load_dwordx4") and " lds" in l]) >= 2
+
+
+CSRC = os.path.join(ROOT, "spleeterrt_amd", "csrc")
+# read once when an object is created (engine, multi-device driver, resampler, the drop-in layers): not per-call switches
+CREATE_TIME_ENV = {"SPLEETERRT_PRECISION", "SPLEETERRT_VARIANT", "SPLEETERRT_ABORT_ON_ERROR", "SPLEETERRT_BATCH_INVARIANT", "SPLEETERRT_NO_RCCL",
+                   "SPLEETERRT_RESAMPLE_ONFLY"}
+
+
+def _switch_table():
+    """(environment name, default) of every row of SRT_SWITCH_TABLE, in order"""
+    txt = open(os.path.join(CSRC, "srt_internal.h")).read()
+    rows = re.findall(r'^\s*X\(\s*\w+\s*,\s*"(\w+)"\s*,\s*(-?\d+)\s*,\s*\w+\s*\)', txt, re.M)
+    assert len(rows) >= 10 and len(set(n for n, _ in rows)) == len(rows), rows
+    return [(n, int(d)) for n, d in rows]
+
+
+def _getenv_sites(path):
+    """(line number, argument text, inside an SRT_TUNING-only region) of every getenv( in a source file, srt_read_switches()'s body left out"""
+    txt = open(path).read()
+    m = re.search(r"^SrtSwitches srt_read_switches\(\)\n\{\n.*?^\}\n", txt, re.S | re.M)
+    if m:
+        txt = txt[:m.start()] + "\n" * m.group(0).count("\n") + txt[m.end():]
+    sites, stack = [], []                                   # stack: [the condition is SRT_TUNING, this branch is the tuning one]
+    for no, ln in enumerate(txt.splitlines(), 1):
+        d = ln.strip()
+        if re.match(r"#\s*if", d):
+            t = re.match(r"#\s*if(n?)def\s+SRT_TUNING\b", d)
+            stack.append([bool(t), bool(t) and not t.group(1)])
+        elif re.match(r"#\s*else", d) and stack and stack[-1][0]:
+            stack[-1][1] = not stack[-1][1]
+        elif re.match(r"#\s*endif", d) and stack:
+            stack.pop()
+        for a in re.finditer(r"\bgetenv\s*\(([^()]*)\)", ln.split("//")[0]):
+            sites.append((no, a.group(1).strip(), any(s[1] for s in stack)))
+    return sites
+
+
+def test_per_call_switches_are_read_in_one_place_only():
+    """Outside srt_read_switches() no getenv in csrc/ names a switch of SRT_SWITCH_TABLE (or takes a name that cannot be read off the source); what else
+    the product library reads from the environment are the create-time names; everything further sits inside #ifdef SRT_TUNING (measurement library)."""
+    table = {n for n, _ in _switch_table()}
+    assert not table & CREATE_TIME_ENV
+    eng = open(os.path.join(CSRC, "srt_engine.hip")).read()
+    assert re.search(r"^SrtSwitches srt_read_switches\(\)\n\{\n.*?getenv\(name\).*?^\}\n", eng, re.S | re.M), "srt_read_switches() not found where the audit expects it"
+    seen = set()
+    for f in sorted(os.listdir(CSRC)):
+        for no, arg, tuning in _getenv_sites(os.path.join(CSRC, f)):
+            lit = re.fullmatch(r'"(\w+)"', arg)
+            assert not (lit and lit.group(1) in table), "%s:%d reads the per-call switch %s outside srt_read_switches()" % (f, no, arg)
+            if tuning:
+                continue
+            assert lit and lit.group(1) in CREATE_TIME_ENV, "%s:%d: getenv(%s) in the product library is neither a table switch nor a create-time name" % (f, no, arg)
+            seen.add(lit.group(1))
+    assert seen == CREATE_TIME_ENV, seen ^ CREATE_TIME_ENV
+
+
+def test_integration_doc_lists_the_switch_table():
+    """INTEGRATION.md's table of measurement switches has the names and defaults of the code's table, in the same order"""
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    rows = [(n, int(d)) for n, d in re.findall(r"^\|\s*`(SPLEETERRT_\w+)`\s*\|\s*(-?\d+)\s*\|", doc, re.M)]
+    assert rows == _switch_table(), (rows, _switch_table())

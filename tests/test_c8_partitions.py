@@ -471,11 +471,11 @@ SWITCH_GEO = (64, 1024, 48, (1,))                             # the smallest bat
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("switch", ["SPLEETERRT_C8", "SPLEETERRT_C8L1", "SPLEETERRT_D1F16"])
+@pytest.mark.parametrize("switch", ["SPLEETERRT_C8", "SPLEETERRT_C8L1", "SPLEETERRT_D1F16", "SPLEETERRT_D1S2"])
 def test_layout_switch_is_part_of_the_graph_key(oracle, coeffs, switch):
     """A layout switch flipped between two graph-mode forwards of the SAME tensors captures a new graph: masks and taps equal an eager forward under
-    the switch (not the first graph replayed), and switching back replays the first graph with its own layout.  (On this batch every one of the three
-    switches moves down1 off srt_down1_f16_kernel, so the masks tell the two graphs apart.)"""
+    the switch (not the first graph replayed), and switching back replays the first graph with its own layout.  (On this batch every one of the four
+    switches moves down1 off srt_down1_f16_kernel - D1S2=0 through srt_down1_c8_ok - so the masks tell the two graphs apart.)"""
     import torch
     T, F, nt, modes = SWITCH_GEO
     assert down1_c8(T, F, nt)
