@@ -66,6 +66,12 @@ S4S_API void Spleeter4StemsProcessSamples(Spleeter4Stems *msr, const float *inLe
 S4S_API void Spleeter4StemsInitLive(Spleeter4Stems *msr, int initSpectralBinLimit, int initTimeStep, void *coeffProvider[4], int hopsPerRun, int lookahead);
 /* the delay in samples for a host that passes 1024-sample blocks (for AudioProcessor::setLatencySamples); 0 for a NULL instance */
 S4S_API int Spleeter4StemsLatency(const Spleeter4Stems *msr);
+/* The live mode at the host's sample rate: sampleRate 8000..384000 Hz is what prepareToPlay gives, maxBlock 1..65536 the largest
+   block it announces (larger calls are processed in slices).  Both rate conversions run on the GPU inside the call.  ProcessSamples then writes
+   exactly inSampleCount samples to every plane, every call, and the stream is the input's separation delayed by the one constant
+   Spleeter4StemsLatency(msr) returns for such an instance, whatever the call sizes.  A change of rate means Free + InitRate. */
+S4S_API void Spleeter4StemsInitRate(Spleeter4Stems *msr, int initSpectralBinLimit, int initTimeStep, void *coeffProvider[4], int hopsPerRun, int lookahead,
+                                    int sampleRate, int maxBlock);
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,30 @@ SRT_API int  srtResample(srt_resampler *r, const float *d_L, const float *d_R, s
 SRT_API int  srtResampleHost(srt_resampler *r, const float *h_L, const float *h_R, size_t n_in,
                              float *h_Lo, float *h_Ro);
 
+/* ---- the converter as a stream: fed block by block, it emits every output frame that has become computable.  The converted stream is the one
+ * srtResample defines, and the concatenation of what the calls emit equals srtResample on the whole input bit for bit, for any partition into
+ * blocks.  Output frame j needs the input up to frame floor(j * fs_in / fs_out) + H, H = srtResampleHorizon (50 input frames for 48 k -> 44.1 k,
+ * 46 for 44.1 k -> 48 k with the built-in filter's layout), so after n_in input frames srtResampleComputable(fs_in, fs_out, H, n_in) =
+ * ceil((n_in - H) * fs_out / fs_in) frames exist (0 up to n_in = H): host integer arithmetic, no device round trip, capturable.
+ * srtResampleHorizon: table_len 0 = the built-in filter's layout (22438, 491); -1 on a bad argument.  Both are pure arithmetic, no device.
+ * srtResamplerStreamCreate: current device; `channels` 1..16 share one history ring in HBM; max_block 1..2^20 is the largest n of a call; table as
+ * srtResamplerCreate.  Every argument is checked before any HIP call.
+ * srtResamplerStreamProcess: d_in holds n frames, interleaved [n][channels] (in_stride 0) or planar with channel c at d_in + c * in_stride; the
+ * frames that became computable are written planar, channel c at d_out + c * out_stride, and their count is returned (it is
+ * srtResampleComputable(have + n) - srtResampleComputable(have): the caller sizes d_out with that).  One kernel launch, asynchronous on the stream.
+ * srtResamplerStreamFlush: the input has ended; emits the frames up to srtResampleLength(frames received) with zeros after the last input frame, as
+ * srtResample computes them.  After it only Reset (a new stream from frame 0) and Destroy are accepted. */
+typedef struct srt_resampler_stream srt_resampler_stream;
+SRT_API int  srtResampleHorizon(int fs_in, int fs_out, int table_len, int index_inc);
+SRT_API long long srtResampleComputable(int fs_in, int fs_out, int horizon, long long n_in);
+SRT_API int  srtResamplerStreamCreate(int fs_in, int fs_out, int channels, int max_block, const float *h_table, int table_len, int index_inc,
+                                      void *stream, srt_resampler_stream **out);
+SRT_API int  srtResamplerStreamProcess(srt_resampler_stream *r, const float *d_in, size_t in_stride, int n, float *d_out, size_t out_stride);
+SRT_API int  srtResamplerStreamFlush(srt_resampler_stream *r, float *d_out, size_t out_stride);
+SRT_API int  srtResamplerStreamReset(srt_resampler_stream *r);
+SRT_API int  srtResamplerStreamHorizon(const srt_resampler_stream *r);
+SRT_API int  srtResamplerStreamDestroy(srt_resampler_stream *r);
+
 /* ---- live separation with a sliding network window: the real-time surface of Spleeter4Stems.h with a short delay.  The networks run
  * every hops_per_run = K hops (1 <= K <= T) on the window of the newest T frames; frame g takes its mask from the run whose window holds it at row
  * T-1-(h_r-g) with h_r-g in [L, L+K-1], L = lookahead (0 <= L <= T-K frames of future context), and is synthesised D = L + 2K hops after it was
@@ -235,6 +259,19 @@ SRT_API int  srtLiveCreate(const srt_config *cfg, int hops_per_run, int lookahea
 SRT_API int  srtLiveProcess(srt_live *s, const float *inL, const float *inR, int n, float *const *out);
 SRT_API int  srtLiveLatency(const srt_live *s);
 SRT_API void srtLiveDestroy(srt_live *s);
+/* The live stream at the host's sample rate.  srtLiveCreateRate: as srtLiveCreate, plus sample_rate 8000..384000 Hz and max_block
+ * 1..65536 (the largest slice one call is processed in; any n is accepted).  Both conversions (sample_rate -> 44.1 kHz in front of the hop path,
+ * 44.1 kHz -> sample_rate behind it) run on the device with the built-in filter of srtResamplerCreate, as streams (srtResamplerStream* above).
+ * On such an instance srtLiveProcess consumes n samples at sample_rate and writes exactly n samples to each plane, every call, and returns n: the
+ * output is the separated input delayed by the constant A = srtLiveLatency(s) = srtLiveRateLatency(sample_rate, K, L) samples, bit-identical for
+ * every way of cutting the input into calls.  A is the smallest delay that is causal for calls of any size, one sample included:
+ * H1 + floor(((D + 2) * 1024 - 1 + H2) * sample_rate / 44100) with D = L + 2K and H1, H2 the horizons of the two converters (srtResampleHorizon)
+ * whenever 44100 / gcd is odd (every common rate); (D + 2) * 1024 - 1 at 44100 Hz, where no converter runs.  That is up to one hop more than the
+ * 44.1 kHz instance's figure for aligned 1024-sample calls: the price of a delay that does not depend on the chunking.  A call costs one upload,
+ * one download and one host wait.  srtLiveRateLatency is pure host arithmetic (-1 on a bad argument). */
+SRT_API int  srtLiveCreateRate(const srt_config *cfg, int hops_per_run, int lookahead, int sample_rate, int max_block,
+                               const void *const *h_coeff, srt_live **out);
+SRT_API int  srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead);
 
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";

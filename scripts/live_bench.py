@@ -2,6 +2,9 @@
 
     python scripts/live_bench.py [--out profiles/live_bench.json]      # the measurements below
     python scripts/live_bench.py --trace                                 # a short K = 4 stream for `rocprofv3 --kernel-trace --stats` (run on its own)
+    python scripts/live_bench.py --rate [--out profiles/live_rate_bench.json]   # the 44.1 kHz instance against the 48 kHz rate instance
+    python scripts/live_bench.py --trace --rate --k K --out DIR/run.json # a short stream on a 48 kHz rate instance, 512-sample calls, under rocprofv3 -d DIR
+    python scripts/live_bench.py --rate-trace-summary BENCH.json DIR...  # adds the traces' summaries (converter launches, copies, GPU time) to BENCH.json
 
 Per precision:
   run_ms          GPU time of one run's network: an Engine(max_tiles=1) of the same config in graph mode replays srtForward on one window,
@@ -12,6 +15,11 @@ Per precision:
                   p50 / p99 / worst over every call after the first D hops;
   gpu_share[K]    run_ms / (K * 23.22 ms): the fraction of one GPU a stream's networks take at that K;
 Latency of each (K, L) in the table: srtLiveLatency in samples and ms at 44.1 kHz.
+--rate: fp32 only, K = 1, 4, 256 with L = 0; per K the 44.1 kHz instance (1024-sample calls) and the 48 kHz rate instance (1024- and 512-sample calls)
+are measured in turn, twice, and the calls of both turns are pooled: p50 / p99 / worst per call after the start-up, and calls_us_per_audio_s = the sum
+of the call times per second of audio (the host thread's share).  The GPU's own time per second of audio comes from `rocprofv3 --kernel-trace
+--stats --output-format csv -d DIR -o t -- python scripts/live_bench.py --trace --rate --k K --out DIR/run.json`, one run of its own per K,
+summarised by --rate-trace-summary: every kernel of the process from the first timed call's start on, per second of the audio those calls carry.
 """
 import argparse
 import json
@@ -79,15 +87,116 @@ def calls(coeffs, precision, K, Lk=0, extra=96):
             "worst_us": round(v[-1], 1), "first_call_us": round(us[0], 1), "latency_samples": lat}
 
 
+def calls_rate(coeffs, K, fs, call, extra=96):
+    """wall time of every srtLiveProcess call of `call` samples: a 44.1 kHz instance (fs None) or a rate instance at fs; the start-up (latency) is not timed"""
+    import numpy as np
+    import ctypes as C
+    import spleeterrt_amd as srt
+    live = srt.Live(F, T, (1, 1, 1, 1), OOB, srt.VARIANT_VST, srt.PREC_F32, K, 0, coeffs, sample_rate=fs, max_block=call)
+    lat = live.latency
+    rate = fs or 44100
+    n = (lat + int(extra * 1024 * rate / 44100.0)) // call
+    rng = np.random.default_rng(K)
+    x = rng.uniform(-0.1, 0.1, (2, call)).astype(np.float32)
+    out = np.zeros((8, call), np.float32)
+    ptrs = (C.c_void_p * 8)(*[out[j].ctypes.data for j in range(8)])
+    us = []
+    for _ in range(n):
+        t0 = time.perf_counter()
+        w = live.L.srtLiveProcess(live.h, C.c_void_p(x[0].ctypes.data), C.c_void_p(x[1].ctypes.data), call, ptrs)
+        us.append((time.perf_counter() - t0) * 1e6)
+        assert w == call
+    live.close()
+    return us[lat // call + 1:], lat
+
+
+def rate_table(coeffs, out):
+    rec = {"geometry": {"F": F, "T": T, "n_stems": 4, "variant": "VST", "precision": "fp32", "lookahead": 0}, "rows": []}
+    for K in (1, 4, 256):
+        configs = [("44100_native_1024", None, 1024), ("48000_rate_1024", 48000, 1024), ("48000_rate_512", 48000, 512)]
+        pool = {name: [] for name, _, _ in configs}
+        lat = {}
+        for _turn in range(2):
+            for name, fs, call in configs:
+                us, lat[name] = calls_rate(coeffs, K, fs, call)
+                pool[name] += us
+        for name, fs, call in configs:
+            v = sorted(pool[name])
+            rate = fs or 44100
+            row = {"K": K, "instance": name, "sample_rate": rate, "call": call, "timed_calls": len(v), "latency_samples": lat[name],
+                   "latency_ms": round(lat[name] / rate * 1e3, 2), "p50_us": round(v[len(v) // 2], 1), "p99_us": round(v[int(0.99 * (len(v) - 1) + 0.5)], 1),
+                   "worst_us": round(v[-1], 1), "calls_us_per_audio_s": round(sum(v) / (len(v) * call / rate), 1)}
+            rec["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    if out:
+        with open(out, "w") as f:
+            json.dump(rec, f, indent=1)
+
+
+def trace_summary(bench_json, dirs):
+    """per trace directory: the converter launches by side (the input side computes one channel pair, grid y = 1; the output side all 2S = 8 channels,
+    grid y = 4), the blit kernels that carry a call's pinned copies, and the GPU time of all kernels per second of audio, create and pre-warm left out"""
+    import csv
+    rec = json.load(open(bench_json))
+    rec["trace"] = []
+    for d in dirs:
+        run = json.load(open(os.path.join(d, "run.json")))
+        rows = list(csv.DictReader(open(os.path.join(d, "t_kernel_trace.csv"))))
+        rows.sort(key=lambda r: int(r["Start_Timestamp"]))
+        conv = [i for i, r in enumerate(rows) if "srt_rsstream_kernel" in r["Kernel_Name"]]
+        # the two pre-warm launches (input side, then output side, one frame each) come first; the stream's calls follow
+        assert len(conv) > 2 and int(rows[conv[0]]["Grid_Size_Y"]) // int(rows[conv[0]]["Workgroup_Size_Y"]) == 1
+        first = conv[2]
+        while first > 0 and "copyBuffer" in rows[first - 1]["Kernel_Name"]:      # the first call's upload
+            first -= 1
+        body = rows[first:]
+        us = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+
+        def st(v):
+            v = sorted(v)
+            return {"launches": len(v), "min_us": round(v[0], 2), "median_us": round(v[len(v) // 2], 2), "max_us": round(v[-1], 2)}
+        side = lambda r: "srt_rsstream_kernel" in r["Kernel_Name"] and int(r["Grid_Size_Y"]) // int(r["Workgroup_Size_Y"])
+        audio = run["calls"] * run["call"] / float(run["sample_rate"])
+        total = sum(us(r) for r in body)
+        copies = [us(r) for r in body if "copyBuffer" in r["Kernel_Name"]]
+        rec["trace"].append({
+            "K": run["K"], "sample_rate": run["sample_rate"], "call": run["call"], "calls": run["calls"], "audio_s": round(audio, 3),
+            "converter_launches_in_trace": len(conv), "of_which_prewarm": 2,
+            "input_side": st([us(r) for r in body if side(r) == 1]), "output_side": st([us(r) for r in body if side(r) == 4]),
+            "copy_kernels": dict(st(copies), per_call=round(len(copies) / run["calls"], 2)),
+            "gpu_ms_all_kernels": round(total / 1e3, 2), "gpu_ms_per_audio_s": round(total / 1e3 / audio, 2)})
+        print(json.dumps(rec["trace"][-1]), flush=True)
+    with open(bench_json, "w") as f:
+        json.dump(rec, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--rate", action="store_true")
+    ap.add_argument("--k", type=int, default=4)
+    ap.add_argument("--rate-trace-summary", nargs="+", default=None, metavar=("BENCH_JSON", "DIR"))
     a = ap.parse_args()
+    if a.rate_trace_summary:
+        trace_summary(a.rate_trace_summary[0], a.rate_trace_summary[1:])
+        return
     import numpy as np
     import spleeterrt_amd as srt
     from oracle import pyoracle as O
     coeffs = [np.ascontiguousarray(O.synth_coeff(k)) for k in range(4)]
+    if a.trace and a.rate:
+        us, lat = calls_rate(coeffs, a.k, 48000, 512, extra=64)
+        run = {"K": a.k, "calls": len(us) + lat // 512 + 1, "call": 512, "sample_rate": 48000, "latency_samples": lat}
+        print(json.dumps(run))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)      # rocprofv3 creates its directory only when the program has ended
+            with open(a.out, "w") as f:
+                json.dump(run, f)
+        return
+    if a.rate:
+        rate_table(coeffs, a.out)
+        return
     if a.trace:
         print(json.dumps(calls(coeffs, srt.PREC_F32, 4, 8, extra=64)))
         return

@@ -95,6 +95,8 @@ def load_library():
     L.srtLiveLatency.argtypes = [vp]
     L.srtLiveDestroy.argtypes = [vp]
     L.srtLiveDestroy.restype = None
+    L.srtLiveCreateRate.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.srtLiveRateLatency.argtypes = [C.c_int, C.c_int, C.c_int]
     # sample-rate converter (csrc/srt_resample.hip)
     L.srtResampleLength.restype = C.c_size_t
     L.srtResampleLength.argtypes = [C.c_size_t, C.c_int, C.c_int]
@@ -102,6 +104,16 @@ def load_library():
     L.srtResamplerDestroy.argtypes = [vp]
     L.srtResample.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_size_t, C.c_size_t, f32p, f32p]
     L.srtResampleHost.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+    # the converter as a stream (csrc/srt_rsstream.hip)
+    L.srtResampleHorizon.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    L.srtResampleComputable.restype = C.c_longlong
+    L.srtResampleComputable.argtypes = [C.c_int, C.c_int, C.c_int, C.c_longlong]
+    L.srtResamplerStreamCreate.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
+    L.srtResamplerStreamProcess.argtypes = [vp, f32p, C.c_size_t, C.c_int, f32p, C.c_size_t]
+    L.srtResamplerStreamFlush.argtypes = [vp, f32p, C.c_size_t]
+    L.srtResamplerStreamReset.argtypes = [vp]
+    L.srtResamplerStreamHorizon.argtypes = [vp]
+    L.srtResamplerStreamDestroy.argtypes = [vp]
     _lib = L
     return L
 
@@ -389,13 +401,24 @@ def live_latency(hops_per_run, lookahead):
     return (int(lookahead) + 2 * int(hops_per_run)) * 1024 + 1024
 
 
+def live_rate_latency(sample_rate, hops_per_run, lookahead):
+    """srtLiveRateLatency: the constant delay in samples of a rate instance (Live(..., sample_rate=fs)); pure host arithmetic, no device"""
+    L = load_library()
+    rc = L.srtLiveRateLatency(int(sample_rate), int(hops_per_run), int(lookahead))
+    if rc < 0:
+        raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (L.srtLastError().decode(), rc))
+    return rc
+
+
 class Live:
     """Live separation with a sliding network window (srtLive*, include/spleeterrt_amd.h) on the current device: the networks
     run every hops_per_run hops on the newest T frames, with `lookahead` frames of future context per frame.  hops_per_run = T, lookahead = 0 with
-    the plugin's config (VST, stem modes 1, oob 0.25 / 0 / 0.25 / 0.25) is Spleeter4Stems.  coeffs: one float32 spleeterCoeff blob per stem."""
+    the plugin's config (VST, stem modes 1, oob 0.25 / 0 / 0.25 / 0.25) is Spleeter4Stems.  coeffs: one float32 spleeterCoeff blob per stem.
+    sample_rate=fs makes a rate instance (srtLiveCreateRate): calls take samples at fs, every call writes as many samples as it got and
+    the delay is the constant `latency` whatever the call sizes; max_block is the largest slice a call is processed in."""
 
     def __init__(self, F, T, stem_modes, oob_weights, variant, precision, hops_per_run, lookahead, coeffs, impl=IMPL_MFMA,
-                 ratio_mask=False, batch_invariant=False, max_tiles=1):
+                 ratio_mask=False, batch_invariant=False, max_tiles=1, sample_rate=None, max_block=4096):
         import numpy as np
         self.L = load_library()
         self.S, self.F, self.T = len(stem_modes), F, T
@@ -411,7 +434,11 @@ class Live:
             assert b is None or b.size == COEFF_FLOATS
         ptrs = (C.c_void_p * max(len(blobs), 1))(*[None if b is None else b.ctypes.data for b in blobs])
         h = C.c_void_p()
-        self._chk(self.L.srtLiveCreate(C.byref(cfg), self.hops_per_run, self.lookahead, ptrs, C.byref(h)))
+        self.sample_rate = None if sample_rate is None else int(sample_rate)
+        if sample_rate is None:
+            self._chk(self.L.srtLiveCreate(C.byref(cfg), self.hops_per_run, self.lookahead, ptrs, C.byref(h)))
+        else:
+            self._chk(self.L.srtLiveCreateRate(C.byref(cfg), self.hops_per_run, self.lookahead, self.sample_rate, int(max_block), ptrs, C.byref(h)))
         self.h = h
 
     def _chk(self, rc):
@@ -421,7 +448,7 @@ class Live:
 
     @property
     def latency(self):
-        """samples between an input sample and its separated output for 1024-sample calls (srtLiveLatency)"""
+        """samples between an input sample and its separated output (srtLiveLatency): for 1024-sample calls, or for any calls on a rate instance"""
         return self._chk(self.L.srtLiveLatency(self.h))
 
     def process(self, L, R, chunks=(1024,)):
@@ -523,6 +550,77 @@ class Resampler:
     def close(self):
         if getattr(self, "h", None):
             self.L.srtResamplerDestroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ResamplerStream:
+    """The converter fed block by block (srtResamplerStream*, include/spleeterrt_amd.h): `channels` channels share one history ring on the device, every
+    process() returns the frames that became computable, and the concatenation equals Resampler.resample of the whole input bit for bit."""
+
+    def __init__(self, fs_in, fs_out, channels=2, max_block=4096, table=None, index_inc=491, stream=None):
+        import numpy as np
+        import torch
+        self.L = load_library()
+        self.fs_in, self.fs_out, self.channels, self.max_block = int(fs_in), int(fs_out), int(channels), int(max_block)
+        self._table = None if table is None else np.ascontiguousarray(table, np.float32)
+        if stream is None and torch.cuda.is_available():
+            stream = torch.cuda.current_stream()
+        self.stream = stream
+        sp = None if stream is None else C.c_void_p(stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream))
+        tp = None if self._table is None else C.c_void_p(self._table.ctypes.data)
+        h = C.c_void_p()
+        self._chk(self.L.srtResamplerStreamCreate(self.fs_in, self.fs_out, self.channels, self.max_block, tp,
+                                                  0 if self._table is None else self._table.size, int(index_inc), sp, C.byref(h)))
+        self.h = h
+        self.received = 0
+
+    _chk = Resampler._chk
+
+    @property
+    def horizon(self):
+        """H: output frame j needs the input up to frame floor(j * fs_in / fs_out) + H"""
+        return self._chk(self.L.srtResamplerStreamHorizon(self.h))
+
+    def computable(self, n_in):
+        """frames a stream that has received n_in input frames can compute (srtResampleComputable)"""
+        return self.L.srtResampleComputable(self.fs_in, self.fs_out, self.horizon, int(n_in))
+
+    def process(self, x, interleaved=False):
+        """x: CUDA float32 [channels, n] (planar) or [n, channels] (interleaved=True), n <= max_block -> [channels, k] newly computable frames"""
+        import torch
+        assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
+        x = x.contiguous()
+        n = x.shape[0] if interleaved else x.shape[1]
+        assert (x.shape[1] if interleaved else x.shape[0]) == self.channels
+        k = self.computable(self.received + n) - self.computable(self.received)
+        out = torch.empty((self.channels, k), device=x.device, dtype=torch.float32)
+        got = self._chk(self.L.srtResamplerStreamProcess(self.h, _ptr(x), 0 if interleaved else n, n, _ptr(out), k))
+        assert got == k, (got, k)
+        self.received += n
+        return out
+
+    def flush(self):
+        """the input has ended: the frames up to Resampler.length(received), zeros after the last input frame"""
+        import torch
+        k = max(self.L.srtResampleLength(self.received, self.fs_in, self.fs_out) - self.computable(self.received), 0)
+        out = torch.empty((self.channels, k), device="cuda", dtype=torch.float32)
+        got = self._chk(self.L.srtResamplerStreamFlush(self.h, _ptr(out), k))
+        assert got == k, (got, k)
+        return out
+
+    def reset(self):
+        self._chk(self.L.srtResamplerStreamReset(self.h))
+        self.received = 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.srtResamplerStreamDestroy(self.h)
             self.h = None
 
     def __del__(self):

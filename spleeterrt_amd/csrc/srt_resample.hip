@@ -13,6 +13,7 @@
 // any partition of the output range gives the same bits.  When the bank would exceed SRT_RS_BANK_BYTES the kernel evaluates the same
 // weight function per tap instead (ONFLY = true): same floats, same FMA order, same bits.
 #include "srt_internal.h"
+#include "srt_rs.h"
 #include "../../include/spleeterrt_amd.h"
 #include <math.h>
 #include <stdio.h>
@@ -20,18 +21,6 @@
 #include <string.h>
 #include <new>
 #include <vector>
-
-#define SRT_RS_BANK_BYTES (8u << 20)     // per-phase weight bank limit: every common rate pair fits (96 k -> 44.1 k: 147 phases x 200 taps = 118 KB)
-#define SRT_RS_LDS_BYTES  (64u << 10)    // input window staged per workgroup
-#define SRT_RS_MIN_RATE 8000
-#define SRT_RS_MAX_RATE 384000
-
-struct SrtRsGeom {
-    long long P, Q;          // fs_in / g, fs_out / g
-    long long inc, maxIdx;   // increment, (table_len - 2) << 12
-    int LO, T4;              // window = input frames [i - LO, i - LO + T4); T4 = taps padded to a multiple of 4 (zero weights)
-    double fi, scale;        // float_increment, float_increment / index_inc
-};
 
 struct SrtRsArgs {
     SrtRsGeom g;
@@ -42,29 +31,6 @@ struct SrtRsArgs {
     int B, opt;              // frames per workgroup, frames per thread (B = blockDim.x * opt)
     long long stepI, stepR, stepM;   // blockDim.x frames further: i += stepI (+1 on carry), (n P) mod Q += stepR, n mod Q += stepM
 };
-
-// start of the filter for phase m = n mod Q  (src_sinc.c:468: double_to_fp(input_index * float_increment))
-__device__ __host__ inline long long rs_start(const SrtRsGeom& g, long long m)
-{
-    const double frac = (double)((m * g.P) % g.Q) / (double)g.Q;
-    return (long long)rint(frac * g.fi * 4096.0);
-}
-
-// weight of window tap t (input frame i - LO + t) for a frame whose filter starts at `start`; zero where the reference takes no tap
-__device__ inline float rs_weight(const SrtRsGeom& g, const float* __restrict__ table, long long start, int t)
-{
-#pragma clang fp contract(off)
-    const long long u = (long long)t - g.LO;
-    long long f;
-    if (u <= 0) f = start - u * g.inc;                          // left half, src_sinc.c:375-394
-    else { f = g.inc - start + (u - 1) * g.inc; if (f <= 0) return 0.0f; }   // right half, :397-412 (filter index 0 excluded)
-    if (f > g.maxIdx) return 0.0f;
-    const long long k = f >> 12;
-    const double fr = (double)(f & 4095) * (1.0 / 4096.0);
-    const double c0 = table[k], c1 = table[k + 1];
-    const double w = c0 + fr * (c1 - c0);
-    return (float)(g.scale * w);
-}
 
 __global__ __launch_bounds__(256) void srt_resample_bank_kernel(SrtRsGeom g, const float* __restrict__ table, float* __restrict__ bank)
 {
@@ -135,14 +101,22 @@ struct srt_resampler {
 };
 
 static int rs_fail(int code, const char* fmt, const char* detail = "") { return srt_set_error(code, fmt, detail); }
+static int rs_fail_who(int code, const char* who, const char* what, const char* detail = "")
+{
+    char fmt[320];
+    snprintf(fmt, sizeof fmt, "%s: %s", who, what);                     // `what` may hold one %s for `detail`; `who` is a plain identifier
+    return srt_set_error(code, fmt, detail);
+}
 static long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
 
 // built-in half filter in the reference's layout (index_inc = 491, 22 438 points): a Kaiser-windowed sinc (beta 12) with its cutoff at
 // 0.918 of the lower rate's Nyquist frequency, the window reaching its edge at the table's last point.  Project's own design: passband
 // flat to 2e-5 dB up to 17 kHz and stopband below -115 dB from 22.5 kHz at 48 k -> 44.1 k (tests/test_resample.py).
+#define SRT_RS_BUILTIN_LEN 22438
+#define SRT_RS_BUILTIN_INC 491
 static void builtin_table(std::vector<float>& c)
 {
-    const int n = 22438, inc = 491;
+    const int n = SRT_RS_BUILTIN_LEN, inc = SRT_RS_BUILTIN_INC;
     const double fc = 0.918, beta = 12.0, half = (n - 1) / (double)inc, PI = 3.141592653589793;
     auto i0 = [](double x) { double s = 1.0, term = 1.0; for (int k = 1; k < 200; ++k) { term *= (x / (2.0 * k)) * (x / (2.0 * k)); s += term; if (term < 1e-18 * s) break; } return s; };
     const double norm = 1.0 / i0(beta);
@@ -160,17 +134,14 @@ size_t srtResampleLength(size_t n_in, int fs_in, int fs_out)
     return (size_t)ceil((double)n_in * (fs_out / (double)fs_in));      // main.c:266
 }
 
-int srtResamplerCreate(int fs_in, int fs_out, const float* h_table, int table_len, int index_inc, void* stream, srt_resampler** out)
+int srt_rs_geometry(int fs_in, int fs_out, bool has_table, int table_len, int index_inc, const char* who, SrtRsGeom* out)
 {
-    if (!out) return rs_fail(-1, "srtResamplerCreate: null output pointer");
-    *out = nullptr;
     if (fs_in < SRT_RS_MIN_RATE || fs_in > SRT_RS_MAX_RATE || fs_out < SRT_RS_MIN_RATE || fs_out > SRT_RS_MAX_RATE)
-        return rs_fail(-1, "srtResamplerCreate: sample rates must lie in 8000..384000 Hz");
-    if (h_table && table_len < 2) return rs_fail(-1, "srtResamplerCreate: table_len must be at least 2");
-    if (h_table && index_inc < 1) return rs_fail(-1, "srtResamplerCreate: index_inc must be at least 1");
-    if (h_table && table_len > (1 << 24)) return rs_fail(-1, "srtResamplerCreate: table_len above 2^24");
-    std::vector<float> tab;
-    if (!h_table) { builtin_table(tab); table_len = (int)tab.size(); index_inc = 491; }
+        return rs_fail_who(-1, who, "sample rates must lie in 8000..384000 Hz");
+    if (has_table && table_len < 2) return rs_fail_who(-1, who, "table_len must be at least 2");
+    if (has_table && index_inc < 1) return rs_fail_who(-1, who, "index_inc must be at least 1");
+    if (has_table && table_len > (1 << 24)) return rs_fail_who(-1, who, "table_len above 2^24");
+    if (!has_table) { table_len = SRT_RS_BUILTIN_LEN; index_inc = SRT_RS_BUILTIN_INC; }
     SrtRsGeom g;
     const long long gc = gcd_ll(fs_in, fs_out);
     g.P = fs_in / gc; g.Q = fs_out / gc;
@@ -179,36 +150,65 @@ int srtResamplerCreate(int fs_in, int fs_out, const float* h_table, int table_le
     g.scale = g.fi / index_inc;
     g.inc = (long long)rint(g.fi * 4096.0);
     g.maxIdx = (long long)(table_len - 2) << 12;
-    if (g.inc < 1) return rs_fail(-1, "srtResamplerCreate: index_inc * min(fs_out / fs_in, 1) rounds to a zero filter increment");
+    if (g.inc < 1) return rs_fail_who(-1, who, "index_inc * min(fs_out / fs_in, 1) rounds to a zero filter increment");
     const long long half = g.maxIdx / g.inc, taps = 2 * half + 2;
     g.LO = (int)half;
     g.T4 = (int)((taps + 3) / 4 * 4);
+    *out = g;
+    return 0;
+}
+
+int srt_rs_filter_create(const SrtRsGeom& g, const float* h_table, int table_len, hipStream_t stream, const char* who, SrtRsFilter* f)
+{
+    std::vector<float> tab;
+    if (!h_table) { builtin_table(tab); table_len = (int)tab.size(); h_table = tab.data(); }
+    const size_t bankBytes = (size_t)g.Q * g.T4 * sizeof(float);
+    const char* of = getenv("SPLEETERRT_RESAMPLE_ONFLY");               // measurement / test aid: skip the bank (the results are the same bits)
+    f->g = g; f->d_table = nullptr; f->d_bank = nullptr;
+    f->onfly = bankBytes > SRT_RS_BANK_BYTES || (of && of[0] == '1');
+    hipError_t e = hipMalloc((void**)&f->d_table, (size_t)table_len * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpyAsync(f->d_table, h_table, (size_t)table_len * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && !f->onfly) e = hipMalloc((void**)&f->d_bank, bankBytes);
+    if (e == hipSuccess && !f->onfly) {
+        const long long n = g.Q * g.T4;
+        SRT_LAUNCH(srt_resample_bank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, g, f->d_table, f->d_bank);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);              // the host table may go away after the call
+    if (e != hipSuccess) { srt_rs_filter_free(f); return rs_fail_who(-2, who, "HIP error: %s", hipGetErrorString(e)); }
+    return 0;
+}
+
+void srt_rs_filter_free(SrtRsFilter* f)
+{
+    if (f->d_table) hipFree(f->d_table);
+    if (f->d_bank) hipFree(f->d_bank);
+    f->d_table = f->d_bank = nullptr;
+}
+
+int srtResamplerCreate(int fs_in, int fs_out, const float* h_table, int table_len, int index_inc, void* stream, srt_resampler** out)
+{
+    const char* who = "srtResamplerCreate";
+    if (!out) return rs_fail(-1, "srtResamplerCreate: null output pointer");
+    *out = nullptr;
+    SrtRsGeom g;
+    if (const int rc = srt_rs_geometry(fs_in, fs_out, h_table != nullptr, table_len, index_inc, who, &g)) return rc;
     // workgroup size: the most frames whose input window fits the LDS budget
     int B = 1024;
     auto window = [&](int b) { return (size_t)(((long long)(b - 1) * g.P) / g.Q + 1 + g.T4) * sizeof(float2); };
     while (B > 64 && window(B) > SRT_RS_LDS_BYTES) B >>= 1;
     if (window(B) > SRT_RS_LDS_BYTES) return rs_fail(-1, "srtResamplerCreate: filter too long for this rate pair (input window above 64 KiB)");
-    const size_t bankBytes = (size_t)g.Q * g.T4 * sizeof(float);
-    const char* of = getenv("SPLEETERRT_RESAMPLE_ONFLY");               // measurement / test aid: skip the bank (the results are the same bits)
-    const int onfly = bankBytes > SRT_RS_BANK_BYTES || (of && of[0] == '1');
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return rs_fail(-3, "srtResamplerCreate: no HIP device (this library has no CPU path)");
     srt_resampler* s = new (std::nothrow) srt_resampler();
     if (!s) return rs_fail(-2, "srtResamplerCreate: out of host memory");
-    s->fs_in = fs_in; s->fs_out = fs_out; s->g = g; s->onfly = onfly; s->B = B; s->threads = B < 256 ? B : 256; s->ldsBytes = window(B);
+    s->fs_in = fs_in; s->fs_out = fs_out; s->g = g; s->B = B; s->threads = B < 256 ? B : 256; s->ldsBytes = window(B);
     s->stream = (hipStream_t)stream; s->d_table = nullptr; s->d_bank = nullptr;
-    const float* src = h_table ? h_table : tab.data();
-    hipError_t e = hipGetDevice(&s->device);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_table, (size_t)table_len * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_table, src, (size_t)table_len * sizeof(float), hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess && !onfly) e = hipMalloc((void**)&s->d_bank, bankBytes);
-    if (e == hipSuccess && !onfly) {
-        const long long n = g.Q * g.T4;
-        SRT_LAUNCH(srt_resample_bank_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, g, s->d_table, s->d_bank);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);          // the host table may go away after the call
-    if (e != hipSuccess) { srtResamplerDestroy(s); return rs_fail(-2, "srtResamplerCreate: HIP error: %s", hipGetErrorString(e)); }
+    const hipError_t e = hipGetDevice(&s->device);
+    if (e != hipSuccess) { delete s; return rs_fail(-2, "srtResamplerCreate: HIP error: %s", hipGetErrorString(e)); }
+    SrtRsFilter f;
+    if (const int rc = srt_rs_filter_create(g, h_table, table_len, s->stream, who, &f)) { delete s; return rc; }
+    s->onfly = f.onfly; s->d_table = f.d_table; s->d_bank = f.d_bank;
     *out = s;
     return 0;
 }

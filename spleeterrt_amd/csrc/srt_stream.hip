@@ -11,6 +11,7 @@
 // threads, Spleeter4Stems.c:135,351-371).  Frame g takes row T-1-(h_r-g) of the run h_r with h_r-g in [L, L+K-1] and is synthesised at
 // hop g + D, D = L + 2K.  The plugin's instance (Spleeter4StemsInit) is K = T, L = 0: runs at the T-hop flips, D = 2T, rows 0..T-1.
 #include "srt_internal.h"
+#include "srt_rs.h"
 #include "../../include/spleeterrt_amd.h"
 #include <math.h>
 #include <stdio.h>
@@ -32,6 +33,7 @@ static bool stream_fail(const char* where, const char* why)
     fprintf(stderr, "libspleeterrt_amd: %s (no CPU fallback exists; the stream is muted)\n", buf);
     return false;
 }
+#define SRT_LIVE_MAX_BLOCK 65536      // largest slice of a rate instance's call (max_block)
 #define HIPTRY(x, where) do { hipError_t _e = (x); if (_e != hipSuccess) { s->failed = true; stream_fail(where, hipGetErrorString(_e)); goto failed; } } while (0)
 
 
@@ -55,6 +57,17 @@ struct srt_live {
     unsigned inPos, needed;
     float* outq[2]; float* pinned; float* hostq; // two queued segments of OUTPUTSEG*2S floats (pinned for the D2H copy; plain host memory on a failed instance)
     int outCount, outReadOff;
+    // rate instance (srtLiveCreateRate): n samples out for n in at the host's rate fs, one constant delay A.  fs != 44100: the block
+    // goes H2D into d_blk, the input-side converter (ring d_hin [capIn][2] of host-rate history) writes the new 44.1 kHz frames into d_ring, every hop's
+    // segment lands in the stem ring d_sring [capS][2S] (hop h at slot h mod capS/1024), the output-side converter writes the call's n frames of
+    // all 2S planes into d_planes [2S][n], one D2H brings them to pinOut.  fs == 44100: no converter; the host ring and a pinned queue of nq segments.
+    bool rate;
+    int fs, maxBlock, A, nq;
+    long long nHost, c44;                // host samples received / 44.1 kHz frames written to d_ring
+    SrtRsFilter fin, fout;
+    int Bin, Bout, capIn, capS;
+    size_t ldsIn, ldsOut;
+    float *d_blk, *d_hin, *d_sring, *d_planes, *pinIn, *pinOut;
 };
 
 namespace {
@@ -95,12 +108,37 @@ SrtStreamHop hop_params(const srt_live* s, long long h)
     return p;
 }
 
+// At every hop h = K-1 (mod K): join the run started K hops ago (its masks serve the next K hops), then start one on the window [h-T+1, h].
+// false: a device call failed (reported, the instance is muted)
+#define HIPOK(x, where) do { hipError_t _e = (x); if (_e != hipSuccess) { s->failed = true; stream_fail(where, hipGetErrorString(_e)); return false; } } while (0)
+bool hop_schedule(srt_live* s, long long h)
+{
+    if (h % s->K != s->K - 1) return true;
+    if (s->nnRunning) {
+        HIPOK(hipStreamWaitEvent(s->hop, s->evNN, 0), "stream join");
+        s->joinedHop = s->runHop; s->joinedBuf = s->runBuf;
+    }
+    const int b = !s->runBuf;                                             // the buffer the joined run's predecessor wrote: its last reader was this hop
+    if (srt_launch_live_gather(s->d_mag, s->d_tmp, s->T, s->F, (int)((h + 1) % s->T), s->hop)) { s->failed = true; return stream_fail("stream window", "kernel launch failed"); }   // replaces the "Prevent race condition" copy (:364-365)
+    HIPOK(hipEventRecord(s->evMag, s->hop), "stream flip");
+    HIPOK(hipStreamWaitEvent(s->nn, s->evMag, 0), "stream flip");
+    if (srtForward(s->eng, s->d_tmp, 1, masks_buf(s, b))) { s->failed = true; return stream_fail("stream networks", nullptr); }
+    if (s->ratio && srtRatioMask(s->eng, masks_buf(s, b), 1)) { s->failed = true; return stream_fail("stream ratio mask", nullptr); }
+    HIPOK(hipEventRecord(s->evNN, s->nn), "stream flip");
+    s->nnRunning = true; s->runHop = h; s->runBuf = b;
+    return true;
+}
+
 void process_hop(srt_live* s)                                                // LLPAMSProcessNPR, Spleeter4Stems.c:257-381
 {
     const size_t seg = (size_t)OUTPUTSEG * 2 * s->S;
-    if (s->outCount >= 2) { float* t = s->outq[0]; s->outq[0] = s->outq[1]; s->outq[1] = t; s->outCount = 1; s->outReadOff = 0; }   // the reference overruns its 2-slot queue here (caller passed > 1024 samples without draining); drop the oldest segment instead
-    float* dst = s->outq[s->outCount];
-    s->outCount++;
+    float* dst;
+    if (s->rate) dst = s->outq[0] + (size_t)(s->hops % s->nq) * seg;        // a 44.1 kHz rate instance: hop h in slot h mod nq of its queue (rate_slice_44100)
+    else {
+        if (s->outCount >= 2) { float* t = s->outq[0]; s->outq[0] = s->outq[1]; s->outq[1] = t; s->outCount = 1; s->outReadOff = 0; }   // the reference overruns its 2-slot queue here (caller passed > 1024 samples without draining); drop the oldest segment instead
+        dst = s->outq[s->outCount];
+        s->outCount++;
+    }
     s->needed = OUTPUTSEG;
     if (s->failed) goto failed;
     {
@@ -111,21 +149,7 @@ void process_hop(srt_live* s)                                                // 
         HIPTRY(hipMemcpyAsync(dst, s->d_out, seg * sizeof(float), hipMemcpyDeviceToHost, s->hop), "stream hop");
         HIPTRY(hipEventRecord(s->evOut, s->hop), "stream hop");
         s->hops = h + 1;
-        if (h % s->K == s->K - 1) {
-            // join the run started K hops ago (its masks serve the next K hops), then start one on the window [h-T+1, h]
-            if (s->nnRunning) {
-                HIPTRY(hipStreamWaitEvent(s->hop, s->evNN, 0), "stream join");
-                s->joinedHop = s->runHop; s->joinedBuf = s->runBuf;
-            }
-            const int b = !s->runBuf;                                         // the buffer the joined run's predecessor wrote: its last reader was this hop
-            if (srt_launch_live_gather(s->d_mag, s->d_tmp, s->T, s->F, (int)((h + 1) % s->T), s->hop)) { s->failed = true; stream_fail("stream window", "kernel launch failed"); goto failed; }   // replaces the "Prevent race condition" copy (:364-365)
-            HIPTRY(hipEventRecord(s->evMag, s->hop), "stream flip");
-            HIPTRY(hipStreamWaitEvent(s->nn, s->evMag, 0), "stream flip");
-            if (srtForward(s->eng, s->d_tmp, 1, masks_buf(s, b))) { s->failed = true; stream_fail("stream networks", nullptr); goto failed; }
-            if (s->ratio && srtRatioMask(s->eng, masks_buf(s, b), 1)) { s->failed = true; stream_fail("stream ratio mask", nullptr); goto failed; }
-            HIPTRY(hipEventRecord(s->evNN, s->nn), "stream flip");
-            s->nnRunning = true; s->runHop = h; s->runBuf = b;
-        }
+        if (!hop_schedule(s, h)) goto failed;
         // the segment must be in host memory before the callback returns.  With K < T the call waits for its segment only, not for the join it just
         // queued (at K = 1 the run the previous call started would otherwise be on every call's critical path); K = T (the plugin) keeps the
         // whole-stream wait it always had
@@ -145,6 +169,7 @@ srt_live* live_new(int F, int T, int S, int K, int L)
     memset(s, 0, sizeof *s);
     s->F = F; s->T = T; s->S = S; s->K = K; s->L = L; s->D = L + 2 * K; s->hw = (size_t)F * T;
     s->needed = OUTPUTSEG;
+    s->nq = 2;
     s->runHop = s->joinedHop = -1;
     s->runBuf = s->joinedBuf = 1;                                             // run 0 writes buffer 0; until it is joined the hops read buffer 1
     s->failed = true;                                                         // until live_init has succeeded
@@ -161,9 +186,14 @@ void live_free(srt_live* s)
     if (s->hop) hipStreamSynchronize(s->hop);
     if (s->nn) hipStreamSynchronize(s->nn);
     if (s->eng) srtDestroy(s->eng);
-    void* d[] = { s->d_ring, s->d_spec, s->d_mag, s->d_tmp, s->d_masks, s->d_overlap, s->d_out, s->d_awin, s->d_swin, s->d_tw };
+    void* d[] = { s->d_ring, s->d_spec, s->d_mag, s->d_tmp, s->d_masks, s->d_overlap, s->d_out, s->d_awin, s->d_swin, s->d_tw,
+                  s->d_blk, s->d_hin, s->d_sring, s->d_planes };
     for (void* q : d) if (q) hipFree(q);
+    srt_rs_filter_free(&s->fin);
+    srt_rs_filter_free(&s->fout);
     if (s->pinned) hipHostFree(s->pinned);
+    if (s->pinIn) hipHostFree(s->pinIn);
+    if (s->pinOut) hipHostFree(s->pinOut);
     free(s->hostq);
     hipEvent_t ev[] = { s->evMag, s->evNN, s->evOut };
     for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
@@ -228,7 +258,7 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     INITTRY(hipMemcpy(s->d_awin, an.data(), FFTSIZE * 4, hipMemcpyHostToDevice));
     INITTRY(hipMemcpy(s->d_swin, sy.data(), FFTSIZE * 4, hipMemcpyHostToDevice));
     INITTRY(hipMemcpy(s->d_tw, tw.data(), 2 * FFTSIZE * 4, hipMemcpyHostToDevice));
-    INITTRY(hipHostMalloc((void**)&s->pinned, 2 * OUTPUTSEG * 2 * S * sizeof(float), hipHostMallocDefault));   // pinned queue for the per-hop D2H copy
+    INITTRY(hipHostMalloc((void**)&s->pinned, s->nq * OUTPUTSEG * 2 * S * sizeof(float), hipHostMallocDefault));   // pinned queue for the per-hop D2H copy
     INITTRY(hipStreamSynchronize(nullptr));               // masks / windows / twiddles (null-stream copies) are in place before the first hop
     // Pre-warm the per-hop path too: the first launch of the hop kernels loads their code, and eight plugin instances making their first call at
     // the same time queued behind each other for it - the slowest call of every instance was its FIRST one, 7.5 ms (round 6, host/rt_latency.c
@@ -248,9 +278,12 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     return 0;
 }
 
+int live_process_rate(srt_live* s, const float* inL, const float* inR, int n, float* const* out);      // rate instances, below
+
 // Spleeter4StemsProcessSamples' accounting (Spleeter4Stems.c:512-582) for 2S planar outputs; returns the samples written to each
 int live_process(srt_live* s, const float* inLeft, const float* inRight, int inSampleCount, float* const* components)
 {
+    if (s->rate) return live_process_rate(s, inLeft, inRight, inSampleCount, components);
     const int nc = 2 * s->S;
     int outSampleCount = 0;
     const int maxOut = inSampleCount;
@@ -282,10 +315,185 @@ int live_process(srt_live* s, const float* inLeft, const float* inRight, int inS
     return outSampleCount;
 }
 
+// ---- rate instances (srtLiveCreateRate)
+long long fdiv_ll(long long a, long long b) { long long q = a / b; if (a - q * b < 0) --q; return q; }      // floor(a / b), b > 0
+long long cdiv_ll(long long a, long long b) { return -fdiv_ll(-a, b); }
+
+// The smallest delay A (host samples) that is causal for every call size.  P / Q = fs / 44100 reduced; H1, H2: horizons of the fs -> 44.1 k and the
+// 44.1 k -> fs converter (0, 0 at fs = 44100).  Hop h + 1 is complete once N_h = floor((1024 h + 1023) P / Q) + H1 + 1 host samples have arrived; the
+// first output sample that needs it is m_h = A + ceil((1024 h - Dl - H2) P / Q), Dl = (D + 1) * 1024, and m_h + 1 >= N_h must hold for every h >= 0.
+// The difference is periodic in h with period Q, so A = H1 + max over one period of floor((1024 h + 1023) P / Q) - ceil((1024 h - Dl - H2) P / Q),
+// which is H1 + floor((1023 + Dl + H2) P / Q) whenever Q is odd (then some h makes the second term an integer).
+int rate_latency(long long P, long long Q, int H1, int H2, int D)
+{
+    const long long Dl = (long long)(D + 1) * OUTPUTSEG;
+    long long best = 0;
+    for (long long h = 0; h < Q; ++h) {
+        const long long v = fdiv_ll((OUTPUTSEG * h + OUTPUTSEG - 1) * P, Q) - cdiv_ll((OUTPUTSEG * h - Dl - H2) * P, Q);
+        if (h == 0 || v > best) best = v;
+    }
+    return (int)(H1 + best);
+}
+
+// geometry of both converters of a rate instance (the built-in filter) and its latency; no HIP call.  0, or -1 with the error set
+int rate_geometry(int fs, int K, int L, const char* who, SrtRsGeom* gin, SrtRsGeom* gout, int* A)
+{
+    if (fs == 44100) { *A = rate_latency(1, 1, 0, 0, L + 2 * K); return 0; }
+    if (const int rc = srt_rs_geometry(fs, 44100, false, 0, 0, who, gin)) return rc;
+    if (const int rc = srt_rs_geometry(44100, fs, false, 0, 0, who, gout)) return rc;
+    *A = rate_latency(gin->P, gin->Q, srt_rs_horizon(*gin), srt_rs_horizon(*gout), L + 2 * K);
+    return 0;
+}
+
+// allocation, filter banks and the pre-warm of the two converter kernels, after live_init
+int live_rate_init(srt_live* s, const SrtRsGeom& gin, const SrtRsGeom& gout, const char* who)
+{
+    if (s->fs == 44100) return 0;
+#define INITTRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) { s->failed = true; stream_fail(who, hipGetErrorString(_e)); return -2; } } while (0)
+    const int nc = 2 * s->S;
+    s->failed = true;                                                          // until everything below has succeeded
+    s->Bin = srt_rsstream_block(gin, &s->ldsIn);
+    s->Bout = srt_rsstream_block(gout, &s->ldsOut);
+    if (!s->Bin || !s->Bout) { stream_fail(who, "filter too long for this sample rate"); return -2; }
+    if (srt_rs_filter_create(gin, nullptr, 0, s->hop, who, &s->fin) || srt_rs_filter_create(gout, nullptr, 0, s->hop, who, &s->fout)) { stream_fail(who, nullptr); return -2; }
+    s->capIn = s->maxBlock + 2 * gin.LO + 1;
+    // stem ring: the frames a call's output windows span (max_block host samples of 44.1 kHz frames + both filter halves) plus the hops that may
+    // already be written ahead of the newest window (one hop of accounting, one of slack), rounded up to whole segments
+    const long long span = cdiv_ll((long long)s->maxBlock * gin.Q, gin.P) + 2 * gout.LO + srt_rs_horizon(gout) + 3 * OUTPUTSEG + 16;
+    s->capS = (int)(cdiv_ll(span, OUTPUTSEG) * OUTPUTSEG);
+    INITTRY(hipMalloc((void**)&s->d_blk, 2 * (size_t)s->maxBlock * sizeof(float)));
+    INITTRY(hipMalloc((void**)&s->d_hin, 2 * (size_t)s->capIn * sizeof(float)));
+    INITTRY(hipMalloc((void**)&s->d_sring, (size_t)s->capS * nc * sizeof(float)));
+    INITTRY(hipMalloc((void**)&s->d_planes, (size_t)nc * s->maxBlock * sizeof(float)));
+    INITTRY(hipHostMalloc((void**)&s->pinIn, 2 * (size_t)s->maxBlock * sizeof(float), hipHostMallocDefault));
+    INITTRY(hipHostMalloc((void**)&s->pinOut, (size_t)nc * s->maxBlock * sizeof(float), hipHostMallocDefault));
+    INITTRY(hipMemsetAsync(s->d_blk, 0, 2 * (size_t)s->maxBlock * sizeof(float), s->hop));
+    INITTRY(hipMemsetAsync(s->d_hin, 0, 2 * (size_t)s->capIn * sizeof(float), s->hop));          // zero weights must meet finite values (padded taps)
+    INITTRY(hipMemsetAsync(s->d_sring, 0, (size_t)s->capS * nc * sizeof(float), s->hop));
+    INITTRY(hipMemsetAsync(s->d_ring, 0, sizeof s->ring, s->hop));
+    // pre-warm: one launch of each converter kernel on silence (loads their code on this thread); the state stays as created - the input side appends
+    // one zero frame at slot 0 and writes one zero frame into d_ring, the output side writes one zero into d_planes
+    {
+        SrtRsStreamArgs a; memset(&a, 0, sizeof a);
+        a.ring = s->d_hin; a.cap = s->capIn; a.C = 2; a.in = s->d_blk; a.inStride = 1; a.have = 0; a.n = 1; a.append = 1; a.end = 1;
+        a.out0 = 0; a.nOut = 1; a.out = s->d_ring; a.outStride = FFTSIZE; a.outPos = 0; a.outMask = FFTSIZE - 1; a.B = s->Bin;
+        if (srt_rsstream_launch(s->fin, a, s->ldsIn, s->hop)) { stream_fail(who, "converter pre-warm: kernel launch failed"); return -2; }
+        memset(&a, 0, sizeof a);
+        a.ring = s->d_sring; a.cap = s->capS; a.C = nc; a.out0 = 0; a.nOut = 1; a.out = s->d_planes; a.outStride = 1; a.outMask = 0x7fffffff; a.B = s->Bout;
+        if (srt_rsstream_launch(s->fout, a, s->ldsOut, s->hop)) { stream_fail(who, "converter pre-warm: kernel launch failed"); return -2; }
+        INITTRY(hipMemcpyAsync(s->pinOut, s->d_planes, nc * sizeof(float), hipMemcpyDeviceToHost, s->hop));
+        INITTRY(hipStreamSynchronize(s->hop));
+    }
+#undef INITTRY
+    s->failed = false;
+    return 0;
+}
+
+// the hop that the 44.1 kHz frames in d_ring complete: hop kernels (segment into the stem ring), then the run / join schedule.  false: failed
+bool rate_hop(srt_live* s)
+{
+    const long long h = s->hops;
+    SrtStreamHop p = hop_params(s, h);
+    p.out = s->d_sring + (size_t)(h % (s->capS / OUTPUTSEG)) * OUTPUTSEG * 2 * s->S;
+    if (srt_launch_stream_hop(p, s->hop)) { s->failed = true; return stream_fail("stream hop", "kernel launch failed"); }
+    s->hops = h + 1;
+    return hop_schedule(s, h);
+}
+
+// one call of n <= max_block samples at fs != 44100: one H2D, converter -> hops -> converter, one D2H, one wait.  false: failed (the caller emits silence)
+bool rate_slice(srt_live* s, const float* inL, const float* inR, int n, float* const* planes)
+{
+    const int nc = 2 * s->S;
+    memcpy(s->pinIn, inL, n * sizeof(float));
+    memcpy(s->pinIn + n, inR, n * sizeof(float));
+    HIPOK(hipMemcpyAsync(s->d_blk, s->pinIn, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->hop), "stream block");
+    const long long cNew = srt_rs_computable(s->fin.g, s->nHost + n);
+    long long j = s->c44;
+    bool first = true;
+    for (;;) {
+        // d_ring holds one 4096-sample frame: the frames of hop h + 1 may only be written after hop h's kernels have read it, so the input side is
+        // launched once per hop the call completes and once for the frames after the last one (stream order does the rest)
+        const long long boundary = (s->hops + 1) * OUTPUTSEG, e = cNew < boundary ? cNew : boundary;
+        if (first || e > j) {
+            SrtRsStreamArgs a; memset(&a, 0, sizeof a);
+            a.ring = s->d_hin; a.cap = s->capIn; a.C = 2;
+            a.in = s->d_blk; a.inStride = n; a.have = s->nHost; a.n = n; a.append = first; a.end = s->nHost + n;
+            a.out0 = j; a.nOut = (int)(e - j);
+            a.out = s->d_ring; a.outStride = FFTSIZE; a.outPos = (int)(j & (FFTSIZE - 1)); a.outMask = FFTSIZE - 1;
+            a.B = s->Bin;
+            if (srt_rsstream_launch(s->fin, a, s->ldsIn, s->hop)) { s->failed = true; return stream_fail("stream converter", "kernel launch failed"); }
+            first = false;
+        }
+        j = e;
+        s->inPos = (unsigned)(j & (FFTSIZE - 1));
+        if (j < boundary) break;
+        if (!rate_hop(s)) return false;
+    }
+    const long long m0 = s->nHost;
+    s->nHost += n; s->c44 = cNew;
+    {
+        // out[m] = the 44.1 k -> fs converter's frame m - A of the stem stream shifted by Dl = (D + 1) * 1024 input frames
+        SrtRsStreamArgs a; memset(&a, 0, sizeof a);
+        a.ring = s->d_sring; a.cap = s->capS; a.C = nc;
+        a.have = a.end = s->hops * OUTPUTSEG; a.shift = (long long)(s->D + 1) * OUTPUTSEG;
+        a.out0 = m0 - s->A; a.nOut = n;
+        a.out = s->d_planes; a.outStride = n; a.outPos = 0; a.outMask = 0x7fffffff;
+        a.B = s->Bout;
+        if (srt_rsstream_launch(s->fout, a, s->ldsOut, s->hop)) { s->failed = true; return stream_fail("stream converter", "kernel launch failed"); }
+    }
+    HIPOK(hipMemcpyAsync(s->pinOut, s->d_planes, (size_t)nc * n * sizeof(float), hipMemcpyDeviceToHost, s->hop), "stream block");
+    HIPOK(hipEventRecord(s->evOut, s->hop), "stream block");
+    if (s->K < s->T) HIPOK(hipEventSynchronize(s->evOut), "stream block");       // as process_hop: the call's own output only, not the run it queued
+    else HIPOK(hipStreamSynchronize(s->hop), "stream block");
+    for (int c = 0; c < nc; ++c) memcpy(planes[c], s->pinOut + (size_t)c * n, n * sizeof(float));
+    return true;
+}
+
+// fs == 44100: the 44.1 kHz hop path as it is (host ring, one H2D and one D2H per hop), the segments queued in nq pinned slots; out[m] = y44[m - 1023].
+// false: failed
+bool rate_slice_44100(srt_live* s, const float* inL, const float* inR, int n, float* const* planes)
+{
+    const int nc = 2 * s->S;
+    int left = n;
+    while (left > 0) {
+        const int c = (int)s->needed < left ? (int)s->needed : left;
+        memcpy(&s->ring[0][s->inPos], inL, c * sizeof(float));
+        memcpy(&s->ring[1][s->inPos], inR, c * sizeof(float));
+        inL += c; inR += c; left -= c;
+        s->inPos = (s->inPos + c) & (FFTSIZE - 1);
+        s->needed -= c;
+        if (s->needed == 0) process_hop(s);
+    }
+    s->nHost += n;
+    if (s->failed) return false;
+    const size_t seg = (size_t)OUTPUTSEG * nc;
+    for (int i = 0; i < n; ++i) {
+        const long long k = s->nHost - n + i - (OUTPUTSEG - 1);
+        if (k < 0) { for (int c = 0; c < nc; ++c) planes[c][i] = 0.0f; continue; }
+        const float* src = s->outq[0] + (size_t)((k / OUTPUTSEG) % s->nq) * seg + (size_t)(k % OUTPUTSEG) * nc;
+        for (int c = 0; c < nc; ++c) planes[c][i] = src[c];
+    }
+    return true;
+}
+
+int live_process_rate(srt_live* s, const float* inL, const float* inR, int n, float* const* out)
+{
+    const int nc = 2 * s->S;
+    float* planes[2 * SRT_MAX_STEMS];
+    for (int done = 0; done < n; ) {
+        const int c = n - done < s->maxBlock ? n - done : s->maxBlock;
+        for (int j = 0; j < nc; ++j) planes[j] = out[j] + done;
+        if (s->failed || !(s->fs == 44100 ? rate_slice_44100(s, inL + done, inR + done, c, planes) : rate_slice(s, inL + done, inR + done, c, planes)))
+            for (int j = 0; j < nc; ++j) memset(planes[j], 0, c * sizeof(float));       // muted: silence, n written per call
+        done += c;
+    }
+    return n;
+}
+
 int live_latency(int K, int L) { return (L + 2 * K) * OUTPUTSEG + OUTPUTSEG; }
 
 // the plugin surface: VST config (4 stems, ELU, oob 0.25 / 0 / 0.25 / 0.25, Spleeter4Stems.c:444-447), K and L as given
-void s4s_init(Spleeter4Stems* msr, int F, int T, void* coeffProvider[4], int K, int L, const char* who)
+void s4s_init(Spleeter4Stems* msr, int F, int T, void* coeffProvider[4], int K, int L, const char* who, int sampleRate = 0, int maxBlock = 0)
 {
     if (!msr) return;
     SrtSetupLock setup;                                      // (srt_internal.h: set-up paths are serialised process-wide)
@@ -297,13 +505,20 @@ void s4s_init(Spleeter4Stems* msr, int F, int T, void* coeffProvider[4], int K, 
     srt_live* s = live_new(F, T, 4, args_ok ? K : (T >= 1 ? T : 1), args_ok ? L : 0);
     if (!s) { stream_fail(who, "out of host memory"); return; }
     msr->impl = s;
+    if (sampleRate) { s->rate = true; s->fs = sampleRate; s->maxBlock = maxBlock >= 1 ? maxBlock : 1; }     // a muted rate instance still writes inSampleCount samples per call
     if (!s->hostq) { stream_fail(who, "out of host memory"); return; }
     if (!args_ok) { stream_fail(who, "hopsPerRun must be in 1..timeStep and lookahead in 0..timeStep-hopsPerRun"); return; }
+    SrtRsGeom gin, gout;
+    if (sampleRate) {
+        if (maxBlock < 1 || maxBlock > SRT_LIVE_MAX_BLOCK) { stream_fail(who, "maxBlock must be in 1..65536"); return; }
+        if (rate_geometry(sampleRate, K, L, who, &gin, &gout, &s->A)) { stream_fail(who, nullptr); return; }
+        if (sampleRate == 44100) s->nq = (maxBlock + OUTPUTSEG - 1) / OUTPUTSEG + 2;    // only the 44.1 kHz path queues segments on the host
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) { stream_fail(who, "no HIP device (this library has no CPU path)"); return; }
     for (int k = 0; k < 4; ++k) if (!coeffProvider || !coeffProvider[k]) { stream_fail(who, "null coefficient pointer"); return; }
     const void* coeff[4] = { coeffProvider[0], coeffProvider[1], coeffProvider[2], coeffProvider[3] };
-    live_init(s, cfg, coeff, who);
+    if (live_init(s, cfg, coeff, who) == 0 && sampleRate) live_rate_init(s, gin, gout, who);
 }
 }  // namespace
 
@@ -317,10 +532,15 @@ void Spleeter4StemsInitLive(Spleeter4Stems* msr, int F, int T, void* coeffProvid
     s4s_init(msr, F, T, coeffProvider, hopsPerRun, lookahead, "Spleeter4StemsInitLive");
 }
 
+void Spleeter4StemsInitRate(Spleeter4Stems* msr, int F, int T, void* coeffProvider[4], int hopsPerRun, int lookahead, int sampleRate, int maxBlock)
+{
+    s4s_init(msr, F, T, coeffProvider, hopsPerRun, lookahead, "Spleeter4StemsInitRate", sampleRate ? sampleRate : -1, maxBlock);
+}
+
 int Spleeter4StemsLatency(const Spleeter4Stems* msr)
 {
     const srt_live* s = msr ? (const srt_live*)msr->impl : nullptr;
-    return s ? live_latency(s->K, s->L) : 0;
+    return s ? (s->rate ? s->A : live_latency(s->K, s->L)) : 0;
 }
 
 void Spleeter4StemsFree(Spleeter4Stems* msr)
@@ -358,6 +578,44 @@ int srtLiveCreate(const srt_config* cfg, int hops_per_run, int lookahead, const 
     return 0;
 }
 
+int srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead)
+{
+    if (hops_per_run < 1 || lookahead < 0) return srt_set_error(-1, "%s", "srtLiveRateLatency: hops_per_run must be at least 1 and lookahead at least 0");
+    SrtRsGeom gin, gout;
+    int A = 0;
+    if (const int rc = rate_geometry(sample_rate, hops_per_run, lookahead, "srtLiveRateLatency", &gin, &gout, &A)) return rc;
+    return A;
+}
+
+int srtLiveCreateRate(const srt_config* cfg, int hops_per_run, int lookahead, int sample_rate, int max_block, const void* const* h_coeff, srt_live** out)
+{
+    const char* who = "srtLiveCreateRate";
+    if (!cfg || !h_coeff || !out) return srt_set_error(-1, "%s", "srtLiveCreateRate: null argument");
+    *out = nullptr;
+    if (const int rc = srt_check_config(cfg, who)) return rc;
+    if (cfg->max_tiles != 1) return srt_set_error(-1, "%s", "srtLiveCreateRate: max_tiles must be 1 (a run is one window)");
+    if (hops_per_run < 1 || hops_per_run > cfg->T) return srt_set_error(-1, "%s", "srtLiveCreateRate: hops_per_run must be in 1..T");
+    if (lookahead < 0 || lookahead > cfg->T - hops_per_run) return srt_set_error(-1, "%s", "srtLiveCreateRate: lookahead must be in 0..T-hops_per_run");
+    if (max_block < 1 || max_block > SRT_LIVE_MAX_BLOCK) return srt_set_error(-1, "%s", "srtLiveCreateRate: max_block must be in 1..65536");
+    SrtRsGeom gin, gout;
+    int A = 0;
+    if (const int rc = rate_geometry(sample_rate, hops_per_run, lookahead, who, &gin, &gout, &A)) return rc;
+    for (int k = 0; k < cfg->n_stems; ++k)
+        if (!h_coeff[k]) return srt_set_error(-1, "%s", "srtLiveCreateRate: null coefficient blob");
+    SrtSetupLock setup;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return srt_set_error(-3, "%s", "srtLiveCreateRate: no HIP device (this library has no CPU path)");
+    srt_live* s = live_new(cfg->F, cfg->T, cfg->n_stems, hops_per_run, lookahead);
+    if (!s || !s->hostq) { live_free(s); return srt_set_error(-2, "%s", "srtLiveCreateRate: out of host memory"); }
+    s->rate = true; s->fs = sample_rate; s->maxBlock = max_block; s->A = A;
+    if (sample_rate == 44100) s->nq = (max_block + OUTPUTSEG - 1) / OUTPUTSEG + 2;     // only the 44.1 kHz path queues segments on the host
+    int rc = live_init(s, *cfg, h_coeff, who);
+    if (rc == 0) rc = live_rate_init(s, gin, gout, who);
+    if (rc) { live_free(s); return rc; }
+    *out = s;
+    return 0;
+}
+
 int srtLiveProcess(srt_live* s, const float* inL, const float* inR, int n, float* const* out)
 {
     if (!s || n < 0 || (n > 0 && (!inL || !inR || !out))) return srt_set_error(-1, "%s", "srtLiveProcess: bad argument");
@@ -368,7 +626,7 @@ int srtLiveProcess(srt_live* s, const float* inL, const float* inR, int n, float
 int srtLiveLatency(const srt_live* s)
 {
     if (!s) return srt_set_error(-1, "%s", "srtLiveLatency: null argument");
-    return live_latency(s->K, s->L);
+    return s->rate ? s->A : live_latency(s->K, s->L);
 }
 
 void srtLiveDestroy(srt_live* s)
