@@ -99,6 +99,25 @@ SRT_API int  srtSeparate(srt_engine *e, const float *d_L, const float *d_R, size
 SRT_API int  srtStftEx(srt_engine *e, const float *d_L, const float *d_R, size_t n, size_t frames, size_t rows, float *d_spec, float *d_mag);
 SRT_API int  srtSeparateEx(srt_engine *e, const float *d_L, const float *d_R, size_t n, size_t frames, size_t rows, float *d_out);
 
+/* ---- overlapped network tiles with cross-faded masks.  By default a signal is cut into back-to-back tiles of T frames (the reference's
+ * processMT): a frame next to a tile boundary sees zero padding where its neighbours should be, and the masks jump every T hops.  With an overlap of
+ * O rows (0 <= O <= T/2) consecutive tiles of one signal share O rows: stride S = T - O, tile j covers spectrum rows [jS, jS + T), and a signal of `rows`
+ * rows takes srtOverlapTiles(rows, T, O) tiles = 1 for rows <= T, else ceil((rows - O) / S) (rows of a tile past the signal's last row hold zero
+ * magnitudes).  Row r has the primary tile j1 = min(r / S, tiles - 1) at offset k = r - j1 S; when j1 > 0 and k < O it is row k + S of tile j1 - 1 as
+ * well, and its mask is a + w (b - a) with a from tile j1 - 1, b from tile j1 and w = (k + 1/2) / O; every other row takes its primary tile's mask.
+ * With ratio_mask the blended masks are normalised (blend first); the fp16 mode's half masks are converted, then blended.
+ * srtSetOverlap: per engine, off (0) by default, takes effect for later calls; -1 outside 0..T/2.  While it is on:
+ *   srtStft / srtStftEx   write d_mag as [srtOverlapTiles(rows, T, O)][2][T][F] in that layout (d_spec is unchanged);
+ *   srtForward            is unchanged (it takes any tile batch);
+ *   srtIstft              reads d_masks [n_stems][srtOverlapTiles(rows, T, O)][2][T][F] in that layout and blends;
+ *   srtSeparate[Ex]       compose the three; the signal must fit max_tiles OVERLAPPED tiles.
+ * Refused with -1, an error text that says "overlap" and nothing written while O > 0: srtSeparateHostStream[Ex], srtSeparateCli, srtSeparateCliHost,
+ * srtSeparateBatch, srtMultiSeparate*Host, srtIstftWiener and srtSeparate[Ex] with the Wiener filter on.  O = 0 is the back-to-back path, bit for bit.
+ * In graph mode the overlap is part of the captured call's key.
+ * srtOverlapTiles is pure host arithmetic (no device, like srtBatchPlan): 0 for rows = 0; 0 with srtLastError() text for T < 1 or O outside 0..T/2. */
+SRT_API int  srtSetOverlap(srt_engine *e, int overlap_rows);
+SRT_API size_t srtOverlapTiles(size_t rows, int T, int overlap_rows);
+
 /* Many independent tracks in one packed batch.  Track k of a batch occupies the packed tiles [tile0[k], tile0[k] + ceil(srtStftRows(n[k]) / T)).
  * srtBatchPlan is pure host arithmetic (no device, like srtRankSpan): tile0 may be NULL; *total_tiles = the sum.  -1 for ntracks < 1, T < 1 or any n[k] < 4096.
  * srtSeparateBatch: K whole tracks (srtSeparate geometry each) in one launch sequence - one batched STFT, one srtForward over the packed tiles, one batched

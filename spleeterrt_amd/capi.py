@@ -54,6 +54,9 @@ def load_library():
     L.srtForwardStems.argtypes = [vp, f32p, C.c_int, f32p, C.c_int, C.c_int]
     L.srtRatioMask.argtypes = [vp, f32p, C.c_int]
     L.srtSetWiener.argtypes = [vp, C.c_int]
+    L.srtSetOverlap.argtypes = [vp, C.c_int]
+    L.srtOverlapTiles.restype = C.c_size_t
+    L.srtOverlapTiles.argtypes = [C.c_size_t, C.c_int, C.c_int]
     L.srtIstftWiener.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_int, f32p]
     L.srtSeparateCli.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.srtSeparateCliHost.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
@@ -126,7 +129,7 @@ class Engine:
     """One engine per (device, stream): nstems sub-networks evaluated over batches of T x F spectrogram tiles."""
 
     def __init__(self, F=1024, T=256, stem_modes=(1, 1, 1, 1), oob_weights=None, variant=VARIANT_EXE, max_tiles=1,
-                 impl=IMPL_MFMA, device=None, precision=PREC_F32, ratio_mask=False, batch_invariant=False, wiener=0):
+                 impl=IMPL_MFMA, device=None, precision=PREC_F32, ratio_mask=False, batch_invariant=False, wiener=0, overlap=0):
         import torch
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: spleeterrt_amd has no CPU path")
@@ -148,8 +151,11 @@ class Engine:
         self._chk(self.L.srtCreate(C.byref(cfg), C.c_void_p(self.stream.cuda_stream), C.byref(h)))
         self.h = h
         self.wiener = 0
+        self.overlap = 0
         if wiener:
             self.set_wiener(wiener)
+        if overlap:
+            self.set_overlap(overlap)
 
     def _chk(self, rc):
         if rc < 0:
@@ -220,6 +226,17 @@ class Engine:
         self._chk(self.L.srtSetWiener(self.h, int(iterations)))
         self.wiener = int(iterations)
 
+    def set_overlap(self, rows):
+        """overlapped network tiles with cross-faded masks (srtSetOverlap): consecutive tiles of a signal share `rows` rows, 0 <= rows <= T/2
+        (0 = off, back-to-back tiles).  stft() then returns mag in the overlapped layout [tiles(rows), 2, T, F] and istft() expects masks in it."""
+        self._chk(self.L.srtSetOverlap(self.h, int(rows)))
+        self.overlap = int(rows)
+
+    def tiles(self, rows):
+        """network tiles of a signal of `rows` spectrum rows at the engine's overlap (stream.overlap_tiles)"""
+        from . import stream
+        return stream.overlap_tiles(rows, self.T, self.overlap)
+
     def istft_wiener(self, spec, masks, iterations=1):
         """spec [2,rows,2052,2], fp32 masks [S,ntiles,2,T,F] -> Wiener-filtered stems [S,2,rows*1024+3072] (srtIstftWiener)"""
         t = self.torch
@@ -241,7 +258,7 @@ class Engine:
         t = self.torch
         n = L.numel()
         rows = self.L.srtStftRows(n)
-        nt = (rows + self.T - 1) // self.T
+        nt = self.tiles(rows)
         spec = t.empty((2, rows, SPEC_LD, 2), device=self.device, dtype=t.float32)
         mag = t.empty((nt, 2, self.T, self.F), device=self.device, dtype=t.float32) if want_mag else None
         self._chk(self.L.srtStft(self.h, _ptr(L.contiguous()), _ptr(R.contiguous()), n, _ptr(spec), _ptr(mag)))

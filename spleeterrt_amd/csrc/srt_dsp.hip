@@ -209,6 +209,47 @@ __device__ __forceinline__ float srt_ratio_of(float own, const float* __restrict
     return (mine + e1) / (sum + eps);
 }
 
+// Overlapped network tiles (srtSetOverlap): consecutive tiles of a signal share O rows, stride S = T - O, tile j covers rows [jS, jS + T).
+// Row f lives at row k of its primary tile j1 = min(f / S, ntiles - 1); when j1 > 0 and k < O it is row k + S of tile j1 - 1 as well, and its mask is
+// a + w (b - a) with a from tile j1 - 1, b from tile j1, w = (k + 1/2) / O.  f is workgroup-uniform wherever this is used: scalar arithmetic.
+struct OvRow { int j1, k; bool two; float w; };
+__device__ __forceinline__ OvRow srt_ov_row(int f, int T, int O, int ntiles)
+{
+    const int S = T - O;
+    OvRow r;
+    r.j1 = min(f / S, ntiles - 1);
+    r.k = f - r.j1 * S;
+    r.two = r.j1 > 0 && r.k < O;
+    r.w = ((float)r.k + 0.5f) / (float)O;
+    return r;
+}
+// the cross-fade, rounded step by step (contract(off)): equal masks stay exactly equal (b - a = 0), so an all-ones mask stays the identity
+__device__ __forceinline__ float srt_blend(float a, float b, float w)
+{
+    const float d = b - a;
+    const float t = w * d;
+    return a + t;
+}
+// srt_ratio_of on BLENDED masks: every stem's value - the workgroup's own included - is blended from the two tiles' rows first (rowb0 / rowa0: mask row of stem 0
+// in the primary / the previous tile; rowa0 is read only when two), then squared and summed as in srt_ratio_of.  The RATIO overlap instantiations do not prefetch
+// their own mask row (it is one of the rows read here; the registers it would be staged in are what the F > 1024 form spills): ratio = false returns the stem's own
+// blended value.
+__device__ __forceinline__ float srt_ratio_of_ov(const float* __restrict__ rowb0, const float* __restrict__ rowa0, bool two, float w,
+                                                 size_t sstride, int nstems, int stem, int k, bool ratio)
+{
+    float sum = 0.0f, own = 0.0f;
+    for (int s = 0; s < nstems; ++s) {
+        float v = rowb0[(size_t)s * sstride + k];
+        if (two) v = srt_blend(rowa0[(size_t)s * sstride + k], v, w);
+        const float sq = v * v;
+        sum = sum + sq;
+        if (s == stem) own = v;
+    }
+    const float mine = own * own;
+    const float eps = 1e-10f, e1 = eps / (float)nstems;
+    return ratio ? (mine + e1) / (sum + eps) : own;
+}
+
 #pragma clang fp contract(fast)
 
 // What a workgroup of the inverse kernels reads and writes of ONE signal: the whole call's signal (srt_istft_ola_kernel / srt_istft_ola3_kernel),
@@ -218,8 +259,10 @@ struct IstftView { const float2* spec; const float* masks; float* out; size_t ou
 __device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { IstftView v = { p.spec, p.masks, p.out, p.out_len, p.frames }; return v; }
 
 #define ISTFT_OLA_LDS_F2 (2 * FFT_SMEM_F2 + FFT_TWB_F2)   // two staging / exchange buffers + the pass-2 twiddles (one LDS object)
-template <bool RATIO>
-__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem)
+// OV: overlapped network tiles (srt_ov_row): the mask row of a frame's primary tile is prefetched as always; inside an overlap the previous tile's row is
+// read when the frame is staged and the two are blended before the ratio / multiply
+template <bool RATIO, bool OV = false>
+__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
 {
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
     cf* sy = s_mem + FFT_SMEM_F2;                        // this frame's exchange 1; the roles swap every frame
@@ -249,7 +292,9 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
     // are read from a harmless table instead of branching on the pointer
     const bool has_mask = w.masks != nullptr;
     auto fetch = [&](int f) {                                               // 0 <= f < w.frames
-        const int tile = f / p.T, t = f % p.T;
+        int tile = f / p.T, t = f % p.T;
+        OvRow ov = { 0, 0, false, 0.0f };
+        if constexpr (OV) { ov = srt_ov_row(f, p.T, O, p.ntiles); tile = ov.j1; t = ov.k; }
         const cf* specL = spec + (size_t)f * SRT_SPEC_LD;
         const cf* specR = specL + p.spec_ch_stride;
         const float* mL = has_mask ? w.masks + ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F : p.tab.postWin;
@@ -258,7 +303,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
         for (int j = 0; j < 9; ++j) {
             const int k = min(tid + 256 * j, 2048), km = min(k, p.F - 1);
             sl[j] = specL[k]; sr[j] = specR[k];
-            gl[j] = mL[km]; gr[j] = mR[km];
+            if constexpr (!(RATIO && OV)) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
         }
     };
     float pw[16];                                       // this thread's 16 synthesis-window taps are the same for every frame
@@ -284,15 +329,34 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
         if (f < w.frames) {                             // workgroup-uniform; false only for the last three segments of the stream
             // staging into sx: its last readers (exchange 1 of the previous frame, when it was `sy`) all passed that frame's
             // second barrier; the first barrier below also orders the twiddle table written before the loop
+            OvRow ov = { 0, 0, false, 0.0f };
+            if constexpr (OV) {
+                ov = srt_ov_row(f, p.T, O, p.ntiles);
+                if (!RATIO && has_mask && ov.two) {      // cross-fade of the two tiles' masks: a (row k + S of the previous tile) + w (b - a).  The a rows are read HERE,
+                    // not with the prefetch (18 more staged registers spill at two workgroups per CU); the other workgroup of the CU covers the wait
+                    const float* aL = w.masks + ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) {
+                        const int km = min(min(tid + 256 * j, 2048), p.F - 1);
+                        gl[j] = srt_blend(aL[km], gl[j], ov.w); gr[j] = srt_blend(aL[tf + km], gr[j], ov.w);
+                    }
+                }
+            }
             if constexpr (RATIO) {
-                if (has_mask && p.ratio) {               // normalise this frame's mask values across the stems (they arrived with the spectrum rows)
-                    const int tile = f / p.T, t = f % p.T;
+                if (has_mask && (p.ratio || OV)) {       // normalise this frame's mask values across the stems (they arrived with the spectrum rows)
+                    const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                     const float* r0 = w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
 #pragma unroll
                     for (int j = 0; j < 9; ++j) {
                         const int km = min(min(tid + 256 * j, 2048), p.F - 1);
-                        gl[j] = srt_ratio_of(gl[j], r0, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
-                        gr[j] = srt_ratio_of(gr[j], r0 + tf, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
+                        if constexpr (OV) {              // every stem's masks, this one's included, are blended the same way before the squares are summed
+                            const float* a0 = r0 - 2 * tf + (size_t)(p.T - O) * p.F;
+                            gl[j] = srt_ratio_of_ov(r0, a0, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
+                            gr[j] = srt_ratio_of_ov(r0 + tf, a0 + tf, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
+                        } else {
+                            gl[j] = srt_ratio_of(gl[j], r0, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
+                            gr[j] = srt_ratio_of(gr[j], r0 + tf, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
+                        }
                     }
                 }
             }
@@ -339,6 +403,14 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_kernel(const SrtIstftPar
     const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
     __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
     istft_ola_run<RATIO>(p, istft_view(p), stem, run, G, s_mem);
+}
+// the same with overlapped network tiles: p.masks in the overlapped layout, p.ntiles = srtOverlapTiles(frames), O = rows two consecutive tiles share (1..T/2)
+template <bool RATIO = false>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_ov_kernel(const SrtIstftParams p, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<RATIO, true>(p, istft_view(p), stem, run, G, s_mem, O);
 }
 
 
@@ -399,7 +471,10 @@ struct StftView { const float* L; const float* R; size_t nsamples; int frames_co
 __device__ __forceinline__ StftView stft_view(const SrtStftParams& p) { StftView v = { p.L, p.R, p.nsamples, p.frames_computed, p.rows_total, p.spec, p.mag }; return v; }
 
 // frames [blk * fpb, (blk + 1) * fpb) of the view (rows past rows_total are not this call's)
-__device__ __forceinline__ void stft_run(const SrtStftParams& p, const StftView& w, int blk, int fpb, cf* s_mem)
+// OV: overlapped network tiles (srt_ov_row): a magnitude row goes to its primary tile and, inside an overlap, to row k + S of the previous tile too -
+// both from the epilogue's registers (the spectrum is unchanged); nt = srtOverlapTiles(rows_total)
+template <bool OV = false>
+__device__ __forceinline__ void stft_run(const SrtStftParams& p, const StftView& w, int blk, int fpb, cf* s_mem, int O = 0, int nt = 0)
 {
     cf* sx = s_mem;
     cf* mir = s_mem + FFT_SMEM_F2;
@@ -440,14 +515,18 @@ __device__ __forceinline__ void stft_run(const SrtStftParams& p, const StftView&
     for (int fi = 0; fi < fpb; ++fi) {
         const int f = blk * fpb + fi;
         if (f >= w.rows_total) break;
-        const int tile = f / p.T, t = f % p.T;
+        const OvRow ov = OV ? srt_ov_row(f, p.T, O, nt) : OvRow{ 0, 0, false, 0.0f };
+        const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
+        const bool two = OV && w.mag && ov.two;          // the row is in an overlap (workgroup-uniform)
         float* magL = w.mag ? w.mag + ((size_t)(tile * 2 + 0) * p.T + t) * p.F : nullptr;
         float* magR = w.mag ? w.mag + ((size_t)(tile * 2 + 1) * p.T + t) * p.F : nullptr;
+        const size_t prev = (size_t)(p.T + O) * p.F;     // floats from (tile, ch, t) back to (tile - 1, ch, t + S)
         cf* specL = reinterpret_cast<cf*>(w.spec) + (size_t)f * SRT_SPEC_LD;
         cf* specR = specL + p.spec_ch_stride;
         if (f >= w.frames_computed) {                    // rows the reference leaves calloc'ed (stftFix.c:368-371)
             for (int k = tid; k < SRT_SPEC_LD; k += 256) { specL[k] = f2(0.f, 0.f); specR[k] = f2(0.f, 0.f); }
             if (w.mag) for (int k = tid; k < p.F; k += 256) { magL[k] = 0.f; magR[k] = 0.f; }
+            if constexpr (OV) { if (two) for (int k = tid; k < p.F; k += 256) { (magL - prev)[k] = 0.f; (magR - prev)[k] = 0.f; } }
             continue;
         }
         cf v[16];
@@ -473,6 +552,7 @@ __device__ __forceinline__ void stft_run(const SrtStftParams& p, const StftView&
             if (w.mag && k < p.F) {
                 magL[k] = hypotf(sl.x, sl.y) * 4096.0f;              // main.c:468-469
                 magR[k] = hypotf(sr.x, sr.y) * 4096.0f;
+                if constexpr (OV) { if (two) { (magL - prev)[k] = hypotf(sl.x, sl.y) * 4096.0f; (magR - prev)[k] = hypotf(sr.x, sr.y) * 4096.0f; } }
             }
             specL[k] = sl;
             specR[k] = sr;
@@ -482,6 +562,7 @@ __device__ __forceinline__ void stft_run(const SrtStftParams& p, const StftView&
             specL[2048 + tid] = sl;
             specR[2048 + tid] = sr;
             if (w.mag && tid == 0 && 2048 < p.F) { magL[2048] = hypotf(sl.x, sl.y) * 4096.0f; magR[2048] = hypotf(sr.x, sr.y) * 4096.0f; }
+            if constexpr (OV) { if (two && tid == 0 && 2048 < p.F) { (magL - prev)[2048] = hypotf(sl.x, sl.y) * 4096.0f; (magR - prev)[2048] = hypotf(sr.x, sr.y) * 4096.0f; } }
         }
     }
 }
@@ -491,12 +572,18 @@ __global__ void __launch_bounds__(256, 3) srt_stft_kernel(const SrtStftParams p,
     __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
     stft_run(p, stft_view(p), blockIdx.x, fpb, s_mem);
 }
+// the same with overlapped network tiles: p.mag is [nt][2][T][F] with nt = srtOverlapTiles(rows_total), O = rows two consecutive tiles share (1..T/2)
+__global__ void __launch_bounds__(256, 3) srt_stft_ov_kernel(const SrtStftParams p, int fpb, int O, int nt)
+{
+    __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
+    stft_run<true>(p, stft_view(p), blockIdx.x, fpb, s_mem, O, nt);
+}
 
 // NM: mask rows cover bins < F <= 256 NM, so only the first NM of a thread's eight bins can carry a mask value (F = 1024: 4 prefetch registers per channel instead of 8)
 // M16: the masks are halves (the engine's own mask buffer in the fp16 mode, written by srt_head_rows_kernel<.., true>; never with RATIO)
 #define ISTFT_OLA3_LDS_F2 (FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2)
-template <int NM, bool RATIO, bool M16>
-__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem)
+template <int NM, bool RATIO, bool M16, bool OV = false>
+__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
 {
     cf* sx = s_mem;
     cf* mir = s_mem + FFT_SMEM_F2;
@@ -521,7 +608,9 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
     cf sl8, sr8;                                        // bin 2048 (only thread 0 uses it; the address is uniform)
     const bool has_mask = w.masks != nullptr;
     auto fetch = [&](int f) {                                               // 0 <= f < w.frames
-        const int tile = f / p.T, t = f % p.T;
+        int tile = f / p.T, t = f % p.T;
+        OvRow ov = { 0, 0, false, 0.0f };
+        if constexpr (OV) { ov = srt_ov_row(f, p.T, O, p.ntiles); tile = ov.j1; t = ov.k; }
         const cf* specL = spec + (size_t)f * SRT_SPEC_LD;
         const cf* specR = specL + p.spec_ch_stride;
         const size_t mo = ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F;
@@ -535,7 +624,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             if (j < NM) {
                 const int km = min(k, p.F - 1);
                 if constexpr (M16) { gl[j] = (float)hL[km]; gr[j] = (float)hL[tf + km]; }
-                else { gl[j] = mL[km]; gr[j] = mR[km]; }
+                else if constexpr (!(RATIO && OV)) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
             }
         }
         sl8 = specL[2048]; sr8 = specR[2048];
@@ -569,15 +658,37 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             // G = F'_L + i F'_R, F' = re - i im, Hermitian-extended; kept swapped (im, re): inverse-by-forward trick.  Bins k = tid + 256 j < 2048 are this
             // thread's own transform inputs n2 = j; their partners 4096 - k go through `mir` to thread 256 - tid (slot 15 - j).
             cf v[16];
+            OvRow ov = { 0, 0, false, 0.0f };
+            if constexpr (OV) {
+                ov = srt_ov_row(f, p.T, O, p.ntiles);
+                if (!RATIO && has_mask && ov.two) {      // cross-fade of the two tiles' masks (halves are converted first): a (row k + S of the previous tile) + w (b - a).
+                    // The a rows are read HERE, not with the prefetch: eight more staged registers do not fit the 168 of three workgroups per CU (9 dwords
+                    // spilled when tried); the wait is covered by the CU's other workgroups and falls on O of every T - O frames only
+                    const size_t ao = ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
+                    const _Float16* hA = reinterpret_cast<const _Float16*>(w.masks) + ao;
+#pragma unroll
+                    for (int j = 0; j < NM; ++j) {
+                        const int km = min(tid + 256 * j, p.F - 1);
+                        const float al = M16 ? (float)hA[km] : w.masks[ao + km], ar = M16 ? (float)hA[tf + km] : w.masks[ao + tf + km];
+                        gl[j] = srt_blend(al, gl[j], ov.w); gr[j] = srt_blend(ar, gr[j], ov.w);
+                    }
+                }
+            }
             if constexpr (RATIO) {
-                if (has_mask && p.ratio) {               // (see srt_ratio_of; the extra loads are why this instantiation is built for two workgroups per CU)
-                    const int tile = f / p.T, t = f % p.T;
+                if (has_mask && (p.ratio || OV)) {       // (see srt_ratio_of; the extra loads are why this instantiation is built for two workgroups per CU)
+                    const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                     const float* r0 = w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
 #pragma unroll
                     for (int j = 0; j < NM; ++j) {
                         const int km = min(tid + 256 * j, p.F - 1);
-                        gl[j] = srt_ratio_of(gl[j], r0, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
-                        gr[j] = srt_ratio_of(gr[j], r0 + tf, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
+                        if constexpr (OV) {              // every stem's masks, this one's included, are blended the same way before the squares are summed
+                            const float* a0 = r0 - 2 * tf + (size_t)(p.T - O) * p.F;
+                            gl[j] = srt_ratio_of_ov(r0, a0, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
+                            gr[j] = srt_ratio_of_ov(r0 + tf, a0 + tf, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
+                        } else {
+                            gl[j] = srt_ratio_of(gl[j], r0, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
+                            gr[j] = srt_ratio_of(gr[j], r0 + tf, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km);
+                        }
                     }
                 }
             }
@@ -621,8 +732,16 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_kernel(cons
     __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
     istft_ola3_run<NM, RATIO, M16>(p, istft_view(p), stem, run, G, s_mem);
 }
+// the same with overlapped network tiles (see srt_istft_ola_ov_kernel)
+template <int NM, bool RATIO = false, bool M16 = false>
+__global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_ov_kernel(const SrtIstftParams p, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, RATIO, M16, true>(p, istft_view(p), stem, run, G, s_mem, O);
+}
 
-int srt_launch_stft(const SrtStftParams& p, hipStream_t s)
+int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_tiles)
 {
     // short signals (one tile, the real-time regime): fewer frames per workgroup so that the frames spread over the CUs
     int fpb = p.rows_total >= 4096 ? STFT_FPB : (p.rows_total >= 1024 ? 2 : 1);
@@ -634,13 +753,19 @@ int srt_launch_stft(const SrtStftParams& p, hipStream_t s)
     }
     const int blocks = (p.rows_total + fpb - 1) / fpb;
     if (blocks <= 0) return 0;
-    SRT_LAUNCH(srt_stft_kernel, dim3(blocks), dim3(256), 0, s, p, fpb);
+    if (overlap > 0) {                                   // the rows of tile j are [j (T - O), j (T - O) + T): every row below rows_total must have a tile
+        if (overlap > p.T / 2 || ov_tiles < 1 || (size_t)(ov_tiles - 1) * (p.T - overlap) + p.T < (size_t)p.rows_total) return -1;
+        SRT_LAUNCH(srt_stft_ov_kernel, dim3(blocks), dim3(256), 0, s, p, fpb, overlap, ov_tiles);
+    } else SRT_LAUNCH(srt_stft_kernel, dim3(blocks), dim3(256), 0, s, p, fpb);
     return srt_launch_status();
 }
 
-int srt_launch_istft(const SrtIstftParams& p, hipStream_t s)
+int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
 {
     if (p.frames <= 0) return 0;
+    // overlapped tiles: p.ntiles tiles of stride T - O must cover every frame (the kernels index masks by srt_ov_row); without masks there is nothing to blend
+    if (overlap < 0 || (overlap > 0 && (overlap > p.T / 2 || p.ntiles < 1 || (size_t)(p.ntiles - 1) * (p.T - overlap) + p.T < (size_t)p.frames))) return -1;
+    const int O = p.masks ? overlap : 0;
     const int nseg = p.frames + 3;
     // One launch for all stems (blockIdx.y = stem): ~4 workgroups per CU over the whole grid when the stream is long enough,
     // runs of at least 13 segments so the 3-frame warm-up stays below ~25 % (64-tile batch, 4 stems: G = 65, 4.6 %).
@@ -656,6 +781,16 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s)
     const int blocks = (nseg + G - 1) / G;
     // one stem per workgroup: 32 accumulator + 54 prefetch registers + the FFT fit in 256 VGPRs at 2 workgroups per CU
     // F > 1024: eight mask registers per channel do not fit the 168-VGPR budget of the three-per-CU form (22 dwords would spill): the two-per-CU kernel
+    if (O > 0) {                                         // the overlap instantiations (the forms below keep their code)
+        const dim3 grid(blocks * p.nstems);
+        if (p.ratio && p.nstems > 1) {
+            if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_ov_kernel<true>), grid, dim3(256), 0, s, p, G, O);
+            else SRT_LAUNCH((srt_istft_ola3_ov_kernel<4, true>), grid, dim3(256), 0, s, p, G, O);
+        } else if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_ov_kernel<false>), grid, dim3(256), 0, s, p, G, O);
+        else if (p.masks16) SRT_LAUNCH((srt_istft_ola3_ov_kernel<4, false, true>), grid, dim3(256), 0, s, p, G, O);
+        else SRT_LAUNCH((srt_istft_ola3_ov_kernel<4>), grid, dim3(256), 0, s, p, G, O);
+        return srt_launch_status();
+    }
     if (p.ratio && p.masks && p.nstems > 1) {            // cross-stem ratio mask applied in the prologue (srt_ratio_of)
         if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_kernel<true>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
         else SRT_LAUNCH((srt_istft_ola3_kernel<4, true>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);

@@ -92,7 +92,8 @@ struct ForwardRecord {
 // `sw`: the run-time switches of the call (SrtSwitches, srt_internal.h) - all of them decide what a forward records, so a flipped switch captures a new
 // graph instead of replaying the old form.  Keys are zeroed before they are filled and compared with memcmp.
 #define SRT_BATCH_SLOTS 4
-struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; };
+// `overlap`: the rows consecutive network tiles share (srtSetOverlap) - a sequence captured at one overlap is never replayed at another.
+struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; int overlap; };
 // left: e->last as the capture left it (an eager call in between may have changed it)
 struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; ForwardRecord left; };
 #define SRT_GRAPH_SLOTS 4
@@ -138,6 +139,8 @@ struct srt_engine {
     size_t rows_cap = 0;
     // multichannel Wiener filter (srt_wiener.hip, srtSetWiener): allocated for max_tiles when it is switched on (or by the first srtIstftWiener)
     int wiener = 0;                                    // EM iterations applied by srtSeparate / srtSeparateEx, 0: off
+    // overlapped network tiles (srtSetOverlap): rows two consecutive tiles of one signal share, 0: back-to-back tiles (the reference's cut)
+    int overlap = 0;
     float* wslab = nullptr;                            // statistics partials + block maxima
     float* wtab = nullptr;                             // R tables, weight sums, a
     float2* wspec = nullptr;                           // filtered spectra [n_stems][2][rows][SRT_SPEC_LD]
@@ -154,6 +157,26 @@ size_t srtCoeffBytes(void) { return (size_t)SRT_COEFF_FLOATS * 4; }
 size_t srtStftRows(size_t n) { return (n + SRT_HOP - 1) / SRT_HOP; }
 size_t srtStftFrames(size_t n) { return n < SRT_FFT ? 0 : (n - SRT_FFT + SRT_HOP / 4) / SRT_HOP + 1; }   // stftFix.c:378 + tail frame
 size_t srtIstftLength(size_t rows) { return rows * SRT_HOP + (SRT_FFT - SRT_HOP); }
+
+// Overlapped network tiles, the one rule (mirrored by spleeterrt_amd/stream.py:overlap_tiles): stride S = T - O, tile j covers rows [jS, jS + T); one tile up
+// to T rows, else ceil((rows - O) / S) - every tile then owns a row no earlier tile covers, and the tiles cover all rows.  O = 0: ceil(rows / T).
+static size_t overlap_tiles(size_t rows, int T, int O) { return rows == 0 ? 0 : rows <= (size_t)T ? 1 : (rows - O + (T - O) - 1) / (T - O); }
+size_t srtOverlapTiles(size_t rows, int T, int overlap_rows)
+{
+    if (T < 1 || overlap_rows < 0 || overlap_rows > T / 2) { fail(-1, "srtOverlapTiles: need T >= 1 and 0 <= overlap <= T / 2"); return 0; }
+    return overlap_tiles(rows, T, overlap_rows);
+}
+static size_t tiles_of(const srt_engine* e, size_t rows) { return overlap_tiles(rows, e->cfg.T, e->overlap); }     // network tiles of a signal of `rows` rows
+static const char* const OVERLAP_REFUSED = "%s: not available with overlapped tiles (srtSetOverlap > 0; DESIGN.md 13 lists it as a follow-up): srtSetOverlap(e, 0) first";
+
+int srtSetOverlap(srt_engine* e, int overlap_rows)
+{
+    if (!e) return fail(-1, "srtSetOverlap: null engine");
+    if (overlap_rows < 0 || overlap_rows > e->cfg.T / 2) return fail(-1, "srtSetOverlap: the overlap must be 0 (off) .. T / 2 rows");
+    e->overlap = overlap_rows;
+    return 0;
+}
+int srt_engine_overlap(const srt_engine* e) { return e->overlap; }
 
 // element offset into an activation tensor whose elements are halves (act16) or floats
 static inline float* eoff(const srt_engine* e, float* base, size_t elems) { return (float*)((char*)base + elems * (e->act16 ? 2 : 4)); }
@@ -786,9 +809,9 @@ int srtStftEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_
     if (!e || !d_L || !d_R || !d_spec) return fail(-1, "srtStft: null argument");
     DeviceScope ds(e->device);
     if (rows < 1 || frames > rows) return fail(-1, "srtStft: need 1 <= frames <= rows");
-    const int T = e->cfg.T;
-    const size_t ntiles = (rows + T - 1) / T;
-    if (d_mag && ntiles > (size_t)e->cfg.max_tiles) return fail(-1, "srtStft: more than max_tiles * T rows");
+    const int T = e->cfg.T, O = d_mag ? e->overlap : 0;
+    const size_t ntiles = tiles_of(e, rows);
+    if (d_mag && ntiles > (size_t)e->cfg.max_tiles) return fail(-1, e->overlap ? "srtStft: more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtStft: more than max_tiles * T rows");
     SrtStftParams p; memset(&p, 0, sizeof p);
     p.L = d_L; p.R = d_R; p.nsamples = n;
     p.frames_computed = (int)frames;
@@ -796,12 +819,12 @@ int srtStftEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_
     p.spec = (float2*)d_spec; p.spec_ch_stride = rows * SRT_SPEC_LD;
     p.mag = nullptr; p.T = T; p.F = e->cfg.F; p.tab = tables_of(e);
     if (d_mag) {
-        // magnitude rows exist for whole tiles: rows..ntiles*T are zero (main.c:507-514)
+        // magnitude rows exist for whole tiles: rows..ntiles*T are zero (main.c:507-514); overlapped tiles end at row (ntiles - 1) (T - O) + T
         p.mag = d_mag;
-        if (ntiles * T > rows) HIPCHK(hipMemsetAsync(d_mag, 0, ntiles * 2 * (size_t)T * e->cfg.F * sizeof(float), e->stream));
+        if ((ntiles - 1) * (T - O) + T > rows) HIPCHK(hipMemsetAsync(d_mag, 0, ntiles * 2 * (size_t)T * e->cfg.F * sizeof(float), e->stream));
     }
     TimerScope ts(e, "stft");
-    if (srt_launch_stft(p, e->stream)) return fail(-2, "stft launch failed");
+    if (srt_launch_stft(p, e->stream, O, (int)ntiles)) return fail(-2, "stft launch failed");
     return 0;
 }
 
@@ -818,13 +841,14 @@ static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const fl
     const int T = e->cfg.T;
     SrtIstftParams p; memset(&p, 0, sizeof p);
     p.spec = spec; p.spec_ch_stride = rows * SRT_SPEC_LD;
-    p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = (int)((rows + T - 1) / T);
+    const int O = masks ? e->overlap : 0;               // (the single-stem callers - CLI flows, Wiener filter - refuse an overlap before they get here)
+    p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = (int)(O ? tiles_of(e, rows) : (rows + T - 1) / T);
     p.T = T; p.F = e->cfg.F;
     for (int s = 0; s < nstems; ++s) p.oob[s] = oob[s];
     p.ratio = ratio ? 1 : 0; p.masks16 = masks16 ? 1 : 0;
     p.frames_out = nullptr; p.out = d_out; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
     TimerScope ts(e, "istft");
-    if (srt_launch_istft(p, e->stream)) return fail(-2, "istft launch failed");
+    if (srt_launch_istft(p, e->stream, O)) return fail(-2, "istft launch failed");
     return 0;
 }
 // ONE stem's mask (or none) into a [2][len] destination
@@ -833,7 +857,7 @@ static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const fl
 {
     if (!e || !d_spec || !d_out) return fail(-1, "srtIstft: null argument");
     if (rows < 1) return fail(-1, "srtIstft: no rows");
-    if (d_masks && (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstft: rows exceed max_tiles * T");
+    if (d_masks && tiles_of(e, rows) > (size_t)e->cfg.max_tiles) return fail(-1, e->overlap ? "srtIstft: more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtIstft: rows exceed max_tiles * T");
     return istft_launch(e, (const float2*)d_spec, rows, d_masks, e->cfg.n_stems, e->cfg.oob_weight, ratio, masks16, d_out);
 }
 // (the public entry applies the masks as they are given: srtRatioMask is its caller's business)
@@ -891,6 +915,7 @@ int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float*
     if (!e || !d_spec || !d_masks || !d_out) return fail(-1, "srtIstftWiener: null argument");
     DeviceScope ds(e->device);
     if (iterations < 1 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtIstftWiener: iterations must be 1..3");
+    if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtIstftWiener");      // its kernels index masks by (row / T, row % T)
     if (rows < 1 || (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstftWiener: need 1 <= rows <= max_tiles * T");
     const int rc = ensure_wiener_ws(e);
     if (rc) return rc;
@@ -917,8 +942,7 @@ static bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw) { return 
 
 static int separate_issue(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
 {
-    const int T = e->cfg.T;
-    const size_t ntiles = (rows + T - 1) / T;
+    const size_t ntiles = tiles_of(e, rows);            // overlapped tiles: the three stages agree on the layout through e->overlap
     int rc = srtStftEx(e, d_L, d_R, n, frames, rows, (float*)e->spec, e->mag);
     if (rc) return rc;
     rc = forward_range(e, sw, e->mag, (int)ntiles, e->masks, 0, e->cfg.n_stems, masks16_wanted(e, sw));
@@ -931,15 +955,15 @@ static int separate_issue(srt_engine* e, const SrtSwitches& sw, const float* d_L
 int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
 {
     if (!e) return fail(-1, "srtSeparate: null engine");
-    const int T = e->cfg.T;
-    const size_t ntiles = (rows + T - 1) / T;
-    if (rows < 1 || ntiles > (size_t)e->cfg.max_tiles) return fail(-1, "srtSeparate: signal longer than max_tiles * T frames");
+    const size_t ntiles = tiles_of(e, rows);
+    if (rows < 1 || ntiles > (size_t)e->cfg.max_tiles) return fail(-1, e->overlap ? "srtSeparate: the signal takes more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtSeparate: signal longer than max_tiles * T frames");
+    if (e->overlap && e->wiener) return fail(-1, OVERLAP_REFUSED, "srtSeparate with the Wiener filter on");
     const SrtSwitches sw = srt_read_switches();
     if (!e->graph_mode) return separate_issue(e, sw, d_L, d_R, n, frames, rows, d_out);
     DeviceScope ds(e->device);
     GraphKey k;
     const bool valid = graph_prepare(e, d_L && d_R && d_out && frames <= rows, ntiles, 2, sw, &k);
-    k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.wiener = e->wiener;
+    k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.wiener = e->wiener; k.overlap = e->overlap;
     return run_graphed(e, k, valid, [&]() { return separate_issue(e, sw, d_L, d_R, n, frames, rows, d_out); });
 }
 
@@ -1006,6 +1030,7 @@ static int cli_check(srt_engine* e, int stems)
     if (stems != 2 && stems != 3) return fail(-1, "srtSeparateCli: stems must be 2 or 3");
     if (e->cfg.n_stems < 2) return fail(-1, "srtSeparateCli: the engine needs sub-networks 0 (drum) and 1 (vocal)");
     if (e->cfg.ratio_mask) return fail(-1, "srtSeparateCli: ratio_mask does not apply to the CLI flows (the sub-networks see different inputs)");
+    if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateCli");       // the residual chain reads masks and writes the second network's magnitudes by tile
     if (e->wiener) return fail(-1, "srtSeparateCli: the Wiener filter does not apply to the CLI flows (the sub-networks see different inputs, and its statistics span the whole signal)");
     return 0;
 }
@@ -1139,6 +1164,7 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
         if (!d_L[k] || !d_R[k] || !d_out[k]) return fail(-1, "srtSeparateBatch: null pointer in track %s", what);
         if (n[k] < SRT_FFT) return fail(-1, "srtSeparateBatch: track %s has fewer than 4096 samples", what);
     }
+    if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateBatch");     // srtBatchPlan has no overlap argument
     if (e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
     const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
     size_t total = 0;
@@ -1205,6 +1231,7 @@ static int host_stream(srt_engine* e, const float* h_L, const float* h_R, size_t
 {
     if (!e || !h_L || !h_R || !h_out) return fail(-1, "srtSeparateHostStream: null argument");
     if (rows < 1 || frames > rows) return fail(-1, "srtSeparateHostStream: need 1 <= frames <= rows");
+    if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateHostStream");  // the blend would have to cross the chunk seams
     if (e->wiener) return fail(-1, "srtSeparateHostStream: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)");
     DeviceScope ds(e->device);
     const int S = cli_stems ? cli_stems : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;

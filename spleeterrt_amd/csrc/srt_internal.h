@@ -191,8 +191,10 @@ struct SrtIstftParams {
     size_t out_len;           // frames*1024 + 3072
     SrtDspTables tab;
 };
-int srt_launch_stft(const SrtStftParams& p, hipStream_t s);
-int srt_launch_istft(const SrtIstftParams& p, hipStream_t s);
+// overlap > 0 (srtSetOverlap): consecutive network tiles share `overlap` rows - p.mag / p.masks are in the overlapped layout of ov_tiles / p.ntiles =
+// srtOverlapTiles(rows) tiles and the kernels' overlap instantiations run; 0: the back-to-back layout and the kernels as they always were
+int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap = 0, int ov_tiles = 0);
+int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap = 0);
 // packed batch of independent tracks (srtSeparateBatch): one row of the device-resident track table per track
 struct SrtBatchTrack {
     const float* L; const float* R; size_t n;    // the track's PCM, n >= 4096 samples
@@ -246,6 +248,7 @@ int srt_launch_wiener_finalize(const SrtWienerParams& p, int pass, hipStream_t s
 int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s);    // W_j x after `iters` iterations for every stem; bins >= F copied
 struct srt_engine;
 int srt_engine_wiener(const srt_engine* e);                                             // iterations switched on (srtSetWiener), 0: off
+int srt_engine_overlap(const srt_engine* e);                                            // rows consecutive network tiles share (srtSetOverlap), 0: off
 
 // streaming (srt_dsp.hip kernels, srt_stream.hip host logic): one hop = 1 forward + n_stems masked inverse FFTs + 50 % OLA
 struct SrtStreamHop {

@@ -242,6 +242,8 @@ static int multi_run(srt_multi* m, const float* h_L, const float* h_R, size_t n,
     if (cli_stems && cli_stems != 2 && cli_stems != 3) return mfail(-1, "srtMultiSeparateCliHost: stems must be 2 or 3");
     const int G = (int)m->eng.size(), T = m->cfg.T, NP = 2 * (cli_stems ? cli_stems : m->cfg.n_stems);
     for (int g = 0; g < G; ++g)
+        if (srt_engine_overlap(m->eng[g])) return mfail(-1, "srtMultiSeparate: not available with overlapped tiles (srtSetOverlap > 0 on an engine; ranks would have to be cut in overlapped strides): srtSetOverlap(engine, 0) first");
+    for (int g = 0; g < G; ++g)
         if (srt_engine_wiener(m->eng[g])) return mfail(-1, "srtMultiSeparate: the Wiener filter's statistics span the whole signal (ranges on several devices would each get their own covariance): srtSetWiener(engine, 0) first");
     const size_t rows = srtStftRows(n), total_len = srtIstftLength(rows), tail = SRT_FFT - SRT_HOP;
     std::vector<srt_span> sp(G);

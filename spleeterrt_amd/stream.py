@@ -86,6 +86,25 @@ def pack_tracks(ns, T, max_tiles):
     return groups
 
 
+def overlap_tiles(rows, T, O):
+    """srtOverlapTiles: network tiles of a signal of `rows` spectrum rows when consecutive tiles share O rows (0 <= O <= T/2).
+    Stride S = T - O, tile j covers rows [jS, jS + T): one tile up to T rows, else ceil((rows - O) / S) - every tile then owns at least one row
+    that no earlier tile covers, and the tiles cover all rows.  O = 0 is ceil(rows / T)."""
+    if T < 1 or O < 0 or O > T // 2:
+        raise ValueError("overlap_tiles: need T >= 1 and 0 <= O <= T / 2 (T = %d, O = %d)" % (T, O))
+    if rows <= 0:
+        return 0
+    S = T - O
+    return 1 if rows <= T else (rows - O + S - 1) // S
+
+
+def _refuse_overlap(engine):
+    """The chunked and ranked paths cut a stream at back-to-back tile boundaries; with overlapped tiles the blend would have to cross those seams."""
+    if getattr(engine, "overlap", 0):
+        raise ValueError("overlapped tiles (set_overlap > 0) are not available on the chunked / ranked paths: the mask blend would have to cross "
+                         "the chunk seams; set_overlap(0), or separate() a signal that fits the engine")
+
+
 def _refuse_wiener(engine, world):
     """The Wiener filter's statistics span the whole signal: ranks would each filter their range with its own covariance."""
     if world > 1 and getattr(engine, "wiener", 0):
@@ -100,6 +119,7 @@ def separate_host_range(engine, L, R, rank=0, world=1, out=None, pinned=False):
     (span, None) when the rank has no tiles.  The reference's counterpart is one tile-range worker of processMT
     (Executable/main.c:544-673); there is no exchange with other ranks."""
     _refuse_wiener(engine, world)
+    _refuse_overlap(engine)
     sp = rank_span(len(L), engine.T, rank, world)
     if sp.rows == 0:
         return sp, None
@@ -116,6 +136,7 @@ def separate_stream(engine, L, R, rank=0, world=1):
     """Run this rank's chunks.  `engine` needs .T, .max_tiles and .separate_ex(L, R, frames, rows) -> [S,2,rows*1024+3072]
     (spleeterrt_amd.Engine on a GPU; tests substitute a CPU stand-in).  Returns [(out_offset, array)]."""
     _refuse_wiener(engine, world)
+    _refuse_overlap(engine)
     parts = []
     for c in plan(len(L), engine.T, engine.max_tiles, rank, world):
         o = engine.separate_ex(L[c.sample0:c.sample0 + c.nsamples], R[c.sample0:c.sample0 + c.nsamples], c.frames, c.rows)
