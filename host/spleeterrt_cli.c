@@ -23,6 +23,10 @@
  *                srtResampleLength(frames, rate, 44100) frames (main.c:266) and the stems are written at 44.1 kHz
  *     source     as 1, then every stem is converted back to the input's rate and written with the input's frame count
  *   The rate is checked before the weights are read; the conversion runs after that, on the first device.
+ *   $SPLEETERRT_OUT_BITS=16 writes 16-bit PCM outputs (format 1) instead of float32: the stems come back from the device as 16-bit frames
+ *   (srtSeparateCliHostIo, SRT_HOST_OUT_PCM16: q = rint(x * 32768) clamped, half the download) and go to the files as they are; a file with clipped
+ *   samples is reported.  Single-engine path only (refused with several workers, and with SPLEETERRT_RESAMPLE=source on input that needs converting
+ *   back).  Unset or 32: the float32 outputs.
  *
  * Out of scope here (SURVEY §2.1 #9,#11,#12): FLAC/MP3 decoding — the input must be a RIFF/WAVE file (PCM 8/16/24/32-bit
  * or float32, 1 or 2 channels).  The reference embeds its weights
@@ -123,6 +127,21 @@ static int write_wav(const char *path, const float *L, const float *R, size_t fr
     return w == frames ? 0 : -1;
 }
 
+/* the call's 16-bit output as it stands: `frames` interleaved stereo frames -> 16-bit PCM stereo RIFF/WAVE at `rate` Hz */
+static int write_wav16(const char *path, const int16_t *il, size_t frames, uint32_t rate)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) { fprintf(stderr, "cannot write %s\n", path); return -1; }
+    const uint32_t data = (uint32_t)(frames * 4);
+    unsigned char h[44];
+    memcpy(h, "RIFF", 4); memcpy(h + 8, "WAVEfmt ", 8); memcpy(h + 36, "data", 4);
+    PUT32(4, 36 + data); PUT32(16, 16); PUT16(20, 1); PUT16(22, 2); PUT32(24, rate); PUT32(28, rate * 4); PUT16(32, 4); PUT16(34, 16); PUT32(40, data);
+    fwrite(h, 1, sizeof h, f);
+    const size_t w = fwrite(il, 4, frames, f);
+    fclose(f);
+    return w == frames ? 0 : -1;
+}
+
 static const char *base_name(const char *p) { const char *s = strrchr(p, '/'); return s ? s + 1 : p; }   /* main.c:114-125 */
 static int is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
@@ -153,12 +172,20 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "SPLEETERRT_RESAMPLE=%s: expected 0, 1 or source\n", rs); return -1; }
     }
 
+    const char *ob = getenv("SPLEETERRT_OUT_BITS");
+    int out16 = 0;
+    if (ob && *ob && strcmp(ob, "32")) {
+        if (!strcmp(ob, "16")) out16 = 1;
+        else { fprintf(stderr, "SPLEETERRT_OUT_BITS=%s: expected 16 or 32\n", ob); return -1; }
+    }
+
     float *pcm = 0; unsigned channels = 0, rate = 0;
     const size_t nframes = read_wav(argv[5], &pcm, &channels, &rate);
     if (!nframes) return -1;
     if (rate != 44100 && !resample) { fprintf(stderr, "%s: %u Hz — only 44.1 kHz input is accepted (set SPLEETERRT_RESAMPLE=1 to convert it on the GPU)\n", argv[5], rate); return -1; }
     if (rate != 44100 && (rate < 8000 || rate > 384000)) { fprintf(stderr, "%s: %u Hz — the converter takes 8000..384000 Hz\n", argv[5], rate); return -1; }
     const int convert = rate != 44100;
+    if (out16 && convert && resample == 2) { fprintf(stderr, "SPLEETERRT_OUT_BITS=16 with SPLEETERRT_RESAMPLE=source: the stems are converted back as floats; write float32 outputs (unset SPLEETERRT_OUT_BITS)\n"); return -1; }
     const size_t n44 = convert ? srtResampleLength(nframes, (int)rate, 44100) : nframes;       /* main.c:266 */
     const size_t nout = resample == 2 ? nframes : n44;                                          /* frames of every output file */
     /* the outputs are float32 stereo RIFF files: 8 bytes per frame under a 32-bit chunk size (main.c writes the same container) */
@@ -217,7 +244,9 @@ int main(int argc, char **argv)
     }
     const size_t per = (ntiles + (size_t)ndev - 1) / (size_t)ndev;       /* tiles of the largest range */
     cfg.variant = SRT_VARIANT_EXE; cfg.max_tiles = (int)(per < cap ? per : cap); cfg.impl = SRT_IMPL_MFMA; cfg.precision = SRT_PREC_F32;
-    float *out = (float *)malloc((size_t)stems * 2 * len * sizeof(float));
+    if (out16 && (ndev > 1 || (dl && *dl))) { fprintf(stderr, "SPLEETERRT_OUT_BITS=16 is honoured on the single-engine path only (the multi-device join adds floats on the host): run one worker, or write float32 outputs\n"); return -1; }
+    unsigned long long clipped[3] = { 0, 0, 0 };
+    void *out = malloc((size_t)stems * 2 * len * (out16 ? sizeof(int16_t) : sizeof(float)));      /* float [stems][2][len] | int16 [stems][len][2] */
     if (!out) { fprintf(stderr, "out of host memory (%zu output samples)\n", (size_t)stems * 2 * len); return -1; }
     if (ndev > 1 || (dl && *dl)) {
         srt_multi *m = 0;
@@ -226,7 +255,7 @@ int main(int argc, char **argv)
         if (srtMultiSetCoeffFp16Host(m, 0, halfs) || srtMultiSetCoeffFp16Host(m, 1, halfs + nhalf)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
         free(halfs);
         t0 = now();
-        if (srtMultiSeparateCliHost(m, inL, inR, finalSize, stems, out)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+        if (srtMultiSeparateCliHost(m, inL, inR, finalSize, stems, (float *)out)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
         srtMultiInfo(m, info, sizeof info);
         printf("Inference neural networks on %d GPU worker(s) takes %1.14lf sec (%zu tiles of %zu x %zu, at most %zu per worker in chunks of %d, %d outputs; %s)\n",
                ndev, now() - t0, ntiles, T, F, per, cfg.max_tiles, stems, info);
@@ -237,7 +266,7 @@ int main(int argc, char **argv)
         if (srtSetCoeffFp16Host(e, 0, halfs) || srtSetCoeffFp16Host(e, 1, halfs + nhalf)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
         free(halfs);
         t0 = now();
-        if (srtSeparateCliHost(e, inL, inR, finalSize, stems, out)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+        if (out16 ? srtSeparateCliHostIo(e, inL, inR, finalSize, stems, out, SRT_HOST_OUT_PCM16, clipped) : srtSeparateCliHost(e, inL, inR, finalSize, stems, (float *)out)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
         printf("Inference neural networks on the GPU takes %1.14lf sec (%zu tiles of %zu x %zu in chunks of %d, %d outputs)\n", now() - t0, ntiles, T, F, cfg.max_tiles, stems);
         srtReleaseStaging(e);                                          /* whole-file device copies of a one-shot program */
         srtDestroy(e);
@@ -257,7 +286,13 @@ int main(int argc, char **argv)
         char path[4096];
         t0 = now();
         snprintf(path, sizeof path, "%s_%s.wav", base_name(argv[5]), names[k]);
-        const float *L = out + (size_t)(2 * k) * len + FFT, *R = out + (size_t)(2 * k + 1) * len + FFT;   /* channel_joinFloat(..., preshift 4096), main.c:806 */
+        if (out16) {                                                   /* the stem's frames [4096, 4096 + nout) as the device packed them */
+            if (write_wav16(path, (const int16_t *)out + ((size_t)k * len + FFT) * 2, nout, 44100)) return -1;
+            if (clipped[k]) printf("%s: %llu clipped sample(s)\n", path, clipped[k]);
+            printf("Saving file -> %s takes %1.14lf sec\n", path, now() - t0);
+            continue;
+        }
+        const float *L = (const float *)out + (size_t)(2 * k) * len + FFT, *R = (const float *)out + (size_t)(2 * k + 1) * len + FFT;   /* channel_joinFloat(..., preshift 4096), main.c:806 */
         if (back) {                                                    /* the stem's 44.1 kHz frames [0, n44), zero outside */
             if (srtResampleHost(back, L, R, n44, bl, br)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
             L = bl; R = br;

@@ -150,6 +150,30 @@ SRT_API int  srtSeparateCli(srt_engine *e, const float *d_L, const float *d_R, s
  * grow-only and kept for later calls, like srtSeparateHostStream's; a one-shot caller frees it with srtReleaseStaging. */
 SRT_API int  srtSeparateCliHost(srt_engine *e, const float *h_L, const float *h_R, size_t n, int stems, float *h_out);
 
+/* ---- 16-bit PCM at the host-stream boundary: the file path is bound by PCIe, and its callers read and write 16-bit WAV data.
+ * Unpack: x = (float)q / 32768 (exact).  Pack: q = rint(x * 32768), ties to even, clamped to [-32768, 32767], NaN -> 0; a sample is CLIPPED when the
+ * unclamped value lies outside that range or is NaN (+1.0f clips, -1.0f does not).
+ * srtPcm16Unpack: d_in interleaved stereo [n][2] -> planar d_L [n], d_R [n].
+ * srtPcm16Pack: `pairs` stereo pairs of planar fp32, pair p at d_planes + 2p * plane_stride (L) and + (2p + 1) * plane_stride (R), samples [0, count)
+ * -> d_out + p * out_stride * 2 as [count][2] (a WAV data chunk's bytes).  d_clipped (may be NULL) [pairs]: each pair's clipped samples are ADDED to it,
+ * exactly and reproducibly (no atomics).  Both: device pointers of any alignment (16-byte aligned pointers and strides of a multiple of 4 take the
+ * vector path), asynchronous on `stream`, capturable; -1 before any device work for a null pointer, pairs < 1, or a stride below count. */
+SRT_API int  srtPcm16Unpack(void *stream, const int16_t *d_in, size_t n, float *d_L, float *d_R);
+SRT_API int  srtPcm16Pack(void *stream, const float *d_planes, size_t plane_stride, int pairs, size_t count, int16_t *d_out, size_t out_stride,
+                          unsigned long long *d_clipped);
+/* srtSeparateHostStreamEx / srtSeparateCliHost with 16-bit host buffers: the conversion runs on the device, per chunk, so half the bytes cross the bus.
+ * SRT_HOST_IN_PCM16: h_in is int16 interleaved stereo [n][2] and h_in2 must be NULL (otherwise h_in = h_L, h_in2 = h_R, floats).
+ * SRT_HOST_OUT_PCM16: h_out is int16 [stems][srtIstftLength(rows)][2] (otherwise float [stems][2][len]); h_clipped (may be NULL) [stems] receives each stem's
+ * clipped samples.  The two flags are independent; the seam arithmetic stays fp32 and every output sample is quantised once.  Without either flag these are the
+ * float calls (h_clipped, when given, is zeroed); SRT_HOST_PINNED keeps its meaning.  With a PCM16 flag srtSeparateCliHostIo always takes the chunked
+ * pipeline (one chunk when the file fits).  -1 as the float forms (overlap, Wiener), and for SRT_HOST_IN_PCM16 with h_in2 != NULL or unknown flag bits. */
+#define SRT_HOST_IN_PCM16  2u
+#define SRT_HOST_OUT_PCM16 4u
+SRT_API int  srtSeparateHostStreamIo(srt_engine *e, const void *h_in, const void *h_in2, size_t n, size_t frames, size_t rows,
+                                     void *h_out, unsigned flags, unsigned long long *h_clipped);
+SRT_API int  srtSeparateCliHostIo(srt_engine *e, const void *h_in, const void *h_in2, size_t n, int stems,
+                                  void *h_out, unsigned flags, unsigned long long *h_clipped);
+
 /* Low-latency callers that repeat the same call (same device pointers and sizes) over and over - the real-time plugin, the tile
  * API on one pair of buffers: with graph mode on, srtForward and srtSeparate / srtSeparateEx capture their launch sequence into
  * a hipGraph the first time an argument tuple is seen and replay it afterwards (one host call instead of ~25 launches; 4 cached

@@ -8,6 +8,7 @@ MAX_STEMS = 8
 VARIANT_EXE, VARIANT_VST = 0, 1
 IMPL_MFMA, IMPL_NAIVE = 0, 1
 PREC_F32, PREC_F16, PREC_F16X2 = 0, 1, 2
+HOST_PINNED, HOST_IN_PCM16, HOST_OUT_PCM16 = 1, 2, 4      # SRT_HOST_* (srtSeparateHostStreamIo / srtSeparateCliHostIo)
 COEFF_FLOATS = 9822725
 SPEC_LD = 2052
 
@@ -62,6 +63,10 @@ def load_library():
     L.srtSeparateCliHost.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.srtSeparateHostStream.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp]
     L.srtSeparateHostStreamEx.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_uint]
+    L.srtSeparateHostStreamIo.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_uint, vp]
+    L.srtSeparateCliHostIo.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_uint, vp]
+    L.srtPcm16Unpack.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    L.srtPcm16Pack.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     for fn in (L.srtStftRows, L.srtStftFrames, L.srtIstftLength):
         fn.restype = C.c_size_t
         fn.argtypes = [C.c_size_t]
@@ -361,6 +366,68 @@ class Engine:
                                                  1 if pinned else 0))
         return out if ret is None else ret
 
+    def _host_io(self, pcm_or_LR, out_pcm16, nstems, rows, out, pinned):
+        """host buffers of the *_io calls -> (keep-alive list, h_in, h_in2, n, h_out, flags, out object, clipped array).  Input by dtype: an int16 array or CPU
+        tensor of shape [n, 2] is interleaved 16-bit PCM, anything else a pair (L, R) of float32 buffers."""
+        import numpy as np
+        t = self.torch
+
+        def host(a, dtype):
+            if hasattr(a, "data_ptr"):                           # CPU torch tensor (e.g. pin_memory=True)
+                assert not a.is_cuda and a.dtype == getattr(t, np.dtype(dtype).name) and a.is_contiguous()
+                return a, a.data_ptr(), a.numel()
+            a = np.ascontiguousarray(a, dtype)
+            return a, a.ctypes.data, a.size
+        flags = HOST_PINNED if pinned else 0
+        is16 = not isinstance(pcm_or_LR, (tuple, list)) and str(pcm_or_LR.dtype) in ("int16", "torch.int16")
+        if is16:
+            assert len(pcm_or_LR.shape) == 2 and pcm_or_LR.shape[1] == 2, "16-bit input is interleaved stereo [n, 2]"
+            a, p_in, cnt = host(pcm_or_LR, np.int16)
+            keep, p_in2, n = [a], None, cnt // 2
+            flags |= HOST_IN_PCM16
+        else:
+            (a, p_in, n), (b, p_in2, nb) = host(pcm_or_LR[0], np.float32), host(pcm_or_LR[1], np.float32)
+            assert n == nb
+            keep = [a, b]
+        rows = self.L.srtStftRows(n) if rows is None else rows
+        ln = self.L.srtIstftLength(rows)
+        shape, dtype = ((nstems, ln, 2), np.int16) if out_pcm16 else ((nstems, 2, ln), np.float32)
+        if out_pcm16:
+            flags |= HOST_OUT_PCM16
+        ret = None
+        if out is None:
+            if pinned:                                           # keep the promise for the output too
+                out = t.empty(shape, dtype=getattr(t, np.dtype(dtype).name), pin_memory=True)
+                ret = out.numpy()
+            else:
+                out = np.empty(shape, dtype)
+        o, p_out, no = host(out, dtype)
+        assert no == shape[0] * shape[1] * shape[2]
+        clipped = np.zeros(nstems, np.uint64)
+        return keep + [o], p_in, p_in2, n, rows, p_out, flags, (o if ret is None else ret), clipped
+
+    def separate_host_stream_io(self, pcm_or_LR, out_pcm16=False, frames=None, rows=None, out=None, pinned=False):
+        """separate_host_stream with 16-bit PCM on either side (srtSeparateHostStreamIo; the conversion runs on the GPU, half the bytes cross the bus).
+        pcm_or_LR: int16 [n, 2] interleaved stereo, or (L, R) float32; out_pcm16: stems as int16 [S, len, 2] (a WAV data chunk per stem) instead of float32
+        [S, 2, len].  -> (out, clipped): clipped uint64 [S], the samples per stem whose value before clamping lay outside [-32768, 32767] (zeros for float output)."""
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.S, rows, out, pinned)
+        frames = self.L.srtStftFrames(n) if frames is None else frames
+        self._chk(self.L.srtSeparateHostStreamIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, frames, rows, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
+        return out, clipped
+
+    def separate_cli_host_io(self, pcm_or_LR, stems, out_pcm16=False, out=None, pinned=False, keep_staging=False):
+        """separate_cli_host with 16-bit PCM on either side (srtSeparateCliHostIo) -> (out, clipped) as separate_host_stream_io, `stems` outputs."""
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, stems, None, out, pinned)
+        try:
+            self._chk(self.L.srtSeparateCliHostIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, stems, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
+        except EngineError:
+            if not keep_staging:
+                self.L.srtReleaseStaging(self.h)              # best effort: the separation's own error is the one to report
+            raise
+        if not keep_staging:
+            self._chk(self.L.srtReleaseStaging(self.h))
+        return out, clipped
+
     def separate_ex(self, L, R, frames, rows, out=None):
         """explicit-geometry form used by spleeterrt_amd.stream for tile ranges of a longer stream"""
         t = self.torch
@@ -645,3 +712,36 @@ class ResamplerStream:
             self.close()
         except Exception:
             pass
+
+
+def pcm16_unpack(t):
+    """int16 CUDA tensor [n, 2] (interleaved stereo) -> (L, R) float32 [n], x = q / 32768 (srtPcm16Unpack, on the tensor's device and the current stream)"""
+    import torch
+    assert t.is_cuda and t.dtype == torch.int16 and t.dim() == 2 and t.shape[1] == 2
+    lib = load_library()
+    t = t.contiguous()
+    with torch.cuda.device(t.device):
+        out = torch.empty((2, t.shape[0]), device=t.device, dtype=torch.float32)
+        rc = lib.srtPcm16Unpack(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(t), t.shape[0], _ptr(out[0]), _ptr(out[1]))
+    if rc < 0:
+        raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (lib.srtLastError().decode(), rc))
+    return out[0], out[1]
+
+
+def pcm16_pack(planes, clipped=None):
+    """float32 CUDA tensor [pairs, 2, count] (planar stereo pairs) -> (int16 [pairs, count, 2], clipped int64 [pairs]); q = clamp(rint(x * 32768)), NaN -> 0
+    (srtPcm16Pack).  clipped: an int64 CUDA tensor [pairs] the counts are ADDED to (default: zeros)."""
+    import torch
+    assert planes.is_cuda and planes.dtype == torch.float32 and planes.dim() == 3 and planes.shape[1] == 2
+    lib = load_library()
+    planes = planes.contiguous()
+    pairs, count = planes.shape[0], planes.shape[2]
+    with torch.cuda.device(planes.device):
+        out = torch.empty((pairs, count, 2), device=planes.device, dtype=torch.int16)
+        if clipped is None:
+            clipped = torch.zeros(pairs, device=planes.device, dtype=torch.int64)
+        assert clipped.is_cuda and clipped.dtype == torch.int64 and clipped.is_contiguous() and clipped.numel() == pairs
+        rc = lib.srtPcm16Pack(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(planes), count, pairs, count, _ptr(out), count, _ptr(clipped))
+    if rc < 0:
+        raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (lib.srtLastError().decode(), rc))
+    return out, clipped

@@ -222,6 +222,14 @@ int srt_launch_residual(const SrtResidualParams& p, hipStream_t s);
 int srt_launch_time_residual(const float* aL, const float* aR, size_t na, const float* b, size_t nb, float* out, size_t lo, size_t hi, hipStream_t s);
 // chunk stitching on the device: out[p][0:3072] += carry[p] (unless first), then carry[p] = out[p][tail : tail+3072] (unless last)
 int srt_launch_carry(float* out, size_t plane_len, int nplanes, size_t tail, float* carry, int first, int last, hipStream_t s);
+// 16-bit PCM at the host-stream boundary (srt_pcm.hip).  unpack: interleaved stereo int16 [n][2] -> planar fp32, x = q / 32768.
+// pack: pair p's planes at planes + 2p * plane_stride (L) and + (2p + 1) * plane_stride (R), samples [0, count) -> out + p * out_stride * 2 as [count][2],
+// q = clamp(rint(x * 32768)), NaN -> 0; clipped (may be NULL) [pairs]: the samples whose unclamped value fell outside the range are ADDED, through `scratch`
+// (srt_pcm16_pack_scratch(pairs) 64-bit words the launch may overwrite; unused without `clipped`).  Any alignment: unaligned arguments take the frame-by-frame path.
+int srt_launch_pcm16_unpack(const int16_t* in, size_t n, float* L, float* R, hipStream_t s);
+size_t srt_pcm16_pack_scratch(int pairs);
+int srt_launch_pcm16_pack(const float* planes, size_t plane_stride, int pairs, size_t count, int16_t* out, size_t out_stride,
+                          unsigned long long* clipped, unsigned long long* scratch, hipStream_t s);
 // cross-stem ratio mask, in place on [nstems][count]: m_s <- (m_s^2 + eps/S) / (sum_j m_j^2 + eps)
 int srt_launch_ratio_mask(float* masks, int nstems, size_t count, hipStream_t s);
 
