@@ -47,7 +47,7 @@ typedef struct srt_config {
     int   T;                        /* timeStep: tile height in frames, multiple of 64                main.c:702 */
     int   n_stems;                  /* sub-networks evaluated per tile, 1..SRT_MAX_STEMS */
     int   stem_mode[SRT_MAX_STEMS]; /* 0: LeakyReLU/ReLU, !=0: ELU/ELU                                spleeter.c:130-139 */
-    float oob_weight[SRT_MAX_STEMS];/* weight of bins F..2048 ("unaffectedWeight" = 0.1)              main.c:773 */
+    float oob_weight[SRT_MAX_STEMS];/* weight of bins F..2048 ("unaffectedWeight" = 0.1)              main.c:773; ignored under SRT_MASK_EXT_AVERAGE */
     int   variant;                  /* SRT_VARIANT_* */
     int   max_tiles;                /* capacity: tiles per batch */
     int   impl;                     /* SRT_IMPL_* */
@@ -117,6 +117,27 @@ SRT_API int  srtSeparateEx(srt_engine *e, const float *d_L, const float *d_R, si
  * srtOverlapTiles is pure host arithmetic (no device, like srtBatchPlan): 0 for rows = 0; 0 with srtLastError() text for T < 1 or O outside 0..T/2. */
 SRT_API int  srtSetOverlap(srt_engine *e, int overlap_rows);
 SRT_API size_t srtOverlapTiles(size_t rows, int T, int overlap_rows);
+
+/* ---- mask extension: the gain of the bins above the analysed band.  The networks see bins 0..F-1; by default every separation path multiplies
+ * bins F..2048 of stem s by the constant oob_weight[s] (the reference's unaffectedWeight; official Spleeter's mask_extension = "zeros" is oob_weight = 0).
+ * SRT_MASK_EXT_AVERAGE is official Spleeter's mask_extension = "average": bins F..2048 of spectrum row r, channel c of stem s are multiplied by
+ *   e_s(r, c) = (sum over k < F of g_s(r, c, k)) / F,
+ * g = the in-band gain the inverse transform really applies: the mask value (the fp16 mode's half masks converted), cross-faded when srtSetOverlap is on,
+ * normalised across the stems when ratio_mask is on and n_stems > 1 - in that order.  fp32, one fixed summation order per F (a row of equal masks gives
+ * exactly that value), a true division by F.  Without masks (srtIstft with d_masks = NULL: all-ones) e = 1.  oob_weight is IGNORED while the mode is on.
+ * With ratio_mask the gains of the stems sum to 1 in every bin, so the stems then sum to the input over the whole band, not only below F.
+ * srtSetMaskExtension: per engine, SRT_MASK_EXT_CONSTANT by default (the paths and kernels as they always were, bit for bit), takes effect for later calls;
+ * switching to SRT_MASK_EXT_AVERAGE allocates the engine's gain table [n_stems][max_tiles * T][2] once (call it before capturing; kept until srtDestroy).
+ * -1 with srtLastError() text for a null engine, an unknown mode, or the Wiener filter on.  Honoured by srtIstft, srtSeparate[Ex] (ratio_mask, srtSetOverlap, the
+ * fp16 mode's half masks, graph mode: the mode is part of the captured call's key), srtSeparateBatch and srtSeparateHostStream[Ex|Io] (the gain is row-local:
+ * chunk seams need nothing), and by engines borrowed from a multi-device object.  Refused with -1 while the mode is on: srtSeparateCli* (its complex-domain
+ * residual chain subtracts oob_weight * spectrum), srtIstftWiener and srtSetWiener(n > 0) (the filter's gains above F are a follow-up).  The live / plugin
+ * surfaces (srtLive*, Spleeter4Stems*) have their own handles and keep the constant rule (a follow-up).
+ * srtCopyTensor(e, "mask_ext", stem, 0, h, 2 * rows) returns the table the last such call left for that stem: [rows][2] (L, R); after srtSeparateBatch the
+ * rows are the packed rows (track k from row tile0[k] * T). */
+#define SRT_MASK_EXT_CONSTANT 0
+#define SRT_MASK_EXT_AVERAGE  1
+SRT_API int  srtSetMaskExtension(srt_engine *e, int mode);
 
 /* Many independent tracks in one packed batch.  Track k of a batch occupies the packed tiles [tile0[k], tile0[k] + ceil(srtStftRows(n[k]) / T)).
  * srtBatchPlan is pure host arithmetic (no device, like srtRankSpan): tile0 may be NULL; *total_tiles = the sum.  -1 for ntracks < 1, T < 1 or any n[k] < 4096.

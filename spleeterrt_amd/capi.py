@@ -8,6 +8,7 @@ MAX_STEMS = 8
 VARIANT_EXE, VARIANT_VST = 0, 1
 IMPL_MFMA, IMPL_NAIVE = 0, 1
 PREC_F32, PREC_F16, PREC_F16X2 = 0, 1, 2
+MASK_EXT_CONSTANT, MASK_EXT_AVERAGE = 0, 1                 # SRT_MASK_EXT_* (srtSetMaskExtension)
 HOST_PINNED, HOST_IN_PCM16, HOST_OUT_PCM16 = 1, 2, 4      # SRT_HOST_* (srtSeparateHostStreamIo / srtSeparateCliHostIo)
 COEFF_FLOATS = 9822725
 SPEC_LD = 2052
@@ -56,6 +57,7 @@ def load_library():
     L.srtRatioMask.argtypes = [vp, f32p, C.c_int]
     L.srtSetWiener.argtypes = [vp, C.c_int]
     L.srtSetOverlap.argtypes = [vp, C.c_int]
+    L.srtSetMaskExtension.argtypes = [vp, C.c_int]
     L.srtOverlapTiles.restype = C.c_size_t
     L.srtOverlapTiles.argtypes = [C.c_size_t, C.c_int, C.c_int]
     L.srtIstftWiener.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_int, f32p]
@@ -134,7 +136,8 @@ class Engine:
     """One engine per (device, stream): nstems sub-networks evaluated over batches of T x F spectrogram tiles."""
 
     def __init__(self, F=1024, T=256, stem_modes=(1, 1, 1, 1), oob_weights=None, variant=VARIANT_EXE, max_tiles=1,
-                 impl=IMPL_MFMA, device=None, precision=PREC_F32, ratio_mask=False, batch_invariant=False, wiener=0, overlap=0):
+                 impl=IMPL_MFMA, device=None, precision=PREC_F32, ratio_mask=False, batch_invariant=False, wiener=0, overlap=0,
+                 mask_extension="constant"):
         import torch
         if not torch.cuda.is_available():
             raise EngineError("no GPU visible: spleeterrt_amd has no CPU path")
@@ -161,6 +164,9 @@ class Engine:
             self.set_wiener(wiener)
         if overlap:
             self.set_overlap(overlap)
+        self.mask_extension = MASK_EXT_CONSTANT
+        if mask_extension not in ("constant", MASK_EXT_CONSTANT):
+            self.set_mask_extension(mask_extension)
 
     def _chk(self, rc):
         if rc < 0:
@@ -236,6 +242,22 @@ class Engine:
         (0 = off, back-to-back tiles).  stft() then returns mag in the overlapped layout [tiles(rows), 2, T, F] and istft() expects masks in it."""
         self._chk(self.L.srtSetOverlap(self.h, int(rows)))
         self.overlap = int(rows)
+
+    def set_mask_extension(self, mode):
+        """the gain of bins >= F (srtSetMaskExtension): "constant" (oob_weights, the default) or "average" (each row's upper bins get the mean of
+        that row's in-band gain, per stem and channel: official Spleeter's mask_extension = "average"; oob_weights are ignored).  Also takes MASK_EXT_*."""
+        m = {"constant": MASK_EXT_CONSTANT, "average": MASK_EXT_AVERAGE}.get(mode, mode)
+        if isinstance(m, str):
+            raise EngineError("mask_extension must be \"constant\" or \"average\", not %r" % (mode,))
+        self._chk(self.L.srtSetMaskExtension(self.h, int(m)))
+        self.mask_extension = int(m)
+
+    def mask_ext(self, stem, rows):
+        """the gains of bins >= F the last inverse transform with mask_extension = "average" applied to one stem: numpy [rows, 2] (L, R)"""
+        import numpy as np
+        a = np.empty((int(rows), 2), np.float32)
+        self._chk(self.L.srtCopyTensor(self.h, b"mask_ext", stem, 0, C.c_void_p(a.ctypes.data), a.size))
+        return a
 
     def tiles(self, rows):
         """network tiles of a signal of `rows` spectrum rows at the engine's overlap (stream.overlap_tiles)"""

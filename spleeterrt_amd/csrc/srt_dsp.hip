@@ -17,6 +17,7 @@
 #include "srt_internal.h"
 #include "srt_device.h"
 #include <stdlib.h>
+#include <type_traits>
 
 #define FFT_EX1_LD 272      // exchange-1 row stride (cf): 272*2 dwords = 32 (mod 64) -> conflict-free b64 reads
 #define FFT_EX2_LD 257      // exchange-2 row stride (cf): odd -> conflict-free strided b64 writes
@@ -255,13 +256,16 @@ __device__ __forceinline__ float srt_ratio_of_ov(const float* __restrict__ rowb0
 // What a workgroup of the inverse kernels reads and writes of ONE signal: the whole call's signal (srt_istft_ola_kernel / srt_istft_ola3_kernel),
 // or one track of a packed batch (srt_istft_batch_kernel: spectrum and masks offset to the track's first packed row / tile, its own frames and output).
 // Everything else (stem count and stride, T, F, oob weights, tables) comes from the launch's SrtIstftParams.
-struct IstftView { const float2* spec; const float* masks; float* out; size_t out_len; int frames; };
-__device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { IstftView v = { p.spec, p.masks, p.out, p.out_len, p.frames }; return v; }
+// ext: the signal's rows of the average mask extension's gain table (stem 0's; EXT instantiations only, see srt_mask_ext_kernel)
+struct IstftView { const float2* spec; const float* masks; float* out; size_t out_len; int frames; const float* ext; };
+__device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { IstftView v = { p.spec, p.masks, p.out, p.out_len, p.frames, p.ext }; return v; }
 
 #define ISTFT_OLA_LDS_F2 (2 * FFT_SMEM_F2 + FFT_TWB_F2)   // two staging / exchange buffers + the pass-2 twiddles (one LDS object)
 // OV: overlapped network tiles (srt_ov_row): the mask row of a frame's primary tile is prefetched as always; inside an overlap the previous tile's row is
 // read when the frame is staged and the two are blended before the ratio / multiply
-template <bool RATIO, bool OV = false>
+// EXT: average mask extension (srtSetMaskExtension): bins >= F of frame f take the two gains ext[stem][f][L, R] instead of oob (fetched with the frame's rows
+// from workgroup-uniform addresses: scalar loads into SGPRs, consumed before the next fetch overwrites them)
+template <bool RATIO, bool OV = false, bool EXT = false>
 __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
 {
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
@@ -288,6 +292,8 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
     // transformed, so the global-load latency is not exposed once per FFT.
     cf sl[9], sr[9];
     float gl[9], gr[9];
+    float eL = oob, eR = oob;
+    const float* __restrict__ const ext = EXT ? w.ext + (size_t)stem * p.ext_stem : nullptr;
     // fetch only ISSUES loads (no value depends on them until the next iteration): without masks the two mask rows
     // are read from a harmless table instead of branching on the pointer
     const bool has_mask = w.masks != nullptr;
@@ -305,6 +311,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
             sl[j] = specL[k]; sr[j] = specR[k];
             if constexpr (!(RATIO && OV)) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
         }
+        if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = ext[fu]; eR = ext[fu + 1]; }
     };
     float pw[16];                                       // this thread's 16 synthesis-window taps are the same for every frame
 #pragma unroll
@@ -360,11 +367,12 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
                     }
                 }
             }
+            const float xl = EXT ? eL : oob, xr = EXT ? eR : oob;              // bins >= F
 #pragma unroll
             for (int j = 0; j < 9; ++j) {
                 const int k = tid + 256 * j;
                 if (k <= 2048) {
-                    const float wl = k < p.F ? (has_mask ? gl[j] : 1.0f) : oob, wr = k < p.F ? (has_mask ? gr[j] : 1.0f) : oob;
+                    const float wl = k < p.F ? (has_mask ? gl[j] : 1.0f) : xl, wr = k < p.F ? (has_mask ? gr[j] : 1.0f) : xr;
                     const cf A = sl[j] * wl, B = sr[j] * wr;                      // masked (re, im) of L and R
                     // G = F'_L + i F'_R, F' = re - i im, Hermitian-extended; stored swapped (im,re): inverse-by-forward trick
                     if (k == 0) sx[0] = f2(B.x, A.x);                             // a[0] = re[0]           (stftFix.c:556-557)
@@ -411,6 +419,21 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_ov_kernel(const SrtIstft
     const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
     __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
     istft_ola_run<RATIO, true>(p, istft_view(p), stem, run, G, s_mem, O);
+}
+// the two with the average mask extension (p.ext; the names stay apart so that the forms above keep theirs)
+template <bool RATIO = false>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_ext_kernel(const SrtIstftParams p, int G)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<RATIO, false, true>(p, istft_view(p), stem, run, G, s_mem);
+}
+template <bool RATIO = false>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_ov_ext_kernel(const SrtIstftParams p, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<RATIO, true, true>(p, istft_view(p), stem, run, G, s_mem, O);
 }
 
 
@@ -582,7 +605,8 @@ __global__ void __launch_bounds__(256, 3) srt_stft_ov_kernel(const SrtStftParams
 // NM: mask rows cover bins < F <= 256 NM, so only the first NM of a thread's eight bins can carry a mask value (F = 1024: 4 prefetch registers per channel instead of 8)
 // M16: the masks are halves (the engine's own mask buffer in the fp16 mode, written by srt_head_rows_kernel<.., true>; never with RATIO)
 #define ISTFT_OLA3_LDS_F2 (FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2)
-template <int NM, bool RATIO, bool M16, bool OV = false>
+// EXT: as istft_ola_run
+template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false>
 __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
 {
     cf* sx = s_mem;
@@ -606,6 +630,8 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
     cf sl[8], sr[8];
     float gl[NM], gr[NM];
     cf sl8, sr8;                                        // bin 2048 (only thread 0 uses it; the address is uniform)
+    float eL = oob, eR = oob;
+    const float* __restrict__ const ext = EXT ? w.ext + (size_t)stem * p.ext_stem : nullptr;
     const bool has_mask = w.masks != nullptr;
     auto fetch = [&](int f) {                                               // 0 <= f < w.frames
         int tile = f / p.T, t = f % p.T;
@@ -628,6 +654,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             }
         }
         sl8 = specL[2048]; sr8 = specR[2048];
+        if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = ext[fu]; eR = ext[fu + 1]; }
     };
     // the 16 synthesis-window taps of this thread (samples tid + 256 k2) are rebuilt per frame from two registers: cos / sin of th = 2 pi (tid + 1/2) / 4096, over 3.
     // (A deviation from the table the F > 1024 kernel reads - postWin, which reproduces InitSTFT's rounding: 1/3 - cos/3 in fp32 is off by up to ~3e-8 absolute,
@@ -692,18 +719,19 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
                     }
                 }
             }
+            const float xl = EXT ? eL : oob, xr = EXT ? eR : oob;              // bins >= F
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = tid + 256 * j;
-                float wl = oob, wr = oob;
-                if (j < NM) { wl = k < p.F ? (has_mask ? gl[j] : 1.0f) : oob; wr = k < p.F ? (has_mask ? gr[j] : 1.0f) : oob; }
+                float wl = xl, wr = xr;
+                if (j < NM) { wl = k < p.F ? (has_mask ? gl[j] : 1.0f) : xl; wr = k < p.F ? (has_mask ? gr[j] : 1.0f) : xr; }
                 const cf A = sl[j] * wl, B = sr[j] * wr;                          // masked (re, im) of L and R
                 v[j] = sub_mi(B, A);                                              // (reR - imL, imR + reL)
                 mir[j * 256 + tid] = herm_hi(B, A);                               // (reR + imL, reL - imR)   (slot (0, 0) is never read)
                 if (j == 0 && tid == 0) v[0] = f2(B.x, A.x);                      // a[0] = re[0]           (stftFix.c:556-557)
             }
             if (tid == 0) {                                                       // rev[2048]: re - im wins (stftFix.c:563-566); F <= 2048, so bin 2048 is always out of band
-                const cf A = sl8 * oob, B = sr8 * oob;
+                const cf A = sl8 * xl, B = sr8 * xr;
                 mir[2048] = f2(B.x - B.y, A.x - A.y);
             }
             __builtin_amdgcn_s_waitcnt(0x0F70);          // all of this frame's rows have arrived: nothing below waits on the stores
@@ -739,6 +767,21 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_ov_kernel(c
     const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
     __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
     istft_ola3_run<NM, RATIO, M16, true>(p, istft_view(p), stem, run, G, s_mem, O);
+}
+// the two with the average mask extension (see srt_istft_ola_ext_kernel)
+template <int NM, bool RATIO = false, bool M16 = false>
+__global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_ext_kernel(const SrtIstftParams p, int G)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, RATIO, M16, false, true>(p, istft_view(p), stem, run, G, s_mem);
+}
+template <int NM, bool RATIO = false, bool M16 = false>
+__global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_ov_ext_kernel(const SrtIstftParams p, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, RATIO, M16, true, true>(p, istft_view(p), stem, run, G, s_mem, O);
 }
 
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_tiles)
@@ -781,6 +824,25 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
     const int blocks = (nseg + G - 1) / G;
     // one stem per workgroup: 32 accumulator + 54 prefetch registers + the FFT fit in 256 VGPRs at 2 workgroups per CU
     // F > 1024: eight mask registers per channel do not fit the 168-VGPR budget of the three-per-CU form (22 dwords would spill): the two-per-CU kernel
+    if (p.ext && (!p.masks || p.ext_stem < (size_t)p.frames * 2)) return -1;      // the table holds [frames][2] gains per stem, derived from masks
+    if (p.ext) {                                         // average mask extension: the same choice among the EXT forms
+        const dim3 grid(blocks * p.nstems);
+        const bool ratio = p.ratio && p.nstems > 1;
+        if (O > 0) {
+            if (ratio) {
+                if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_ov_ext_kernel<true>), grid, dim3(256), 0, s, p, G, O);
+                else SRT_LAUNCH((srt_istft_ola3_ov_ext_kernel<4, true>), grid, dim3(256), 0, s, p, G, O);
+            } else if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_ov_ext_kernel<false>), grid, dim3(256), 0, s, p, G, O);
+            else if (p.masks16) SRT_LAUNCH((srt_istft_ola3_ov_ext_kernel<4, false, true>), grid, dim3(256), 0, s, p, G, O);
+            else SRT_LAUNCH((srt_istft_ola3_ov_ext_kernel<4>), grid, dim3(256), 0, s, p, G, O);
+        } else if (ratio) {
+            if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_ext_kernel<true>), grid, dim3(256), 0, s, p, G);
+            else SRT_LAUNCH((srt_istft_ola3_ext_kernel<4, true>), grid, dim3(256), 0, s, p, G);
+        } else if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_ext_kernel<false>), grid, dim3(256), 0, s, p, G);
+        else if (p.masks16) SRT_LAUNCH((srt_istft_ola3_ext_kernel<4, false, true>), grid, dim3(256), 0, s, p, G);
+        else SRT_LAUNCH((srt_istft_ola3_ext_kernel<4>), grid, dim3(256), 0, s, p, G);
+        return srt_launch_status();
+    }
     if (O > 0) {                                         // the overlap instantiations (the forms below keep their code)
         const dim3 grid(blocks * p.nstems);
         if (p.ratio && p.nstems > 1) {
@@ -797,6 +859,121 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
     } else if (p.F > 1024) SRT_LAUNCH((srt_istft_ola_kernel<false>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
     else if (p.masks16) SRT_LAUNCH((srt_istft_ola3_kernel<4, false, true>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
     else SRT_LAUNCH((srt_istft_ola3_kernel<4>), dim3(blocks * p.nstems), dim3(256), 0, s, p, G);
+    return srt_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------- average mask extension (srtSetMaskExtension)
+// ext[s][r][c] = (sum over k < F of g_s(r, c, k)) / F, g = the in-band gain the inverse kernels above apply to stem s at row r, channel c: the mask value
+// (halves converted), cross-faded between the two tiles of an overlapped row (srt_blend), normalised across the stems (srt_ratio_of / srt_ratio_of_ov) - formed
+// by the very helpers the inverse kernels call, so the averaged values are bit for bit the applied ones.  The EXT inverse instantiations multiply bins >= F of
+// that row and channel by it.  One wave per (row, channel), all stems at once (the ratio needs every stem's value of a bin): a lane loads 16 bytes per stem and
+// step, the wave's lanes contiguous, and adds its values in ascending k into one running sum per stem; then a fixed xor butterfly over the 64 lanes and a true
+// division by F.  The order depends on F alone - not on the grid, the batch packing or the chunking - and the longest chain is F / 64 + 6 additions.
+// No atomics, no LDS.  NS (the stem count), the mask type, the ratio and the overlap are compile-time: the stem loops unroll over registers and no load
+// sits behind a per-element select.
+#pragma clang fp contract(off)
+template <bool M16>
+__device__ __forceinline__ void srt_mask_load16(const float* __restrict__ masks, size_t off, float (&v)[M16 ? 8 : 4])
+{
+    if constexpr (M16) {
+        typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+        const half8 h = *reinterpret_cast<const half8*>(reinterpret_cast<const _Float16*>(masks) + off);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (float)h[j];
+    } else {
+        const float4 x = *reinterpret_cast<const float4*>(masks + off);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    }
+}
+
+template <int NS, bool M16, bool RATIO, bool OV>
+__device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int O, int f, int c, int lane)
+{
+    constexpr int V = M16 ? 8 : 4;                      // mask values per 16-byte load
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    int tile = f / p.T, t = f % p.T;
+    OvRow ov = { 0, 0, false, 0.0f };
+    if constexpr (OV) { ov = srt_ov_row(f, p.T, O, p.ntiles); tile = ov.j1; t = ov.k; }
+    const size_t bo = ((size_t)tile * 2 + c) * tf + (size_t)t * p.F;                     // stem 0's row in the primary tile
+    const size_t ao = ov.two ? bo - 2 * tf + (size_t)(p.T - O) * p.F : bo;              // ... and row k + S of the previous tile
+    float sum[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) sum[s] = 0.0f;
+    auto walk = [&](auto two_c) {                        // (the row is inside an overlap or not: decided once per row, outside the load loop)
+        constexpr bool TWO = decltype(two_c)::value;
+        for (int k = lane * V; k < p.F; k += 64 * V) {
+            float b[NS][V], a[NS][V];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                srt_mask_load16<M16>(p.masks, (size_t)s * sstride + bo + k, b[s]);
+                if constexpr (TWO) srt_mask_load16<M16>(p.masks, (size_t)s * sstride + ao + k, a[s]);
+                else {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) a[s][j] = b[s][j];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    float g;
+                    if constexpr (RATIO && OV) g = srt_ratio_of_ov(&b[0][j], &a[0][j], TWO, ov.w, V, NS, s, 0, true);
+                    else if constexpr (RATIO) g = srt_ratio_of(b[s][j], &b[0][j], V, NS, s, 0);
+                    else if constexpr (TWO) g = srt_blend(a[s][j], b[s][j], ov.w);
+                    else g = b[s][j];
+                    sum[s] = sum[s] + g;
+                }
+            }
+        }
+    };
+    if (OV && ov.two) walk(std::true_type{}); else walk(std::false_type{});
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        float v = sum[s];
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+        if (lane == 0) p.ext[(size_t)s * p.ext_stem + (size_t)f * 2 + c] = v / (float)p.F;
+    }
+}
+
+template <bool M16, bool RATIO, bool OV>
+__global__ void __launch_bounds__(256) srt_mask_ext_kernel(const SrtMaskExtParams p, int O)
+{
+    const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (wave >= p.rows * 2) return;                      // (wave-uniform; the kernel has no barrier)
+    const int f = wave >> 1, c = wave & 1;
+    switch (p.nstems) {
+    case 1: srt_mask_ext_row<1, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 2: srt_mask_ext_row<2, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 3: srt_mask_ext_row<3, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 4: srt_mask_ext_row<4, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 5: srt_mask_ext_row<5, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 6: srt_mask_ext_row<6, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 7: srt_mask_ext_row<7, M16, RATIO, OV>(p, O, f, c, lane); break;
+    default: srt_mask_ext_row<8, M16, RATIO, OV>(p, O, f, c, lane); break;
+    }
+}
+#pragma clang fp contract(fast)
+
+// the form follows the inverse launchers' gates: ratio when p.ratio && p.nstems > 1, halves never with the ratio, the overlap only with O > 0
+int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap)
+{
+    if (p.rows <= 0) return 0;
+    static_assert(SRT_MAX_STEMS == 8, "srt_mask_ext_kernel dispatches on 1..8 stems");
+    if (!p.masks || !p.ext || p.nstems < 1 || p.nstems > SRT_MAX_STEMS || p.F < 64 || p.F % 64 || p.ext_stem < (size_t)p.rows * 2) return -1;
+    if (((uintptr_t)p.masks & 15) != 0) return -1;      // 16-byte loads
+    if (overlap < 0 || (overlap > 0 && (overlap > p.T / 2 || p.ntiles < 1 || (size_t)(p.ntiles - 1) * (p.T - overlap) + p.T < (size_t)p.rows))) return -1;
+    if (overlap == 0 && (size_t)p.ntiles * p.T < (size_t)p.rows) return -1;
+    const bool ratio = p.ratio && p.nstems > 1;
+    if (p.masks16 && (ratio || p.F > 1024)) return -1;
+    const dim3 grid((p.rows * 2 + 3) / 4), block(256);
+    if (overlap > 0) {
+        if (ratio) SRT_LAUNCH((srt_mask_ext_kernel<false, true, true>), grid, block, 0, s, p, overlap);
+        else if (p.masks16) SRT_LAUNCH((srt_mask_ext_kernel<true, false, true>), grid, block, 0, s, p, overlap);
+        else SRT_LAUNCH((srt_mask_ext_kernel<false, false, true>), grid, block, 0, s, p, overlap);
+    } else if (ratio) SRT_LAUNCH((srt_mask_ext_kernel<false, true, false>), grid, block, 0, s, p, 0);
+    else if (p.masks16) SRT_LAUNCH((srt_mask_ext_kernel<true, false, false>), grid, block, 0, s, p, 0);
+    else SRT_LAUNCH((srt_mask_ext_kernel<false, false, false>), grid, block, 0, s, p, 0);
     return srt_launch_status();
 }
 
@@ -852,8 +1029,25 @@ __global__ void __launch_bounds__(256, OLA3 && !RATIO ? 3 : 2) srt_istft_batch_k
     w.spec = p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD;
     w.masks = !p.masks ? nullptr : M16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(p.masks) + mo) : p.masks + mo;
     w.out = tk.out; w.out_len = tk.out_len; w.frames = tk.rows;
+    w.ext = nullptr;
     if constexpr (OLA3) istft_ola3_run<4, RATIO, M16>(p, w, stem, run - tk.wg_istft, G, s_mem);
     else istft_ola_run<RATIO>(p, w, stem, run - tk.wg_istft, G, s_mem);
+}
+// the same with the average mask extension: the table is indexed by packed row, so the track's rows start at tile0 * T
+template <bool OLA3, bool RATIO, bool M16>
+__global__ void __launch_bounds__(256, OLA3 && !RATIO ? 3 : 2) srt_istft_batch_ext_kernel(const SrtIstftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int G)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[OLA3 ? ISTFT_OLA3_LDS_F2 : ISTFT_OLA_LDS_F2];
+    const SrtBatchTrack tk = tracks[srt_batch_track<true>(tracks, ntracks, run)];
+    const size_t mo = (size_t)tk.tile0 * 2 * p.T * p.F;
+    IstftView w;
+    w.spec = p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD;
+    w.masks = M16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(p.masks) + mo) : p.masks + mo;      // (the launcher checks that masks are given)
+    w.out = tk.out; w.out_len = tk.out_len; w.frames = tk.rows;
+    w.ext = p.ext + (size_t)tk.tile0 * p.T * 2;
+    if constexpr (OLA3) istft_ola3_run<4, RATIO, M16, false, true>(p, w, stem, run - tk.wg_istft, G, s_mem);
+    else istft_ola_run<RATIO, false, true>(p, w, stem, run - tk.wg_istft, G, s_mem);
 }
 
 // smallest q >= q0 with count(q) <= limit (count falls as q grows); q0 when even qmax does not get there
@@ -918,6 +1112,16 @@ int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_track
     if (g.istft_runs <= 0) return -1;
     if (p.masks16 && (!p.masks || p.F > 1024 || (p.ratio && p.nstems > 1))) return -1;
     const dim3 grid(g.istft_runs * p.nstems);
+    if (p.ext) {
+        if (!p.masks || p.ext_stem < (size_t)p.frames * 2) return -1;
+        if (p.ratio && p.nstems > 1) {
+            if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_ext_kernel<false, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+            else SRT_LAUNCH((srt_istft_batch_ext_kernel<true, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+        } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_ext_kernel<false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+        else if (p.masks16) SRT_LAUNCH((srt_istft_batch_ext_kernel<true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+        else SRT_LAUNCH((srt_istft_batch_ext_kernel<true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+        return srt_launch_status();
+    }
     if (p.ratio && p.masks && p.nstems > 1) {
         if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_kernel<false, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
         else SRT_LAUNCH((srt_istft_batch_kernel<true, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);

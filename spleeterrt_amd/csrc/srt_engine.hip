@@ -88,6 +88,7 @@ struct ForwardRecord {
     bool c8, c8_l1, masks16;           // raw2..6 / act2..5 / up1..4 are channel-interleaved by eight (srt_nn5.hip); conv1 / act1 too; the engine's OWN mask buffer holds halves
     unsigned up6_fused; int up6_s0; SrtConvParams up6_params;     // bit s: stem s ran up6 + head in one pass (no up6 plane stored) - srtCopyTensor("up6") re-launches up6 alone from that launch's stem range and parameters
     int wiener_last;                   // iterations of the last filtered call: the R tables srtCopyTensor("wiener_cov") can return
+    int ext_rows;                      // rows of the gain table the last inverse transform with the average mask extension filled (srtCopyTensor("mask_ext")); 0: none
 };
 
 // hipGraph replay of the launch sequences a low-latency caller repeats with the same arguments (srtSetGraphMode): the real-time
@@ -97,7 +98,8 @@ struct ForwardRecord {
 // graph instead of replaying the old form.  Keys are zeroed before they are filled and compared with memcmp.
 #define SRT_BATCH_SLOTS 4
 // `overlap`: the rows consecutive network tiles share (srtSetOverlap) - a sequence captured at one overlap is never replayed at another.
-struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; int overlap; };
+// `mask_ext`: the rule for bins >= F (srtSetMaskExtension), for the same reason.
+struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; int overlap, mask_ext; };
 // left: e->last as the capture left it (an eager call in between may have changed it)
 struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; ForwardRecord left; };
 #define SRT_GRAPH_SLOTS 4
@@ -148,6 +150,9 @@ struct srt_engine {
     float* wslab = nullptr;                            // statistics partials + block maxima
     float* wtab = nullptr;                             // R tables, weight sums, a
     float2* wspec = nullptr;                           // filtered spectra [n_stems][2][rows][SRT_SPEC_LD]
+    // average mask extension (srtSetMaskExtension): the gain table [n_stems][rows_cap][2], allocated when the mode is first switched on
+    int mask_ext = SRT_MASK_EXT_CONSTANT;
+    float* ext = nullptr;
     // packed batches of tracks (srtSeparateBatch): the device track table (max_tiles rows: every track takes at least one tile) and a ring of pinned
     // host slots it is uploaded from, each reused only after the copy from it issued SRT_BATCH_SLOTS calls earlier has completed (bev)
     SrtBatchTrack* btab = nullptr; SrtBatchTrack* bpin = nullptr;
@@ -181,6 +186,24 @@ int srtSetOverlap(srt_engine* e, int overlap_rows)
     return 0;
 }
 int srt_engine_overlap(const srt_engine* e) { return e->overlap; }
+
+static const char* const MASK_EXT_REFUSED = "%s: not available with the average mask extension (srtSetMaskExtension; DESIGN.md 15 lists it as a follow-up): srtSetMaskExtension(e, SRT_MASK_EXT_CONSTANT) first";
+static bool stream_capturing(const srt_engine* e);
+
+int srtSetMaskExtension(srt_engine* e, int mode)
+{
+    if (!e) return fail(-1, "srtSetMaskExtension: null engine");
+    if (mode != SRT_MASK_EXT_CONSTANT && mode != SRT_MASK_EXT_AVERAGE) return fail(-1, "srtSetMaskExtension: the mode must be SRT_MASK_EXT_CONSTANT (0) or SRT_MASK_EXT_AVERAGE (1)");
+    if (mode && e->wiener) return fail(-1, "srtSetMaskExtension: not available with the Wiener filter on (its gains above F are a follow-up, DESIGN.md 15): srtSetWiener(e, 0) first");
+    DeviceScope ds(e->device);
+    if (mode && !e->ext) {                               // the gain table, once: never inside a capture, kept until srtDestroy (a captured graph holds its address)
+        if (stream_capturing(e)) return fail(-1, "srtSetMaskExtension: the gain table is not allocated yet (switch the mode on before capturing)");
+        SrtSetupLock setup;
+        HIPCHK(hipMalloc((void**)&e->ext, (size_t)e->cfg.n_stems * e->rows_cap * 2 * sizeof(float)));
+    }
+    e->mask_ext = mode;
+    return 0;
+}
 
 // element offset into an activation tensor whose elements are halves (act16) or floats
 static inline float* eoff(const srt_engine* e, float* base, size_t elems) { return (float*)((char*)base + elems * (e->act16 ? 2 : 4)); }
@@ -235,7 +258,7 @@ static void free_all(srt_engine* e)
         void* layer[] = { e->wpack16_down[i], e->wpack16_up[i], e->wino_u[i], e->wino_e[i], e->act32[i], e->wpack_down[i], e->wpack_up[i], e->raw[i], e->up[i], i < 5 ? e->act16buf[i] : nullptr };
         for (void* m : layer) if (m) hipFree(m);
     }
-    void* misc[] = { e->coeff_all, e->ws, e->wpack2_d1, e->wpack2_u5, e->wpack16cs_u5, e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->wslab, e->wtab, e->wspec, e->btab };
+    void* misc[] = { e->coeff_all, e->ws, e->wpack2_d1, e->wpack2_u5, e->wpack16cs_u5, e->preWin, e->postWin, e->twiddle, e->spec, e->spec2, e->mag, e->masks, e->wslab, e->wtab, e->wspec, e->btab, e->ext };
     for (void* m : misc) if (m) hipFree(m);
     if (e->bpin) hipHostFree(e->bpin);
     for (hipEvent_t ev : e->bev) if (ev) hipEventDestroy(ev);
@@ -466,9 +489,10 @@ static int run_graphed(srt_engine* e, const GraphKey& key, bool valid, F&& issue
         if (g.exec && !memcmp(&g.key, &key, sizeof key)) {
             g.used = ++e->gclock;
             HIPCHK(hipGraphLaunch(g.exec, e->stream));
-            const int tables = e->last.wiener_last;
+            const int tables = e->last.wiener_last, ext_rows = e->last.ext_rows;
             e->last = g.left;
             if (!key.wiener) e->last.wiener_last = tables;                  // a sequence without the filter leaves the R tables of an earlier call as they are
+            if (!key.mask_ext) e->last.ext_rows = ext_rows;                 // ... and one without the mask extension the gain table
             return 0;
         }
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -841,6 +865,20 @@ int srtStft(srt_engine* e, const float* d_L, const float* d_R, size_t n, float* 
     return srtStftEx(e, d_L, d_R, n, srtStftFrames(n), srtStftRows(n), d_spec, d_mag);
 }
 
+// average mask extension: the gain table of the inverse transform that follows on the same stream, from the masks that transform will apply
+// (rows <= rows_cap: every caller has checked its tiles against max_tiles)
+static int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O)
+{
+    if (!e->ext || (size_t)rows > e->rows_cap || nstems != e->cfg.n_stems) return fail(-1, "mask extension: no gain table for this call (srtSetMaskExtension allocates it for n_stems x max_tiles * T rows)");
+    SrtMaskExtParams m; memset(&m, 0, sizeof m);
+    m.masks = masks; m.masks16 = masks16; m.nstems = nstems; m.ntiles = ntiles; m.T = e->cfg.T; m.F = e->cfg.F; m.rows = rows; m.ratio = ratio;
+    m.ext = e->ext; m.ext_stem = e->rows_cap * 2;
+    TimerScope ts(e, "mask_ext");
+    if (srt_launch_mask_ext(m, e->stream, O)) return fail(-2, "mask extension launch failed (the masks must be 16-byte aligned)");
+    e->last.ext_rows = rows;
+    return 0;
+}
+
 // inverse transform of `nstems` stems of one spectrum under their masks (nullptr: all-ones) into [nstems][2][srtIstftLength(rows)]; oob: per stem, the weight of bins >= F
 static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out)
 {
@@ -851,9 +889,15 @@ static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const fl
     const int O = masks ? e->overlap : 0;               // (the single-stem callers - CLI flows, Wiener filter - refuse an overlap before they get here)
     p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = (int)(O ? tiles_of(e, rows) : (rows + T - 1) / T);
     p.T = T; p.F = e->cfg.F;
-    for (int s = 0; s < nstems; ++s) p.oob[s] = oob[s];
+    const bool ext = e->mask_ext == SRT_MASK_EXT_AVERAGE;      // (its single-stem callers - CLI flows, Wiener filter - refuse the mode before they get here)
+    for (int s = 0; s < nstems; ++s) p.oob[s] = ext ? 1.0f : oob[s];     // the mean of an all-ones mask is 1 exactly: no table without masks
     p.ratio = ratio ? 1 : 0; p.masks16 = masks16 ? 1 : 0;
     p.frames_out = nullptr; p.out = d_out; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
+    if (ext && masks) {
+        const int rc = mask_ext_issue(e, masks, p.masks16, nstems, p.ntiles, (int)rows, p.ratio, O);
+        if (rc) return rc;
+        p.ext = e->ext; p.ext_stem = e->rows_cap * 2;
+    }
     TimerScope ts(e, "istft");
     if (srt_launch_istft(p, e->stream, O)) return fail(-2, "istft launch failed");
     return 0;
@@ -923,6 +967,7 @@ int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float*
     DeviceScope ds(e->device);
     if (iterations < 1 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtIstftWiener: iterations must be 1..3");
     if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtIstftWiener");      // its kernels index masks by (row / T, row % T)
+    if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtIstftWiener");    // the filter's own gains above F would have to be defined first
     if (rows < 1 || (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstftWiener: need 1 <= rows <= max_tiles * T");
     const int rc = ensure_wiener_ws(e);
     if (rc) return rc;
@@ -934,6 +979,7 @@ int srtSetWiener(srt_engine* e, int iterations)
     if (!e) return fail(-1, "srtSetWiener: null engine");
     if (iterations < 0 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtSetWiener: iterations must be 0 (off) or 1..3");
     if (iterations && e->cfg.ratio_mask) return fail(-1, "srtSetWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
+    if (iterations && e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtSetWiener");
     DeviceScope ds(e->device);
     if (iterations) { const int rc = ensure_wiener_ws(e); if (rc) return rc; }
     e->wiener = iterations;
@@ -970,7 +1016,7 @@ int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, s
     DeviceScope ds(e->device);
     GraphKey k;
     const bool valid = graph_prepare(e, d_L && d_R && d_out && frames <= rows, ntiles, 2, sw, &k);
-    k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.wiener = e->wiener; k.overlap = e->overlap;
+    k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.wiener = e->wiener; k.overlap = e->overlap; k.mask_ext = e->mask_ext;
     return run_graphed(e, k, valid, [&]() { return separate_issue(e, sw, d_L, d_R, n, frames, rows, d_out); });
 }
 
@@ -1038,6 +1084,7 @@ static int cli_check(srt_engine* e, int stems)
     if (e->cfg.n_stems < 2) return fail(-1, "srtSeparateCli: the engine needs sub-networks 0 (drum) and 1 (vocal)");
     if (e->cfg.ratio_mask) return fail(-1, "srtSeparateCli: ratio_mask does not apply to the CLI flows (the sub-networks see different inputs)");
     if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateCli");       // the residual chain reads masks and writes the second network's magnitudes by tile
+    if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtSeparateCli");     // the complex-domain residual chain subtracts oob * spec (srt_residual_kernel)
     if (e->wiener) return fail(-1, "srtSeparateCli: the Wiener filter does not apply to the CLI flows (the sub-networks see different inputs, and its statistics span the whole signal)");
     return 0;
 }
@@ -1259,6 +1306,10 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
     for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
     q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
     q.tab = tables_of(e);
+    if (e->mask_ext == SRT_MASK_EXT_AVERAGE) {                 // row-local: one table over the packed rows, each track reads its own (tile0 * T onwards)
+        if ((rc = mask_ext_issue(e, q.masks, q.masks16, S, q.ntiles, q.frames, q.ratio, 0))) return rc;
+        q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
+    }
     TimerScope ts(e, "istft_batch");
     if (srt_launch_istft_batch(q, e->btab, ntracks, g, e->stream)) return fail(-2, "batched istft launch failed");
     return 0;
@@ -1417,6 +1468,14 @@ int srtCopyTensor(srt_engine* e, const char* name, int stem, int tile, float* h_
         HIPCHK(hipMemcpy(h_dst, e->wtab + o * 4, (size_t)F * 4 * sizeof(float), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(h_dst + 4 * F, wsum + o, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(h_dst + 5 * F, wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F, sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    if (!strcmp(name, "mask_ext")) {                                         // the gains of bins >= F the last inverse transform applied: [rows][2] of one stem
+        const size_t rows = (size_t)e->last.ext_rows;
+        if (!e->ext || !rows || stem < 0 || stem >= e->cfg.n_stems || tile != 0) return fail(-1, "srtCopyTensor: mask_ext needs a stem, tile 0 and an earlier call with the average mask extension on");
+        if (max_floats < 2 * rows) return fail(-1, "srtCopyTensor: destination too small");
+        HIPCHK(hipStreamSynchronize(e->stream));
+        HIPCHK(hipMemcpy(h_dst, e->ext + (size_t)stem * e->rows_cap * 2, 2 * rows * sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
     const ForwardRecord& last = e->last;

@@ -190,7 +190,18 @@ struct SrtIstftParams {
     float* out;               // [nstems][2][out_len]
     size_t out_len;           // frames*1024 + 3072
     SrtDspTables tab;
+    const float* ext;         // average mask extension (srtSetMaskExtension): gains of bins >= F, [nstems][..][frames][2] with ext_stem floats between stems, written by
+    size_t ext_stem;          // srt_launch_mask_ext from the same masks / ratio / overlap; nullptr: the constant rule (oob).  Batch: indexed by packed row
 };
+// average mask extension: ext[s][r][c] = mean over k < F of the in-band gain the inverse transform applies to stem s, row r, channel c
+struct SrtMaskExtParams {
+    const float* masks;       // as SrtIstftParams::masks (never null), halves with masks16
+    int masks16, nstems, ntiles, T, F;
+    int rows;                 // rows to fill (batch: every packed row)
+    int ratio;                // as SrtIstftParams::ratio
+    float* ext; size_t ext_stem;
+};
+int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap = 0);
 // overlap > 0 (srtSetOverlap): consecutive network tiles share `overlap` rows - p.mag / p.masks are in the overlapped layout of ov_tiles / p.ntiles =
 // srtOverlapTiles(rows) tiles and the kernels' overlap instantiations run; 0: the back-to-back layout and the kernels as they always were
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap = 0, int ov_tiles = 0);
