@@ -794,6 +794,9 @@ int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_t
         const int slots = 768, rounds = (p.rows_total + slots * cap - 1) / (slots * cap);
         fpb = (p.rows_total + slots * rounds - 1) / (slots * rounds);
     }
+    // (tests/test_dsp_float64.py holds every row to float64 at one shape per regime of this rule: rows = 37 -> fpb 1, 1025 -> 2 and 4099 -> 6 (both with a last
+    // workgroup of one frame), 9000 -> 12.  Nothing reads this rule from the tests: launcher_fpb / launcher_G in that file restate it and this function's sibling below
+    // by hand, for the printed tags only.  Whoever changes a rule edits the restatement and moves the shapes, or the regimes lose their coverage with every test green.)
     const int blocks = (p.rows_total + fpb - 1) / fpb;
     if (blocks <= 0) return 0;
     if (overlap > 0) {                                   // the rows of tile j are [j (T - O), j (T - O) + T): every row below rows_total must have a tile
@@ -821,6 +824,8 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
     int G = (nseg + max_runs - 1) / max_runs;
     const int gmin = (size_t)nseg * p.nstems >= 4096 ? 13 : 5;          // short signals: shorter runs (more warm-up, but all CUs busy)
     if (G < gmin) G = gmin;
+    // (tests/test_dsp_float64.py, every output hop against float64: frames 1..4 and 13..17, one stem -> G = 5 with nseg mod G taking every value; 1400 frames x 3 stems
+    // -> G = 13; 2100 x 5 -> G = 14, 755 workgroups; 4500 x 3 at F = 1088 -> G = 14 on the table kernel.  A change to this rule moves those shapes as well.)
     const int blocks = (nseg + G - 1) / G;
     // one stem per workgroup: 32 accumulator + 54 prefetch registers + the FFT fit in 256 VGPRs at 2 workgroups per CU
     // F > 1024: eight mask registers per channel do not fit the 168-VGPR budget of the three-per-CU form (22 dwords would spill): the two-per-CU kernel
