@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <utility>
+#include <vector>
 
 #define SRT_MAX_STEMS 8
 #define SRT_FFT 4096
@@ -23,6 +25,27 @@ int srt_set_error(int code, const char* fmt, const char* detail);
 // plugin instances initialised from two threads at once otherwise come up muted now and then.  Steady-state calls never take this lock: they
 // use explicit streams only and replay graphs that already exist.
 struct SrtSetupLock { SrtSetupLock(); ~SrtSetupLock(); };
+
+// Owner of device and pinned host allocations: alloc() is one hipMalloc / hipHostMalloc of exactly `bytes` and records the pointer, release() frees one of them,
+// clear() (and the destructor) what is left, in allocation order.  The live stream (srt_stream.hip) frees through this only.
+struct SrtMem {
+    std::vector<std::pair<void*, bool>> blocks;          // (pointer, pinned)
+    SrtMem() = default; SrtMem(const SrtMem&) = delete;
+    ~SrtMem() { clear(); }
+    template <class T> hipError_t alloc(T** out, size_t bytes, bool pinned = false)
+    {
+        void* p = nullptr;
+        const hipError_t er = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+        if (er == hipSuccess) { blocks.emplace_back(p, pinned); *out = (T*)p; }
+        return er;
+    }
+    static void free_one(const std::pair<void*, bool>& b) { if (b.second) hipHostFree(b.first); else hipFree(b.first); }
+    template <class T> void release(T*& q)               // q: null, or a pointer alloc() gave
+    {
+        for (size_t i = 0; q && i < blocks.size(); ++i) if (blocks[i].first == (void*)q) { free_one(blocks[i]); blocks.erase(blocks.begin() + i); q = nullptr; }
+    }
+    void clear() { for (const auto& b : blocks) free_one(b); blocks.clear(); }
+};
 
 enum { SRT_ACT_LEAKY = 0, SRT_ACT_RELU = 1, SRT_ACT_ELU = 2 };
 

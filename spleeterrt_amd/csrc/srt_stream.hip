@@ -38,6 +38,7 @@ static bool stream_fail(const char* where, const char* why)
 
 
 struct srt_live {
+    SrtMem mem;                          // every device and pinned buffer below
     srt_engine* eng;
     hipStream_t hop, nn;
     hipEvent_t evMag, evNN, evOut;
@@ -164,16 +165,14 @@ failed:
 // host state only: a failed instance still accounts for samples (and emits silence) through its queue.  NULL: out of host memory.
 srt_live* live_new(int F, int T, int S, int K, int L)
 {
-    srt_live* s = new (std::nothrow) srt_live();
+    srt_live* s = new (std::nothrow) srt_live();           // value-initialised: every field zero
     if (!s) return nullptr;
-    memset(s, 0, sizeof *s);
     s->F = F; s->T = T; s->S = S; s->K = K; s->L = L; s->D = L + 2 * K; s->hw = (size_t)F * T;
     s->needed = OUTPUTSEG;
     s->nq = 2;
     s->runHop = s->joinedHop = -1;
     s->runBuf = s->joinedBuf = 1;                                             // run 0 writes buffer 0; until it is joined the hops read buffer 1
     s->failed = true;                                                         // until live_init has succeeded
-    s->pinned = nullptr;
     const size_t seg = (size_t)OUTPUTSEG * 2 * S;
     s->hostq = (float*)calloc(2 * seg, sizeof(float));
     s->outq[0] = s->hostq; s->outq[1] = s->hostq ? s->hostq + seg : nullptr;
@@ -186,14 +185,9 @@ void live_free(srt_live* s)
     if (s->hop) hipStreamSynchronize(s->hop);
     if (s->nn) hipStreamSynchronize(s->nn);
     if (s->eng) srtDestroy(s->eng);
-    void* d[] = { s->d_ring, s->d_spec, s->d_mag, s->d_tmp, s->d_masks, s->d_overlap, s->d_out, s->d_awin, s->d_swin, s->d_tw,
-                  s->d_blk, s->d_hin, s->d_sring, s->d_planes };
-    for (void* q : d) if (q) hipFree(q);
+    s->mem.clear();
     srt_rs_filter_free(&s->fin);
     srt_rs_filter_free(&s->fout);
-    if (s->pinned) hipHostFree(s->pinned);
-    if (s->pinIn) hipHostFree(s->pinIn);
-    if (s->pinOut) hipHostFree(s->pinOut);
     free(s->hostq);
     hipEvent_t ev[] = { s->evMag, s->evNN, s->evOut };
     for (hipEvent_t e : ev) if (e) hipEventDestroy(e);
@@ -227,16 +221,16 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
         if (srtSetCoeffHost(s->eng, k, coeff[k])) { stream_fail(who, nullptr); return -2; }
     srtSetGraphMode(s->eng, 1);                           // the U-Nets run on the same buffers every K hops: replay one hipGraph per mask buffer
     const size_t S = s->S, specF = 2 * (size_t)s->D * SRT_SPEC_LD * 2, maskF = 2 * S * 2 * s->hw;
-    INITTRY(hipMalloc((void**)&s->d_ring, sizeof s->ring));
-    INITTRY(hipMalloc((void**)&s->d_spec, specF * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_mag, 2 * s->hw * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_tmp, 2 * s->hw * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_masks, maskF * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_overlap, 2 * S * 1024 * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_out, OUTPUTSEG * 2 * S * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_awin, FFTSIZE * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_swin, FFTSIZE * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_tw, FFTSIZE * sizeof(float2)));
+    INITTRY(s->mem.alloc(&s->d_ring, sizeof s->ring));
+    INITTRY(s->mem.alloc(&s->d_spec, specF * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_mag, 2 * s->hw * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_tmp, 2 * s->hw * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_masks, maskF * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_overlap, 2 * S * 1024 * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_out, OUTPUTSEG * 2 * S * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_awin, FFTSIZE * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_swin, FFTSIZE * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_tw, FFTSIZE * sizeof(float2)));
     INITTRY(hipMemset(s->d_spec, 0, specF * sizeof(float)));              // zero spectrum for the first D hops (:423-438)
     INITTRY(hipMemset(s->d_mag, 0, 2 * s->hw * sizeof(float)));           // frames before 0 have zero magnitude
     INITTRY(hipMemset(s->d_overlap, 0, 2 * S * 1024 * sizeof(float)));
@@ -258,7 +252,7 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     INITTRY(hipMemcpy(s->d_awin, an.data(), FFTSIZE * 4, hipMemcpyHostToDevice));
     INITTRY(hipMemcpy(s->d_swin, sy.data(), FFTSIZE * 4, hipMemcpyHostToDevice));
     INITTRY(hipMemcpy(s->d_tw, tw.data(), 2 * FFTSIZE * 4, hipMemcpyHostToDevice));
-    INITTRY(hipHostMalloc((void**)&s->pinned, s->nq * OUTPUTSEG * 2 * S * sizeof(float), hipHostMallocDefault));   // pinned queue for the per-hop D2H copy
+    INITTRY(s->mem.alloc(&s->pinned, s->nq * OUTPUTSEG * 2 * S * sizeof(float), true));   // pinned queue for the per-hop D2H copy
     INITTRY(hipStreamSynchronize(nullptr));               // masks / windows / twiddles (null-stream copies) are in place before the first hop
     // Pre-warm the per-hop path too: the first launch of the hop kernels loads their code, and eight plugin instances making their first call at
     // the same time queued behind each other for it - the slowest call of every instance was its FIRST one, 7.5 ms (round 6, host/rt_latency.c
@@ -361,12 +355,12 @@ int live_rate_init(srt_live* s, const SrtRsGeom& gin, const SrtRsGeom& gout, con
     // already be written ahead of the newest window (one hop of accounting, one of slack), rounded up to whole segments
     const long long span = cdiv_ll((long long)s->maxBlock * gin.Q, gin.P) + 2 * gout.LO + srt_rs_horizon(gout) + 3 * OUTPUTSEG + 16;
     s->capS = (int)(cdiv_ll(span, OUTPUTSEG) * OUTPUTSEG);
-    INITTRY(hipMalloc((void**)&s->d_blk, 2 * (size_t)s->maxBlock * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_hin, 2 * (size_t)s->capIn * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_sring, (size_t)s->capS * nc * sizeof(float)));
-    INITTRY(hipMalloc((void**)&s->d_planes, (size_t)nc * s->maxBlock * sizeof(float)));
-    INITTRY(hipHostMalloc((void**)&s->pinIn, 2 * (size_t)s->maxBlock * sizeof(float), hipHostMallocDefault));
-    INITTRY(hipHostMalloc((void**)&s->pinOut, (size_t)nc * s->maxBlock * sizeof(float), hipHostMallocDefault));
+    INITTRY(s->mem.alloc(&s->d_blk, 2 * (size_t)s->maxBlock * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_hin, 2 * (size_t)s->capIn * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_sring, (size_t)s->capS * nc * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_planes, (size_t)nc * s->maxBlock * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->pinIn, 2 * (size_t)s->maxBlock * sizeof(float), true));
+    INITTRY(s->mem.alloc(&s->pinOut, (size_t)nc * s->maxBlock * sizeof(float), true));
     INITTRY(hipMemsetAsync(s->d_blk, 0, 2 * (size_t)s->maxBlock * sizeof(float), s->hop));
     INITTRY(hipMemsetAsync(s->d_hin, 0, 2 * (size_t)s->capIn * sizeof(float), s->hop));          // zero weights must meet finite values (padded taps)
     INITTRY(hipMemsetAsync(s->d_sring, 0, (size_t)s->capS * nc * sizeof(float), s->hop));
