@@ -131,7 +131,7 @@ SRT_API size_t srtOverlapTiles(size_t rows, int T, int overlap_rows);
  * -1 with srtLastError() text for a null engine, an unknown mode, or the Wiener filter on.  Honoured by srtIstft, srtSeparate[Ex] (ratio_mask, srtSetOverlap, the
  * fp16 mode's half masks, graph mode: the mode is part of the captured call's key), srtSeparateBatch and srtSeparateHostStream[Ex|Io] (the gain is row-local:
  * chunk seams need nothing), and by engines borrowed from a multi-device object.  Refused with -1 while the mode is on: srtSeparateCli* (its complex-domain
- * residual chain subtracts oob_weight * spectrum), srtIstftWiener and srtSetWiener(n > 0) (the filter's gains above F are a follow-up).  The live / plugin
+ * residual chain subtracts oob_weight * spectrum), srtIstftWiener, srtSeparateBatchWiener and srtSetWiener(n > 0) (the filter's gains above F are a follow-up).  The live / plugin
  * surfaces (srtLive*, Spleeter4Stems*) have their own handles and keep the constant rule (a follow-up).
  * srtCopyTensor(e, "mask_ext", stem, 0, h, 2 * rows) returns the table the last such call left for that stem: [rows][2] (L, R); after srtSeparateBatch the
  * rows are the packed rows (track k from row tile0[k] * T). */
@@ -147,7 +147,7 @@ SRT_API int  srtSetMaskExtension(srt_engine *e, int mode);
  * The track table is uploaded in stream order into engine memory, so the host arrays may be reused once the call returns; the call does not wait for the GPU
  * (it only waits for the table upload it issued four calls earlier).  It always launches eagerly, also in graph mode, and is refused inside a stream capture.
  * -1, with nothing launched, for ntracks < 1, a null array or entry, any n[k] < 4096, more than max_tiles packed tiles, or the Wiener filter on (its
- * statistics would have to be per track).  srtCopyTensor afterwards addresses the packed tiles: tile = tile0[k] + the tile within track k. */
+ * statistics have to be per track: srtSeparateBatchWiener).  srtCopyTensor afterwards addresses the packed tiles: tile = tile0[k] + the tile within track k. */
 SRT_API int  srtBatchPlan(const size_t *n, int ntracks, int T, size_t *tile0, size_t *total_tiles);
 SRT_API int  srtSeparateBatch(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
                               const size_t *n, float *const *d_out);
@@ -224,6 +224,19 @@ SRT_API int  srtSetWiener(srt_engine *e, int iterations);
  * `iterations` 1..3 whatever srtSetWiener says; d_out as srtIstft.  srtCopyTensor(e, "wiener_cov", stem, iteration, h, 5F + 1) then returns R_j of
  * that iteration of the last filtered call as [F][4] (R00, R11, Re R01, Im R01), the weight sums sum_t v_j [F] (spectrum units) and a [1]. */
 SRT_API int  srtIstftWiener(srt_engine *e, const float *d_spec, size_t rows, const float *d_masks, int iterations, float *d_out);
+/* srtSeparateBatch with the filter per track: arguments, layout, track table and packing as srtSeparateBatch (srtBatchPlan; d_out[k]:
+ * [n_stems][2][srtIstftLength(srtStftRows(n[k]))]); `iterations` 1..3 whatever srtSetWiener says (the engine's setting may be on or off).  One batched STFT,
+ * one srtForward over the packed tiles (fp32 masks, in the fp16 mode too), `iterations` x (statistics + finalize) and one filter pass over the packed rows,
+ * one batched inverse transform.  Track k's stems are what srtSeparate gives for track k alone with srtSetWiener(e, iterations) - bit for bit with
+ * batch_invariant, up to the network's batch-dependent kernel choice otherwise: the statistics window is the track's own srtStftRows(n[k]) rows (not the
+ * rows that pad it to its tile boundary, not another track), a = max(1, max |x| / 10) is the track's, and its row chunks follow the single call's rule, so
+ * its R tables equal the single call's whatever else the batch holds and wherever the track sits in it.  Always eager, refused inside a stream capture,
+ * the only host wait is the table upload issued four calls earlier; the workspace (per-track tables, a statistics slab of max_tiles * T / 16 + max_tiles
+ * chunks) is allocated by the first call and kept until srtDestroy.  -1, with nothing launched or written, for everything srtSeparateBatch refuses,
+ * iterations outside 1..3, ratio_mask set, srtSetOverlap > 0 and SRT_MASK_EXT_AVERAGE; -5 when a stem's weights are not set.
+ * srtCopyTensor(e, "wiener_cov", stem, 4 * k + iteration, h, 5F + 1) then returns track k's tables (as after srtIstftWiener: R, weight sums, a). */
+SRT_API int  srtSeparateBatchWiener(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
+                                    const size_t *n, float *const *d_out, int iterations);
 
 /* ---- one node, several devices: the reference CLI's tile-range fan-out (Executable/main.c:544-673, `processMT`: spawnNthreads workers, each with
  * its own network instance and a contiguous tile range, one shared read-only weight blob) with a GPU where the reference has a CPU thread.
@@ -339,7 +352,7 @@ SRT_API int  srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead
 
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";
-                                                                                                                   "wiener_cov": tile = iteration (see srtIstftWiener);
+                                                                                                                   "wiener_cov": tile = 4 * track + iteration (see srtIstftWiener);
                                                                                                                    after srtSeparateBatch: packed tile indices */
 SRT_API int  srtSetTiming(srt_engine *e, int enable);                    /* record HIP events around every launch of the next calls */
 SRT_API int  srtGetTiming(srt_engine *e, char *names, size_t names_bytes, float *ms, int max_entries); /* returns count; syncs the stream */

@@ -80,6 +80,7 @@ def load_library():
     L.srtCopyTensor.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, vp, C.c_size_t]
     L.srtBatchPlan.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.srtSeparateBatch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
+    L.srtSeparateBatchWiener.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
     L.srtSetGraphMode.argtypes = [vp, C.c_int]
     L.srtPrepareForward.argtypes = [vp, f32p, C.c_int, f32p]
     L.srtReleaseStaging.argtypes = [vp]
@@ -273,11 +274,14 @@ class Engine:
         self._chk(self.L.srtIstftWiener(self.h, _ptr(spec.contiguous()), rows, _ptr(masks), int(iterations), _ptr(out)))
         return out
 
-    def wiener_cov(self, stem, iteration):
-        """(R [F,4] = R00, R11, Re R01, Im R01; weight sums [F]; a) of one stem and iteration of the last filtered call"""
+    def wiener_cov(self, stem, iteration, track=0):
+        """(R [F,4] = R00, R11, Re R01, Im R01; weight sums [F]; a) of one stem and iteration of the last filtered call; after a filtered batch call
+        (separate_batch with wiener), of track `track` of that call"""
         import numpy as np
+        if not 1 <= int(iteration) <= 3 or int(track) < 0:
+            raise EngineError("wiener_cov: iteration must be 1..3 and track >= 0")
         a = np.empty(5 * self.F + 1, np.float32)
-        self._chk(self.L.srtCopyTensor(self.h, b"wiener_cov", stem, iteration, C.c_void_p(a.ctypes.data), a.size))
+        self._chk(self.L.srtCopyTensor(self.h, b"wiener_cov", stem, 4 * int(track) + int(iteration), C.c_void_p(a.ctypes.data), a.size))
         return a[:4 * self.F].reshape(self.F, 4), a[4 * self.F:5 * self.F], float(a[5 * self.F])
 
     def stft(self, L, R, want_mag=True):
@@ -309,9 +313,11 @@ class Engine:
         self._chk(self.L.srtSeparate(self.h, _ptr(L), _ptr(R), n, _ptr(out)))
         return out
 
-    def separate_batch(self, tracks, outs=None):
+    def separate_batch(self, tracks, outs=None, wiener=None):
         """many independent tracks: [(L, R)] CUDA float32 tensors -> [stems [S,2,rows_k*1024+3072]], each equal to separate(L, R) of that track.
-        The list is cut in order into calls of at most max_tiles packed tiles (stream.pack_tracks); one srtSeparateBatch per call."""
+        The list is cut in order into calls of at most max_tiles packed tiles (stream.pack_tracks); one srtSeparateBatch per call.
+        wiener: None = the engine's own setting (set_wiener), 0 = no filter, 1..3 = the multichannel Wiener filter per track with that many iterations
+        (one srtSeparateBatchWiener per call): each track as separate(L, R) on an engine with set_wiener(wiener)."""
         from . import stream
         t = self.torch
         ns = [L.numel() for L, _ in tracks]
@@ -323,11 +329,20 @@ class Engine:
         for o, n in zip(outs, ns):
             assert o.is_cuda and o.is_contiguous() and o.numel() >= self.S * 2 * self.L.srtIstftLength(self.L.srtStftRows(n))
         src = [(L.contiguous(), R.contiguous()) for L, R in tracks]      # (kept alive until the calls are issued; the stream orders any reuse)
-        for g in stream.pack_tracks(ns, self.T, self.max_tiles):
-            k = len(g.tracks)
-            P = C.c_void_p * k
-            self._chk(self.L.srtSeparateBatch(self.h, k, P(*[src[i][0].data_ptr() for i in g.tracks]), P(*[src[i][1].data_ptr() for i in g.tracks]),
-                                              (C.c_size_t * k)(*[ns[i] for i in g.tracks]), P(*[outs[i].data_ptr() for i in g.tracks])))
+        wiener = self.wiener if wiener is None else int(wiener)
+        own = self.wiener
+        if own and not wiener:                                           # srtSeparateBatch refuses while the engine's filter is on: off for these calls
+            self.set_wiener(0)
+        try:
+            for g in stream.pack_tracks(ns, self.T, self.max_tiles):
+                k = len(g.tracks)
+                P = C.c_void_p * k
+                args = (self.h, k, P(*[src[i][0].data_ptr() for i in g.tracks]), P(*[src[i][1].data_ptr() for i in g.tracks]),
+                        (C.c_size_t * k)(*[ns[i] for i in g.tracks]), P(*[outs[i].data_ptr() for i in g.tracks]))
+                self._chk(self.L.srtSeparateBatchWiener(*args, wiener) if wiener else self.L.srtSeparateBatch(*args))
+        finally:
+            if own and not wiener:
+                self.set_wiener(own)
         return outs
 
     def separate_cli(self, L, R, stems):

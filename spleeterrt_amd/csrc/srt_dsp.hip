@@ -1055,6 +1055,24 @@ __global__ void __launch_bounds__(256, OLA3 && !RATIO ? 3 : 2) srt_istft_batch_e
     else istft_ola_run<RATIO, false, true>(p, w, stem, run - tk.wg_istft, G, s_mem);
 }
 
+// per-stem spectra instead of masks (srtSeparateBatchWiener: the filter wrote one spectrum per stem over the packed rows): stem s of a track reads
+// p.spec + s * stem_stride at the track's packed rows, all-ones in band and p.oob[s] above F - the single-signal filter path's mask-free, single-stem launches
+// (srt_istft_ola3_kernel<4> / srt_istft_ola_kernel<false>) for every (track, stem) at once.  The stride is an argument of its own: SrtIstftParams stays as it is.
+template <bool OLA3>
+__global__ void __launch_bounds__(256, OLA3 ? 3 : 2) srt_istft_batch_spec_kernel(const SrtIstftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int G, size_t stem_stride)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[OLA3 ? ISTFT_OLA3_LDS_F2 : ISTFT_OLA_LDS_F2];
+    const SrtBatchTrack tk = tracks[srt_batch_track<true>(tracks, ntracks, run)];
+    IstftView w;
+    w.spec = p.spec + (size_t)stem * stem_stride + (size_t)tk.tile0 * p.T * SRT_SPEC_LD;
+    w.masks = nullptr;
+    w.out = tk.out; w.out_len = tk.out_len; w.frames = tk.rows;
+    w.ext = nullptr;
+    if constexpr (OLA3) istft_ola3_run<4, false, false>(p, w, stem, run - tk.wg_istft, G, s_mem);
+    else istft_ola_run<false>(p, w, stem, run - tk.wg_istft, G, s_mem);
+}
+
 // smallest q >= q0 with count(q) <= limit (count falls as q grows); q0 when even qmax does not get there
 template <class C>
 static int srt_batch_step(int q0, int qmax, long limit, C&& count)
@@ -1133,6 +1151,16 @@ int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_track
     } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_kernel<false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     else if (p.masks16) SRT_LAUNCH((srt_istft_batch_kernel<true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     else SRT_LAUNCH((srt_istft_batch_kernel<true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+    return srt_launch_status();
+}
+
+// the same two forms per geometry for per-stem spectra without masks (p.masks, p.ext and p.ratio are not used)
+int srt_launch_istft_batch_spec(const SrtIstftParams& p, size_t stem_stride, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s)
+{
+    if (g.istft_runs <= 0 || p.masks || p.masks16 || p.ext || stem_stride < 2 * p.spec_ch_stride) return -1;
+    const dim3 grid(g.istft_runs * p.nstems);
+    if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_spec_kernel<false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, stem_stride);
+    else SRT_LAUNCH((srt_istft_batch_spec_kernel<true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, stem_stride);
     return srt_launch_status();
 }
 

@@ -88,6 +88,7 @@ struct ForwardRecord {
     bool c8, c8_l1, masks16;           // raw2..6 / act2..5 / up1..4 are channel-interleaved by eight (srt_nn5.hip); conv1 / act1 too; the engine's OWN mask buffer holds halves
     unsigned up6_fused; int up6_s0; SrtConvParams up6_params;     // bit s: stem s ran up6 + head in one pass (no up6 plane stored) - srtCopyTensor("up6") re-launches up6 alone from that launch's stem range and parameters
     int wiener_last;                   // iterations of the last filtered call: the R tables srtCopyTensor("wiener_cov") can return
+    int wiener_tracks;                 // ... which was a batch of this many tracks (srtSeparateBatchWiener: the per-track tables); 0: a single-signal call
     int ext_rows;                      // rows of the gain table the last inverse transform with the average mask extension filled (srtCopyTensor("mask_ext")); 0: none
 };
 
@@ -157,6 +158,13 @@ struct srt_engine {
     // host slots it is uploaded from, each reused only after the copy from it issued SRT_BATCH_SLOTS calls earlier has completed (bev)
     SrtBatchTrack* btab = nullptr; SrtBatchTrack* bpin = nullptr;
     hipEvent_t bev[SRT_BATCH_SLOTS] = {}; bool bused[SRT_BATCH_SLOTS] = {}; int bslot = 0;
+    // ... with the Wiener filter per track (srtSeparateBatchWiener): the second table (device + the same ring of pinned slots), the statistics slab of
+    // max_tiles * T / 16 + max_tiles chunks with its block maxima, and the per-track tables [max_tiles] x (R [3][S][F][4], weight sums [3][S][F]) + a [max_tiles].
+    // Allocated by the first such call and owned by bwmem; separate from wslab / wtab, whose addresses a captured single-signal graph may hold (wspec, written
+    // and read inside one call, is shared).
+    SrtMem bwmem;
+    SrtBatchWiener* bwtab = nullptr; SrtBatchWiener* bwpin = nullptr;
+    float* bwslab = nullptr; float* bwtabf = nullptr;
     // timing
     bool timing = false; std::vector<TimingEntry> tlog;
 };
@@ -489,9 +497,9 @@ static int run_graphed(srt_engine* e, const GraphKey& key, bool valid, F&& issue
         if (g.exec && !memcmp(&g.key, &key, sizeof key)) {
             g.used = ++e->gclock;
             HIPCHK(hipGraphLaunch(g.exec, e->stream));
-            const int tables = e->last.wiener_last, ext_rows = e->last.ext_rows;
+            const int tables = e->last.wiener_last, wtracks = e->last.wiener_tracks, ext_rows = e->last.ext_rows;
             e->last = g.left;
-            if (!key.wiener) e->last.wiener_last = tables;                  // a sequence without the filter leaves the R tables of an earlier call as they are
+            if (!key.wiener) { e->last.wiener_last = tables; e->last.wiener_tracks = wtracks; }      // a sequence without the filter leaves the R tables of an earlier call as they are
             if (!key.mask_ext) e->last.ext_rows = ext_rows;                 // ... and one without the mask extension the gain table
             return 0;
         }
@@ -952,7 +960,7 @@ static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const f
         { TimerScope ts(e, "wiener_cov"); if (srt_launch_wiener_finalize(w, pass, e->stream)) return fail(-2, "Wiener finalize launch failed"); }
     }
     { TimerScope ts(e, "wiener_filter"); if (srt_launch_wiener_filter(w, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
-    e->last.wiener_last = iters;
+    e->last.wiener_last = iters; e->last.wiener_tracks = 0;
     const size_t len = srtIstftLength(rows);
     for (int j = 0; j < S; ++j) {
         const int rc = istft_one(e, e->wspec + (size_t)j * w.out_stem, rows, nullptr, e->cfg.oob_weight[j], d_out + (size_t)j * 2 * len);
@@ -1247,31 +1255,54 @@ static int ensure_batch(srt_engine* e)
     return 0;
 }
 
-int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
+// the per-track filter's workspace (see srt_engine::bwmem): sizes follow from the configuration, so it is allocated once, by the first srtSeparateBatchWiener
+static size_t batch_wiener_chunk_cap(const srt_engine* e) { return (size_t)e->cfg.max_tiles * e->cfg.T / 16 + e->cfg.max_tiles; }
+static size_t batch_wiener_track_floats(const srt_engine* e) { return (size_t)SRT_WIENER_MAX_ITERS * e->cfg.n_stems * e->cfg.F; }      // R: x 4, weight sums: x 1
+static int ensure_batch_wiener(srt_engine* e)
 {
-    if (!e) return fail(-1, "srtSeparateBatch: null engine");
-    DeviceScope ds(e->device);
-    if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "srtSeparateBatch: need ntracks >= 1 and the four track arrays");
-    const SrtSwitches sw = srt_read_switches();
-    char what[48];
-    for (int k = 0; k < ntracks; ++k) {
-        snprintf(what, sizeof what, "%d", k);
-        if (!d_L[k] || !d_R[k] || !d_out[k]) return fail(-1, "srtSeparateBatch: null pointer in track %s", what);
-        if (n[k] < SRT_FFT) return fail(-1, "srtSeparateBatch: track %s has fewer than 4096 samples", what);
+    if (e->bwtab && e->bwpin && e->bwslab && e->bwtabf && e->wspec) return 0;
+    SrtSetupLock setup;
+    const size_t cap = (size_t)e->cfg.max_tiles, S = e->cfg.n_stems, F = e->cfg.F;
+    if (!e->bwtab) HIPCHK(e->bwmem.alloc(&e->bwtab, cap * sizeof(SrtBatchWiener)));
+    if (!e->bwpin) HIPCHK(e->bwmem.alloc(&e->bwpin, SRT_BATCH_SLOTS * cap * sizeof(SrtBatchWiener), true));
+    if (!e->bwslab) HIPCHK(e->bwmem.alloc(&e->bwslab, batch_wiener_chunk_cap(e) * (S * 4 * F + SRT_WIENER_BINBLK) * sizeof(float)));
+    if (!e->bwtabf) {
+        const size_t bytes = (cap * batch_wiener_track_floats(e) * 5 + cap) * sizeof(float);
+        HIPCHK(e->bwmem.alloc(&e->bwtabf, bytes));
+        HIPCHK(hipMemset(e->bwtabf, 0, bytes));
     }
-    if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateBatch");     // srtBatchPlan has no overlap argument
-    if (e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
+    if (!e->wspec) HIPCHK(hipMalloc((void**)&e->wspec, S * 2 * e->rows_cap * SRT_SPEC_LD * sizeof(float2)));      // (ensure_wiener_ws's size rule: max_tiles tiles)
+    return 0;
+}
+
+// What the two batch entry points share, up to and including the forward: the argument checks (`who` names the entry point; wiener = the iterations of
+// srtSeparateBatchWiener, 0 for srtSeparateBatch), the track table(s) and their upload from a pinned slot, the batched STFT and the network over the packed tiles.
+struct BatchCall { size_t total; SrtBatchGrid g; size_t ch_stride; int wchunks; };
+static int batch_forward(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
+                         int wiener, BatchCall* bc)
+{
+    if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "%s: need ntracks >= 1 and the four track arrays", who);
+    const SrtSwitches sw = srt_read_switches();
+    char what[160];
+    for (int k = 0; k < ntracks; ++k) {
+        if (!d_L[k] || !d_R[k] || !d_out[k]) { snprintf(what, sizeof what, "%s: null pointer in track %d", who, k); return fail(-1, "%s", what); }
+        if (n[k] < SRT_FFT) { snprintf(what, sizeof what, "%s: track %d has fewer than 4096 samples", who, k); return fail(-1, "%s", what); }
+    }
+    if (e->overlap) return fail(-1, OVERLAP_REFUSED, who);                    // srtBatchPlan has no overlap argument
+    if (!wiener && e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
     const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
     size_t total = 0;
     if (srtBatchPlan(n, ntracks, T, nullptr, &total)) return -1;
     if (total > (size_t)e->cfg.max_tiles) {
-        snprintf(what, sizeof what, "%zu", total);
-        return fail(-1, "srtSeparateBatch: the tracks take %s tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", what);
+        snprintf(what, sizeof what, "%s: the tracks take %zu tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", who, total);
+        return fail(-1, "%s", what);
     }
-    for (int s = 0; s < S; ++s) if (!e->have_coeff[s]) return fail(-5, "srtSeparateBatch: weights not set for every stem");
-    if (stream_capturing(e)) return fail(-1, "srtSeparateBatch: not capturable (the track table is uploaded per call): call it outside stream capture");
+    if (wiener && total * T / 16 > 65535) return fail(-1, "%s: more than 65535 blocks of 16 packed rows (the filter's grid)", who);
+    for (int s = 0; s < S; ++s) if (!e->have_coeff[s]) return fail(-5, "%s: weights not set for every stem", who);
+    if (stream_capturing(e)) return fail(-1, "%s: not capturable (the track table is uploaded per call): call it outside stream capture", who);
     int rc = ensure_batch(e);
     if (rc) return rc;
+    if (wiener && (rc = ensure_batch_wiener(e))) return rc;
     // the table goes up in stream order from a pinned slot; the slot's previous copy (SRT_BATCH_SLOTS calls ago) must have left it first
     const int slot = e->bslot;
     if (e->bused[slot]) HIPCHK(hipEventSynchronize(e->bev[slot]));
@@ -1284,25 +1315,41 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
         t.tile0 = (int)tile0; t.ntiles = (t.rows + T - 1) / T; tile0 += t.ntiles;
         t.out = d_out[k]; t.out_len = srtIstftLength(t.rows);
     }
-    SrtBatchGrid g;
-    if (srt_batch_geometry(h, ntracks, T, F, S, &g)) return fail(-1, "srtSeparateBatch: batch geometry out of range");
+    if (srt_batch_geometry(h, ntracks, T, F, S, &bc->g)) return fail(-1, "%s: batch geometry out of range", who);
+    bc->wchunks = 0;
+    SrtBatchWiener* hw = wiener ? e->bwpin + (size_t)slot * e->cfg.max_tiles : nullptr;
+    if (wiener) {
+        bc->wchunks = srt_batch_wiener_geometry(h, hw, ntracks);
+        if (bc->wchunks < 1 || (size_t)bc->wchunks > batch_wiener_chunk_cap(e)) return fail(-1, "%s: batch geometry out of range", who);
+    }
     HIPCHK(hipMemcpyAsync(e->btab, h, (size_t)ntracks * sizeof(SrtBatchTrack), hipMemcpyHostToDevice, e->stream));
+    if (wiener) HIPCHK(hipMemcpyAsync(e->bwtab, hw, (size_t)ntracks * sizeof(SrtBatchWiener), hipMemcpyHostToDevice, e->stream));
     HIPCHK(hipEventRecord(e->bev[slot], e->stream));
     e->bused[slot] = true; e->bslot = (slot + 1) % SRT_BATCH_SLOTS;
-    const size_t ch_stride = total * T * SRT_SPEC_LD;          // the packed spectrum: [2][total * T][SRT_SPEC_LD]
+    bc->total = total;
+    bc->ch_stride = total * T * SRT_SPEC_LD;                   // the packed spectrum: [2][total * T][SRT_SPEC_LD]
     {
         SrtStftParams p; memset(&p, 0, sizeof p);
-        p.spec = e->spec; p.spec_ch_stride = ch_stride; p.mag = e->mag;
+        p.spec = e->spec; p.spec_ch_stride = bc->ch_stride; p.mag = e->mag;
         p.rows_total = (int)(total * T); p.T = T; p.F = F; p.tab = tables_of(e);
         TimerScope ts(e, "stft_batch");
-        if (srt_launch_stft_batch(p, e->btab, ntracks, g, e->stream)) return fail(-2, "batched stft launch failed");
+        if (srt_launch_stft_batch(p, e->btab, ntracks, bc->g, e->stream)) return fail(-2, "batched stft launch failed");
     }
-    // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue
-    rc = forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, masks16_wanted(e, sw));
+    // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue (never with the filter, which reads fp32 masks)
+    return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, !wiener && masks16_wanted(e, sw));
+}
+
+int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
+{
+    if (!e) return fail(-1, "srtSeparateBatch: null engine");
+    DeviceScope ds(e->device);
+    BatchCall bc;
+    int rc = batch_forward(e, "srtSeparateBatch", ntracks, d_L, d_R, n, d_out, 0, &bc);
     if (rc) return rc;
+    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
     SrtIstftParams q; memset(&q, 0, sizeof q);
-    q.spec = e->spec; q.spec_ch_stride = ch_stride; q.frames = (int)(total * T);
-    q.masks = e->masks; q.masks16 = e->last.masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)total; q.T = T; q.F = F;
+    q.spec = e->spec; q.spec_ch_stride = bc.ch_stride; q.frames = (int)(bc.total * T);
+    q.masks = e->masks; q.masks16 = e->last.masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)bc.total; q.T = T; q.F = F;
     for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
     q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
     q.tab = tables_of(e);
@@ -1311,7 +1358,45 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
         q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
     }
     TimerScope ts(e, "istft_batch");
-    if (srt_launch_istft_batch(q, e->btab, ntracks, g, e->stream)) return fail(-2, "batched istft launch failed");
+    if (srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream)) return fail(-2, "batched istft launch failed");
+    return 0;
+}
+
+// srtSeparateBatch with the Wiener filter per track: the shared front (fp32 masks), `iterations` x (statistics + finalize) and the filter over the packed rows
+// with every track's own window, a and tables (srt_wiener.hip), then ONE batched inverse of the per-stem filtered spectra
+int srtSeparateBatchWiener(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int iterations)
+{
+    static const char* const who = "srtSeparateBatchWiener";
+    if (!e) return fail(-1, "srtSeparateBatchWiener: null engine");
+    DeviceScope ds(e->device);
+    if (iterations < 1 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtSeparateBatchWiener: iterations must be 1..3");
+    if (e->cfg.ratio_mask) return fail(-1, "srtSeparateBatchWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
+    if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, who);
+    BatchCall bc;
+    const int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, iterations, &bc);
+    if (rc) return rc;
+    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
+    const size_t cap = (size_t)e->cfg.max_tiles, tf = batch_wiener_track_floats(e);
+    SrtWienerParams w; memset(&w, 0, sizeof w);
+    w.spec = e->spec; w.spec_ch_stride = bc.ch_stride; w.rows = (int)(bc.total * T);
+    w.masks = e->masks; w.nstems = S; w.ntiles = (int)bc.total; w.T = T; w.F = F;
+    w.nchunks = bc.wchunks;
+    w.slab = e->bwslab; w.slab_max = e->bwslab + batch_wiener_chunk_cap(e) * S * 4 * F;
+    w.rtab = e->bwtabf; w.wsum = e->bwtabf + cap * tf * 4; w.scal = w.wsum + cap * tf;
+    w.out = e->wspec; w.out_stem = 2 * bc.ch_stride;
+    for (int pass = 1; pass <= iterations; ++pass) {
+        { TimerScope ts(e, "wiener_stats_batch"); if (srt_launch_wiener_stats_batch(w, e->btab, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener statistics launch failed"); }
+        { TimerScope ts(e, "wiener_cov_batch"); if (srt_launch_wiener_finalize_batch(w, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener finalize launch failed"); }
+    }
+    { TimerScope ts(e, "wiener_filter_batch"); if (srt_launch_wiener_filter_batch(w, e->btab, e->bwtab, ntracks, iterations, e->stream)) return fail(-2, "batched Wiener filter launch failed"); }
+    e->last.wiener_last = iterations; e->last.wiener_tracks = ntracks;
+    SrtIstftParams q; memset(&q, 0, sizeof q);
+    q.spec = e->wspec; q.spec_ch_stride = bc.ch_stride; q.frames = (int)(bc.total * T);
+    q.nstems = S; q.ntiles = (int)bc.total; q.T = T; q.F = F;
+    for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
+    q.tab = tables_of(e);
+    TimerScope ts(e, "istft_batch");
+    if (srt_launch_istft_batch_spec(q, w.out_stem, e->btab, ntracks, bc.g, e->stream)) return fail(-2, "batched istft launch failed");
     return 0;
 }
 
@@ -1458,16 +1543,20 @@ int srtCopyTensor(srt_engine* e, const char* name, int stem, int tile, float* h_
     if (!e || !name || !h_dst) return fail(-1, "srtCopyTensor: null argument");
     DeviceScope ds(e->device);
     if (!name[0]) return fail(-1, "srtCopyTensor: empty tensor name");
-    if (!strcmp(name, "wiener_cov")) {                                       // R_j of iteration `tile` [F][4], its weight sums [F], a [1]
-        const int S = e->cfg.n_stems, F = e->cfg.F, it = tile;
-        if (!e->wtab || stem < 0 || stem >= S || it < 1 || it > e->last.wiener_last) return fail(-1, "srtCopyTensor: wiener_cov needs a stem and 1 <= iteration <= the iterations of the last filtered call");
+    if (!strcmp(name, "wiener_cov")) {                                       // R_j of one iteration [F][4], its weight sums [F], a [1]; tile = 4 * track + iteration
+        const int S = e->cfg.n_stems, F = e->cfg.F, trk = tile < 0 ? -1 : tile / 4, it = tile < 0 ? 0 : tile % 4, K = e->last.wiener_tracks;     // (track 0 of a single-signal call: tile = iteration)
+        const float* tab = K ? e->bwtabf : e->wtab;
+        if (!tab || stem < 0 || stem >= S || it < 1 || it > e->last.wiener_last || trk < 0 || trk >= (K ? K : 1))
+            return fail(-1, "srtCopyTensor: wiener_cov needs a stem and 1 <= iteration <= the iterations of the last filtered call (after srtSeparateBatchWiener: tile = 4 * track + iteration)");
         if ((size_t)5 * F + 1 > max_floats) return fail(-1, "srtCopyTensor: destination too small");
-        const size_t o = (size_t)(it - 1) * S * F + (size_t)stem * F;
-        const float* wsum = e->wtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4;
+        // slots of [SRT_WIENER_MAX_ITERS][S][F]: one (the call's) in wtab, max_tiles (one per track) in the batch tables
+        const size_t slots = K ? (size_t)e->cfg.max_tiles : 1, per = (size_t)SRT_WIENER_MAX_ITERS * S * F;
+        const size_t o = (size_t)trk * per + (size_t)(it - 1) * S * F + (size_t)stem * F;
+        const float* wsum = tab + slots * per * 4;
         HIPCHK(hipStreamSynchronize(e->stream));
-        HIPCHK(hipMemcpy(h_dst, e->wtab + o * 4, (size_t)F * 4 * sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_dst, tab + o * 4, (size_t)F * 4 * sizeof(float), hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(h_dst + 4 * F, wsum + o, (size_t)F * sizeof(float), hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(h_dst + 5 * F, wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F, sizeof(float), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(h_dst + 5 * F, wsum + slots * per + trk, sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
     if (!strcmp(name, "mask_ext")) {                                         // the gains of bins >= F the last inverse transform applied: [rows][2] of one stem

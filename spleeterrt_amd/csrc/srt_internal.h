@@ -288,6 +288,20 @@ struct SrtWienerParams {
 int srt_launch_wiener_stats(const SrtWienerParams& p, int pass, hipStream_t s);      // pass 1..n: statistics of the estimates after pass - 1 iterations
 int srt_launch_wiener_finalize(const SrtWienerParams& p, int pass, hipStream_t s);   // R tables of that pass (and a, pass 1)
 int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s);    // W_j x after `iters` iterations for every stem; bins >= F copied
+// The filter per track of a packed batch (srtSeparateBatchWiener): a second device table beside SrtBatchTrack's, one row per track - the track's row chunks of
+// the statistics pass (wiener_issue's rule on the track's own rows) as a run [chunk0, chunk0 + nchunks) of the call's global chunk numbering.
+struct SrtBatchWiener { int chunk0, nchunks, rpc, tab; };     // tab: the track's slot in the per-track tables (its index in the call)
+int srt_batch_wiener_geometry(const SrtBatchTrack* t, SrtBatchWiener* w, int ntracks);      // host: fills every row; returns the call's chunk total
+// p on the packed buffers: spec / spec_ch_stride / masks as the batched transforms see them, ntiles = the packed tile count (the masks' stem stride), rows =
+// ntiles * T, nchunks = the call's chunk total (rpc unused); slab [nchunks][nstems][4][F], slab_max [nchunks][SRT_WIENER_BINBLK]; rtab / wsum / scal: slot 0 of
+// the per-track tables [slots][SRT_WIENER_MAX_ITERS][nstems][F][4] / [slots][SRT_WIENER_MAX_ITERS][nstems][F] / [slots]; out: [nstems][2][rows][SRT_SPEC_LD].
+// A track's statistics cover its own rows [0, rows_k) only, so its tables are those of the single-signal launches on it alone, bit for bit.
+int srt_launch_wiener_stats_batch(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int pass, hipStream_t s);
+int srt_launch_wiener_finalize_batch(const SrtWienerParams& p, const SrtBatchWiener* d_wt, int ntracks, int pass, hipStream_t s);
+int srt_launch_wiener_filter_batch(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int iters, hipStream_t s);
+// batched inverse of per-stem spectra (the filter's output): stem s of every track reads p.spec + s * stem_stride (float2 elements) at its packed rows, no masks
+// (all-ones in band, p.oob[s] above F) - srt_launch_istft's single-stem, mask-free form for every (track, stem) in one launch
+int srt_launch_istft_batch_spec(const SrtIstftParams& p, size_t stem_stride, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s);
 struct srt_engine;
 int srt_engine_wiener(const srt_engine* e);                                             // iterations switched on (srtSetWiener), 0: off
 int srt_engine_overlap(const srt_engine* e);                                            // rows consecutive network tiles share (srtSetOverlap), 0: off

@@ -211,3 +211,194 @@ int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s)
     SRT_LAUNCH(srt_wiener_filter_kernel, dim3(SRT_WIENER_BINBLK, (p.rows + W_FILTER_ROWS - 1) / W_FILTER_ROWS), dim3(256), 0, s, p, iters);
     return srt_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------- per track of a packed batch (srtSeparateBatchWiener)
+// The three kernels above with "the call" replaced by "the track": a track's statistics window is its own rows [0, rows_k) - not the rows that pad it to its
+// tile boundary, not another track - its a is the maximum over those rows, and its chunks follow wiener_issue's rule on rows_k.  The per-row arithmetic
+// (w_start / w_iter), the accumulation statements and the order of every sum are the ones above, so track k's R tables, weight sums and a are the
+// single-signal launches' on that track alone, bit for bit, whatever else the batch holds and wherever the track sits in it.
+// Chunks are numbered through the call (track k: [chunk0, chunk0 + nchunks)); slab and slab_max are indexed by that number, the tables by track.
+
+// the track of global chunk c: the last k with chunk0(k) <= c.  c is workgroup-uniform, so every probe is a uniform (scalar) load, as in srt_batch_track
+__device__ __forceinline__ int w_chunk_track(const SrtBatchWiener* __restrict__ w, int ntracks, int c)
+{
+    int lo = 0, hi = ntracks - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (w[mid].chunk0 <= c) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// the track of packed tile `tile`: the last k with tile0(k) <= tile
+__device__ __forceinline__ int w_tile_track(const SrtBatchTrack* __restrict__ t, int ntracks, int tile)
+{
+    int lo = 0, hi = ntracks - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (t[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) srt_wiener_stats_batch_kernel(const SrtWienerParams p, const SrtBatchTrack* __restrict__ tracks,
+                                                                     const SrtBatchWiener* __restrict__ wt, int ntracks, int pass)
+{
+    __shared__ float red[4];
+    const int k = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, S = p.nstems;
+    const int trk = w_chunk_track(wt, ntracks, c);
+    const SrtBatchWiener g = wt[trk];
+    const int rows = tracks[trk].rows, tile0 = tracks[trk].tile0;
+    const int r0 = (c - g.chunk0) * g.rpc, r1 = min(r0 + g.rpc, rows);           // rows of the TRACK
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const float* scal = p.scal + g.tab;
+    const float4* rtab = reinterpret_cast<const float4*>(p.rtab) + (size_t)g.tab * SRT_WIENER_MAX_ITERS * S * p.F;
+    const float al = (pass > 1 ? scal[0] : 1.0f) * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F, anyb = k < SRT_HALF;
+    const float2* sLp = p.spec + (size_t)tile0 * p.T * SRT_SPEC_LD + (anyb ? k : 0);       // the track's first packed row
+    const float2* sRp = sLp + p.spec_ch_stride;
+    const float* masks = p.masks + (size_t)tile0 * 2 * tf;                                 // ... and first packed tile
+    float acc[SRT_MAX_STEMS][4];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
+    float mx = 0.0f;
+    if (anyb) {
+        for (int t = r0; t < r1; ++t) {
+            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD];
+            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y)));
+            if (!inb) continue;
+            const float* m = masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;
+            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+            w_start(yl, yr, sL, sR, m, sstride, tf, S);
+            for (int i = 0; i < pass - 1; ++i)
+                w_iter(yl, yr, sL, sR, rtab + (size_t)i * S * p.F + k, p.F, delta, S);
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y;
+                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y;
+                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      // y_L conj(y_R)
+                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y;
+            }
+        }
+    }
+    if (inb) {
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k] = acc[j][q];
+    }
+    if (pass == 1) {                                             // (block-uniform branch: every thread reaches the barriers)
+        mx = w_block_max(mx, red);
+        if (threadIdx.x == 0) p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] = mx;
+    }
+}
+
+// grid (ceil(S F / 256), ntracks): blockIdx.y is the track
+__global__ void __launch_bounds__(256) srt_wiener_finalize_batch_kernel(const SrtWienerParams p, const SrtBatchWiener* __restrict__ wt, int pass)
+{
+    __shared__ float red[4];
+    const int S = p.nstems;
+    const SrtBatchWiener g = wt[blockIdx.y];
+    float* scal = p.scal + g.tab;
+    float a;
+    if (pass == 1) {                                             // every block of a track reduces the track's maxima: the same a everywhere
+        float mx = 0.0f;
+        const float* smax = p.slab_max + (size_t)g.chunk0 * SRT_WIENER_BINBLK;
+        for (int i = threadIdx.x; i < g.nchunks * SRT_WIENER_BINBLK; i += 256) mx = fmaxf(mx, smax[i]);
+        mx = w_block_max(mx, red);
+        a = fmaxf(1.0f, mx * 4096.0f / 10.0f);
+        if (blockIdx.x == 0 && threadIdx.x == 0) scal[0] = a;
+    } else a = scal[0];
+    const int idx = blockIdx.x * 256 + threadIdx.x;              // j * F + k
+    if (idx >= S * p.F) return;
+    const int j = idx / p.F, k = idx - j * p.F;
+    float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+    for (int c = g.chunk0; c < g.chunk0 + g.nchunks; ++c) {      // the track's chunks in chunk order: the same sums every call
+        const float* q = p.slab + (((size_t)c * S + j) * 4) * p.F + k;
+        s0 += q[0]; s1 += q[p.F]; s2 += q[2 * (size_t)p.F]; s3 += q[3 * (size_t)p.F];
+    }
+    const float al = a * (1.0f / 4096.0f);
+    const float w = 0.5f * (s0 + s1);
+    const float inv = 1.0f / (W_EPS * al * al + w);
+    const size_t o = ((size_t)g.tab * SRT_WIENER_MAX_ITERS + (pass - 1)) * S * p.F + idx;
+    reinterpret_cast<float4*>(p.rtab)[o] = make_float4(s0 * inv, s1 * inv, s2 * inv, s3 * inv);
+    p.wsum[o] = w;
+}
+
+// blocks of W_FILTER_ROWS packed rows: T is a multiple of 64, so a block lies in one tile, hence in one track; rows at or past the track's own are skipped
+// (the batched inverse never reads them)
+__global__ void __launch_bounds__(256) srt_wiener_filter_batch_kernel(const SrtWienerParams p, const SrtBatchTrack* __restrict__ tracks,
+                                                                      const SrtBatchWiener* __restrict__ wt, int ntracks, int iters)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x, S = p.nstems;
+    if (k >= SRT_HALF) return;
+    const int r0 = blockIdx.y * W_FILTER_ROWS;                                   // packed rows
+    const int trk = w_tile_track(tracks, ntracks, r0 / p.T);
+    const int tab = wt[trk].tab;
+    const int r1 = min(r0 + W_FILTER_ROWS, tracks[trk].tile0 * p.T + tracks[trk].rows);
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf, och = p.out_stem / 2;
+    const float4* rtab = reinterpret_cast<const float4*>(p.rtab) + (size_t)tab * SRT_WIENER_MAX_ITERS * S * p.F;
+    const float al = p.scal[tab] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F;
+    for (int t = r0; t < r1; ++t) {
+        const size_t o = (size_t)t * SRT_SPEC_LD + k;
+        const float2 sL = p.spec[o], sR = p.spec[p.spec_ch_stride + o];
+        if (!inb) {                                              // bins >= F: the input spectrum (oob_weight is applied by the inverse transform)
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j)
+                if (j < S) { p.out[j * p.out_stem + o] = sL; p.out[j * p.out_stem + och + o] = sR; }
+            continue;
+        }
+        const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;      // packed tile = the track's first + the tile within it
+        float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+        w_start(yl, yr, sL, sR, m, sstride, tf, S);
+        for (int i = 0; i < iters; ++i)
+            w_iter(yl, yr, sL, sR, rtab + (size_t)i * S * p.F + k, p.F, delta, S);
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S) { p.out[j * p.out_stem + o] = yl[j]; p.out[j * p.out_stem + och + o] = yr[j]; }
+    }
+}
+
+int srt_batch_wiener_geometry(const SrtBatchTrack* t, SrtBatchWiener* w, int ntracks)
+{
+    long c = 0;
+    for (int k = 0; k < ntracks; ++k) {
+        const int rows = t[k].rows;
+        if (rows < 1) return -1;
+        int nch = (rows + 15) / 16; if (nch > SRT_WIENER_MAX_CHUNKS) nch = SRT_WIENER_MAX_CHUNKS;     // wiener_issue's rule on the track's rows
+        w[k].rpc = (rows + nch - 1) / nch; w[k].nchunks = (rows + w[k].rpc - 1) / w[k].rpc;
+        w[k].chunk0 = (int)c; w[k].tab = k;
+        c += w[k].nchunks;
+        if (c > 65535) return -1;                                // the statistics grid's y extent
+    }
+    return (int)c;
+}
+
+static bool w_batch_args_ok(const SrtWienerParams& p, int ntracks)
+{
+    return ntracks >= 1 && ntracks <= p.ntiles && p.nstems >= 1 && p.nstems <= SRT_MAX_STEMS && p.F >= 1 && p.F <= SRT_HALF - 1 && p.T >= W_FILTER_ROWS &&
+           p.T % W_FILTER_ROWS == 0 && p.rows == p.ntiles * p.T && p.nchunks >= ntracks && p.nchunks <= 65535;
+}
+
+int srt_launch_wiener_stats_batch(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || !w_batch_args_ok(p, ntracks)) return -1;
+    const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
+    SRT_LAUNCH(srt_wiener_stats_batch_kernel, dim3(bx, p.nchunks), dim3(256), 0, s, p, d_tracks, d_wt, ntracks, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_finalize_batch(const SrtWienerParams& p, const SrtBatchWiener* d_wt, int ntracks, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || !w_batch_args_ok(p, ntracks) || ntracks > 65535) return -1;
+    SRT_LAUNCH(srt_wiener_finalize_batch_kernel, dim3((p.nstems * p.F + 255) / 256, ntracks), dim3(256), 0, s, p, d_wt, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_filter_batch(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int iters, hipStream_t s)
+{
+    if (iters < 1 || iters > SRT_WIENER_MAX_ITERS || !w_batch_args_ok(p, ntracks) || p.rows / W_FILTER_ROWS > 65535 || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD) return -1;
+    SRT_LAUNCH(srt_wiener_filter_batch_kernel, dim3(SRT_WIENER_BINBLK, p.rows / W_FILTER_ROWS), dim3(256), 0, s, p, d_tracks, d_wt, ntracks, iters);
+    return srt_launch_status();
+}
