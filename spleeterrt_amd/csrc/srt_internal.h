@@ -64,7 +64,8 @@ enum { SRT_ACT_LEAKY = 0, SRT_ACT_RELU = 1, SRT_ACT_ELU = 2 };
     X(c8_wgs,    "SPLEETERRT_C8_WGS",    0,  INT)           /* workgroups per C8 launch, overrides the table and the measurement; 0: those */ \
     X(c8_nr2,    "SPLEETERRT_C8_NR2",    1,  INT)           /* bit 0: two sub-tiles per wave in up2..up4; 0: one everywhere */ \
     X(c8_wres,   "SPLEETERRT_C8_WRES",   1,  INT)           /* the weight slab stays in LDS where a unit is one K chunk; 0: moved every step */ \
-    X(c8_tune,   "SPLEETERRT_C8_TUNE",   1,  INT)           /* the first launch of a C8 layer shape measures its workgroup count; 0: table values, 2: and print the choice */
+    X(c8_tune,   "SPLEETERRT_C8_TUNE",   1,  INT)           /* the first launch of a C8 layer shape measures its workgroup count; 0: table values, 2: and print the choice */ \
+    X(wino_ph,   "SPLEETERRT_WINO_PH",   7,  INT)           /* fp32 Winograd decoder (srt_nn4.hip), barrier phase offset per layer group: bit 0 up1, bit 1 up2..up4, bit 2 up5; 0: every wave meets the barrier at quad 0 */
 enum { SRT_SW_FLAG, SRT_SW_INT, SRT_SW_INT_NONEMPTY };
 #define SRT_SW_FIELD(field, name, dflt, rule) int field;
 struct SrtSwitches { SRT_SWITCH_TABLE(SRT_SW_FIELD) };
@@ -177,7 +178,7 @@ void srt_fp16_expand(const uint16_t* d_in, float* d_out, size_t n, hipStream_t s
 // Winograd decoder kernels (srt_nn4.hip): U = transformed weights [Cin/4][Cout/16][4][16][52] per stem; the launcher returns 1
 // when the layer is not covered.  srt_wino_mask(): bit i set = up(i+1) runs this form (large batches, fp32 MFMA path).
 int  srt_launch_pack_wino(const float* w, float* u, int Cin, int Cout, hipStream_t s);
-int  srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, hipStream_t s);
+int  srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, const SrtSwitches& sw, hipStream_t s);
 // encoder layers in Winograd form (srt_nn4.hip, srt_enc_wino32): U from the OIHW weights; the layer reads act(BN(raw)) of its input (srcA) and
 int srt_enc_producer_copy();          // tuning builds: SRT_TUNE=...,enccopy=0 keeps the separate bn+act pass in front of the first Winograd-form encoder layer
 // writes raw (outRaw) + optionally its own act(BN(.)) copy (outAct with bnScale / bnShift).  srt_enc_wino_covers: geometry test of the launcher.

@@ -38,7 +38,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define WINO_C00 40                // class (0, 0): 3 x 3
 
 // ------------------------------------------------------------------------------------------- weight transform
-// 1-D: p = 1 taps (k = 4, 2, 0) -> [g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2];  p = 0 taps (k = 3, 1) -> [g0, g0+g1, g1]
+// 1-D: p = 1 taps (k = 4, 2, 0) -> [g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2];  p = 0 taps (k = 3, 1) -> [g0, (g0+g1)/2, (g0-g1)/2]: F(2,2) on the evaluation
+// points 0, +1, -1, i.e. F(2,3) with a zero third tap and its last point (which that tap alone feeds) dropped.  Its input transform is then the first three
+// values of F(2,3)'s, so the transformed patch of a 2-tap class is a subset of the 3-tap class's over the same block (srt_dec_wino computes it once).
+// The encoder's classes read different pixels, nothing is shared there: ENC keeps F(2,2) on the points 0, 1, infinity: [g0, g0+g1, g1].
 // ENC: the taps in ascending order (stride-2 convolution of the encoder: odd input plane k = 0, 2, 4, even plane k = 1, 3) instead of the
 // transposed convolution's descending one
 template <bool ENC = false>
@@ -50,7 +53,8 @@ __device__ __forceinline__ int wino_w1d(int p, const float* g, int stride, float
         return 4;
     }
     const float g0 = g[(ENC ? 1 : 3) * stride], g1 = g[(ENC ? 3 : 1) * stride];
-    o[0] = g0; o[1] = g0 + g1; o[2] = g1;
+    if (ENC) { o[0] = g0; o[1] = g0 + g1; o[2] = g1; }
+    else { o[0] = g0; o[1] = 0.5f * (g0 + g1); o[2] = 0.5f * (g0 - g1); }
     return 3;
 }
 // ENC: w is the encoder's OIHW [Cout][Cin][5][5]; otherwise the decoder's [Cin][Cout][5][5].  Same packed layout either way.
@@ -103,45 +107,55 @@ int srt_launch_pack_wino_enc(const float* w, float* u, int Cin, int Cout, hipStr
 }
 
 // ------------------------------------------------------------------------------------------- transforms (registers)
-// input: B3 = [d0-d2, d1+d2, d2-d1, d1-d3] (4 points), B2 = [d0-d1, d1, d1-d2] (3 points, d3 unused)
+// input: B3 = [d0-d2, d1+d2, d2-d1, d1-d3] (4 points), B2 = the first three of them (d3 unused); ENC: B2 = [d0-d1, d1, d1-d2]
 __device__ __forceinline__ void wino_in3(float d0, float d1, float d2, float d3, float* o) { o[0] = d0 - d2; o[1] = d1 + d2; o[2] = d2 - d1; o[3] = d1 - d3; }
 // (the middle point is d1 itself; it gets its own register - an opaque v_mov - so that the loaded patch registers die with the row
 //  transforms and the next patch can be loaded straight into them: otherwise the value lives on as t2[r][1] until the last quad, the
 //  loads land elsewhere and a copy at the loop end waits for them)
-__device__ __forceinline__ void wino_in2(float d0, float d1, float d2, float* o)
+template <bool ENC = false> __device__ __forceinline__ void wino_in2(float d0, float d1, float d2, float* o)
 {
-    float c; asm("v_mov_b32 %0, %1" : "=v"(c) : "v"(d1));
-    o[0] = d0 - d1; o[1] = c; o[2] = d1 - d2;
+    if constexpr (ENC) {
+        float c; asm("v_mov_b32 %0, %1" : "=v"(c) : "v"(d1));
+        o[0] = d0 - d1; o[1] = c; o[2] = d1 - d2;
+    } else { o[0] = d0 - d2; o[1] = d1 + d2; o[2] = d2 - d1; }
 }
-// output: A3: y0 = m0+m1+m2, y1 = m1-m2-m3;  A2: y0 = m0+m1, y1 = m1-m2
-template <int N> __device__ __forceinline__ void wino_out1d(const float* m, int stride, float& y0, float& y1)
+// output: A3: y0 = m0+m1+m2, y1 = m1-m2-m3;  A2: y0 = m0+m1+m2, y1 = m1-m2;  ENC: A2: y0 = m0+m1, y1 = m1-m2
+template <int N, bool ENC = false> __device__ __forceinline__ void wino_out1d(const float* m, int stride, float& y0, float& y1)
 {
     if (N == 4) { y0 = (m[0] + m[stride]) + m[2 * stride]; y1 = (m[stride] - m[2 * stride]) - m[3 * stride]; }
-    else { y0 = m[0] + m[stride]; y1 = m[stride] - m[2 * stride]; }
+    else if (ENC) { y0 = m[0] + m[stride]; y1 = m[stride] - m[2 * stride]; }
+    else { y0 = (m[0] + m[stride]) + m[2 * stride]; y1 = m[stride] - m[2 * stride]; }
 }
-template <int NY, int NX> __device__ __forceinline__ void wino_out2d(const float* m, float (&y)[2][2])      // m[NY][NX]
+template <int NY, int NX, bool ENC = false> __device__ __forceinline__ void wino_out2d(const float* m, float (&y)[2][2])      // m[NY][NX]
 {
     float z[4][2];
 #pragma unroll
-    for (int i = 0; i < NY; ++i) wino_out1d<NX>(m + i * NX, 1, z[i][0], z[i][1]);
+    for (int i = 0; i < NY; ++i) wino_out1d<NX, ENC>(m + i * NX, 1, z[i][0], z[i][1]);
 #pragma unroll
     for (int d = 0; d < 2; ++d) {
         const float c[4] = { z[0][d], z[1][d], z[2][d], NY == 4 ? z[3][d] : 0.0f };
-        wino_out1d<NY>(c, 1, y[0][d], y[1][d]);
+        wino_out1d<NY, ENC>(c, 1, y[0][d], y[1][d]);
     }
 }
 
 // transform point X (compile-time) of the next K step from the row-transformed patch: class-major, then [i][j] inside the class
-template <int X> __device__ __forceinline__ float wino_point(const float (&t3)[4][4], const float (&t2)[4][3])
+template <int X, bool ENC = false> __device__ __forceinline__ float wino_point(const float (&t3)[4][4], const float (&t2)[4][3])
 {
     constexpr int cls = X < WINO_C10 ? 0 : X < WINO_C01 ? 1 : X < WINO_C00 ? 2 : 3;
     constexpr int e = X - (cls == 0 ? WINO_C11 : cls == 1 ? WINO_C10 : cls == 2 ? WINO_C01 : WINO_C00);
     constexpr bool y3 = cls < 2, x3 = !(cls & 1);                            // 3-tap (4-point) transform along y / x
     constexpr int nx = x3 ? 4 : 3, i = e / nx, j = e % nx;
     auto c = [&](int r) { if constexpr (x3) return t3[r][j]; else return t2[r][j]; };
-    if constexpr (y3) return i == 0 ? c(0) - c(2) : i == 1 ? c(1) + c(2) : i == 2 ? c(2) - c(1) : c(1) - c(3);
-    else return i == 0 ? c(0) - c(1) : i == 1 ? c(1) : c(1) - c(2);      // (patch row 3 is not used by the even output rows)
+    if constexpr (y3 || !ENC) return i == 0 ? c(0) - c(2) : i == 1 ? c(1) + c(2) : i == 2 ? c(2) - c(1) : c(1) - c(3);      // (a 2-tap class stops at i = 2: patch row 3 is not used by the even output rows)
+    else return i == 0 ? c(0) - c(1) : i == 1 ? c(1) : c(1) - c(2);
 }
+// point I of the y transform of column J of the row-transformed patch (3-tap rows): value (I, J) of a class with 4 points along x, and of the one with 3 for J < 3
+template <int I, int J> __device__ __forceinline__ float wino_vpoint(const float (&t3)[4][4])
+{
+    return I == 0 ? t3[0][J] - t3[2][J] : I == 1 ? t3[1][J] + t3[2][J] : I == 2 ? t3[2][J] - t3[1][J] : t3[1][J] - t3[3][J];
+}
+template <int I> __device__ __forceinline__ float wino_f4(const float4 (&b)[3]) { constexpr int w = I / 4, c = I % 4; return c == 0 ? b[w].x : c == 1 ? b[w].y : c == 2 ? b[w].z : b[w].w; }
+
 // C operand of a K step's MFMAs: the accumulator, or - first K step of a unit - the constant 0 (an inline operand: the unit's accumulators are never
 // zeroed with 64-128 v_mov per wave; same bits, 0 + a b either way)
 template <bool FIRST> __device__ __forceinline__ f32x4 wino_c(const f32x4& acc) { if constexpr (FIRST) return f32x4{0.0f, 0.0f, 0.0f, 0.0f}; else return acc; }
@@ -196,15 +210,23 @@ constexpr int wino_vmcnt(int n) { return 0x0F70 | (n & 15) | ((n >> 4) << 14); }
 // issued UR - 1 steps before the step that reads it (UR = 3 was the round-2 kernel).
 // CS 1: the units of a workgroup run as ONE stream of K steps (see srt_dec_wino32): no per-unit DMA drain, barrier or separate first transform.
 // RB 1 (round 5): conflict-free patch reads - channel pitch padded to 32 mod 64 floats, a row read as three aligned b64 pairs (see srt_dec_wino32)
-template <int BA, int BB, int NI, int ABL = 0, int UR = 3, int SB = 0, int CS = 0, int RB = 1>   // SB 1: a quad's VALU work fenced behind its MFMAs (see srt_dec_wino32); ABL (SRT_TUNING builds): timing ablations with wrong results - 1 no barrier, 2 no patch DMA, 3 no U DMA, 4 no transform, 5 no A reads
+// D: the lead of both rings in K steps (step k issues U slab k+D and patch k+1+D); UR - 1, the full ring, unless given.
+// PH q > 0: barrier phase offset as in srt_dec_wino32 (its comment has the derivation): the waves of row parity 1 (waves 4-7, four groups per step) execute the
+// step's s_waitcnt + barrier in front of their group q.  Needs D <= UR - 2.  Derived for separate units (CS 0) only: a unit ends with a barrier behind the K loop,
+// which every wave reaches after its last step, and starts with vmcnt(0) + barrier, at which slabs 0..D-1 and patches 0..D-1 are complete - what waves 4-7 read
+// ahead of the rendezvous of steps 0 and 1 (D = 3); patch D, issued behind that barrier, is older than everything the wait of step 1 leaves in flight.
+constexpr int WINO16_QU = 1, WINO16_QP = 2;                                  // the groups that issue a wave's two U pieces / its PPW patch pieces of a K step
+constexpr int wino16_early_pieces(int ppw, int qb) { return (WINO16_QU < qb ? 2 : 0) + (WINO16_QP < qb ? ppw : 0); }      // pieces of a K step issued in groups < qb
+template <int BA, int BB, int NI, int ABL = 0, int UR = 3, int SB = 0, int CS = 0, int RB = 1, int D = UR - 1, int PH = 0>   // SB 1: a quad's VALU work fenced behind its MFMAs (see srt_dec_wino32); ABL (SRT_TUNING builds): timing ablations with wrong results - 1 no barrier, 2 no patch DMA, 3 no U DMA, 4 no transform, 5 no A reads
 __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, const float* __restrict__ U, size_t u_stem, int tpw)
 {
-    static_assert(UR >= 3 && UR <= 6, "ring depth");
+    static_assert(UR >= 3 && UR <= 6 && D >= 2 && D <= UR - 1, "ring depth / lead");
+    static_assert(PH == 0 || (PH <= 3 && CS == 0 && UR >= D + 2), "phase offset: a piece issued in step k must not land in what a wave still in step k-1 reads");
     static_assert(BA * BB * NI == 64 && (BA * BB) % 16 == 0, "tile");
     constexpr int UBUF = 4 * 16 * WINO_LD;                                   // 3328 floats = 13 KiB = 13 DMA pieces
     constexpr int TH = 2 * BA, TW = 2 * BB;
-    constexpr int PH = TH + 2, PROW = TW + 8, PR4 = PROW / 4;                // patch: PH rows of PROW floats per (channel, instance)
-    constexpr int PCH0 = NI * PH * PROW;                                     // floats of one channel's patch
+    constexpr int PRH = TH + 2, PROW = TW + 8, PR4 = PROW / 4;                // patch: PRH rows of PROW floats per (channel, instance)
+    constexpr int PCH0 = NI * PRH * PROW;                                     // floats of one channel's patch
     constexpr int PCH = RB ? (PCH0 + 31) / 64 * 64 + 32 : PCH0;              // channel pitch in LDS (RB: the smallest value >= PCH0 that is 32 mod 64)
     constexpr int NF4 = PCH, NPP = (NF4 + 63) / 64, PBUF = NPP * 256;        // float4s (4 channels), DMA pieces and floats per patch buffer
     constexpr int PPW = (NPP + 7) / 8;                                       // patch pieces per wave
@@ -249,7 +271,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
         const unsigned dst = dm0[i] + (unsigned)buf * (unsigned)(UBUF * 4);
         asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(dvoff[i]), "s"(src), "s"(dst) : "memory");
     };
-    // ---- patch DMA: float4 e = ((c * NI + il) * PH + row) * PR4 + j of the patch buffer <- channel 4k+c, instance tile0+il,
+    // ---- patch DMA: float4 e = ((c * NI + il) * PRH + row) * PR4 + j of the patch buffer <- channel 4k+c, instance tile0+il,
     // image row ty0-1+row, columns tx0-4+4j..+3.  Wave w moves pieces w, w+8 (a piece past the last one repeats it).
     constexpr unsigned OOR = 0x80000000u;                                    // >= num_records: lands as zeros
     unsigned pvoff[PPW], pm0[PPW];
@@ -265,7 +287,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
         for (int i = 0; i < PPW; ++i) {
             const int piece = min(wave + 8 * i, NPP - 1), e = piece * 64 + lane;
             const int c = e / (PCH / 4), rem = e % (PCH / 4);                // float4 `rem` of channel c's patch (rem >= PCH0 / 4: padding of the pitch)
-            const int j = rem % PR4, row = (rem / PR4) % PH, ii = rem / (PR4 * PH);
+            const int j = rem % PR4, row = (rem / PR4) % PRH, ii = rem / (PR4 * PRH);
             const int gy = ty0 - 1 + row, gx = tx0 - 4 + 4 * j;
             const bool ok = e < NF4 && rem < PCH0 / 4 && tile0 + ii < p.ntiles && gy >= 0 && gy < p.H && gx >= 0 && gx + 3 < p.W;
             pvoff[i] = ok ? 4u * (unsigned)((size_t)ii * p.srcA_tile + (size_t)c * hw + (size_t)gy * p.W + gx) : OOR;  // srcA_tile == srcB_tile (launcher)
@@ -305,7 +327,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
         const unsigned dst = pm0[i] + (unsigned)slot * (unsigned)(PBUF * 4);
         asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" :: "v"(pvoff[i]), "s"(rs), "s"(dst), "s"(soff) : "memory");
     };
-    const int poff = kq * PCH + (il * PH + 2 * ba) * PROW + 2 * bb + 3;      // this lane's patch: rows +0..3, columns +0..3 (b0-1..b0+2)
+    const int poff = kq * PCH + (il * PRH + 2 * ba) * PROW + 2 * bb + 3;      // this lane's patch: rows +0..3, columns +0..3 (b0-1..b0+2)
     const int aoff = (kq * 16 + l15) * WINO_LD;
     const int nk = p.Cin / 4;
     const int Wo = p.W << 1;
@@ -328,10 +350,12 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
     // ---- everything below is specialised on the wave's row parity H (a wave-uniform branch; both paths run the same barriers)
     auto body = [&](auto hc) {
         constexpr int H = decltype(hc)::value;
-        constexpr int X0 = H ? 0 : 28, NP = H ? 28 : 21, NQ = H ? 7 : 6, NROW = H ? 4 : 3;   // points xi = X0 .. X0+NP-1; patch rows used
+        constexpr int X0 = H ? 0 : 28, NP = H ? 28 : 21, NY = H ? 4 : 3, NV = 4 * NY, NQ = NY, NROW = H ? 4 : 3;   // points xi = X0 .. X0+NP-1; patch rows used
         f32x4 acc[NP];
-        // the transform in two stages: rows (x direction) of the patch -> t3 / t2, then one transform point at a time
-        float t3[4][4], t2[4][3];
+        // The wave's two classes share their transformed patch: value (i, j) of class (H, 0) - 3 points along x - IS value (i, j) of class (H, 1) (wino_w1d), so
+        // only the NV = 4 NY values of class (H, 1) are computed and kept, and the MFMAs of class (H, 0) read the same registers.
+        // The transform in two stages: rows (x direction) of the patch -> t3, then one transform point at a time.
+        float t3[4][4];
         float2 xm[4], xo[4];                                                 // patch row r: columns (b0, b0+1) | (b0-1, b0+2)
         auto read_row = [&](const float* pbuf, int r) {
             const float* q = pbuf + poff + r * PROW;
@@ -339,18 +363,24 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
             if constexpr (RB) xo[r] = make_float2(reinterpret_cast<const float2*>(q - 1)->y, reinterpret_cast<const float2*>(q + 3)->x);
             else xo[r] = make_float2(q[0], q[3]);
         };
-        auto rows = [&](int r) {
-            wino_in3(xo[r].x, xm[r].x, xm[r].y, xo[r].y, t3[r]);
-            wino_in2(xo[r].x, xm[r].x, xm[r].y, t2[r]);
+        auto rows = [&](int r) { wino_in3(xo[r].x, xm[r].x, xm[r].y, xo[r].y, t3[r]); };
+        // K step k, in groups q = 0..NQ-1 of 7 MFMAs: row q of V (4 values) against the 4 points (q, .) of class (H, 1) and the 3 points (q, .) of class (H, 0),
+        // so both readers of a register have issued before its refill.  ONE GROUP LATER the row is refilled with the values of step k+1, computed from the row
+        // transforms of patch k+1 (a VALU write to a register that an MFMA issued just before still reads as its B operand has to wait for it).
+        // Group 0 first refills the last row from the OLD row transforms, then reads its patch (k+1) and transforms the rows.
+        float v[NV];
+        auto refill = [&](auto ic) __attribute__((always_inline)) {       // row I of V from t3
+            constexpr int I = decltype(ic)::value;
+            v[4 * I] = wino_vpoint<I, 0>(t3); v[4 * I + 1] = wino_vpoint<I, 1>(t3); v[4 * I + 2] = wino_vpoint<I, 2>(t3); v[4 * I + 3] = wino_vpoint<I, 3>(t3);
         };
-        // K step k, in MFMA quads q = 0..NQ-1 (4 transform points each; the last quad of H = 0 has one).  Quad q issues its MFMAs on this
-        // step's points; ONE QUAD LATER those registers are refilled with the points of step k+1, computed from the row transforms of
-        // patch k+1 (a VALU write to a register that an MFMA issued just before still reads as its B operand has to wait for it).
-        // Quad 0 first refills the last quad's points from the OLD row transforms, then reads its patch (k+1) and transforms the rows.
-        float v[NP];
-        auto issue_first = [&]() {                                           // U slabs 0..UR-2 -> buffers 0..UR-2; patches 0..UR-2 -> slots 0..UR-2 of the unit set by set_dma_unit
+        // the K step's one s_waitcnt + barrier sits in front of group QB; VMW: what may still be in flight at it - PH 0: this wave's pieces of the last D - 1 steps;
+        // PH: of the last D - 2 steps (U slab k+1 and patch k+2 are complete at the rendezvous of step k) plus, waves 4-7, the pieces of this step issued ahead of group QB
+        constexpr int QB = (PH && H) ? PH : 0;
+        constexpr int VMW = PH ? (D - 2) * (2 + PPW) + wino16_early_pieces(PPW, QB) : (D - 1) * (2 + PPW);
+        static_assert(QB < NQ && VMW >= 0 && VMW < 64, "barrier position / vmcnt range");
+        auto issue_first = [&]() {                                           // U slabs 0..D-1 -> buffers 0..D-1; patches 0..D-1 -> slots 0..D-1 of the unit set by set_dma_unit
 #pragma unroll
-            for (int j = 0; j < UR - 1; ++j) {
+            for (int j = 0; j < D; ++j) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) dma_u(min(j, nk - 1), j, i);
 #pragma unroll
@@ -360,15 +390,15 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
         set_dma_unit(unit0);
         if (CS) { if (tpw > 1) set_dma_next(unit0 + 1); else dma_keep_as_next(); }
         issue_first();
-        int slot = 0;                                                        // k % UR (CS: of the running step count): U slab k is in buffer `slot`, patch k+1 in slot+1; patch k+UR goes to `slot`
+        int slot = 0;                                                        // k % UR (CS: of the running step count): U slab k is in buffer `slot`, patch k+1 in slot+1; slab k+D goes to slot+D, patch k+1+D to slot+1+D
         auto unit_prologue = [&]() __attribute__((always_inline)) {
             __builtin_amdgcn_s_waitcnt(0x0F70);                              // vmcnt(0): the unit's first slab and patches (and whatever the previous unit left in flight)
             __syncthreads();
 #pragma unroll
             for (int r = 0; r < NROW; ++r) { read_row(s_p, r); rows(r); }
-            WinoFor<0, NP>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x>(t3, t2); });
+            WinoFor<0, NY>::run(refill);
 #pragma unroll
-            for (int i = 0; i < PPW; ++i) dma_patch(min(UR - 1, nk - 1), UR - 1, i);
+            for (int i = 0; i < PPW; ++i) dma_patch(min(D, nk - 1), D, i);
             slot = 0;
         };
         if (CS) unit_prologue();
@@ -376,54 +406,61 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
         if (!CS) unit_prologue();
         auto kstep = [&](int k, auto fc) __attribute__((always_inline)) {
             constexpr bool FIRST = decltype(fc)::value;                      // first K step of a unit: C = 0
-            // vmcnt((UR-2)(2 + PPW)): everything older than this wave's pieces of the last UR-2 steps has landed - its pieces of U slab k
-            // and of patch k+1 (both issued in step k+1-UR).  After the barrier so have everyone's, and every wave is done with step k-1:
-            // U buffer (k-1)%UR and patch slot k%UR are free.
-            if (ABL != 1) { __builtin_amdgcn_s_waitcnt(wino_vmcnt((UR - 2) * (2 + PPW))); __syncthreads(); }
+            // PH 0, vmcnt((D-1)(2 + PPW)): everything older than this wave's pieces of the last D-1 steps has landed - its pieces of U slab k
+            // and of patch k+1 (both issued in step k-D).  After the barrier so have everyone's, and every wave is done with step k-1:
+            // U buffer (k-1)%UR and patch slot k%UR are free.  (Waves 4-7 under PH meet it in front of group QB, below.)
+            if (ABL != 1 && QB == 0) { __builtin_amdgcn_s_waitcnt(wino_vmcnt(VMW)); __syncthreads(); }
             // past the end of the unit: CS - the first slabs / patches of the workgroup's next unit (the DMA state switches to it at the first step
             // whose patch belongs to it; U does not depend on the unit); otherwise the last slab / patch again, unused
-            if (CS && k + UR == nk) dma_advance();
-            const int kd = CS ? (k + UR - 1 >= nk ? k + UR - 1 - nk : k + UR - 1) : min(k + UR - 1, nk - 1);
-            const int kp = CS ? (k + UR >= nk ? k + UR - nk : k + UR) : min(k + UR, nk - 1);
-            const int ubn = slot == 0 ? UR - 1 : slot - 1;                   // (k + UR - 1) % UR
+            if (CS && k + 1 + D == nk) dma_advance();
+            const int kd = CS ? (k + D >= nk ? k + D - nk : k + D) : min(k + D, nk - 1);
+            const int kp = CS ? (k + 1 + D >= nk ? k + 1 + D - nk : k + 1 + D) : min(k + 1 + D, nk - 1);
+            const int ubn = slot + D >= UR ? slot + D - UR : slot + D;       // (k + D) % UR
+            const int pbn = ubn == UR - 1 ? 0 : ubn + 1;                     // (k + 1 + D) % UR
             const float* ub = s_u + slot * UBUF + aoff + X0;
             const float* pbuf = s_p + (slot == UR - 1 ? 0 : slot + 1) * PBUF;
+            // A operands: class (H, 1) one float4 per group, read two groups ahead; class (H, 0) its 3 NY points (and, H = 0, the slab's padding) as three float4s, the
+            // second and third read one group ahead of the group that needs them (group q takes floats 3 q .. 3 q + 2)
             float4 a0 = *reinterpret_cast<const float4*>(ub), a1 = *reinterpret_cast<const float4*>(ub + 4);
+            float4 b[3];
+            b[0] = *reinterpret_cast<const float4*>(ub + NV);
+            if constexpr (ABL == 5) b[1] = b[2] = b[0];
             __builtin_amdgcn_sched_barrier(0);
             WinoFor<0, NQ>::run([&](auto qc) {
                 constexpr int q = decltype(qc)::value;
-                constexpr int nm = (4 * q + 4 <= NP) ? 4 : NP - 4 * q;       // MFMAs of this quad
+                if constexpr (QB > 0 && q == QB && ABL != 1) { __builtin_amdgcn_s_waitcnt(wino_vmcnt(VMW)); __syncthreads(); }
                 const float4 a = a0;
                 a0 = a1;
-                if constexpr (q + 2 < NQ && ABL != 5) a1 = *reinterpret_cast<const float4*>(ub + 4 * (q + 2));      // two quads ahead
-                if constexpr (q == 1 && ABL != 3) { dma_u(kd, ubn, 0); dma_u(kd, ubn, 1); }
-                if constexpr (q == 2 && ABL != 2) {
+                if constexpr (q + 2 < NQ && ABL != 5) a1 = *reinterpret_cast<const float4*>(ub + 4 * (q + 2));      // two groups ahead
+                if constexpr (q < 2 && ABL != 5) b[q + 1] = *reinterpret_cast<const float4*>(ub + NV + 4 * (q + 1));
+                if constexpr (q == WINO16_QU && ABL != 3) { dma_u(kd, ubn, 0); dma_u(kd, ubn, 1); }
+                if constexpr (q == WINO16_QP && ABL != 2) {
 #pragma unroll
-                    for (int i = 0; i < PPW; ++i) dma_patch(kp, slot, i);
+                    for (int i = 0; i < PPW; ++i) dma_patch(kp, pbn, i);
                 }
                 acc[4 * q] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, v[4 * q], wino_c<FIRST>(acc[4 * q]), 0, 0, 0);
-                if constexpr (nm > 1) {
-                    acc[4 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, v[4 * q + 1], wino_c<FIRST>(acc[4 * q + 1]), 0, 0, 0);
-                    acc[4 * q + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, v[4 * q + 2], wino_c<FIRST>(acc[4 * q + 2]), 0, 0, 0);
-                    acc[4 * q + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, v[4 * q + 3], wino_c<FIRST>(acc[4 * q + 3]), 0, 0, 0);
-                }
+                acc[4 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, v[4 * q + 1], wino_c<FIRST>(acc[4 * q + 1]), 0, 0, 0);
+                acc[4 * q + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, v[4 * q + 2], wino_c<FIRST>(acc[4 * q + 2]), 0, 0, 0);
+                acc[4 * q + 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, v[4 * q + 3], wino_c<FIRST>(acc[4 * q + 3]), 0, 0, 0);
+                acc[NV + 3 * q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wino_f4<3 * q>(b), v[4 * q], wino_c<FIRST>(acc[NV + 3 * q]), 0, 0, 0);
+                acc[NV + 3 * q + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wino_f4<3 * q + 1>(b), v[4 * q + 1], wino_c<FIRST>(acc[NV + 3 * q + 1]), 0, 0, 0);
+                acc[NV + 3 * q + 2] = __builtin_amdgcn_mfma_f32_16x16x4f32(wino_f4<3 * q + 2>(b), v[4 * q + 2], wino_c<FIRST>(acc[NV + 3 * q + 2]), 0, 0, 0);
                 if constexpr (SB == 1) __builtin_amdgcn_sched_barrier(0);
                 if constexpr (ABL != 4) {
                     if constexpr (q == 0) {
-                        constexpr int l0 = 4 * (NQ - 1);                     // the last quad's points, from the old row transforms
-                        WinoFor<l0, NP>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x>(t3, t2); });
+                        refill(std::integral_constant<int, NQ - 1>{});       // the last row, from the old row transforms
 #pragma unroll
                         for (int r = 0; r < NROW; ++r) read_row(pbuf, r);
-                        // row transforms where the refills first need them (H = 1: quad 1 refills i = 0 of class (1,1): rows 0, 2; quad 2
-                        // i = 1: row 1; quad 4 i = 3: row 3.  H = 0: quad 1 refills i = 0 of class (0,1): rows 0, 1; quad 3 i = 2: row 2)
-                        rows(0); rows(H ? 2 : 1);
+                        // row transforms where the refills first need them: group 1 refills row 0 (patch rows 0, 2), group 2 row 1 (patch rows 1, 2),
+                        // the last row of H = 1 (patch rows 1, 3) waits for the next step's group 0
+                        rows(0); rows(2);
                     } else {
-                        if constexpr (q == 1) rows(H ? 1 : 2);
+                        if constexpr (q == 1) rows(1);
                         if constexpr (q == 2 && H) rows(3);
-                        WinoFor<4 * q - 4, 4 * q>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x>(t3, t2); });
+                        refill(std::integral_constant<int, q - 1>{});
                     }
                 }
-                __builtin_amdgcn_sched_barrier(0);                           // quads stay in order: bounded live ranges, no accumulator copies
+                __builtin_amdgcn_sched_barrier(0);                           // groups stay in order: bounded live ranges, no accumulator copies
             });
             slot = slot == UR - 1 ? 0 : slot + 1;
         };
@@ -506,16 +543,26 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
 // the natural pitch of 240 floats (48 mod 64) the b64 of the middle columns and the two b32 of the outer ones are all 2-way conflicted (12 LDS cycles per row of a
 // 3-tap class).  RB 1 pads the pitch to 32 mod 64 floats (288: one more DMA piece per K step, still four DMA instructions per wave) and reads a row as THREE aligned
 // b64 pairs (columns b0-2..b0-1, b0..b0+1, b0+2..b0+3): within each 32-lane group kq 0 covers one half of the banks and kq 1 the other - 6 cycles, conflict-free.
-template <int BA, int BB, int ABL = 0, int UR = 3, int D = UR - 1, int BPS = 1, int SB = 0, int EA = 0, int ST = 0, int CS = 0, int NI = 1, int PEEL = 0, int RB = 1>   // PEEL 1: a unit's first K step starts from C = 0 instead of zeroed accumulators (measured slower here, faster in srt_dec_wino)
+// PH q > 0: barrier phase offset.  Waves 0-3 keep the step's s_waitcnt + barrier in front of quad 0; waves 4-7 (the second wave of every SIMD) execute it in front
+// of their quad q, so the two waves of a SIMD no longer leave the rendezvous at the same point of the step and wait for their A fragments and patch rows together.
+// Every wave still executes one barrier per K step; the MFMAs of every accumulator and their order are unchanged (bit-identical outputs).  Waves 4-7 then read
+// U slab k and patch k+1 BEFORE the rendezvous of step k, so both must have landed at the rendezvous of step k-1 (issued in step k-D: D - 2 whole steps of this
+// wave's pieces may still be in flight there, plus - waves 4-7 - the pieces of step k-1 issued before quad q: wino32_early_pieces), and a piece issued in step k
+// must not land in what a wave still in step k-1 reads: UR >= D + 2 (slab k+D never shares a buffer with slab k-1, patch k+1+D never a slot with patch k).
+constexpr int wino32_piece_quad(int i, int nq, int dpw) { return i * nq / dpw; }                                    // the quad in which a wave issues its piece i of a K step (the K loop issues by this function)
+constexpr int wino32_early_pieces(int nq, int dpw, int qb) { int n = 0; for (int i = 0; i < dpw; ++i) n += (wino32_piece_quad(i, nq, dpw) < qb) ? 1 : 0; return n; }      // pieces of a K step issued in quads < qb
+static_assert(wino32_early_pieces(3, 4, 0) == 0 && wino32_early_pieces(3, 4, 1) == 2 && wino32_early_pieces(3, 4, 2) == 3 && wino32_early_pieces(3, 4, 3) == 4, "pieces of a 3-quad wave ahead of its barrier");
+template <int BA, int BB, int ABL = 0, int UR = 3, int D = UR - 1, int BPS = 1, int SB = 0, int EA = 0, int ST = 0, int CS = 0, int NI = 1, int PEEL = 0, int RB = 1, int PH = 0>   // PEEL 1: a unit's first K step starts from C = 0 instead of zeroed accumulators (measured slower here, faster in srt_dec_wino)
 __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, const float* __restrict__ U, size_t u_stem, int tpw)
 {
-    static_assert(UR >= 3 && UR <= 5 && D >= BPS + EA && UR >= D + BPS && !(CS && EA), "rings (5 x 30 KiB = 150 KiB of LDS)");
+    static_assert(UR >= 3 && UR <= 5 && D >= BPS + EA && UR >= D + BPS && !(CS && EA), "rings (5 x 31 KiB = 155 KiB of LDS)");
+    static_assert(PH == 0 || (PH <= 2 && BPS == 1 && EA == 0 && CS == 1 && D >= 2 && UR >= D + 2), "phase offset: the high waves run their first PH quads ahead of the rendezvous (derived for the continuous K stream only)");
     static_assert(BA * BB * NI == 32 && (BA * BB) % 16 == 0, "tile");
     constexpr int UB1 = 4 * 16 * WINO_LD;                                    // one M block: 3328 floats = 13 pieces
     constexpr int UBUF = 2 * UB1, NUP = 26;                                  // two M blocks (consecutive in the packed layout)
     constexpr int TH = 2 * BA, TW = 2 * BB;
-    constexpr int PH = TH + 2, PROW = TW + 8, PR4 = PROW / 4;
-    constexpr int PCH0 = NI * PH * PROW;                                     // floats of one channel's patch
+    constexpr int PRH = TH + 2, PROW = TW + 8, PR4 = PROW / 4;               // patch: PRH rows of PROW floats per (channel, instance)
+    constexpr int PCH0 = NI * PRH * PROW;                                    // floats of one channel's patch
     constexpr int PCH = RB ? (PCH0 + 31) / 64 * 64 + 32 : PCH0;              // channel pitch in LDS (RB: the smallest value >= PCH0 that is 32 mod 64)
     constexpr int NF4 = PCH, NPP = (NF4 + 63) / 64, PBUF = NPP * 256;
     constexpr int NPIECE = NUP + NPP, DPW = (NPIECE + 7) / 8;                // DMA pieces per K step, per wave (the tail repeats the last piece)
@@ -588,7 +635,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
         const int tile0 = (unit / nsp) * NI, tx0 = sx_ * TW, ty0 = sy_ * TH;
         const int e = (lpiece - NUP) * 64 + lane;
         const int c = e / (PCH / 4), rem = e % (PCH / 4);                    // float4 `rem` of channel c's patch (rem >= PCH0 / 4: padding of the pitch)
-        const int j = rem % PR4, row = (rem / PR4) % PH, ii = rem / (PR4 * PH);
+        const int j = rem % PR4, row = (rem / PR4) % PRH, ii = rem / (PR4 * PRH);
         const int gy = ty0 - 1 + row, gx = tx0 - 4 + 4 * j;
         const bool ok = e >= 0 && e < NF4 && rem < PCH0 / 4 && tile0 + ii < p.ntiles && gy >= 0 && gy < p.H && gx >= 0 && gx + 3 < p.W;
         const unsigned pvoff = ok ? 4u * (unsigned)((size_t)ii * p.srcA_tile + (size_t)c * hw + (size_t)gy * p.W + gx) : OOR;   // srcA_tile == srcB_tile (launcher)
@@ -621,7 +668,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
         if (i == DPW - 1) dma_flex(ku, ubuf, kp, pslot);
         else dma_u(i, ku, ubuf);
     };
-    const int poff = kq * PCH + (il * PH + 2 * ba) * PROW + 2 * bb + 3;      // this lane's patch: rows +0..3, columns +0..3 (b0-1..b0+2)
+    const int poff = kq * PCH + (il * PRH + 2 * ba) * PROW + 2 * bb + 3;      // this lane's patch: rows +0..3, columns +0..3 (b0-1..b0+2)
     const int aoff = (kq * 16 + l15) * WINO_LD;
     const int nk = p.Cin / 4;
     const int Wo = p.W << 1;
@@ -641,6 +688,11 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
         constexpr int NY = Y3 ? 4 : 3, NX = X3 ? 4 : 3, NP = NY * NX, NQ = (NP + 3) / 4, NROW = Y3 ? 4 : 3;
         constexpr int PY = CLS < 2 ? 1 : 0, PX = X3 ? 1 : 0;
         constexpr int RQ = ((ST == 1 && CLS >= 2) || (ST == 2 && CLS < 2)) ? 0 : 1;                         // quad whose burst carries the row transforms
+        // the K step's one s_waitcnt + barrier sits in front of quad QB: 0, or PH for the second wave of a SIMD (classes C01 / C00 are waves 4-7).  VMW: what may
+        // still be in flight at it (see PH above; PH 0: the pieces of this wave's last D - BPS steps)
+        constexpr int QB = (PH && CLS >= 2) ? PH : 0;
+        constexpr int VMW = PH ? (D - 2) * DPW + wino32_early_pieces(NQ, DPW, QB) : (D - BPS - EA) * DPW;
+        static_assert(QB < NQ && VMW >= 0 && VMW < 64, "barrier position / vmcnt range");
         f32x4 acc[2][NP];
         float t3[4][4], t2[4][3];
         float2 xm[4]; float xa[4], xb[4];                                    // patch row r: columns (b0, b0+1) | b0-1 | b0+2 (3-tap classes only)
@@ -692,6 +744,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
             WinoFor<0, NQ>::run([&](auto qc) {
                 constexpr int q = decltype(qc)::value;
                 constexpr int nm = (4 * q + 4 <= NP) ? 4 : NP - 4 * q;       // points of this quad
+                if constexpr (QB > 0 && q == QB && ABL != 1) { __builtin_amdgcn_s_waitcnt(wino_vmcnt(VMW)); __syncthreads(); }
                 float4 a[2];
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) {
@@ -703,7 +756,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
                 }
                 if constexpr (ABL != 3) {                                    // DMA spread over the quads (NQ is 3 or 4, DPW 4)
 #pragma unroll
-                    for (int i = 0; i < DPW; ++i) if (i * NQ / DPW == q) dma(i, kd, sd, kp, sd1);
+                    for (int i = 0; i < DPW; ++i) if (wino32_piece_quad(i, NQ, DPW) == q) dma(i, kd, sd, kp, sd1);
                 }
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb) {
@@ -769,7 +822,8 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
         auto kgroup = [&](int k, auto fc) __attribute__((always_inline)) {
             // vmcnt((D-BPS) DPW): everything older than the pieces of this wave's last D-BPS steps has landed: U slabs up to k+BPS-1 and patches up
             // to k+BPS (issued in step k+BPS-1-D).  After the barrier so have everyone's, and every wave has finished step k-1.
-            if (ABL != 1) { __builtin_amdgcn_s_waitcnt(wino_vmcnt((D - BPS - EA) * DPW)); __syncthreads(); }
+            // (PH: slab k and patch k+1 had landed one rendezvous earlier, and waves 4-7 meet this one in front of their quad QB, inside kstep)
+            if (ABL != 1 && QB == 0) { __builtin_amdgcn_s_waitcnt(wino_vmcnt(VMW)); __syncthreads(); }
 #pragma unroll
             for (int b = 0; b < BPS; ++b) {
                 if (b == 0) kstep(k, su, sp1, sd, sd1, fc);
@@ -857,8 +911,8 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
     static_assert(PR >= 3 && PR <= 4, "patch ring");
     constexpr int UB1 = 4 * 16 * WINO_LD, UBUF = 2 * UB1, NUP = 26;
     constexpr int TH = 2 * BA, TW = 2 * BB;                                  // OUTPUT pixels per instance
-    constexpr int PH = 4 * BA + 3, PROW = 4 * BB + 8, PR4 = PROW / 4;        // input patch
-    constexpr int PCH0 = NI * PH * PROW;                                     // floats of one channel's patch
+    constexpr int PRH = 4 * BA + 3, PROW = 4 * BB + 8, PR4 = PROW / 4;        // input patch
+    constexpr int PCH0 = NI * PRH * PROW;                                     // floats of one channel's patch
     constexpr int PCH = (RB == 1 || RB == 2) ? (PCH0 + 63) / 64 * 64 : PCH0; // channel pitch in LDS (RB 1 / 2: a multiple of 64 floats)
     constexpr int NF4 = PCH, NPP = (NF4 + 63) / 64, PBUF = NPP * 256;        // float4 of a K step's four channels; DMA pieces
     constexpr int NPIECE = NUP + NPP, DPW = (NPIECE + 7) / 8;
@@ -916,14 +970,14 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
         u.flo = __builtin_amdgcn_readfirstlane(flex_patch ? (unsigned)bi_ : (unsigned)bu_); u.fhi = __builtin_amdgcn_readfirstlane(flex_patch ? (unsigned)(bi_ >> 32) : (unsigned)(bu_ >> 32));
         return u;
     };
-    // patch float4 e = ((c * NI + ii) * PH + row) * PR4 + j  <-  channel 4k+c, instance tile0+ii, input row 4 ty0 - 1 + row, columns 4 tx0 - 4 + 4j .. +3
+    // patch float4 e = ((c * NI + ii) * PRH + row) * PR4 + j  <-  channel 4k+c, instance tile0+ii, input row 4 ty0 - 1 + row, columns 4 tx0 - 4 + 4j .. +3
     auto patch_voff = [&](int unit, int piece) {
         if (ABL == 10) unit = 0;                                             // (tuning builds: every patch from one place - L2 hits - to see what the patch traffic costs)
         int sx_, sy_; wino_sp_xy(unit % nsp, tilesX, colrun, sx_, sy_);
         const int tile0 = (unit / nsp) * NI, tx0 = sx_ * BB, ty0 = sy_ * BA;     // tile origin in BLOCKS
         const int e = piece * 64 + lane;
         const int c = e / (PCH / 4), rem = e % (PCH / 4);                    // float4 `rem` of channel c's patch (rem >= PCH0 / 4: padding of the pitch)
-        const int j = rem % PR4, row = (rem / PR4) % PH, ii = rem / (PR4 * PH);
+        const int j = rem % PR4, row = (rem / PR4) % PRH, ii = rem / (PR4 * PRH);
         const int gy = 4 * ty0 - 1 + row, gx = 4 * tx0 - 4 + 4 * j;
         const bool ok = piece >= 0 && e < NF4 && rem < PCH0 / 4 && tile0 + ii < p.ntiles && gy >= 0 && gy < p.H && gx >= 0 && gx + 3 < p.W;
         return ok ? 4u * (unsigned)((size_t)ii * p.srcA_tile + (size_t)c * hw + (size_t)gy * p.W + gx) : OOR;
@@ -963,7 +1017,7 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
         else if (i == 3) dma_flex(ku, ubuf, kp, pslot);
         else dma_patch(kp, pslot);
     };
-    const int poff = kq * PCH + (il * PH + 4 * ba) * PROW + 4 * bb + 3;      // this lane's block: patch rows +0..6, columns +0..6 (input column 4xb-1 first)
+    const int poff = kq * PCH + (il * PRH + 4 * ba) * PROW + 4 * bb + 3;      // this lane's block: patch rows +0..6, columns +0..6 (input column 4xb-1 first)
     const int aoff = (kq * 16 + l15) * WINO_LD;
     const int nk = p.Cin / 4;
     const size_t ohw = (size_t)Ho * Wo;
@@ -1000,7 +1054,7 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
         };
         auto rows = [&](int r) {
             if constexpr (X3) wino_in3(xr[r][0], xr[r][1], xr[r][2], xr[r][3], t3[r]);
-            else wino_in2(xr[r][0], xr[r][1], xr[r][2], t2[r]);
+            else wino_in2<true>(xr[r][0], xr[r][1], xr[r][2], t2[r]);
         };
         float v[NP];
         auto issue_first = [&]() {
@@ -1052,7 +1106,7 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
                 if constexpr (ABL != 4) {
                     if constexpr (q == 0) {
                         constexpr int l0 = 4 * (NQ - 1);
-                        WinoFor<l0, NP>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x>(t3, t2); });
+                        WinoFor<l0, NP>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x, true>(t3, t2); });
                         if constexpr (RQ == 0) {
 #pragma unroll
                             for (int r = 0; r < NROW; ++r) rows(r);
@@ -1065,7 +1119,7 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
 #pragma unroll
                             for (int r = 0; r < NROW; ++r) rows(r);
                         }
-                        WinoFor<4 * q - 4, 4 * q>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x>(t3, t2); });
+                        WinoFor<4 * q - 4, 4 * q>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x, true>(t3, t2); });
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -1086,7 +1140,7 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < NROW; ++r) { read_row(s_p, r); rows(r); }
-        WinoFor<0, NP>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x>(t3, t2); });
+        WinoFor<0, NP>::run([&](auto xc) { constexpr int x = decltype(xc)::value; v[x] = wino_point<X0 + x, true>(t3, t2); });
         // patch D -> slot D: the wave's patch pieces only (its U pieces of this round went out above); from here on exactly DPW DMA instructions per step
         if (flex_patch) dma_flex(0, 0, min(PD, nk - 1), PD % PR);
         dma_patch(min(PD, nk - 1), PD % PR);
@@ -1142,7 +1196,7 @@ __global__ void __launch_bounds__(512, 1) srt_enc_wino32(const SrtConvParams p, 
 #pragma unroll
                     for (int x = 0; x < NP; ++x) m[x] = acc[mb][x][r];
                     float y[2][2];
-                    wino_out2d<NY, NX>(m, y);
+                    wino_out2d<NY, NX, true>(m, y);
                     const float4 y4 = make_float4(y[0][0], y[0][1], y[1][0], y[1][1]);
                     if (r == CLS) own[mb] = y4;
                     else if (mb == 0) { if constexpr (ABL != 9) *reinterpret_cast<float4*>(&s_x[xo + (r < CLS ? r : r - 1) * 64]) = y4; else own[0].x += y4.y; }
@@ -1274,7 +1328,12 @@ static int wino_mfast_bit(size_t ubytes, int mb2)
 #define SRT_WINO32_DEFAULT 1
 #endif
 #define SRT_WINO32_SHIPPED 2, 16, 0, 3, 2, 1, 1, 0, 1, 1
+// ... and with the barrier phase offset (srt_dec_wino32's PH): rings of five, slabs and patches three steps ahead, waves 4-7 meet the barrier in front of their
+// quad 1.  sw.wino_ph (SPLEETERRT_WINO_PH) picks it per layer group: bit 0 the two-instance form (up1 of 256-row tiles), bit 1 the one-instance form (up2..up4), bit 2 srt_dec_wino (up5);
+// 0 is the arrangement above.  Same MFMAs in the same order either way: the two forms are bit-identical (tests/test_wino_phase.py).
+#define SRT_WINO32_PHASED(BB, NI) 2, BB, 0, 5, 3, 1, 1, 0, 1, 1, NI, 0, 1, 1
 #define SRT_WINO_RING 3
+#define SRT_WINO_PHASED 4, 16, 1, 0, 5, 0, 0, 1, 3, 2                        // srt_dec_wino (up5, sw.wino_ph bit 2): rings of five (100 KiB), lead 3, waves 4-7 meet the barrier in front of their group 2 of 4
 static int wino32_on()
 {
 #ifdef SRT_TUNING
@@ -1283,17 +1342,18 @@ static int wino32_on()
 #endif
     return SRT_WINO32_DEFAULT;
 }
-int srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, hipStream_t s)
+int srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, const SrtSwitches& sw, hipStream_t s)
 {
     if (!U || p.in16 || p.out16 || p.srcA_tile != p.srcB_tile || (size_t)16 * p.srcA_tile > 0x7fffffffu || p.Cout % 16 || p.Cin % 4 || p.CA % 4 || (p.H & 1) || (p.W & 3)) return 1;
     const int MB = p.Cout / 16;
     if (p.Cout % 32 == 0 && p.Cin >= 32 && p.H >= 4 && p.W >= 16 && p.W < 32 && wino32_on()) {     // 4 x 16 .. 28 inputs (up1 of 256 x 1024 tiles): two instances per workgroup
         const long units = (long)((p.W + 15) / 16) * ((p.H + 3) / 4) * ((p.ntiles + 1) / 2), wgs = units * (p.Cout / 32) * p.nstems;
         const int tpw = wino_tpw(wgs, units);
-        SRT_LAUNCH((srt_dec_wino32<2, 8, 0, 3, 2, 1, 1, 0, 1, 1, 2>), dim3((unsigned)(wgs / tpw)), dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit());
+        if (sw.wino_ph & 1) SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_PHASED(8, 2)>), dim3((unsigned)(wgs / tpw)), dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit());
+        else SRT_LAUNCH((srt_dec_wino32<2, 8, 0, 3, 2, 1, 1, 0, 1, 1, 2>), dim3((unsigned)(wgs / tpw)), dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit());
         return srt_launch_status();
     }
-    if (p.Cout % 32 == 0 && p.Cin >= 32 && p.H >= 4 && p.W >= 32 && wino32_on()) {      // (Cin >= 32: at least 8 K steps, the continuous stream looks D + 1 = 3 steps ahead)
+    if (p.Cout % 32 == 0 && p.Cin >= 32 && p.H >= 4 && p.W >= 32 && wino32_on()) {      // (Cin >= 32: at least 8 K steps, the continuous stream looks D + 1 = 3 steps ahead - 4 with the phase offset - and switches to the next unit's patches at step nk - 1 - D >= 0)
         const long units = (long)((p.W + 31) / 32) * ((p.H + 3) / 4) * p.ntiles, wgs = units * (p.Cout / 32) * p.nstems;
         int tpw = wino_tpw(wgs, units);
         const dim3 grid((unsigned)(wgs / tpw));
@@ -1317,11 +1377,19 @@ int srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, h
         case 8: W32(0, 5, 3, 2, 1, 0, 1, 1);                                 // rings of 5, barrier per two steps, continuous K stream across units
         case 10: W32(0, 5, 3, 2, 1, 0, 1, 0);                                // the same without the continuous stream
         }
+        switch (wino_tune("winoph=")) {                                      // barrier phase offset <.., NI, PEEL, RB, PH>: the variants measured for DESIGN.md section 6
+        case 1: W32(0, 5, 3, 1, 1, 0, 1, 1, 1, 0, 1, 1);                     // = the shipped phased form
+        case 2: W32(0, 5, 3, 1, 1, 0, 1, 1, 1, 0, 1, 2);                     // waves 4-7 meet in front of their LAST quad
+        case 3: W32(0, 4, 2, 1, 1, 0, 1, 1, 1, 0, 1, 1);                     // rings of four, two steps ahead: waves 0-3 wait for vmcnt(0)
+        case 4: W32(0, 4, 2, 1, 1, 0, 1, 1, 1, 0, 1, 2);
+        case 5: W32(0, 5, 3, 1, 1, 0, 1, 1, 1, 0, 1, 0);                     // the deeper rings alone, every wave at quad 0
+        }
         if (wino_tune("winopeel=") == 1) W32(0, 3, 2, 1, 1, 0, 1, 1, 1, 1);            // the shipped arrangement with the first K step peeled (C = 0)
         if (wino_tune("decrb=") == 0) { SRT_LAUNCH((srt_dec_wino32<2, 16, 0, 3, 2, 1, 1, 0, 1, 1, 1, 0, 0>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32)); return 0; }      // round-4 patch reads (natural pitch, b32 outer columns)
 #undef W32
 #endif
-        SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_SHIPPED>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32));
+        if (sw.wino_ph & 2) SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_PHASED(16, 1)>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32));
+        else SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_SHIPPED>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32));
         return srt_launch_status();
     }
     if (p.H >= 8 && p.W >= 32) {
@@ -1340,13 +1408,21 @@ int srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, h
         if (wino_tune("winosb=") == 1) { SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 3, 1>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0; }
         if (wino_tune("winocs=") == 1) { SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 3, 0, 1>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0; }
         if (wino_tune("winocs=") == 2) { SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 4, 0, 1>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0; }
+        switch (wino_tune("winoph5=")) {                                     // barrier phase offset <.., UR, SB, CS, RB, D, PH>
+        case 1: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 5, 0, 0, 1, 3, 1>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;
+        case 2: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 5, 0, 0, 1, 3, 2>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;
+        case 3: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 5, 0, 0, 1, 3, 3>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;
+        case 4: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 4, 0, 0, 1, 2, 2>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;      // rings of four, lead 2
+        case 5: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 5, 0, 0, 1, 3, 0>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;      // rings of five, lead 3, no offset
+        }
         switch (wino_tune("winoring=")) {
         case 4: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 4>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;
         case 5: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 5>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;
         case 6: SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, 6>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit()); return 0;
         }
 #endif
-        SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, SRT_WINO_RING>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit());
+        if (sw.wino_ph & 4) SRT_LAUNCH((srt_dec_wino<SRT_WINO_PHASED>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit());
+        else SRT_LAUNCH((srt_dec_wino<4, 16, 1, 0, SRT_WINO_RING>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit());
     } else if (p.H >= 4 && p.W >= 16) {
         const long units = (long)((p.W + 15) / 16) * ((p.H + 3) / 4) * ((p.ntiles + 3) / 4), wgs = units * MB * p.nstems;
         const int tpw = wino_tpw(wgs, units);
