@@ -139,6 +139,32 @@ SRT_API size_t srtOverlapTiles(size_t rows, int T, int overlap_rows);
 #define SRT_MASK_EXT_AVERAGE  1
 SRT_API int  srtSetMaskExtension(srt_engine *e, int mode);
 
+/* ---- stem remix inside the inverse transform.  Most callers want a mix of the stems (karaoke = everything minus the vocals, an accompaniment
+ * next to the vocals, one gain per stem, the stems plus their residual), not the stems.  The masking is linear, out_m = iSTFT(X * sum_s G[m][s] g_s), so the
+ * mix is formed on the gains in the inverse transform's prologue: M mixes cost M inverse transforms instead of n_stems, and only the M results exist in memory
+ * or cross the bus.
+ * n_out = 0 (h_gain ignored): off, the default - every path and kernel as it always was, bit for bit.
+ * 1 <= n_out <= SRT_MAX_STEMS: h_gain is [n_out][n_stems + 1], row-major, copied.
+ *   G[m][s], s < n_stems: gain of stem s in output m.
+ *   G[m][n_stems]: gain of the unmasked input.
+ * Takes effect for later calls.
+ * While the mix is on, srtIstft (also with d_masks = NULL), srtSeparate[Ex] (ratio_mask, srtSetOverlap, both mask-extension modes, graph mode: a changed
+ * matrix never replays a graph captured with the old one) and srtSeparateHostStream[Ex|Io] (staging, seam carry, download and the 16-bit pack over n_out
+ * planes; h_clipped has n_out entries) write n_out stereo pairs [n_out][2][len] instead of n_stems.  Output m, channel c, spectrum row r, bin k is the
+ * inverse transform of X(r,c,k) * h_m(r,c,k),
+ *   h = G[m][n_stems];  for s = 0 .. n_stems-1 (ascending):  h = fmaf(G[m][s], g_s(r,c,k), h)
+ * in fp32, one fused multiply-add per stem in that fixed order.  g_s is the gain the inverse transform applies for stem s with the mix off: in band (k < F)
+ * the mask value (1 without masks), cross-faded under srtSetOverlap, then normalised across the stems with ratio_mask and n_stems > 1 (blend first, then
+ * normalise); above F oob_weight[s], or under SRT_MASK_EXT_AVERAGE the table value e_s(r,c) (1 without masks).  A row that is 1 on stem m and 0 elsewhere
+ * reproduces stem m bit for bit; G[m] = (0, .., 0, 1) is the plain STFT -> iSTFT round trip.  The fp16 mode keeps its masks as floats while the mix is on.
+ * srtSetMix returns -1 with srtLastError() text (before any device work) for a null engine, n_out outside 0..SRT_MAX_STEMS, a null h_gain with n_out > 0, an
+ * entry that is not finite, or the Wiener filter on; srtSetWiener(n > 0) returns -1 while the mix is on.
+ * Refused with -1, a text that says "mix" and nothing launched or written while the mix is on: srtSeparateCli, srtSeparateCliHost[Io] (no stem axis),
+ * srtIstftWiener, srtSeparateBatch, srtSeparateBatchWiener (follow-ups) and srtMultiSeparate*Host when any engine of the object has it on.  The live / plugin
+ * surfaces (srtLive*, Spleeter4Stems*) have their own handles and write every stem (a follow-up). */
+SRT_API int srtSetMix(srt_engine *e, int n_out, const float *h_gain);
+SRT_API int srtMixOutputs(const srt_engine *e);   /* n_out while on, 0 while off or for a null engine */
+
 /* Many independent tracks in one packed batch.  Track k of a batch occupies the packed tiles [tile0[k], tile0[k] + ceil(srtStftRows(n[k]) / T)).
  * srtBatchPlan is pure host arithmetic (no device, like srtRankSpan): tile0 may be NULL; *total_tiles = the sum.  -1 for ntracks < 1, T < 1 or any n[k] < 4096.
  * srtSeparateBatch: K whole tracks (srtSeparate geometry each) in one launch sequence - one batched STFT, one srtForward over the packed tiles, one batched

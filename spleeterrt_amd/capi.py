@@ -58,6 +58,8 @@ def load_library():
     L.srtSetWiener.argtypes = [vp, C.c_int]
     L.srtSetOverlap.argtypes = [vp, C.c_int]
     L.srtSetMaskExtension.argtypes = [vp, C.c_int]
+    L.srtSetMix.argtypes = [vp, C.c_int, vp]
+    L.srtMixOutputs.argtypes = [vp]
     L.srtOverlapTiles.restype = C.c_size_t
     L.srtOverlapTiles.argtypes = [C.c_size_t, C.c_int, C.c_int]
     L.srtIstftWiener.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_int, f32p]
@@ -253,6 +255,29 @@ class Engine:
         self._chk(self.L.srtSetMaskExtension(self.h, int(m)))
         self.mask_extension = int(m)
 
+    def set_mix(self, matrix):
+        """stem remix inside the inverse transform (srtSetMix): matrix [n_out, S + 1] - G[m][s] the gain of stem s in output m, G[m][S] the gain of
+        the unmasked input - or None / an empty matrix for off.  While it is on istft, separate, separate_ex and separate_host_stream[_io] return n_out pairs
+        instead of S."""
+        import numpy as np
+        if matrix is None or np.size(matrix) == 0:
+            self._chk(self.L.srtSetMix(self.h, 0, None))
+            return
+        g = np.ascontiguousarray(matrix, np.float32)
+        if g.ndim != 2 or g.shape[1] != self.S + 1:
+            raise EngineError("set_mix: the matrix must be [n_out, n_stems + 1] = [*, %d], not %r" % (self.S + 1, tuple(g.shape)))
+        self._chk(self.L.srtSetMix(self.h, int(g.shape[0]), C.c_void_p(g.ctypes.data)))
+
+    @property
+    def mix_outputs(self):
+        """outputs of the stem remix (srtMixOutputs): n_out while set_mix is on, 0 while it is off"""
+        return int(self.L.srtMixOutputs(self.h)) if getattr(self, "h", None) else 0
+
+    @property
+    def outputs(self):
+        """stereo pairs istft / separate / separate_ex / separate_host_stream[_io] write: mix_outputs while the remix is on, else the stems"""
+        return self.mix_outputs or self.S
+
     def mask_ext(self, stem, rows):
         """the gains of bins >= F the last inverse transform with mask_extension = "average" applied to one stem: numpy [rows, 2] (L, R)"""
         import numpy as np
@@ -296,20 +321,20 @@ class Engine:
         return spec, mag
 
     def istft(self, spec, masks=None):
-        """spec [2,rows,2052,2], masks [S,ntiles,2,T,F] or None -> out [S,2,rows*1024+3072]"""
+        """spec [2,rows,2052,2], masks [S,ntiles,2,T,F] or None -> out [S,2,rows*1024+3072] (set_mix on: [n_out,2,..])"""
         t = self.torch
         rows = spec.shape[1]
-        out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
+        out = t.empty((self.outputs, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
         self._chk(self.L.srtIstft(self.h, _ptr(spec), rows, _ptr(masks), _ptr(out)))
         return out
 
     def separate(self, L, R, out=None):
-        """whole path: planar PCM [n] x2 -> stems [S,2,rows*1024+3072]"""
+        """whole path: planar PCM [n] x2 -> stems [S,2,rows*1024+3072] (set_mix on: the mixes [n_out,2,..])"""
         t = self.torch
         n = L.numel()
         rows = self.L.srtStftRows(n)
         if out is None:
-            out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
+            out = t.empty((self.outputs, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
         self._chk(self.L.srtSeparate(self.h, _ptr(L), _ptr(R), n, _ptr(out)))
         return out
 
@@ -389,7 +414,7 @@ class Engine:
         assert n == nR
         rows = self.L.srtStftRows(n) if rows is None else rows
         frames = self.L.srtStftFrames(n) if frames is None else frames
-        shape = (self.S, 2, self.L.srtIstftLength(rows))
+        shape = (self.outputs, 2, self.L.srtIstftLength(rows))
         ret = None
         if out is None:
             if pinned:                                           # keep the promise for the output too
@@ -447,7 +472,7 @@ class Engine:
         """separate_host_stream with 16-bit PCM on either side (srtSeparateHostStreamIo; the conversion runs on the GPU, half the bytes cross the bus).
         pcm_or_LR: int16 [n, 2] interleaved stereo, or (L, R) float32; out_pcm16: stems as int16 [S, len, 2] (a WAV data chunk per stem) instead of float32
         [S, 2, len].  -> (out, clipped): clipped uint64 [S], the samples per stem whose value before clamping lay outside [-32768, 32767] (zeros for float output)."""
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.S, rows, out, pinned)
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, rows, out, pinned)
         frames = self.L.srtStftFrames(n) if frames is None else frames
         self._chk(self.L.srtSeparateHostStreamIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, frames, rows, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
@@ -469,7 +494,7 @@ class Engine:
         """explicit-geometry form used by spleeterrt_amd.stream for tile ranges of a longer stream"""
         t = self.torch
         if out is None:
-            out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
+            out = t.empty((self.outputs, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
         self._chk(self.L.srtSeparateEx(self.h, _ptr(L.contiguous()), _ptr(R.contiguous()), L.numel(), frames, rows, _ptr(out)))
         return out
 

@@ -251,6 +251,72 @@ __device__ __forceinline__ float srt_ratio_of_ov(const float* __restrict__ rowb0
     return ratio ? (mine + e1) / (sum + eps) : own;
 }
 
+// Stem remix (srtSetMix): output m of a MIX launch multiplies a bin by h = G[m][S], then h = fmaf(G[m][s], g_s, h) for s = 0 .. S-1 ascending, where
+// g_s is the gain the forms above apply for stem s - the mask value, blended (srt_blend), then normalised across the stems; the arithmetic of srt_ratio_of /
+// srt_ratio_of_ov step for step (blend first, squares summed over the stems ascending, (m_s^2 + eps/S) / (sum + eps)), so a one-hot row gives stem m's bits.
+// The stem loop is the OUTER one: a pass over the stems for the square sums (ratio only), a second one for the chain (its re-reads are cache hits) - one matrix
+// entry per stem (a uniform load) and no per-stem array.  hl / hr: the NB bins tid + 256 j of the two channels.
+// r0 / a0: stem 0's L row of the frame in its primary / previous tile (r0 null: no masks, g_s = 1; a0 read only when two); ratio: a run-time flag here.
+template <int NB, int JC>
+__device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const float* __restrict__ r0, const float* __restrict__ a0, bool two, float w, bool ratio, int m, int tid,
+                                              float (&hl)[NB], float (&hr)[NB])
+{
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const float eps = 1e-10f, e1 = eps / (float)p.nstems;
+    auto value = [&](const float* __restrict__ b, const float* __restrict__ a, int km) {
+        float v = b[km];
+        if (two) v = srt_blend(a[km], v, w);
+        return v;
+    };
+    // JC bins at a time: the square sums of a chunk are dead before the next one starts (all nine bins of the F > 1024 form at once spill)
+#pragma unroll
+    for (int j0 = 0; j0 < NB; j0 += JC) {
+        float suml[JC], sumr[JC];
+#pragma unroll
+        for (int i = 0; i < JC; ++i) { suml[i] = 0.0f; sumr[i] = 0.0f; }
+#pragma unroll
+        for (int i = 0; i < JC; ++i) if (j0 + i < NB) { hl[j0 + i] = p.mix[m][p.nstems]; hr[j0 + i] = hl[j0 + i]; }
+        if (r0 && ratio) {
+            for (int s = 0; s < p.nstems; ++s) {
+                const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * sstride;
+#pragma unroll
+                for (int i = 0; i < JC; ++i) {
+                    if (j0 + i >= NB) continue;
+                    const int km = min(min(tid + 256 * (j0 + i), 2048), p.F - 1);
+                    const float vl = value(b, a, km), vr = value(b + tf, a + tf, km);
+                    const float ql = vl * vl, qr = vr * vr;
+                    suml[i] = suml[i] + ql; sumr[i] = sumr[i] + qr;
+                }
+            }
+        }
+        for (int s = 0; s < p.nstems; ++s) {
+            const float gm = p.mix[m][s];
+            const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * sstride;
+#pragma unroll
+            for (int i = 0; i < JC; ++i) {
+                if (j0 + i >= NB) continue;
+                const int km = min(min(tid + 256 * (j0 + i), 2048), p.F - 1);
+                float vl = 1.0f, vr = 1.0f;
+                if (r0) {
+                    vl = value(b, a, km); vr = value(b + tf, a + tf, km);
+                    if (ratio) {
+                        const float ml = vl * vl, mr = vr * vr;
+                        vl = (ml + e1) / (suml[i] + eps); vr = (mr + e1) / (sumr[i] + eps);
+                    }
+                }
+                hl[j0 + i] = fmaf(gm, vl, hl[j0 + i]); hr[j0 + i] = fmaf(gm, vr, hr[j0 + i]);
+            }
+        }
+    }
+}
+// the same chain over one value per stem (workgroup-uniform): x[s * stride], s ascending - the constant weights of bins >= F, or a row of the extension's table
+__device__ __forceinline__ float srt_mix_chain(const SrtIstftParams& p, int m, const float* __restrict__ x, size_t stride)
+{
+    float h = p.mix[m][p.nstems];
+    for (int s = 0; s < p.nstems; ++s) h = fmaf(p.mix[m][s], x[(size_t)s * stride], h);
+    return h;
+}
+
 #pragma clang fp contract(fast)
 
 // What a workgroup of the inverse kernels reads and writes of ONE signal: the whole call's signal (srt_istft_ola_kernel / srt_istft_ola3_kernel),
@@ -265,7 +331,8 @@ __device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { Istft
 // read when the frame is staged and the two are blended before the ratio / multiply
 // EXT: average mask extension (srtSetMaskExtension): bins >= F of frame f take the two gains ext[stem][f][L, R] instead of oob (fetched with the frame's rows
 // from workgroup-uniform addresses: scalar loads into SGPRs, consumed before the next fetch overwrites them)
-template <bool RATIO, bool OV = false, bool EXT = false>
+// MIX: stem remix (srt_mix_gains): `stem` is the OUTPUT index m; no mask row is prefetched (every stem's row is read in the prologue), RATIO = false (a run-time flag)
+template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false>
 __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
 {
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
@@ -277,7 +344,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
     const size_t tf = (size_t)p.T * p.F;
     const int nseg = w.frames + 3;
     const int s0 = run * G, s1 = min(s0 + G, nseg);
-    const float oob = p.oob[stem];                                           // bins >= F: "unaffectedWeight" (main.c:486-493)
+    const float oob = MIX ? srt_mix_chain(p, stem, p.oob, 1) : p.oob[stem];   // bins >= F: "unaffectedWeight" (main.c:486-493)
     const cf* spec = reinterpret_cast<const cf*>(w.spec);
     float* oL = w.out + (size_t)(stem * 2 + 0) * w.out_len;
     float* oR = w.out + (size_t)(stem * 2 + 1) * w.out_len;
@@ -293,7 +360,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
     cf sl[9], sr[9];
     float gl[9], gr[9];
     float eL = oob, eR = oob;
-    const float* __restrict__ const ext = EXT ? w.ext + (size_t)stem * p.ext_stem : nullptr;
+    const float* __restrict__ const ext = EXT ? w.ext + (MIX ? 0 : (size_t)stem * p.ext_stem) : nullptr;
     // fetch only ISSUES loads (no value depends on them until the next iteration): without masks the two mask rows
     // are read from a harmless table instead of branching on the pointer
     const bool has_mask = w.masks != nullptr;
@@ -309,9 +376,9 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
         for (int j = 0; j < 9; ++j) {
             const int k = min(tid + 256 * j, 2048), km = min(k, p.F - 1);
             sl[j] = specL[k]; sr[j] = specR[k];
-            if constexpr (!(RATIO && OV)) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
+            if constexpr (!(RATIO && OV) && !MIX) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
         }
-        if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = ext[fu]; eR = ext[fu + 1]; }
+        if constexpr (EXT && !MIX) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = ext[fu]; eR = ext[fu + 1]; }
     };
     float pw[16];                                       // this thread's 16 synthesis-window taps are the same for every frame
 #pragma unroll
@@ -339,7 +406,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
             OvRow ov = { 0, 0, false, 0.0f };
             if constexpr (OV) {
                 ov = srt_ov_row(f, p.T, O, p.ntiles);
-                if (!RATIO && has_mask && ov.two) {      // cross-fade of the two tiles' masks: a (row k + S of the previous tile) + w (b - a).  The a rows are read HERE,
+                if (!RATIO && !MIX && has_mask && ov.two) {      // cross-fade of the two tiles' masks: a (row k + S of the previous tile) + w (b - a).  The a rows are read HERE,
                     // not with the prefetch (18 more staged registers spill at two workgroups per CU); the other workgroup of the CU covers the wait
                     const float* aL = w.masks + ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
 #pragma unroll
@@ -367,12 +434,19 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
                     }
                 }
             }
+            if constexpr (MIX) {                         // every stem's gains of this frame, chained with output `stem`'s matrix row
+                const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
+                const float* r0 = has_mask ? w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F : nullptr;
+                const float* a0 = OV && has_mask ? r0 - 2 * tf + (size_t)(p.T - O) * p.F : r0;
+                srt_mix_gains<9, 3>(p, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, stem, tid, gl, gr);
+                if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, stem, ext + fu, p.ext_stem); eR = srt_mix_chain(p, stem, ext + fu + 1, p.ext_stem); }
+            }
             const float xl = EXT ? eL : oob, xr = EXT ? eR : oob;              // bins >= F
 #pragma unroll
             for (int j = 0; j < 9; ++j) {
                 const int k = tid + 256 * j;
                 if (k <= 2048) {
-                    const float wl = k < p.F ? (has_mask ? gl[j] : 1.0f) : xl, wr = k < p.F ? (has_mask ? gr[j] : 1.0f) : xr;
+                    const float wl = k < p.F ? (has_mask || MIX ? gl[j] : 1.0f) : xl, wr = k < p.F ? (has_mask || MIX ? gr[j] : 1.0f) : xr;
                     const cf A = sl[j] * wl, B = sr[j] * wr;                      // masked (re, im) of L and R
                     // G = F'_L + i F'_R, F' = re - i im, Hermitian-extended; stored swapped (im,re): inverse-by-forward trick
                     if (k == 0) sx[0] = f2(B.x, A.x);                             // a[0] = re[0]           (stftFix.c:556-557)
@@ -606,7 +680,8 @@ __global__ void __launch_bounds__(256, 3) srt_stft_ov_kernel(const SrtStftParams
 // M16: the masks are halves (the engine's own mask buffer in the fp16 mode, written by srt_head_rows_kernel<.., true>; never with RATIO)
 #define ISTFT_OLA3_LDS_F2 (FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2)
 // EXT: as istft_ola_run
-template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false>
+// MIX: as istft_ola_run (RATIO = M16 = false)
+template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false>
 __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
 {
     cf* sx = s_mem;
@@ -618,7 +693,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
     const size_t tf = (size_t)p.T * p.F;
     const int nseg = w.frames + 3;
     const int s0 = run * G, s1 = min(s0 + G, nseg);
-    const float oob = p.oob[stem];                                           // bins >= F: "unaffectedWeight" (main.c:486-493)
+    const float oob = MIX ? srt_mix_chain(p, stem, p.oob, 1) : p.oob[stem];   // bins >= F: "unaffectedWeight" (main.c:486-493)
     const cf* spec = reinterpret_cast<const cf*>(w.spec);
     float* oL = w.out + (size_t)(stem * 2 + 0) * w.out_len;
     float* oR = w.out + (size_t)(stem * 2 + 1) * w.out_len;
@@ -631,7 +706,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
     float gl[NM], gr[NM];
     cf sl8, sr8;                                        // bin 2048 (only thread 0 uses it; the address is uniform)
     float eL = oob, eR = oob;
-    const float* __restrict__ const ext = EXT ? w.ext + (size_t)stem * p.ext_stem : nullptr;
+    const float* __restrict__ const ext = EXT ? w.ext + (MIX ? 0 : (size_t)stem * p.ext_stem) : nullptr;
     const bool has_mask = w.masks != nullptr;
     auto fetch = [&](int f) {                                               // 0 <= f < w.frames
         int tile = f / p.T, t = f % p.T;
@@ -650,11 +725,11 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             if (j < NM) {
                 const int km = min(k, p.F - 1);
                 if constexpr (M16) { gl[j] = (float)hL[km]; gr[j] = (float)hL[tf + km]; }
-                else if constexpr (!(RATIO && OV)) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
+                else if constexpr (!(RATIO && OV) && !MIX) { gl[j] = mL[km]; gr[j] = mR[km]; }      // (RATIO && OV: see srt_ratio_of_ov)
             }
         }
         sl8 = specL[2048]; sr8 = specR[2048];
-        if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = ext[fu]; eR = ext[fu + 1]; }
+        if constexpr (EXT && !MIX) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = ext[fu]; eR = ext[fu + 1]; }
     };
     // the 16 synthesis-window taps of this thread (samples tid + 256 k2) are rebuilt per frame from two registers: cos / sin of th = 2 pi (tid + 1/2) / 4096, over 3.
     // (A deviation from the table the F > 1024 kernel reads - postWin, which reproduces InitSTFT's rounding: 1/3 - cos/3 in fp32 is off by up to ~3e-8 absolute,
@@ -688,7 +763,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             OvRow ov = { 0, 0, false, 0.0f };
             if constexpr (OV) {
                 ov = srt_ov_row(f, p.T, O, p.ntiles);
-                if (!RATIO && has_mask && ov.two) {      // cross-fade of the two tiles' masks (halves are converted first): a (row k + S of the previous tile) + w (b - a).
+                if (!RATIO && !MIX && has_mask && ov.two) {      // cross-fade of the two tiles' masks (halves are converted first): a (row k + S of the previous tile) + w (b - a).
                     // The a rows are read HERE, not with the prefetch: eight more staged registers do not fit the 168 of three workgroups per CU (9 dwords
                     // spilled when tried); the wait is covered by the CU's other workgroups and falls on O of every T - O frames only
                     const size_t ao = ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
@@ -719,12 +794,19 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
                     }
                 }
             }
+            if constexpr (MIX) {                         // every stem's gains of this frame, chained with output `stem`'s matrix row
+                const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
+                const float* r0 = has_mask ? w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F : nullptr;
+                const float* a0 = OV && has_mask ? r0 - 2 * tf + (size_t)(p.T - O) * p.F : r0;
+                srt_mix_gains<NM, NM>(p, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, stem, tid, gl, gr);
+                if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, stem, ext + fu, p.ext_stem); eR = srt_mix_chain(p, stem, ext + fu + 1, p.ext_stem); }
+            }
             const float xl = EXT ? eL : oob, xr = EXT ? eR : oob;              // bins >= F
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int k = tid + 256 * j;
                 float wl = xl, wr = xr;
-                if (j < NM) { wl = k < p.F ? (has_mask ? gl[j] : 1.0f) : xl; wr = k < p.F ? (has_mask ? gr[j] : 1.0f) : xr; }
+                if (j < NM) { wl = k < p.F ? (has_mask || MIX ? gl[j] : 1.0f) : xl; wr = k < p.F ? (has_mask || MIX ? gr[j] : 1.0f) : xr; }
                 const cf A = sl[j] * wl, B = sr[j] * wr;                          // masked (re, im) of L and R
                 v[j] = sub_mi(B, A);                                              // (reR - imL, imR + reL)
                 mir[j * 256 + tid] = herm_hi(B, A);                               // (reR + imL, reL - imR)   (slot (0, 0) is never read)
@@ -784,6 +866,23 @@ __global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_ov_ext_kern
     istft_ola3_run<NM, RATIO, M16, true, true>(p, istft_view(p), stem, run, G, s_mem, O);
 }
 
+// Stem remix (srtSetMix): the workgroup index is the OUTPUT m, fastest in the XCD order - the outputs of a run share the spectrum rows (and every stem's mask
+// rows) in L2.  Two workgroups per CU as the RATIO forms, which read every stem's row in the prologue too; O is unused without OV.
+template <int NM, bool OV, bool EXT>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola3_mix_kernel(const SrtIstftParams p, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), m = pos % p.n_out, run = pos / p.n_out;
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, false, false, OV, EXT, true>(p, istft_view(p), m, run, G, s_mem, O);
+}
+template <bool OV, bool EXT>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_mix_kernel(const SrtIstftParams p, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), m = pos % p.n_out, run = pos / p.n_out;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<false, OV, EXT, true>(p, istft_view(p), m, run, G, s_mem, O);
+}
+
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_tiles)
 {
     // short signals (one tile, the real-time regime): fewer frames per workgroup so that the frames spread over the CUs
@@ -820,9 +919,11 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
     if (p.masks16 && (!p.masks || p.F > 1024 || (p.ratio && p.nstems > 1))) return -1;      // halves are read by the three-per-CU kernel only
     const int target = p.F > 1024 ? 1024 : 768;
     // (runs x stems must not exceed the resident workgroups: five stems at 768 / 5 = 153.6 runs would leave two workgroups for a second round)
-    const int max_runs = target / p.nstems > 0 ? target / p.nstems : 1;
+    if (p.n_out < 0 || p.n_out > SRT_MAX_STEMS || (p.n_out && (p.masks16 || p.nstems < 1 || p.nstems > SRT_MAX_STEMS))) return -1;      // remix: fp32 masks only
+    const int ncol = p.n_out ? p.n_out : p.nstems;      // workgroup columns of the grid: the stems, or the outputs of a remix
+    const int max_runs = target / ncol > 0 ? target / ncol : 1;
     int G = (nseg + max_runs - 1) / max_runs;
-    const int gmin = (size_t)nseg * p.nstems >= 4096 ? 13 : 5;          // short signals: shorter runs (more warm-up, but all CUs busy)
+    const int gmin = (size_t)nseg * ncol >= 4096 ? 13 : 5;          // short signals: shorter runs (more warm-up, but all CUs busy)
     if (G < gmin) G = gmin;
     // (tests/test_dsp_float64.py, every output hop against float64: frames 1..4 and 13..17, one stem -> G = 5 with nseg mod G taking every value; 1400 frames x 3 stems
     // -> G = 13; 2100 x 5 -> G = 14, 755 workgroups; 4500 x 3 at F = 1088 -> G = 14 on the table kernel.  A change to this rule moves those shapes as well.)
@@ -830,6 +931,19 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
     // one stem per workgroup: 32 accumulator + 54 prefetch registers + the FFT fit in 256 VGPRs at 2 workgroups per CU
     // F > 1024: eight mask registers per channel do not fit the 168-VGPR budget of the three-per-CU form (22 dwords would spill): the two-per-CU kernel
     if (p.ext && (!p.masks || p.ext_stem < (size_t)p.frames * 2)) return -1;      // the table holds [frames][2] gains per stem, derived from masks
+    if (p.n_out) {                                       // stem remix: the MIX forms by the same F rule (ratio is their run-time flag)
+        const dim3 grid(blocks * p.n_out);
+        if (p.F > 1024) {
+            if (O > 0 && p.ext) SRT_LAUNCH((srt_istft_ola_mix_kernel<true, true>), grid, dim3(256), 0, s, p, G, O);
+            else if (O > 0) SRT_LAUNCH((srt_istft_ola_mix_kernel<true, false>), grid, dim3(256), 0, s, p, G, O);
+            else if (p.ext) SRT_LAUNCH((srt_istft_ola_mix_kernel<false, true>), grid, dim3(256), 0, s, p, G, 0);
+            else SRT_LAUNCH((srt_istft_ola_mix_kernel<false, false>), grid, dim3(256), 0, s, p, G, 0);
+        } else if (O > 0 && p.ext) SRT_LAUNCH((srt_istft_ola3_mix_kernel<4, true, true>), grid, dim3(256), 0, s, p, G, O);
+        else if (O > 0) SRT_LAUNCH((srt_istft_ola3_mix_kernel<4, true, false>), grid, dim3(256), 0, s, p, G, O);
+        else if (p.ext) SRT_LAUNCH((srt_istft_ola3_mix_kernel<4, false, true>), grid, dim3(256), 0, s, p, G, 0);
+        else SRT_LAUNCH((srt_istft_ola3_mix_kernel<4, false, false>), grid, dim3(256), 0, s, p, G, 0);
+        return srt_launch_status();
+    }
     if (p.ext) {                                         // average mask extension: the same choice among the EXT forms
         const dim3 grid(blocks * p.nstems);
         const bool ratio = p.ratio && p.nstems > 1;

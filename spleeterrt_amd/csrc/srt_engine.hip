@@ -100,7 +100,9 @@ struct ForwardRecord {
 #define SRT_BATCH_SLOTS 4
 // `overlap`: the rows consecutive network tiles share (srtSetOverlap) - a sequence captured at one overlap is never replayed at another.
 // `mask_ext`: the rule for bins >= F (srtSetMaskExtension), for the same reason.
-struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; int overlap, mask_ext; };
+// `mix_gen`: the generation of the stem remix matrix (srtSetMix bumps it; 0 while the mix is off) - a changed matrix never replays a graph captured with the old one
+// (the matrix travels by value in the captured launch).
+struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; int overlap, mask_ext; unsigned mix_gen; };
 // left: e->last as the capture left it (an eager call in between may have changed it)
 struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; ForwardRecord left; };
 #define SRT_GRAPH_SLOTS 4
@@ -154,6 +156,10 @@ struct srt_engine {
     // average mask extension (srtSetMaskExtension): the gain table [n_stems][rows_cap][2], allocated when the mode is first switched on
     int mask_ext = SRT_MASK_EXT_CONSTANT;
     float* ext = nullptr;
+    // stem remix (srtSetMix): mix_out > 0 - the inverse transform of srtIstft / srtSeparate / the host stream writes mix_out pairs, each the chain
+    // of mix[m] over the stems' gains; mix_gen counts the calls that switched it on (the graph key)
+    int mix_out = 0; unsigned mix_gen = 0;
+    float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1] = {};
     // packed batches of tracks (srtSeparateBatch): the device track table (max_tiles rows: every track takes at least one tile) and a ring of pinned
     // host slots it is uploaded from, each reused only after the copy from it issued SRT_BATCH_SLOTS calls earlier has completed (bev)
     SrtBatchTrack* btab = nullptr; SrtBatchTrack* bpin = nullptr;
@@ -194,6 +200,24 @@ int srtSetOverlap(srt_engine* e, int overlap_rows)
     return 0;
 }
 int srt_engine_overlap(const srt_engine* e) { return e->overlap; }
+
+static const char* const MIX_REFUSED = "%s: not available with the stem remix on (srtSetMix; DESIGN.md 16 lists it as a follow-up): srtSetMix(e, 0, NULL) first";
+int srtSetMix(srt_engine* e, int n_out, const float* h_gain)
+{
+    if (!e) return fail(-1, "srtSetMix: null engine");
+    if (n_out < 0 || n_out > SRT_MAX_STEMS) return fail(-1, "srtSetMix: n_out must be 0 (off) .. SRT_MAX_STEMS");
+    if (n_out && !h_gain) return fail(-1, "srtSetMix: null gain matrix");
+    const int S = e->cfg.n_stems;
+    for (int i = 0; i < n_out * (S + 1); ++i) if (!isfinite(h_gain[i])) return fail(-1, "srtSetMix: every gain must be finite");
+    if (n_out && e->wiener) return fail(-1, "srtSetMix: the stem remix is not available with the Wiener filter on (the mix of filtered spectra is a follow-up, DESIGN.md 16): srtSetWiener(e, 0) first");
+    memset(e->mix, 0, sizeof e->mix);
+    for (int m = 0; m < n_out; ++m) for (int s = 0; s <= S; ++s) e->mix[m][s] = h_gain[m * (S + 1) + s];
+    e->mix_out = n_out;
+    if (n_out) { if (!++e->mix_gen) ++e->mix_gen; }
+    return 0;
+}
+int srtMixOutputs(const srt_engine* e) { return e ? e->mix_out : 0; }
+int srt_engine_mix(const srt_engine* e) { return e->mix_out; }
 
 static const char* const MASK_EXT_REFUSED = "%s: not available with the average mask extension (srtSetMaskExtension; DESIGN.md 15 lists it as a follow-up): srtSetMaskExtension(e, SRT_MASK_EXT_CONSTANT) first";
 static bool stream_capturing(const srt_engine* e);
@@ -888,7 +912,8 @@ static int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int ns
 }
 
 // inverse transform of `nstems` stems of one spectrum under their masks (nullptr: all-ones) into [nstems][2][srtIstftLength(rows)]; oob: per stem, the weight of bins >= F
-static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out)
+// mix (srtSetMix; only istft_issue sets it): d_out is [mix_out][2][len], output m the chain of e->mix[m] over the stems' gains
+static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out, bool mix = false)
 {
     DeviceScope ds(e->device);
     const int T = e->cfg.T;
@@ -901,6 +926,7 @@ static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const fl
     for (int s = 0; s < nstems; ++s) p.oob[s] = ext ? 1.0f : oob[s];     // the mean of an all-ones mask is 1 exactly: no table without masks
     p.ratio = ratio ? 1 : 0; p.masks16 = masks16 ? 1 : 0;
     p.frames_out = nullptr; p.out = d_out; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
+    if (mix) { p.n_out = e->mix_out; memcpy(p.mix, e->mix, sizeof p.mix); }
     if (ext && masks) {
         const int rc = mask_ext_issue(e, masks, p.masks16, nstems, p.ntiles, (int)rows, p.ratio, O);
         if (rc) return rc;
@@ -917,7 +943,7 @@ static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const fl
     if (!e || !d_spec || !d_out) return fail(-1, "srtIstft: null argument");
     if (rows < 1) return fail(-1, "srtIstft: no rows");
     if (d_masks && tiles_of(e, rows) > (size_t)e->cfg.max_tiles) return fail(-1, e->overlap ? "srtIstft: more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtIstft: rows exceed max_tiles * T");
-    return istft_launch(e, (const float2*)d_spec, rows, d_masks, e->cfg.n_stems, e->cfg.oob_weight, ratio, masks16, d_out);
+    return istft_launch(e, (const float2*)d_spec, rows, d_masks, e->cfg.n_stems, e->cfg.oob_weight, ratio, masks16, d_out, e->mix_out > 0);
 }
 // (the public entry applies the masks as they are given: srtRatioMask is its caller's business)
 int srtIstft(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out) { return istft_issue(e, d_spec, rows, d_masks, d_out, false); }
@@ -974,6 +1000,7 @@ int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float*
     if (!e || !d_spec || !d_masks || !d_out) return fail(-1, "srtIstftWiener: null argument");
     DeviceScope ds(e->device);
     if (iterations < 1 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtIstftWiener: iterations must be 1..3");
+    if (e->mix_out) return fail(-1, MIX_REFUSED, "srtIstftWiener");
     if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtIstftWiener");      // its kernels index masks by (row / T, row % T)
     if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtIstftWiener");    // the filter's own gains above F would have to be defined first
     if (rows < 1 || (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles) return fail(-1, "srtIstftWiener: need 1 <= rows <= max_tiles * T");
@@ -988,6 +1015,7 @@ int srtSetWiener(srt_engine* e, int iterations)
     if (iterations < 0 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtSetWiener: iterations must be 0 (off) or 1..3");
     if (iterations && e->cfg.ratio_mask) return fail(-1, "srtSetWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
     if (iterations && e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtSetWiener");
+    if (iterations && e->mix_out) return fail(-1, MIX_REFUSED, "srtSetWiener");
     DeviceScope ds(e->device);
     if (iterations) { const int rc = ensure_wiener_ws(e); if (rc) return rc; }
     e->wiener = iterations;
@@ -999,7 +1027,8 @@ int srt_engine_wiener(const srt_engine* e) { return e->wiener; }
 // fp16 mode: the masks between the head and the inverse transform - the engine's own buffer, never seen by a caller - are halves where both kernels take them
 // (srt_head_rows_kernel<.., true> / srt_istft_ola3_kernel<.., true>: F <= 1024, no ratio mask, no Wiener filter (fp32 masks), head launches of >= 1024
 // workgroups: srt_head_out16_ok; sw.m16 = 0: floats, for A/B runs)
-static bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw) { return e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && !e->wiener && e->cfg.F <= 1024 && sw.m16; }
+// (nor with the stem remix: there is no half-mask MIX kernel)
+static bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw) { return e->cfg.precision == SRT_PREC_F16 && e->act16 && !e->cfg.ratio_mask && !e->wiener && !e->mix_out && e->cfg.F <= 1024 && sw.m16; }
 
 static int separate_issue(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out)
 {
@@ -1025,6 +1054,7 @@ int srtSeparateEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, s
     GraphKey k;
     const bool valid = graph_prepare(e, d_L && d_R && d_out && frames <= rows, ntiles, 2, sw, &k);
     k.p0 = d_L; k.p1 = d_R; k.p2 = d_out; k.n = n; k.frames = frames; k.rows = rows; k.wiener = e->wiener; k.overlap = e->overlap; k.mask_ext = e->mask_ext;
+    k.mix_gen = e->mix_out ? e->mix_gen : 0;
     return run_graphed(e, k, valid, [&]() { return separate_issue(e, sw, d_L, d_R, n, frames, rows, d_out); });
 }
 
@@ -1092,6 +1122,7 @@ static int cli_check(srt_engine* e, int stems)
     if (e->cfg.n_stems < 2) return fail(-1, "srtSeparateCli: the engine needs sub-networks 0 (drum) and 1 (vocal)");
     if (e->cfg.ratio_mask) return fail(-1, "srtSeparateCli: ratio_mask does not apply to the CLI flows (the sub-networks see different inputs)");
     if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateCli");       // the residual chain reads masks and writes the second network's magnitudes by tile
+    if (e->mix_out) return fail(-1, MIX_REFUSED, "srtSeparateCli");           // the flows have no stem axis to mix over
     if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtSeparateCli");     // the complex-domain residual chain subtracts oob * spec (srt_residual_kernel)
     if (e->wiener) return fail(-1, "srtSeparateCli: the Wiener filter does not apply to the CLI flows (the sub-networks see different inputs, and its statistics span the whole signal)");
     return 0;
@@ -1289,6 +1320,7 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         if (n[k] < SRT_FFT) { snprintf(what, sizeof what, "%s: track %d has fewer than 4096 samples", who, k); return fail(-1, "%s", what); }
     }
     if (e->overlap) return fail(-1, OVERLAP_REFUSED, who);                    // srtBatchPlan has no overlap argument
+    if (e->mix_out) return fail(-1, MIX_REFUSED, who);
     if (!wiener && e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
     const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
     size_t total = 0;
@@ -1428,7 +1460,7 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
     if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateHostStream");  // the blend would have to cross the chunk seams
     if (e->wiener) return fail(-1, "srtSeparateHostStream: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)");
     DeviceScope ds(e->device);
-    const int S = cli_stems ? cli_stems : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;
+    const int S = cli_stems ? cli_stems : e->mix_out ? e->mix_out : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;     // pairs staged, carried, packed and downloaded: the outputs of a remix
     const size_t chunk_rows = (size_t)e->cfg.max_tiles * T, tail = SRT_FFT - SRT_HOP;
     const size_t nchunks = (rows + chunk_rows - 1) / chunk_rows, total_len = seam.out_stride ? seam.out_stride : srtIstftLength(rows);
     const size_t in_cap = chunk_rows * SRT_HOP + tail, out_cap = srtIstftLength(chunk_rows);

@@ -216,6 +216,10 @@ struct SrtIstftParams {
     SrtDspTables tab;
     const float* ext;         // average mask extension (srtSetMaskExtension): gains of bins >= F, [nstems][..][frames][2] with ext_stem floats between stems, written by
     size_t ext_stem;          // srt_launch_mask_ext from the same masks / ratio / overlap; nullptr: the constant rule (oob).  Batch: indexed by packed row
+    // stem remix (srtSetMix): n_out > 0 - the launch writes n_out pairs [n_out][2][out_len] instead of nstems; output m applies the gain
+    // h = mix[m][nstems], then h = fmaf(mix[m][s], g_s, h) for s ascending, g_s = the gain stem s would get (the srt_istft_ola*_mix_kernel forms).  0: off
+    int n_out;
+    float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1];
 };
 // average mask extension: ext[s][r][c] = mean over k < F of the in-band gain the inverse transform applies to stem s, row r, channel c
 struct SrtMaskExtParams {
@@ -306,6 +310,7 @@ int srt_launch_istft_batch_spec(const SrtIstftParams& p, size_t stem_stride, con
 struct srt_engine;
 int srt_engine_wiener(const srt_engine* e);                                             // iterations switched on (srtSetWiener), 0: off
 int srt_engine_overlap(const srt_engine* e);                                            // rows consecutive network tiles share (srtSetOverlap), 0: off
+int srt_engine_mix(const srt_engine* e);                                                // outputs of the stem remix (srtSetMix), 0: off
 
 // streaming (srt_dsp.hip kernels, srt_stream.hip host logic): one hop = 1 forward + n_stems masked inverse FFTs + 50 % OLA
 struct SrtStreamHop {

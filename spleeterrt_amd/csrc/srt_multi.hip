@@ -244,6 +244,8 @@ static int multi_run(srt_multi* m, const float* h_L, const float* h_R, size_t n,
     for (int g = 0; g < G; ++g)
         if (srt_engine_overlap(m->eng[g])) return mfail(-1, "srtMultiSeparate: not available with overlapped tiles (srtSetOverlap > 0 on an engine; ranks would have to be cut in overlapped strides): srtSetOverlap(engine, 0) first");
     for (int g = 0; g < G; ++g)
+        if (srt_engine_mix(m->eng[g])) return mfail(-1, "srtMultiSeparate: not available with the stem remix on (srtSetMix on an engine; the seam join works on n_stems planes): srtSetMix(engine, 0, NULL) first");
+    for (int g = 0; g < G; ++g)
         if (srt_engine_wiener(m->eng[g])) return mfail(-1, "srtMultiSeparate: the Wiener filter's statistics span the whole signal (ranges on several devices would each get their own covariance): srtSetWiener(engine, 0) first");
     const size_t rows = srtStftRows(n), total_len = srtIstftLength(rows), tail = SRT_FFT - SRT_HOP;
     std::vector<srt_span> sp(G);
