@@ -112,7 +112,8 @@ SRT_API int  srtSeparateEx(srt_engine *e, const float *d_L, const float *d_R, si
  *   srtIstft              reads d_masks [n_stems][srtOverlapTiles(rows, T, O)][2][T][F] in that layout and blends;
  *   srtSeparate[Ex]       compose the three; the signal must fit max_tiles OVERLAPPED tiles.
  * Refused with -1, an error text that says "overlap" and nothing written while O > 0: srtSeparateHostStream[Ex], srtSeparateCli, srtSeparateCliHost,
- * srtSeparateBatch, srtMultiSeparate*Host, srtIstftWiener and srtSeparate[Ex] with the Wiener filter on.  O = 0 is the back-to-back path, bit for bit.
+ * srtSeparateBatch (srtSeparateBatchOverlap takes an overlap of its own), srtMultiSeparate*Host, srtIstftWiener and srtSeparate[Ex] with the Wiener filter on.
+ * O = 0 is the back-to-back path, bit for bit.
  * In graph mode the overlap is part of the captured call's key.
  * srtOverlapTiles is pure host arithmetic (no device, like srtBatchPlan): 0 for rows = 0; 0 with srtLastError() text for T < 1 or O outside 0..T/2. */
 SRT_API int  srtSetOverlap(srt_engine *e, int overlap_rows);
@@ -177,6 +178,24 @@ SRT_API int srtMixOutputs(const srt_engine *e);   /* n_out while on, 0 while off
 SRT_API int  srtBatchPlan(const size_t *n, int ntracks, int T, size_t *tile0, size_t *total_tiles);
 SRT_API int  srtSeparateBatch(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
                               const size_t *n, float *const *d_out);
+
+/* srtSeparateBatch with overlapped tiles inside every track: the overlap of srtSetOverlap, per track of a packed batch.
+ * srtBatchPlanOverlap: track k takes srtOverlapTiles(srtStftRows(n[k]), T, overlap_rows) packed tiles from tile0[k]; overlap_rows = 0 is srtBatchPlan.  Pure host
+ * arithmetic; -1 with srtLastError() text for everything srtBatchPlan refuses and for overlap_rows outside 0..T/2.
+ * srtSeparateBatchOverlap: arguments, output layout, track-table upload and slot ring as srtSeparateBatch; always eager, refused inside a stream capture.
+ * overlap_rows holds for this call whatever srtSetOverlap says - the engine's own setting is neither read nor changed - and 0 issues exactly the launches of
+ * srtSeparateBatch.  With O = overlap_rows in 1..T/2 track k's spectrum stays at the packed rows from tile0[k] * T (rows <= tiles * T), its magnitudes and masks
+ * use the overlapped layout inside its own tiles [tile0[k], tile0[k] + tiles_k) - no row of a track is ever written to or blended with a tile of another - and
+ * its stems are what srtSeparate gives for that track alone after srtSetOverlap(e, O): bit for bit with batch_invariant, up to the network's batch-dependent
+ * kernel choice otherwise.  ratio_mask (blend, then normalise), the fp16 mode's half masks and both mask-extension modes as in srtSeparate; after a call with
+ * SRT_MASK_EXT_AVERAGE srtCopyTensor("mask_ext") holds track k's rows from packed row tile0[k] * T (rows between a track's last row and its next tile boundary
+ * are not written).
+ * -1, with nothing launched or written, for everything srtSeparateBatch refuses except the engine's overlap setting, overlap_rows outside 0..T/2, more than
+ * max_tiles overlapped packed tiles (srtBatchPlanOverlap counts them), the stem remix on, or the Wiener filter on; -5 when a stem's weights are not set.
+ * srtSeparateBatch keeps refusing while srtSetOverlap > 0, and srtSeparateBatchWiener keeps refusing an overlap. */
+SRT_API int  srtBatchPlanOverlap(const size_t *n, int ntracks, int T, int overlap_rows, size_t *tile0, size_t *total_tiles);
+SRT_API int  srtSeparateBatchOverlap(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
+                                     const size_t *n, float *const *d_out, int overlap_rows);
 
 /* A long HOST-resident stream through one GPU: cut into chunks of max_tiles tiles, upload / compute / download overlapped on
  * three HIP streams with double buffers, chunk overlaps (3072 samples) added on the device.  Geometry as srtSeparateEx.

@@ -83,6 +83,8 @@ def load_library():
     L.srtBatchPlan.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.srtSeparateBatch.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp)]
     L.srtSeparateBatchWiener.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
+    L.srtBatchPlanOverlap.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.srtSeparateBatchOverlap.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
     L.srtSetGraphMode.argtypes = [vp, C.c_int]
     L.srtPrepareForward.argtypes = [vp, f32p, C.c_int, f32p]
     L.srtReleaseStaging.argtypes = [vp]
@@ -338,36 +340,49 @@ class Engine:
         self._chk(self.L.srtSeparate(self.h, _ptr(L), _ptr(R), n, _ptr(out)))
         return out
 
-    def separate_batch(self, tracks, outs=None, wiener=None):
+    def separate_batch(self, tracks, outs=None, wiener=None, overlap=None):
         """many independent tracks: [(L, R)] CUDA float32 tensors -> [stems [S,2,rows_k*1024+3072]], each equal to separate(L, R) of that track.
         The list is cut in order into calls of at most max_tiles packed tiles (stream.pack_tracks); one srtSeparateBatch per call.
         wiener: None = the engine's own setting (set_wiener), 0 = no filter, 1..3 = the multichannel Wiener filter per track with that many iterations
-        (one srtSeparateBatchWiener per call): each track as separate(L, R) on an engine with set_wiener(wiener)."""
+        (one srtSeparateBatchWiener per call): each track as separate(L, R) on an engine with set_wiener(wiener).
+        overlap: None = the engine's own setting (set_overlap), 0 = back-to-back tiles, 1..T/2 = overlapped tiles with cross-faded masks inside every track
+        (one srtSeparateBatchOverlap per call, the list cut by overlapped tiles): each track as separate(L, R) on an engine with set_overlap(overlap).  The
+        filter and an overlap exclude each other."""
         from . import stream
         t = self.torch
         ns = [L.numel() for L, _ in tracks]
         for L, R in tracks:
             assert L.is_cuda and R.is_cuda and L.dtype == t.float32 and R.dtype == t.float32 and R.numel() == L.numel()
+        wiener = self.wiener if wiener is None else int(wiener)
+        overlap = self.overlap if overlap is None else int(overlap)
+        if overlap > 0 and wiener:
+            raise EngineError("separate_batch: the Wiener filter is not available with overlapped tiles (overlap = %d, wiener = %d): pass overlap=0 or wiener=0" % (overlap, wiener))
         if outs is None:
             outs = [t.empty((self.S, 2, self.L.srtIstftLength(self.L.srtStftRows(n))), device=self.device, dtype=t.float32) for n in ns]
         assert len(outs) == len(tracks)
         for o, n in zip(outs, ns):
             assert o.is_cuda and o.is_contiguous() and o.numel() >= self.S * 2 * self.L.srtIstftLength(self.L.srtStftRows(n))
         src = [(L.contiguous(), R.contiguous()) for L, R in tracks]      # (kept alive until the calls are issued; the stream orders any reuse)
-        wiener = self.wiener if wiener is None else int(wiener)
-        own = self.wiener
+        own, own_ov = self.wiener, self.overlap
         if own and not wiener:                                           # srtSeparateBatch refuses while the engine's filter is on: off for these calls
             self.set_wiener(0)
+        if own_ov and not overlap:                                       # ... and while its overlap is on (srtSeparateBatchOverlap never reads the setting)
+            self.set_overlap(0)
         try:
-            for g in stream.pack_tracks(ns, self.T, self.max_tiles):
+            for g in stream.pack_tracks(ns, self.T, self.max_tiles, overlap):
                 k = len(g.tracks)
                 P = C.c_void_p * k
                 args = (self.h, k, P(*[src[i][0].data_ptr() for i in g.tracks]), P(*[src[i][1].data_ptr() for i in g.tracks]),
                         (C.c_size_t * k)(*[ns[i] for i in g.tracks]), P(*[outs[i].data_ptr() for i in g.tracks]))
-                self._chk(self.L.srtSeparateBatchWiener(*args, wiener) if wiener else self.L.srtSeparateBatch(*args))
+                if overlap > 0:
+                    self._chk(self.L.srtSeparateBatchOverlap(*args, overlap))
+                else:
+                    self._chk(self.L.srtSeparateBatchWiener(*args, wiener) if wiener else self.L.srtSeparateBatch(*args))
         finally:
             if own and not wiener:
                 self.set_wiener(own)
+            if own_ov and not overlap:
+                self.set_overlap(own_ov)
         return outs
 
     def separate_cli(self, L, R, stems):

@@ -332,8 +332,10 @@ __device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { Istft
 // EXT: average mask extension (srtSetMaskExtension): bins >= F of frame f take the two gains ext[stem][f][L, R] instead of oob (fetched with the frame's rows
 // from workgroup-uniform addresses: scalar loads into SGPRs, consumed before the next fetch overwrites them)
 // MIX: stem remix (srt_mix_gains): `stem` is the OUTPUT index m; no mask row is prefetched (every stem's row is read in the prologue), RATIO = false (a run-time flag)
-template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false>
-__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
+// TRK (with OV): the view is a track of a packed batch - p.ntiles is the packed total there (the masks' stem stride), and srt_ov_row clamps the primary tile with the
+// track's own overlapped count, the argument ov_tiles (unused otherwise: a whole call's count is p.ntiles)
+template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false>
+__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0)
 {
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
     cf* sy = s_mem + FFT_SMEM_F2;                        // this frame's exchange 1; the roles swap every frame
@@ -367,7 +369,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
     auto fetch = [&](int f) {                                               // 0 <= f < w.frames
         int tile = f / p.T, t = f % p.T;
         OvRow ov = { 0, 0, false, 0.0f };
-        if constexpr (OV) { ov = srt_ov_row(f, p.T, O, p.ntiles); tile = ov.j1; t = ov.k; }
+        if constexpr (OV) { ov = srt_ov_row(f, p.T, O, TRK ? ov_tiles : p.ntiles); tile = ov.j1; t = ov.k; }
         const cf* specL = spec + (size_t)f * SRT_SPEC_LD;
         const cf* specR = specL + p.spec_ch_stride;
         const float* mL = has_mask ? w.masks + ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F : p.tab.postWin;
@@ -405,7 +407,7 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
             // second barrier; the first barrier below also orders the twiddle table written before the loop
             OvRow ov = { 0, 0, false, 0.0f };
             if constexpr (OV) {
-                ov = srt_ov_row(f, p.T, O, p.ntiles);
+                ov = srt_ov_row(f, p.T, O, TRK ? ov_tiles : p.ntiles);
                 if (!RATIO && !MIX && has_mask && ov.two) {      // cross-fade of the two tiles' masks: a (row k + S of the previous tile) + w (b - a).  The a rows are read HERE,
                     // not with the prefetch (18 more staged registers spill at two workgroups per CU); the other workgroup of the CU covers the wait
                     const float* aL = w.masks + ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
@@ -681,8 +683,9 @@ __global__ void __launch_bounds__(256, 3) srt_stft_ov_kernel(const SrtStftParams
 #define ISTFT_OLA3_LDS_F2 (FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2)
 // EXT: as istft_ola_run
 // MIX: as istft_ola_run (RATIO = M16 = false)
-template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false>
-__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0)
+// TRK: as istft_ola_run
+template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false>
+__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0)
 {
     cf* sx = s_mem;
     cf* mir = s_mem + FFT_SMEM_F2;
@@ -711,7 +714,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
     auto fetch = [&](int f) {                                               // 0 <= f < w.frames
         int tile = f / p.T, t = f % p.T;
         OvRow ov = { 0, 0, false, 0.0f };
-        if constexpr (OV) { ov = srt_ov_row(f, p.T, O, p.ntiles); tile = ov.j1; t = ov.k; }
+        if constexpr (OV) { ov = srt_ov_row(f, p.T, O, TRK ? ov_tiles : p.ntiles); tile = ov.j1; t = ov.k; }
         const cf* specL = spec + (size_t)f * SRT_SPEC_LD;
         const cf* specR = specL + p.spec_ch_stride;
         const size_t mo = ((size_t)(stem * p.ntiles + tile) * 2) * tf + (size_t)t * p.F;
@@ -762,7 +765,7 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             cf v[16];
             OvRow ov = { 0, 0, false, 0.0f };
             if constexpr (OV) {
-                ov = srt_ov_row(f, p.T, O, p.ntiles);
+                ov = srt_ov_row(f, p.T, O, TRK ? ov_tiles : p.ntiles);
                 if (!RATIO && !MIX && has_mask && ov.two) {      // cross-fade of the two tiles' masks (halves are converted first): a (row k + S of the previous tile) + w (b - a).
                     // The a rows are read HERE, not with the prefetch: eight more staged registers do not fit the 168 of three workgroups per CU (9 dwords
                     // spilled when tried); the wait is covered by the CU's other workgroups and falls on O of every T - O frames only
@@ -1005,15 +1008,19 @@ __device__ __forceinline__ void srt_mask_load16(const float* __restrict__ masks,
     }
 }
 
-template <int NS, bool M16, bool RATIO, bool OV>
-__device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int O, int f, int c, int lane)
+// nt: the tile count srt_ov_row clamps the primary tile with (OV only): p.ntiles for a whole call, the track's own in a packed batch (where p.ntiles is the packed
+// total, the stem stride)
+// TRK: the row belongs to a track of a packed batch - mo / eo: its first mask element (halves for M16) / its first float of a stem's table
+template <int NS, bool M16, bool RATIO, bool OV, bool TRK = false>
+__device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int O, int f, int c, int lane, int nt, size_t mo = 0, size_t eo = 0)
 {
     constexpr int V = M16 ? 8 : 4;                      // mask values per 16-byte load
     const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
     int tile = f / p.T, t = f % p.T;
     OvRow ov = { 0, 0, false, 0.0f };
-    if constexpr (OV) { ov = srt_ov_row(f, p.T, O, p.ntiles); tile = ov.j1; t = ov.k; }
-    const size_t bo = ((size_t)tile * 2 + c) * tf + (size_t)t * p.F;                     // stem 0's row in the primary tile
+    if constexpr (OV) { ov = srt_ov_row(f, p.T, O, nt); tile = ov.j1; t = ov.k; }
+    size_t bo = ((size_t)tile * 2 + c) * tf + (size_t)t * p.F;                           // stem 0's row in the primary tile
+    if constexpr (TRK) bo += mo;
     const size_t ao = ov.two ? bo - 2 * tf + (size_t)(p.T - O) * p.F : bo;              // ... and row k + S of the previous tile
     float sum[NS];
 #pragma unroll
@@ -1051,7 +1058,7 @@ __device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int 
         float v = sum[s];
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
-        if (lane == 0) p.ext[(size_t)s * p.ext_stem + (size_t)f * 2 + c] = v / (float)p.F;
+        if (lane == 0) p.ext[(size_t)s * p.ext_stem + (TRK ? eo : 0) + (size_t)f * 2 + c] = v / (float)p.F;
     }
 }
 
@@ -1062,14 +1069,14 @@ __global__ void __launch_bounds__(256) srt_mask_ext_kernel(const SrtMaskExtParam
     if (wave >= p.rows * 2) return;                      // (wave-uniform; the kernel has no barrier)
     const int f = wave >> 1, c = wave & 1;
     switch (p.nstems) {
-    case 1: srt_mask_ext_row<1, M16, RATIO, OV>(p, O, f, c, lane); break;
-    case 2: srt_mask_ext_row<2, M16, RATIO, OV>(p, O, f, c, lane); break;
-    case 3: srt_mask_ext_row<3, M16, RATIO, OV>(p, O, f, c, lane); break;
-    case 4: srt_mask_ext_row<4, M16, RATIO, OV>(p, O, f, c, lane); break;
-    case 5: srt_mask_ext_row<5, M16, RATIO, OV>(p, O, f, c, lane); break;
-    case 6: srt_mask_ext_row<6, M16, RATIO, OV>(p, O, f, c, lane); break;
-    case 7: srt_mask_ext_row<7, M16, RATIO, OV>(p, O, f, c, lane); break;
-    default: srt_mask_ext_row<8, M16, RATIO, OV>(p, O, f, c, lane); break;
+    case 1: srt_mask_ext_row<1, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    case 2: srt_mask_ext_row<2, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    case 3: srt_mask_ext_row<3, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    case 4: srt_mask_ext_row<4, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    case 5: srt_mask_ext_row<5, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    case 6: srt_mask_ext_row<6, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    case 7: srt_mask_ext_row<7, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
+    default: srt_mask_ext_row<8, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
     }
 }
 #pragma clang fp contract(fast)
@@ -1187,6 +1194,81 @@ __global__ void __launch_bounds__(256, OLA3 ? 3 : 2) srt_istft_batch_spec_kernel
     else istft_ola_run<false>(p, w, stem, run - tk.wg_istft, G, s_mem);
 }
 
+// ---- overlapped tiles inside a packed batch (srtSeparateBatchOverlap): track k owns the packed tiles [tile0, tile0 + ntiles) with ntiles =
+// srtOverlapTiles(rows, T, O), in the overlapped layout of section 13 INSIDE those tiles; its spectrum stays at packed rows from tile0 * T (rows <= ntiles * T).
+// Each workgroup runs the single-signal overlap bodies on its track's view with the track's own tile count, so a row's second magnitude copy and a frame's
+// blend partner are always a tile of the same track (srt_ov_row: only when j1 > 0 inside the track).
+
+// stft_run<true> per track.  The pad: rows of a tile past the track's last row exist only in its last tile J = ntiles - 1 (tile J - 1 ends at row J S + O <= rows);
+// its slots (J, t), t in [rows - J S, T), are zeroed and shared out over the track's workgroups after their transforms, as in srt_stft_batch_kernel.
+__global__ void __launch_bounds__(256, 3) srt_stft_batch_ov_kernel(const SrtStftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int fpb, int O)
+{
+    __shared__ cf s_mem[FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2];
+    const SrtBatchTrack tk = tracks[srt_batch_track<false>(tracks, ntracks, blockIdx.x)];
+    const int blk = blockIdx.x - tk.wg_stft;
+    float* mag = p.mag + (size_t)tk.tile0 * 2 * p.T * p.F;
+    const StftView w = { tk.L, tk.R, tk.n, tk.frames, tk.rows, p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD, mag };
+    stft_run<true>(p, w, blk, fpb, s_mem, O, tk.ntiles);
+    const int J = tk.ntiles - 1, t0 = tk.rows - J * (p.T - O);              // 1 <= t0 <= T: the last tile's first pad slot
+    const int nwg = (tk.rows + fpb - 1) / fpb, pad = p.T - t0;
+    float* magL = mag + (size_t)J * 2 * p.T * p.F;
+    float* magR = magL + (size_t)p.T * p.F;
+    const int tb = t0 + (int)((long)(blk + 1) * pad / nwg);
+    for (int t = t0 + (int)((long)blk * pad / nwg); t < tb; ++t)
+        for (int k = threadIdx.x; k < p.F; k += 256) { magL[(size_t)t * p.F + k] = 0.f; magR[(size_t)t * p.F + k] = 0.f; }
+}
+
+// srt_istft_batch_kernel with the overlap bodies: srt_ov_row's tile count is the track's (the bodies' TRK form), p.ntiles stays the packed count (the stem stride).
+// EXT: the average mask extension (the table is indexed by packed row: srt_mask_ext_batch_kernel) - a template argument here, not a second kernel name
+template <bool OLA3, bool RATIO, bool M16, bool EXT>
+__global__ void __launch_bounds__(256, OLA3 && !RATIO ? 3 : 2) srt_istft_batch_ov_kernel(const SrtIstftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int G, int O)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[OLA3 ? ISTFT_OLA3_LDS_F2 : ISTFT_OLA_LDS_F2];
+    const SrtBatchTrack tk = tracks[srt_batch_track<true>(tracks, ntracks, run)];
+    const size_t mo = (size_t)tk.tile0 * 2 * p.T * p.F;
+    IstftView w;
+    w.spec = p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD;
+    w.masks = M16 ? reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(p.masks) + mo) : p.masks + mo;      // (the launcher checks that masks are given)
+    w.out = tk.out; w.out_len = tk.out_len; w.frames = tk.rows;
+    w.ext = EXT ? p.ext + (size_t)tk.tile0 * p.T * 2 : nullptr;
+    if constexpr (OLA3) istft_ola3_run<4, RATIO, M16, true, EXT, false, true>(p, w, stem, run - tk.wg_istft, G, s_mem, O, tk.ntiles);
+    else istft_ola_run<RATIO, true, EXT, false, true>(p, w, stem, run - tk.wg_istft, G, s_mem, O, tk.ntiles);
+}
+
+// The gain table of the average mask extension for such a batch: one wave per (packed row, channel), as srt_mask_ext_kernel.  The row's track is the last one
+// with tile0 * T <= row (the wave index is made uniform first, so every probe of the table is a scalar load); the row is mapped with the TRACK's tile count, its
+// blend partner is read inside the track's tiles, and ext is written at the packed row.  Rows past the track's own (the rest of its last tile) are skipped.
+// Per row the arithmetic and the order of the additions are srt_mask_ext_row's: a track's table is the single call's, bit for bit.
+#pragma clang fp contract(off)
+template <bool M16, bool RATIO>
+__global__ void __launch_bounds__(256) srt_mask_ext_batch_kernel(const SrtMaskExtParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int O)
+{
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    if (wave >= p.rows * 2) return;                      // (wave-uniform; the kernel has no barrier)
+    const int row = wave >> 1, c = wave & 1;
+    int lo = 0, hi = ntracks - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tracks[mid].tile0 * p.T <= row) lo = mid; else hi = mid - 1;
+    }
+    const int tile0 = tracks[lo].tile0, rows = tracks[lo].rows, nt = tracks[lo].ntiles;
+    const int f = row - tile0 * p.T;
+    if (f >= rows) return;
+    const size_t mo = (size_t)tile0 * 2 * p.T * p.F, eo = (size_t)tile0 * p.T * 2;      // the track's first mask element (halves for M16) and table entry
+    switch (p.nstems) {
+    case 1: srt_mask_ext_row<1, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    case 2: srt_mask_ext_row<2, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    case 3: srt_mask_ext_row<3, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    case 4: srt_mask_ext_row<4, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    case 5: srt_mask_ext_row<5, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    case 6: srt_mask_ext_row<6, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    case 7: srt_mask_ext_row<7, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    default: srt_mask_ext_row<8, M16, RATIO, true, true>(p, O, f, c, lane, nt, mo, eo); break;
+    }
+}
+#pragma clang fp contract(fast)
+
 // smallest q >= q0 with count(q) <= limit (count falls as q grows); q0 when even qmax does not get there
 template <class C>
 static int srt_batch_step(int q0, int qmax, long limit, C&& count)
@@ -1236,19 +1318,41 @@ int srt_batch_geometry(SrtBatchTrack* t, int ntracks, int T, int F, int nstems, 
     return 0;
 }
 
-int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s)
+// overlap > 0: every track's magnitudes in the overlapped layout inside its own tiles (the table's ntiles = srtOverlapTiles(rows, T, overlap), checked by the caller, which
+// filled the table); 0: the back-to-back kernels as they always were
+int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap)
 {
-    if (!p.mag || g.stft_blocks <= 0) return -1;
-    SRT_LAUNCH(srt_stft_batch_kernel, dim3(g.stft_blocks), dim3(256), 0, s, p, d_tracks, ntracks, g.fpb);
+    if (!p.mag || g.stft_blocks <= 0 || overlap < 0 || overlap > p.T / 2) return -1;
+    if (overlap > 0) SRT_LAUNCH(srt_stft_batch_ov_kernel, dim3(g.stft_blocks), dim3(256), 0, s, p, d_tracks, ntracks, g.fpb, overlap);
+    else SRT_LAUNCH(srt_stft_batch_kernel, dim3(g.stft_blocks), dim3(256), 0, s, p, d_tracks, ntracks, g.fpb);
     return srt_launch_status();
 }
 
-// the same form per geometry as srt_launch_istft
-int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s)
+// the same form per geometry as srt_launch_istft; overlap as srt_launch_stft_batch (the masks are required then: there is nothing to blend without them)
+int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap)
 {
-    if (g.istft_runs <= 0) return -1;
+    if (g.istft_runs <= 0 || overlap < 0 || overlap > p.T / 2 || (overlap > 0 && !p.masks)) return -1;
     if (p.masks16 && (!p.masks || p.F > 1024 || (p.ratio && p.nstems > 1))) return -1;
     const dim3 grid(g.istft_runs * p.nstems);
+    if (overlap > 0) {                                   // the overlap instantiations (the forms below keep their code)
+        const int O = overlap;
+        const bool ratio = p.ratio && p.nstems > 1;
+        if (p.ext) {
+            if (p.ext_stem < (size_t)p.frames * 2) return -1;
+            if (ratio) {
+                if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_ov_kernel<false, true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+                else SRT_LAUNCH((srt_istft_batch_ov_kernel<true, true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+            } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_ov_kernel<false, false, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+            else if (p.masks16) SRT_LAUNCH((srt_istft_batch_ov_kernel<true, false, true, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+            else SRT_LAUNCH((srt_istft_batch_ov_kernel<true, false, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+        } else if (ratio) {
+            if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_ov_kernel<false, true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+            else SRT_LAUNCH((srt_istft_batch_ov_kernel<true, true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+        } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_ov_kernel<false, false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+        else if (p.masks16) SRT_LAUNCH((srt_istft_batch_ov_kernel<true, false, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+        else SRT_LAUNCH((srt_istft_batch_ov_kernel<true, false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O);
+        return srt_launch_status();
+    }
     if (p.ext) {
         if (!p.masks || p.ext_stem < (size_t)p.frames * 2) return -1;
         if (p.ratio && p.nstems > 1) {
@@ -1265,6 +1369,24 @@ int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_track
     } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_kernel<false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     else if (p.masks16) SRT_LAUNCH((srt_istft_batch_kernel<true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     else SRT_LAUNCH((srt_istft_batch_kernel<true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+    return srt_launch_status();
+}
+
+// srt_launch_mask_ext for a packed batch with overlapped tiles: p on the packed buffers (ntiles = the packed tile count, rows = every packed row = ntiles * T),
+// the per-track rows and tile counts from the table; the gates are srt_launch_mask_ext's.  (overlap = 0 needs no table: a packed row maps to its packed tile.)
+int srt_launch_mask_ext_batch(const SrtMaskExtParams& p, const SrtBatchTrack* d_tracks, int ntracks, hipStream_t s, int overlap)
+{
+    if (overlap == 0) return srt_launch_mask_ext(p, s, 0);
+    if (p.rows <= 0) return 0;
+    if (!p.masks || !p.ext || !d_tracks || ntracks < 1 || p.nstems < 1 || p.nstems > SRT_MAX_STEMS || p.F < 64 || p.F % 64 || p.ext_stem < (size_t)p.rows * 2) return -1;
+    if (((uintptr_t)p.masks & 15) != 0) return -1;      // 16-byte loads (a track's first tile keeps the alignment: F % 64 == 0)
+    if (overlap < 0 || overlap > p.T / 2 || (size_t)p.ntiles * p.T < (size_t)p.rows) return -1;
+    const bool ratio = p.ratio && p.nstems > 1;
+    if (p.masks16 && (ratio || p.F > 1024)) return -1;
+    const dim3 grid((p.rows * 2 + 3) / 4), block(256);
+    if (ratio) SRT_LAUNCH((srt_mask_ext_batch_kernel<false, true>), grid, block, 0, s, p, d_tracks, ntracks, overlap);
+    else if (p.masks16) SRT_LAUNCH((srt_mask_ext_batch_kernel<true, false>), grid, block, 0, s, p, d_tracks, ntracks, overlap);
+    else SRT_LAUNCH((srt_mask_ext_batch_kernel<false, false>), grid, block, 0, s, p, d_tracks, ntracks, overlap);
     return srt_launch_status();
 }
 

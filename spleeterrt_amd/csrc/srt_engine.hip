@@ -899,14 +899,15 @@ int srtStft(srt_engine* e, const float* d_L, const float* d_R, size_t n, float* 
 
 // average mask extension: the gain table of the inverse transform that follows on the same stream, from the masks that transform will apply
 // (rows <= rows_cap: every caller has checked its tiles against max_tiles)
-static int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O)
+// (tracks: a packed batch with overlapped tiles - rows = the packed rows, each mapped inside its own track: srt_launch_mask_ext_batch)
+static int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks = nullptr, int ntracks = 0)
 {
     if (!e->ext || (size_t)rows > e->rows_cap || nstems != e->cfg.n_stems) return fail(-1, "mask extension: no gain table for this call (srtSetMaskExtension allocates it for n_stems x max_tiles * T rows)");
     SrtMaskExtParams m; memset(&m, 0, sizeof m);
     m.masks = masks; m.masks16 = masks16; m.nstems = nstems; m.ntiles = ntiles; m.T = e->cfg.T; m.F = e->cfg.F; m.rows = rows; m.ratio = ratio;
     m.ext = e->ext; m.ext_stem = e->rows_cap * 2;
     TimerScope ts(e, "mask_ext");
-    if (srt_launch_mask_ext(m, e->stream, O)) return fail(-2, "mask extension launch failed (the masks must be 16-byte aligned)");
+    if (tracks ? srt_launch_mask_ext_batch(m, tracks, ntracks, e->stream, O) : srt_launch_mask_ext(m, e->stream, O)) return fail(-2, "mask extension launch failed (the masks must be 16-byte aligned)");
     e->last.ext_rows = rows;
     return 0;
 }
@@ -1274,6 +1275,21 @@ int srtBatchPlan(const size_t* n, int ntracks, int T, size_t* tile0, size_t* tot
     return 0;
 }
 
+// the same with overlapped tiles inside every track (srtSeparateBatchOverlap): track k takes overlap_tiles(rows_k, T, O) packed tiles; O = 0 is srtBatchPlan
+int srtBatchPlanOverlap(const size_t* n, int ntracks, int T, int overlap_rows, size_t* tile0, size_t* total_tiles)
+{
+    if (!n || !total_tiles || ntracks < 1 || T < 1) return fail(-1, "srtBatchPlanOverlap: need ntracks >= 1, T >= 1, n and total_tiles");
+    if (overlap_rows < 0 || overlap_rows > T / 2) return fail(-1, "srtBatchPlanOverlap: the overlap must be 0 .. T / 2 rows");
+    for (int k = 0; k < ntracks; ++k) if (n[k] < SRT_FFT) return fail(-1, "srtBatchPlanOverlap: every track needs at least 4096 samples");
+    size_t t = 0;
+    for (int k = 0; k < ntracks; ++k) {
+        if (tile0) tile0[k] = t;
+        t += overlap_tiles(srtStftRows(n[k]), T, overlap_rows);
+    }
+    *total_tiles = t;
+    return 0;
+}
+
 // the device track table and the pinned upload slots, allocated on the first batch call and kept until srtDestroy
 static int ensure_batch(srt_engine* e)
 {
@@ -1306,11 +1322,13 @@ static int ensure_batch_wiener(srt_engine* e)
     return 0;
 }
 
-// What the two batch entry points share, up to and including the forward: the argument checks (`who` names the entry point; wiener = the iterations of
-// srtSeparateBatchWiener, 0 for srtSeparateBatch), the track table(s) and their upload from a pinned slot, the batched STFT and the network over the packed tiles.
+// What the batch entry points share, up to and including the forward: the argument checks (`who` names the entry point; wiener = the iterations of
+// srtSeparateBatchWiener, 0 for the others), the track table(s) and their upload from a pinned slot, the batched STFT and the network over the packed tiles.
+// overlap: -1 for the entry points that have no overlap argument (they refuse while the engine's own setting is on); >= 0: srtSeparateBatchOverlap's argument, which
+// holds for the call whatever the engine's setting says (0: the back-to-back plan and kernels)
 struct BatchCall { size_t total; SrtBatchGrid g; size_t ch_stride; int wchunks; };
 static int batch_forward(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
-                         int wiener, BatchCall* bc)
+                         int wiener, int overlap, BatchCall* bc)
 {
     if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "%s: need ntracks >= 1 and the four track arrays", who);
     const SrtSwitches sw = srt_read_switches();
@@ -1319,14 +1337,18 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         if (!d_L[k] || !d_R[k] || !d_out[k]) { snprintf(what, sizeof what, "%s: null pointer in track %d", who, k); return fail(-1, "%s", what); }
         if (n[k] < SRT_FFT) { snprintf(what, sizeof what, "%s: track %d has fewer than 4096 samples", who, k); return fail(-1, "%s", what); }
     }
-    if (e->overlap) return fail(-1, OVERLAP_REFUSED, who);                    // srtBatchPlan has no overlap argument
-    if (e->mix_out) return fail(-1, MIX_REFUSED, who);
-    if (!wiener && e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
     const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
+    if (overlap < 0 && e->overlap) return fail(-1, OVERLAP_REFUSED, who);     // srtBatchPlan has no overlap argument: srtSeparateBatchOverlap
+    if (overlap > T / 2) return fail(-1, "%s: the overlap must be 0 .. T / 2 rows", who);
+    const int O = overlap > 0 ? overlap : 0;
+    if (e->mix_out) return fail(-1, MIX_REFUSED, who);
+    if (overlap >= 0 && e->wiener) return fail(-1, "%s: not available with the Wiener filter on (its kernels index masks by back-to-back tiles): srtSetWiener(e, 0) first", who);
+    if (!wiener && e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
     size_t total = 0;
-    if (srtBatchPlan(n, ntracks, T, nullptr, &total)) return -1;
+    if (O ? srtBatchPlanOverlap(n, ntracks, T, O, nullptr, &total) : srtBatchPlan(n, ntracks, T, nullptr, &total)) return -1;
     if (total > (size_t)e->cfg.max_tiles) {
-        snprintf(what, sizeof what, "%s: the tracks take %zu tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", who, total);
+        if (O) snprintf(what, sizeof what, "%s: the tracks take %zu overlapped tiles, more than max_tiles (srtBatchPlanOverlap counts them; split the list into calls that fit)", who, total);
+        else snprintf(what, sizeof what, "%s: the tracks take %zu tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", who, total);
         return fail(-1, "%s", what);
     }
     if (wiener && total * T / 16 > 65535) return fail(-1, "%s: more than 65535 blocks of 16 packed rows (the filter's grid)", who);
@@ -1344,7 +1366,7 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         SrtBatchTrack& t = h[k];
         t.L = d_L[k]; t.R = d_R[k]; t.n = n[k];
         t.frames = (int)srtStftFrames(n[k]); t.rows = (int)srtStftRows(n[k]);
-        t.tile0 = (int)tile0; t.ntiles = (t.rows + T - 1) / T; tile0 += t.ntiles;
+        t.tile0 = (int)tile0; t.ntiles = (int)overlap_tiles((size_t)t.rows, T, O); tile0 += t.ntiles;      // (O = 0: ceil(rows / T))
         t.out = d_out[k]; t.out_len = srtIstftLength(t.rows);
     }
     if (srt_batch_geometry(h, ntracks, T, F, S, &bc->g)) return fail(-1, "%s: batch geometry out of range", who);
@@ -1365,20 +1387,20 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         p.spec = e->spec; p.spec_ch_stride = bc->ch_stride; p.mag = e->mag;
         p.rows_total = (int)(total * T); p.T = T; p.F = F; p.tab = tables_of(e);
         TimerScope ts(e, "stft_batch");
-        if (srt_launch_stft_batch(p, e->btab, ntracks, bc->g, e->stream)) return fail(-2, "batched stft launch failed");
+        if (srt_launch_stft_batch(p, e->btab, ntracks, bc->g, e->stream, O)) return fail(-2, "batched stft launch failed");
     }
     // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue (never with the filter, which reads fp32 masks)
     return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, !wiener && masks16_wanted(e, sw));
 }
 
-int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
+// srtSeparateBatch (overlap = -1) and srtSeparateBatchOverlap (overlap >= 0): the shared front, the gain table of the average mask extension, one batched inverse
+static int batch_separate(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap)
 {
-    if (!e) return fail(-1, "srtSeparateBatch: null engine");
     DeviceScope ds(e->device);
     BatchCall bc;
-    int rc = batch_forward(e, "srtSeparateBatch", ntracks, d_L, d_R, n, d_out, 0, &bc);
+    int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, 0, overlap, &bc);
     if (rc) return rc;
-    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
+    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems, O = overlap > 0 ? overlap : 0;
     SrtIstftParams q; memset(&q, 0, sizeof q);
     q.spec = e->spec; q.spec_ch_stride = bc.ch_stride; q.frames = (int)(bc.total * T);
     q.masks = e->masks; q.masks16 = e->last.masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)bc.total; q.T = T; q.F = F;
@@ -1386,12 +1408,27 @@ int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const 
     q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
     q.tab = tables_of(e);
     if (e->mask_ext == SRT_MASK_EXT_AVERAGE) {                 // row-local: one table over the packed rows, each track reads its own (tile0 * T onwards)
-        if ((rc = mask_ext_issue(e, q.masks, q.masks16, S, q.ntiles, q.frames, q.ratio, 0))) return rc;
+        // (with an overlap a packed row's tile and blend partner depend on the track it lies in: the batch form of the table kernel)
+        if ((rc = mask_ext_issue(e, q.masks, q.masks16, S, q.ntiles, q.frames, q.ratio, O, O ? e->btab : nullptr, ntracks))) return rc;
         q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
     }
     TimerScope ts(e, "istft_batch");
-    if (srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream)) return fail(-2, "batched istft launch failed");
+    if (srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
     return 0;
+}
+
+int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
+{
+    if (!e) return fail(-1, "srtSeparateBatch: null engine");
+    return batch_separate(e, "srtSeparateBatch", ntracks, d_L, d_R, n, d_out, -1);
+}
+
+// srtSeparateBatch with overlapped tiles inside every track: overlap_rows holds for this call, the engine's own srtSetOverlap is neither read nor changed
+int srtSeparateBatchOverlap(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap_rows)
+{
+    if (!e) return fail(-1, "srtSeparateBatchOverlap: null engine");
+    if (overlap_rows < 0) return fail(-1, "srtSeparateBatchOverlap: the overlap must be 0 .. T / 2 rows");
+    return batch_separate(e, "srtSeparateBatchOverlap", ntracks, d_L, d_R, n, d_out, overlap_rows);
 }
 
 // srtSeparateBatch with the Wiener filter per track: the shared front (fp32 masks), `iterations` x (statistics + finalize) and the filter over the packed rows
@@ -1405,7 +1442,7 @@ int srtSeparateBatchWiener(srt_engine* e, int ntracks, const float* const* d_L, 
     if (e->cfg.ratio_mask) return fail(-1, "srtSeparateBatchWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
     if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, who);
     BatchCall bc;
-    const int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, iterations, &bc);
+    const int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, iterations, -1, &bc);
     if (rc) return rc;
     const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
     const size_t cap = (size_t)e->cfg.max_tiles, tf = batch_wiener_track_floats(e);

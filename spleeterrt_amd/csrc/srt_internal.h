@@ -239,14 +239,18 @@ struct SrtBatchTrack {
     const float* L; const float* R; size_t n;    // the track's PCM, n >= 4096 samples
     float* out; size_t out_len;                  // its stems [nstems][2][out_len], out_len = rows * 1024 + 3072
     int frames, rows;                            // srtStftFrames(n), srtStftRows(n)
-    int tile0, ntiles;                           // packed tiles [tile0, tile0 + ntiles) = ceil(rows / T) (spectrum rows from tile0 * T)
+    int tile0, ntiles;                           // packed tiles [tile0, tile0 + ntiles), ntiles = srtOverlapTiles(rows, T, O) = ceil(rows / T) at O = 0 (spectrum rows from tile0 * T)
     int wg_stft, wg_istft;                       // the track's first workgroup of the batched STFT / first run of the batched inverse (srt_batch_geometry)
 };
 struct SrtBatchGrid { int fpb, stft_blocks, G, istft_runs; };
 int srt_batch_geometry(SrtBatchTrack* t, int ntracks, int T, int F, int nstems, SrtBatchGrid* g);       // host: fills wg_stft / wg_istft
 // p as srt_launch_stft / srt_launch_istft on the packed buffers (mag required; p.ntiles = the packed tile count); the per-track fields are taken from d_tracks
-int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s);
-int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s);
+// overlap > 0 (srtSeparateBatchOverlap): every track's magnitudes / masks are in the overlapped layout inside its own tiles, the table's ntiles =
+// srtOverlapTiles(rows, T, overlap); the overlap is an argument of its own, as in srt_launch_stft / srt_launch_istft.  0: the kernels as they always were
+int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap = 0);
+int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap = 0);
+// the gain table of the average mask extension over the packed rows of such a batch (p.rows = p.ntiles * T packed rows; rows past a track's own are left alone)
+int srt_launch_mask_ext_batch(const SrtMaskExtParams& p, const SrtBatchTrack* d_tracks, int ntracks, hipStream_t s, int overlap);
 
 // residual chain of the offline CLI (main.c:845-866): res = spec - spec*mask (bins >= F: spec - spec*oob), |res|*4096 -> mag
 struct SrtResidualParams {

@@ -64,15 +64,16 @@ def rank_span(n, T, rank=0, world=1):
 BatchGroup = namedtuple("BatchGroup", "tracks tile0 ntiles")
 
 
-def pack_tracks(ns, T, max_tiles):
+def pack_tracks(ns, T, max_tiles, overlap=0):
     """Greedy grouping, in order, of independent tracks of ns[k] samples into srtSeparateBatch calls of at most max_tiles packed
     tiles: a call takes tracks until the next one would not fit.  Track k takes ceil(stft_rows(ns[k]) / T) tiles, packed from
-    tile0.  Returns [BatchGroup(tracks = indices into ns, tile0 = each track's first tile in its call, ntiles = the call's total)]."""
+    tile0; with overlap = O > 0 (srtSeparateBatchOverlap, srtBatchPlanOverlap) it takes overlap_tiles(stft_rows(ns[k]), T, O).
+    Returns [BatchGroup(tracks = indices into ns, tile0 = each track's first tile in its call, ntiles = the call's total)]."""
     groups, cur, tile0, used = [], [], [], 0
     for k, n in enumerate(ns):
         if n < FFT:
             raise ValueError("track %d: %d samples, at least %d needed" % (k, n, FFT))
-        nt = (stft_rows(n) + T - 1) // T
+        nt = overlap_tiles(stft_rows(n), T, overlap)
         if nt > max_tiles:
             raise ValueError("track %d alone takes %d tiles, more than max_tiles = %d: separate it with the chunked paths" % (k, nt, max_tiles))
         if used + nt > max_tiles:
