@@ -132,8 +132,8 @@ SRT_API size_t srtOverlapTiles(size_t rows, int T, int overlap_rows);
  * -1 with srtLastError() text for a null engine, an unknown mode, or the Wiener filter on.  Honoured by srtIstft, srtSeparate[Ex] (ratio_mask, srtSetOverlap, the
  * fp16 mode's half masks, graph mode: the mode is part of the captured call's key), srtSeparateBatch and srtSeparateHostStream[Ex|Io] (the gain is row-local:
  * chunk seams need nothing), and by engines borrowed from a multi-device object.  Refused with -1 while the mode is on: srtSeparateCli* (its complex-domain
- * residual chain subtracts oob_weight * spectrum), srtIstftWiener, srtSeparateBatchWiener and srtSetWiener(n > 0) (the filter's gains above F are a follow-up).  The live / plugin
- * surfaces (srtLive*, Spleeter4Stems*) have their own handles and keep the constant rule (a follow-up).
+ * residual chain subtracts oob_weight * spectrum), srtIstftWiener, srtSeparateBatchWiener and srtSetWiener(n > 0) (the filter's gains above F are a follow-up).  The live
+ * stream has the mode as an option of its own handle (srtLiveCreateEx); the plugin surface (Spleeter4Stems*) keeps the constant rule.
  * srtCopyTensor(e, "mask_ext", stem, 0, h, 2 * rows) returns the table the last such call left for that stem: [rows][2] (L, R); after srtSeparateBatch the
  * rows are the packed rows (track k from row tile0[k] * T). */
 #define SRT_MASK_EXT_CONSTANT 0
@@ -161,8 +161,8 @@ SRT_API int  srtSetMaskExtension(srt_engine *e, int mode);
  * srtSetMix returns -1 with srtLastError() text (before any device work) for a null engine, n_out outside 0..SRT_MAX_STEMS, a null h_gain with n_out > 0, an
  * entry that is not finite, or the Wiener filter on; srtSetWiener(n > 0) returns -1 while the mix is on.
  * Refused with -1, a text that says "mix" and nothing launched or written while the mix is on: srtSeparateCli, srtSeparateCliHost[Io] (no stem axis),
- * srtIstftWiener, srtSeparateBatch, srtSeparateBatchWiener (follow-ups) and srtMultiSeparate*Host when any engine of the object has it on.  The live / plugin
- * surfaces (srtLive*, Spleeter4Stems*) have their own handles and write every stem (a follow-up). */
+ * srtIstftWiener, srtSeparateBatch, srtSeparateBatchWiener (follow-ups) and srtMultiSeparate*Host when any engine of the object has it on.  The live
+ * stream has the mix on its own handle (srtLiveCreateEx, srtLiveSetMix); the plugin surface (Spleeter4Stems*) writes every stem. */
 SRT_API int srtSetMix(srt_engine *e, int n_out, const float *h_gain);
 SRT_API int srtMixOutputs(const srt_engine *e);   /* n_out while on, 0 while off or for a null engine */
 
@@ -394,6 +394,35 @@ SRT_API void srtLiveDestroy(srt_live *s);
 SRT_API int  srtLiveCreateRate(const srt_config *cfg, int hops_per_run, int lookahead, int sample_rate, int max_block,
                                const void *const *h_coeff, srt_live **out);
 SRT_API int  srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead);
+/* The stem remix and the average mask extension in the hop path.  srtLiveCreateEx is srtLiveCreate / srtLiveCreateRate with options; opts =
+ * NULL or all fields zero is srtLiveCreate, sample_rate != 0 with the other fields zero is srtLiveCreateRate, both bit for bit (the same launches).
+ * n_out > 0: a call takes and fills 2 * n_out planar planes (pair-major L/R) instead of 2 * n_stems.  At hop h the frame g = h - D is synthesised, for output
+ * m, from X(c,k) * h_m(c,k),
+ *   h = G[m][n_stems];  for s = 0 .. n_stems-1 (ascending):  h = fmaf(G[m][s], g_s(c,k), h)
+ * in fp32, one fused multiply-add per stem (srtSetMix's arithmetic), G = the matrix in force when hop h is processed.  g_s, k < F: the mask value the hop
+ * reads with the mix off (after the ratio mask when ratio_mask is set; 1 before the first run is joined).  g_s, k >= F: oob_weight[s], or under
+ * SRT_MASK_EXT_AVERAGE e_s(c) = (sum over k < F of g_s(c,k)) / F in srtSetMaskExtension's summation order (exactly 1 before the first join; oob_weight is
+ * ignored).  The extension also works with n_out = 0: every stem is written, with e_s(c) above F.  A row that is 1 on stem m reproduces g_s exactly; the
+ * row (0, .., 0, 1) is the input delayed by the stream's latency.
+ * The number of outputs is fixed at creation (every buffer is sized then; srtLiveProcess still never allocates).  srtLiveSetMix replaces the matrix values
+ * (the same n_out; [n_out][n_stems + 1], copied): call it from the thread that calls srtLiveProcess; it does no device work, the matrix travels by value in
+ * the next hop's launch.  Frames synthesised later use the new matrix, the kept half of the previous frame the old one: the 50 % overlap-add is the
+ * cross-fade between the two.  srtLiveOutputs: the stereo pairs a call writes, n_out while the mix is on, else n_stems; 0 for NULL.
+ * Accounting, latency, the silent first D hops and the failure policy (silence, over 2 * srtLiveOutputs planes) are those of srtLiveCreate[Rate].
+ * -1 with srtLastError() text, before any HIP call: everything srtLiveCreate / srtLiveCreateRate refuse, n_out outside 0..SRT_MAX_STEMS, n_out > 0 with a
+ * null h_gain, an entry that is not finite, an unknown mask_extension; srtLiveSetMix on a null handle, on an instance created with n_out = 0, with a null
+ * matrix or a non-finite entry (the old matrix stays in force).  The plugin surface (Spleeter4Stems*) keeps its eight planes and the constant rule. */
+typedef struct srt_live_opts {
+    int sample_rate;      /* 0: srtLiveCreate's instance (the reference's accounting); else a rate instance, as srtLiveCreateRate */
+    int max_block;        /* rate instances only (ignored when sample_rate == 0) */
+    int n_out;            /* 0: every stem (off); 1..SRT_MAX_STEMS: outputs of the mix */
+    const float *h_gain;  /* [n_out][n_stems + 1], row-major, copied; last column = the unmasked input (srtSetMix's layout) */
+    int mask_extension;   /* SRT_MASK_EXT_CONSTANT | SRT_MASK_EXT_AVERAGE */
+} srt_live_opts;
+SRT_API int srtLiveCreateEx(const srt_config *cfg, int hops_per_run, int lookahead, const srt_live_opts *opts,
+                            const void *const *h_coeff, srt_live **out);
+SRT_API int srtLiveSetMix(srt_live *s, const float *h_gain);   /* same n_out as at creation; holds from the next hop processed */
+SRT_API int srtLiveOutputs(const srt_live *s);                 /* stereo pairs a call writes: n_out while the mix is on, else n_stems; 0 for NULL */
 
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";

@@ -24,6 +24,11 @@ class _Config(C.Structure):
                 ("ratio_mask", C.c_int), ("batch_invariant", C.c_int)]
 
 
+class _LiveOpts(C.Structure):
+    """srt_live_opts (include/spleeterrt_amd.h): the options of srtLiveCreateEx"""
+    _fields_ = [("sample_rate", C.c_int), ("max_block", C.c_int), ("n_out", C.c_int), ("h_gain", C.POINTER(C.c_float)), ("mask_extension", C.c_int)]
+
+
 class Span(C.Structure):
     """srt_span (include/spleeterrt_amd.h): one rank's share of a stream, as srtRankSpan fills it."""
     _fields_ = [(k, C.c_size_t) for k in ("tile0", "tile1", "sample0", "nsamples", "frames", "rows", "out_offset")]
@@ -112,6 +117,9 @@ def load_library():
     L.srtLiveDestroy.restype = None
     L.srtLiveCreateRate.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), C.POINTER(vp)]
     L.srtLiveRateLatency.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.srtLiveCreateEx.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, C.POINTER(_LiveOpts), C.POINTER(vp), C.POINTER(vp)]
+    L.srtLiveSetMix.argtypes = [vp, vp]
+    L.srtLiveOutputs.argtypes = [vp]
     # sample-rate converter (csrc/srt_resample.hip)
     L.srtResampleLength.restype = C.c_size_t
     L.srtResampleLength.argtypes = [C.c_size_t, C.c_int, C.c_int]
@@ -576,10 +584,14 @@ class Live:
     run every hops_per_run hops on the newest T frames, with `lookahead` frames of future context per frame.  hops_per_run = T, lookahead = 0 with
     the plugin's config (VST, stem modes 1, oob 0.25 / 0 / 0.25 / 0.25) is Spleeter4Stems.  coeffs: one float32 spleeterCoeff blob per stem.
     sample_rate=fs makes a rate instance (srtLiveCreateRate): calls take samples at fs, every call writes as many samples as it got and
-    the delay is the constant `latency` whatever the call sizes; max_block is the largest slice a call is processed in."""
+    the delay is the constant `latency` whatever the call sizes; max_block is the largest slice a call is processed in.
+    mix=G ([n_out][S + 1], srtSetMix's layout: the last column is the unmasked input) makes the calls write n_out stereo pairs, the mix of the stems formed
+    inside the hop's inverse transform; set_mix replaces the values later.  mask_extension="average" lets the bins above F follow each
+    stem's mean mask instead of oob_weights.  Either one creates through srtLiveCreateEx (create_ex=True does so with no option set)."""
 
     def __init__(self, F, T, stem_modes, oob_weights, variant, precision, hops_per_run, lookahead, coeffs, impl=IMPL_MFMA,
-                 ratio_mask=False, batch_invariant=False, max_tiles=1, sample_rate=None, max_block=4096):
+                 ratio_mask=False, batch_invariant=False, max_tiles=1, sample_rate=None, max_block=4096, mix=None, mask_extension="constant",
+                 create_ex=False):
         import numpy as np
         self.L = load_library()
         self.S, self.F, self.T = len(stem_modes), F, T
@@ -596,7 +608,17 @@ class Live:
         ptrs = (C.c_void_p * max(len(blobs), 1))(*[None if b is None else b.ctypes.data for b in blobs])
         h = C.c_void_p()
         self.sample_rate = None if sample_rate is None else int(sample_rate)
-        if sample_rate is None:
+        ext = {"constant": MASK_EXT_CONSTANT, "average": MASK_EXT_AVERAGE}.get(mask_extension, mask_extension)
+        if mix is not None or ext != MASK_EXT_CONSTANT or create_ex:
+            o = _LiveOpts()
+            if sample_rate is not None:
+                o.sample_rate, o.max_block = self.sample_rate, int(max_block)
+            if mix is not None:
+                g = self._gain(mix, None)
+                o.n_out, o.h_gain = g.shape[0], g.ctypes.data_as(C.POINTER(C.c_float))
+            o.mask_extension = int(ext)
+            self._chk(self.L.srtLiveCreateEx(C.byref(cfg), self.hops_per_run, self.lookahead, C.byref(o), ptrs, C.byref(h)))
+        elif sample_rate is None:
             self._chk(self.L.srtLiveCreate(C.byref(cfg), self.hops_per_run, self.lookahead, ptrs, C.byref(h)))
         else:
             self._chk(self.L.srtLiveCreateRate(C.byref(cfg), self.hops_per_run, self.lookahead, self.sample_rate, int(max_block), ptrs, C.byref(h)))
@@ -607,13 +629,30 @@ class Live:
             raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (self.L.srtLastError().decode(), rc))
         return rc
 
+    def _gain(self, G, n_out):
+        import numpy as np
+        g = np.ascontiguousarray(G, np.float32)
+        if g.ndim != 2 or g.shape[1] != self.S + 1 or (n_out is not None and g.shape[0] != n_out):
+            raise ValueError("the mix matrix must be [%s][%d] (the last column is the unmasked input)" % ("n_out" if n_out is None else n_out, self.S + 1))
+        return g
+
+    @property
+    def outputs(self):
+        """stereo pairs a call writes (srtLiveOutputs): the mix's n_out, or the stem count while it is off"""
+        return self.L.srtLiveOutputs(self.h)
+
+    def set_mix(self, G):
+        """srtLiveSetMix: replace the matrix values (the same [n_out][S + 1]); holds from the next hop processed"""
+        g = self._gain(G, self.outputs)
+        self._chk(self.L.srtLiveSetMix(self.h, C.c_void_p(g.ctypes.data)))
+
     @property
     def latency(self):
         """samples between an input sample and its separated output (srtLiveLatency): for 1024-sample calls, or for any calls on a rate instance"""
         return self._chk(self.L.srtLiveLatency(self.h))
 
     def process(self, L, R, chunks=(1024,)):
-        """Feed planar float32 L, R in calls of the sizes in `chunks` (cycled).  Returns (written [2S][m], timeline [2S][n]): the concatenation of what
+        """Feed planar float32 L, R in calls of the sizes in `chunks` (cycled).  Returns (written [2P][m], timeline [2P][n]), P = outputs: the concatenation of what
         the calls wrote (the counts srtLiveProcess returned) and the same samples placed where each call's output starts in the caller's buffers
         (zero where nothing was written), the form tests/test_stream.py's _run builds for the plugin."""
         import numpy as np
@@ -621,7 +660,7 @@ class Live:
         R = np.ascontiguousarray(R, np.float32)
         n = L.size
         assert R.size == n
-        nc = 2 * self.S
+        nc = 2 * self.outputs
         timeline = np.zeros((nc, n), np.float32)
         pieces = []
         pos = i = 0

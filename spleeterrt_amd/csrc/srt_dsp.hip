@@ -1672,6 +1672,94 @@ int srt_launch_stream_hop(const SrtStreamHop& p, hipStream_t s)
     return srt_launch_status();
 }
 
+// The hop inverse of a live stream that combines its stems (srtLiveCreateEx): one workgroup per OUTPUT m.  The prologue forms the gain of
+// the thread's nine bins for both channels from all S mask rows,
+//   h = G[m][S];  for s = 0 .. S-1 ascending:  h = fmaf(G[m][s], g_s, h)
+// (srt_mix_chain's arithmetic: fp32, one fused multiply-add per stem, nothing else contracted), g_s = the mask value below F and above it oob[s] or, EXT, the
+// row's value of the average extension's table.  G travels by value in the launch; the stem loop is workgroup-uniform, so its entries, the weights and the
+// table values are scalar loads.  Stems outermost: the 18 mask loads of a stem are in flight together.  Everything after the gains is srt_stream_inverse_body.
+#pragma clang fp contract(off)
+template <bool EXT>
+__device__ __forceinline__ void srt_live_combine_gains(const SrtLiveCombineHop& p, int m, int tid, float (&hl)[9], float (&hr)[9])
+{
+    const float dry = p.gain[m][p.nstems];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) hl[j] = hr[j] = dry;
+    for (int s = 0; s < p.nstems; ++s) {
+        const float gm = p.gain[m][s];
+        const float* mL = p.maskRow + (size_t)s * p.maskStemStride;
+        const float* mR = mL + p.maskChStride;
+        float ol = p.oob[s], orr = ol;
+        if constexpr (EXT) { ol = p.ext[(size_t)s * p.extStemStride]; orr = p.ext[(size_t)s * p.extStemStride + 1]; }
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const int k = tid + 256 * j, km = min(k, p.F - 1);           // (bins >= F read the row's last value and drop it: no load past the row)
+            float vl = mL[km], vr = mR[km];
+            if (k >= p.F) { vl = ol; vr = orr; }
+            hl[j] = fmaf(gm, vl, hl[j]); hr[j] = fmaf(gm, vr, hr[j]);
+        }
+    }
+}
+#pragma clang fp contract(fast)
+
+template <bool EXT>
+__global__ void __launch_bounds__(256) srt_live_combine_inverse_kernel(const SrtLiveCombineHop p)
+{
+    __shared__ cf s_tw[FFT_TW_F2];
+    __shared__ cf s_x[FFT_SMEM_F2];
+    const int tid = threadIdx.x, m = blockIdx.x;
+    fft_load_twiddles(s_tw, p.twiddle, tid);
+    const cf* specL = reinterpret_cast<const cf*>(p.specRow);
+    const cf* specR = reinterpret_cast<const cf*>(p.specRow) + p.specChStride;
+    float hl[9], hr[9];
+    srt_live_combine_gains<EXT>(p, m, tid, hl, hr);
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+        const int k = tid + 256 * j;
+        if (k <= 2048) {
+            const cf sl = specL[k], sr = specR[k];
+            const float gl = hl[j], gr = hr[j];
+            const float reL = sl.x * gl, imL = sl.y * gl, reR = sr.x * gr, imR = sr.y * gr;
+            if (k == 0) s_x[0] = f2(reR, reL);
+            else if (k == 2048) s_x[2048] = f2(reR - imR, reL - imL);
+            else {
+                s_x[k] = f2(reR - imL, reL + imR);
+                s_x[4096 - k] = f2(reR + imL, reL - imR);
+            }
+        }
+    }
+    __syncthreads();
+    cf v[16];
+#pragma unroll
+    for (int n2 = 0; n2 < 16; ++n2) v[n2] = s_x[tid + 256 * n2];
+    __syncthreads();
+    fft4096(v, s_x, s_tw, tid);
+    float* ovL = p.overlap + (size_t)(2 * m) * 1024;
+    float* ovR = ovL + 1024;
+    const int os = 2 * p.n_out;
+#pragma unroll
+    for (int k2 = 8; k2 < 12; ++k2) {                                         // as srt_stream_inverse_body: k2 = 8..11 -> output, 12..15 -> kept half
+        const int i = tid + 256 * (k2 - 8);
+        const float w0 = p.synthesisWnd[i], w1 = p.synthesisWnd[i + 1024];
+        const cf y0 = v[FFT16_AT(k2)], y1 = v[FFT16_AT(k2 + 4)];
+        p.out[(size_t)i * os + 2 * m + 0] = ovL[i] + y0.y * w0;
+        p.out[(size_t)i * os + 2 * m + 1] = ovR[i] + y0.x * w0;
+        ovL[i] = y1.y * w1;
+        ovR[i] = y1.x * w1;
+    }
+}
+
+// q: the combining inverse (n_out workgroups); p: the hop's SrtStreamHop, of which only the forward transform's fields are used
+int srt_launch_live_combine_hop(const SrtLiveCombineHop& q, const SrtStreamHop& p, hipStream_t s)
+{
+    if (q.nstems < 1 || q.nstems > SRT_MAX_STEMS || q.n_out < 1 || q.n_out > SRT_MAX_STEMS || q.F < 1) return -1;
+    if (q.ext) SRT_LAUNCH((srt_live_combine_inverse_kernel<true>), dim3(q.n_out), dim3(256), 0, s, q);
+    else SRT_LAUNCH((srt_live_combine_inverse_kernel<false>), dim3(q.n_out), dim3(256), 0, s, q);
+    if (hipGetLastError() != hipSuccess) return -1;
+    SRT_LAUNCH(srt_stream_forward_kernel, dim3(1), dim3(256), 0, s, p);     // after the inverse has read the delayed row, as srt_launch_stream_hop
+    return srt_launch_status();
+}
+
 // Live window gather (srt_stream.hip): the magnitude ring holds frame g in row g mod T of each channel; the network wants the
 // window's oldest frame in row 0.  dst[c][i][:] = ring[c][(i + rot) mod T][:], one workgroup per (row, 512 columns), 16-byte
 // loads and stores.  rot = 0 is a plain copy (the plugin's geometry, where every window starts at a multiple of T).

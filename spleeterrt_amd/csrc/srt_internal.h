@@ -334,6 +334,21 @@ struct SrtStreamHop {
     const float* analysisWnd; const float* synthesisWnd; const float2* twiddle;
 };
 int srt_launch_stream_hop(const SrtStreamHop& p, hipStream_t s);
+// the hop inverse of a live stream with the stem remix and / or the average mask extension (srtLiveCreateEx): one workgroup per output
+struct SrtLiveCombineHop {
+    const float2* specRow; size_t specChStride;                               // as SrtStreamHop
+    const float* maskRow; size_t maskStemStride, maskChStride;
+    int F, nstems;
+    int n_out;                // outputs (workgroups), 1..SRT_MAX_STEMS
+    float oob[SRT_MAX_STEMS]; // gain of stem s above F under the constant rule
+    const float* ext;         // average extension: stem s, channel c of the frame's row at ext[s * extStemStride + c]; nullptr: the constant rule
+    size_t extStemStride;
+    float gain[SRT_MAX_STEMS][SRT_MAX_STEMS + 1];                             // G[m][s], G[m][nstems] = the unmasked input (srtSetMix's layout)
+    float* overlap;           // [2*n_out][1024]
+    float* out;               // [1024][2*n_out] interleaved segment
+    const float* synthesisWnd; const float2* twiddle;
+};
+int srt_launch_live_combine_hop(const SrtLiveCombineHop& q, const SrtStreamHop& p, hipStream_t s);
 // Live window gather: dst[c][i] = ring[c][(i + rot) mod T] for the [2][T][F] magnitude ring (rows of F floats, F % 4 == 0)
 int srt_launch_live_gather(const float* ring, float* dst, int T, int F, int rot, hipStream_t s);
 struct srt_config;

@@ -10,6 +10,9 @@
 // magnitude ring is gathered into the window [h-T+1, h] and the U-Nets start on it on the engine's own stream (the reference's task_type2
 // threads, Spleeter4Stems.c:135,351-371).  Frame g takes row T-1-(h_r-g) of the run h_r with h_r-g in [L, L+K-1] and is synthesised at
 // hop g + D, D = L + 2K.  The plugin's instance (Spleeter4StemsInit) is K = T, L = 0: runs at the T-hop flips, D = 2T, rows 0..T-1.
+// An instance of srtLiveCreateEx with a stem remix and / or the average mask extension writes P = n_out pairs instead of S: its hops run
+//   srt_live_combine_inverse_kernel x P outputs : frame h-D's spectrum x the chain over all S mask rows under the matrix in force
+// and every run is followed, on the network stream, by the extension's table for the K rows it serves.
 #include "srt_internal.h"
 #include "srt_rs.h"
 #include "../../include/spleeterrt_amd.h"
@@ -48,20 +51,27 @@ struct srt_live {
     int runBuf, joinedBuf;               // mask buffer each of them writes / wrote (run r writes buffer r & 1)
     bool nnRunning, failed, ratio;
     float oob[SRT_MAX_STEMS];
+    // srtLiveCreateEx.  P: stereo pairs a call writes (nOut while the mix is on, else S); combine: the hops run the combining inverse (the
+    // mix and / or the average extension; off: exactly the launches of srtLiveCreate).  G: the matrix in force, by value into every hop's launch (mix off
+    // with the extension: the S x S identity).  d_ext: the extension's table [2 buffers][S][K][2], buffer b written by the run that writes mask buffer b
+    int P, nOut;
+    bool combine, ext;
+    float G[SRT_MAX_STEMS][SRT_MAX_STEMS + 1];
+    float* d_ext;
     // device: input ring [2][4096], spectrum ring [2][D][SPEC_LD] (frame g at row g mod D), magnitude ring [2][T][F] (frame g at row g mod T),
-    // network window [2][T][F], masks [2 buffers][S][2][T][F], overlap [2S][1024], segment [1024][2S]
+    // network window [2][T][F], masks [2 buffers][S][2][T][F], overlap [2P][1024], segment [1024][2P]
     float* d_ring; float2* d_spec; float* d_mag; float* d_tmp; float* d_masks; float* d_overlap; float* d_out;
     float *d_awin, *d_swin; float2* d_tw;
     size_t hw;
     // host state, mirrors Spleeter4Stems.h:35-47
     float ring[2][FFTSIZE];
     unsigned inPos, needed;
-    float* outq[2]; float* pinned; float* hostq; // two queued segments of OUTPUTSEG*2S floats (pinned for the D2H copy; plain host memory on a failed instance)
+    float* outq[2]; float* pinned; float* hostq; // two queued segments of OUTPUTSEG*2P floats (pinned for the D2H copy; plain host memory on a failed instance)
     int outCount, outReadOff;
     // rate instance (srtLiveCreateRate): n samples out for n in at the host's rate fs, one constant delay A.  fs != 44100: the block
     // goes H2D into d_blk, the input-side converter (ring d_hin [capIn][2] of host-rate history) writes the new 44.1 kHz frames into d_ring, every hop's
-    // segment lands in the stem ring d_sring [capS][2S] (hop h at slot h mod capS/1024), the output-side converter writes the call's n frames of
-    // all 2S planes into d_planes [2S][n], one D2H brings them to pinOut.  fs == 44100: no converter; the host ring and a pinned queue of nq segments.
+    // segment lands in the stem ring d_sring [capS][2P] (hop h at slot h mod capS/1024), the output-side converter writes the call's n frames of
+    // all 2P planes into d_planes [2P][n], one D2H brings them to pinOut.  fs == 44100: no converter; the host ring and a pinned queue of nq segments.
     bool rate;
     int fs, maxBlock, A, nq;
     long long nHost, c44;                // host samples received / 44.1 kHz frames written to d_ring
@@ -109,6 +119,41 @@ SrtStreamHop hop_params(const srt_live* s, long long h)
     return p;
 }
 
+// the combining inverse's arguments for the same hop: frame h-D under the matrix in force now; the extension's row f = prow - (T-L-K) of the joined run's table
+SrtLiveCombineHop combine_params(const srt_live* s, const SrtStreamHop& p, long long h)
+{
+    SrtLiveCombineHop q; memset(&q, 0, sizeof q);
+    const long long g = h - s->D;
+    const int f = s->joinedHop >= 0 ? s->K - 1 - (int)(s->joinedHop - g - s->L) : s->K - 1;     // before the first join: a row of the initial table (1.0)
+    q.specRow = p.specRow; q.specChStride = p.specChStride;
+    q.maskRow = p.maskRow; q.maskStemStride = p.maskStemStride; q.maskChStride = p.maskChStride;
+    q.F = s->F; q.nstems = s->S; q.n_out = s->P;
+    for (int k = 0; k < s->S; ++k) q.oob[k] = s->oob[k];
+    if (s->ext) { q.ext = s->d_ext + ((size_t)s->joinedBuf * s->S * s->K + f) * 2; q.extStemStride = (size_t)s->K * 2; }
+    memcpy(q.gain, s->G, sizeof q.gain);
+    q.overlap = s->d_overlap; q.out = p.out;
+    q.synthesisWnd = s->d_swin; q.twiddle = s->d_tw;
+    return q;
+}
+
+// one hop's kernels: the inverse of frame h-D (one workgroup per output pair) and the forward transform of frame h.  0, or -1: launch failed
+int launch_hop(const srt_live* s, const SrtStreamHop& p, long long h)
+{
+    if (!s->combine) return srt_launch_stream_hop(p, s->hop);
+    return srt_launch_live_combine_hop(combine_params(s, p, h), p, s->hop);
+}
+
+// the average extension's table for the run that has just been queued into mask buffer b: srt_launch_mask_ext over the K rows T-L-K .. T-L-1 the run serves
+// (the masks as the hops read them: after srtRatioMask, so no ratio here), on the network stream behind the run
+int launch_ext_table(const srt_live* s, int b)
+{
+    SrtMaskExtParams m; memset(&m, 0, sizeof m);
+    m.masks = masks_buf(s, b) + (size_t)(s->T - s->L - s->K) * s->F;
+    m.nstems = s->S; m.ntiles = 1; m.T = s->T; m.F = s->F; m.rows = s->K;
+    m.ext = s->d_ext + (size_t)b * s->S * s->K * 2; m.ext_stem = (size_t)s->K * 2;
+    return srt_launch_mask_ext(m, s->nn);
+}
+
 // At every hop h = K-1 (mod K): join the run started K hops ago (its masks serve the next K hops), then start one on the window [h-T+1, h].
 // false: a device call failed (reported, the instance is muted)
 #define HIPOK(x, where) do { hipError_t _e = (x); if (_e != hipSuccess) { s->failed = true; stream_fail(where, hipGetErrorString(_e)); return false; } } while (0)
@@ -125,6 +170,7 @@ bool hop_schedule(srt_live* s, long long h)
     HIPOK(hipStreamWaitEvent(s->nn, s->evMag, 0), "stream flip");
     if (srtForward(s->eng, s->d_tmp, 1, masks_buf(s, b))) { s->failed = true; return stream_fail("stream networks", nullptr); }
     if (s->ratio && srtRatioMask(s->eng, masks_buf(s, b), 1)) { s->failed = true; return stream_fail("stream ratio mask", nullptr); }
+    if (s->ext && launch_ext_table(s, b)) { s->failed = true; return stream_fail("stream mask extension", "kernel launch failed"); }
     HIPOK(hipEventRecord(s->evNN, s->nn), "stream flip");
     s->nnRunning = true; s->runHop = h; s->runBuf = b;
     return true;
@@ -132,7 +178,7 @@ bool hop_schedule(srt_live* s, long long h)
 
 void process_hop(srt_live* s)                                                // LLPAMSProcessNPR, Spleeter4Stems.c:257-381
 {
-    const size_t seg = (size_t)OUTPUTSEG * 2 * s->S;
+    const size_t seg = (size_t)OUTPUTSEG * 2 * s->P;
     float* dst;
     if (s->rate) dst = s->outq[0] + (size_t)(s->hops % s->nq) * seg;        // a 44.1 kHz rate instance: hop h in slot h mod nq of its queue (rate_slice_44100)
     else {
@@ -146,7 +192,7 @@ void process_hop(srt_live* s)                                                // 
         const long long h = s->hops;
         HIPTRY(hipMemcpyAsync(s->d_ring, s->ring, sizeof s->ring, hipMemcpyHostToDevice, s->hop), "stream hop");
         const SrtStreamHop p = hop_params(s, h);
-        if (srt_launch_stream_hop(p, s->hop)) { s->failed = true; stream_fail("stream hop", "kernel launch failed"); goto failed; }
+        if (launch_hop(s, p, h)) { s->failed = true; stream_fail("stream hop", "kernel launch failed"); goto failed; }
         HIPTRY(hipMemcpyAsync(dst, s->d_out, seg * sizeof(float), hipMemcpyDeviceToHost, s->hop), "stream hop");
         HIPTRY(hipEventRecord(s->evOut, s->hop), "stream hop");
         s->hops = h + 1;
@@ -163,17 +209,18 @@ failed:
 }
 
 // host state only: a failed instance still accounts for samples (and emits silence) through its queue.  NULL: out of host memory.
-srt_live* live_new(int F, int T, int S, int K, int L)
+srt_live* live_new(int F, int T, int S, int K, int L, int P)
 {
     srt_live* s = new (std::nothrow) srt_live();           // value-initialised: every field zero
     if (!s) return nullptr;
     s->F = F; s->T = T; s->S = S; s->K = K; s->L = L; s->D = L + 2 * K; s->hw = (size_t)F * T;
+    s->P = P;
     s->needed = OUTPUTSEG;
     s->nq = 2;
     s->runHop = s->joinedHop = -1;
     s->runBuf = s->joinedBuf = 1;                                             // run 0 writes buffer 0; until it is joined the hops read buffer 1
     s->failed = true;                                                         // until live_init has succeeded
-    const size_t seg = (size_t)OUTPUTSEG * 2 * S;
+    const size_t seg = (size_t)OUTPUTSEG * 2 * P;
     s->hostq = (float*)calloc(2 * seg, sizeof(float));
     s->outq[0] = s->hostq; s->outq[1] = s->hostq ? s->hostq + seg : nullptr;
     return s;
@@ -220,20 +267,21 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     for (int k = 0; k < s->S; ++k)
         if (srtSetCoeffHost(s->eng, k, coeff[k])) { stream_fail(who, nullptr); return -2; }
     srtSetGraphMode(s->eng, 1);                           // the U-Nets run on the same buffers every K hops: replay one hipGraph per mask buffer
-    const size_t S = s->S, specF = 2 * (size_t)s->D * SRT_SPEC_LD * 2, maskF = 2 * S * 2 * s->hw;
+    const size_t S = s->S, P = s->P, specF = 2 * (size_t)s->D * SRT_SPEC_LD * 2, maskF = 2 * S * 2 * s->hw;
     INITTRY(s->mem.alloc(&s->d_ring, sizeof s->ring));
     INITTRY(s->mem.alloc(&s->d_spec, specF * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_mag, 2 * s->hw * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_tmp, 2 * s->hw * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_masks, maskF * sizeof(float)));
-    INITTRY(s->mem.alloc(&s->d_overlap, 2 * S * 1024 * sizeof(float)));
-    INITTRY(s->mem.alloc(&s->d_out, OUTPUTSEG * 2 * S * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_overlap, 2 * P * 1024 * sizeof(float)));
+    INITTRY(s->mem.alloc(&s->d_out, OUTPUTSEG * 2 * P * sizeof(float)));
+    if (s->ext) INITTRY(s->mem.alloc(&s->d_ext, 2 * S * s->K * 2 * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_awin, FFTSIZE * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_swin, FFTSIZE * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_tw, FFTSIZE * sizeof(float2)));
     INITTRY(hipMemset(s->d_spec, 0, specF * sizeof(float)));              // zero spectrum for the first D hops (:423-438)
     INITTRY(hipMemset(s->d_mag, 0, 2 * s->hw * sizeof(float)));           // frames before 0 have zero magnitude
-    INITTRY(hipMemset(s->d_overlap, 0, 2 * S * 1024 * sizeof(float)));
+    INITTRY(hipMemset(s->d_overlap, 0, 2 * P * 1024 * sizeof(float)));
     // Pre-warm on THIS thread: the split-K workspace allocation and the capture + instantiation of one hipGraph per mask buffer
     // would otherwise happen inside the host's audio callback at the first runs (an allocation and a graph build there risk a dropout).
     INITTRY(hipMemset(s->d_tmp, 0, 2 * s->hw * sizeof(float)));
@@ -252,7 +300,15 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     INITTRY(hipMemcpy(s->d_awin, an.data(), FFTSIZE * 4, hipMemcpyHostToDevice));
     INITTRY(hipMemcpy(s->d_swin, sy.data(), FFTSIZE * 4, hipMemcpyHostToDevice));
     INITTRY(hipMemcpy(s->d_tw, tw.data(), 2 * FFTSIZE * 4, hipMemcpyHostToDevice));
-    INITTRY(s->mem.alloc(&s->pinned, s->nq * OUTPUTSEG * 2 * S * sizeof(float), true));   // pinned queue for the per-hop D2H copy
+    INITTRY(s->mem.alloc(&s->pinned, s->nq * OUTPUTSEG * 2 * P * sizeof(float), true));   // pinned queue for the per-hop D2H copy
+    if (s->ext) {
+        INITTRY(hipStreamSynchronize(nullptr));           // the unit masks are in place
+        // the table launch loads its kernel's code now, on unit masks (every mean is exactly 1.0); then both buffers start at 1.0 as the masks do
+        if (launch_ext_table(s, 0)) { stream_fail(who, "mask extension pre-warm: kernel launch failed"); return -2; }
+        INITTRY(hipStreamSynchronize(s->nn));
+        const std::vector<float> one(2 * S * s->K * 2, 1.0f);
+        INITTRY(hipMemcpy(s->d_ext, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     INITTRY(hipStreamSynchronize(nullptr));               // masks / windows / twiddles (null-stream copies) are in place before the first hop
     // Pre-warm the per-hop path too: the first launch of the hop kernels loads their code, and eight plugin instances making their first call at
     // the same time queued behind each other for it - the slowest call of every instance was its FIRST one, 7.5 ms (round 6, host/rt_latency.c
@@ -261,24 +317,24 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     INITTRY(hipMemsetAsync(s->d_ring, 0, sizeof s->ring, s->hop));
     {
         const SrtStreamHop p = hop_params(s, 0);
-        if (srt_launch_stream_hop(p, s->hop)) { stream_fail(who, "hop pre-warm: kernel launch failed"); return -2; }
+        if (launch_hop(s, p, 0)) { stream_fail(who, "hop pre-warm: kernel launch failed"); return -2; }
         if (srt_launch_live_gather(s->d_mag, s->d_tmp, s->T, s->F, 0, s->hop)) { stream_fail(who, "window pre-warm: kernel launch failed"); return -2; }
-        INITTRY(hipMemcpyAsync(s->pinned, s->d_out, OUTPUTSEG * 2 * S * sizeof(float), hipMemcpyDeviceToHost, s->hop));
+        INITTRY(hipMemcpyAsync(s->pinned, s->d_out, OUTPUTSEG * 2 * P * sizeof(float), hipMemcpyDeviceToHost, s->hop));
         INITTRY(hipStreamSynchronize(s->hop));
     }
 #undef INITTRY
-    s->outq[0] = s->pinned; s->outq[1] = s->pinned + OUTPUTSEG * 2 * S;
+    s->outq[0] = s->pinned; s->outq[1] = s->pinned + OUTPUTSEG * 2 * P;
     s->failed = false;
     return 0;
 }
 
 int live_process_rate(srt_live* s, const float* inL, const float* inR, int n, float* const* out);      // rate instances, below
 
-// Spleeter4StemsProcessSamples' accounting (Spleeter4Stems.c:512-582) for 2S planar outputs; returns the samples written to each
+// Spleeter4StemsProcessSamples' accounting (Spleeter4Stems.c:512-582) for 2P planar outputs; returns the samples written to each
 int live_process(srt_live* s, const float* inLeft, const float* inRight, int inSampleCount, float* const* components)
 {
     if (s->rate) return live_process_rate(s, inLeft, inRight, inSampleCount, components);
-    const int nc = 2 * s->S;
+    const int nc = 2 * s->P;
     int outSampleCount = 0;
     const int maxOut = inSampleCount;
     while (inSampleCount > 0) {                                             // Spleeter4Stems.c:518-537
@@ -344,7 +400,7 @@ int live_rate_init(srt_live* s, const SrtRsGeom& gin, const SrtRsGeom& gout, con
 {
     if (s->fs == 44100) return 0;
 #define INITTRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) { s->failed = true; stream_fail(who, hipGetErrorString(_e)); return -2; } } while (0)
-    const int nc = 2 * s->S;
+    const int nc = 2 * s->P;
     s->failed = true;                                                          // until everything below has succeeded
     s->Bin = srt_rsstream_block(gin, &s->ldsIn);
     s->Bout = srt_rsstream_block(gout, &s->ldsOut);
@@ -388,8 +444,8 @@ bool rate_hop(srt_live* s)
 {
     const long long h = s->hops;
     SrtStreamHop p = hop_params(s, h);
-    p.out = s->d_sring + (size_t)(h % (s->capS / OUTPUTSEG)) * OUTPUTSEG * 2 * s->S;
-    if (srt_launch_stream_hop(p, s->hop)) { s->failed = true; return stream_fail("stream hop", "kernel launch failed"); }
+    p.out = s->d_sring + (size_t)(h % (s->capS / OUTPUTSEG)) * OUTPUTSEG * 2 * s->P;
+    if (launch_hop(s, p, h)) { s->failed = true; return stream_fail("stream hop", "kernel launch failed"); }
     s->hops = h + 1;
     return hop_schedule(s, h);
 }
@@ -397,7 +453,7 @@ bool rate_hop(srt_live* s)
 // one call of n <= max_block samples at fs != 44100: one H2D, converter -> hops -> converter, one D2H, one wait.  false: failed (the caller emits silence)
 bool rate_slice(srt_live* s, const float* inL, const float* inR, int n, float* const* planes)
 {
-    const int nc = 2 * s->S;
+    const int nc = 2 * s->P;
     memcpy(s->pinIn, inL, n * sizeof(float));
     memcpy(s->pinIn + n, inR, n * sizeof(float));
     HIPOK(hipMemcpyAsync(s->d_blk, s->pinIn, 2 * (size_t)n * sizeof(float), hipMemcpyHostToDevice, s->hop), "stream block");
@@ -447,7 +503,7 @@ bool rate_slice(srt_live* s, const float* inL, const float* inR, int n, float* c
 // false: failed
 bool rate_slice_44100(srt_live* s, const float* inL, const float* inR, int n, float* const* planes)
 {
-    const int nc = 2 * s->S;
+    const int nc = 2 * s->P;
     int left = n;
     while (left > 0) {
         const int c = (int)s->needed < left ? (int)s->needed : left;
@@ -472,7 +528,7 @@ bool rate_slice_44100(srt_live* s, const float* inL, const float* inR, int n, fl
 
 int live_process_rate(srt_live* s, const float* inL, const float* inR, int n, float* const* out)
 {
-    const int nc = 2 * s->S;
+    const int nc = 2 * s->P;
     float* planes[2 * SRT_MAX_STEMS];
     for (int done = 0; done < n; ) {
         const int c = n - done < s->maxBlock ? n - done : s->maxBlock;
@@ -496,7 +552,7 @@ void s4s_init(Spleeter4Stems* msr, int F, int T, void* coeffProvider[4], int K, 
     cfg.F = F; cfg.T = T; cfg.n_stems = 4; cfg.variant = SRT_VARIANT_VST; cfg.max_tiles = 1; cfg.impl = SRT_IMPL_MFMA;
     for (int k = 0; k < 4; ++k) { cfg.stem_mode[k] = 1; cfg.oob_weight[k] = k == 1 ? 0.0f : 0.25f; }      // Spleeter4Stems.c:444-447
     const bool args_ok = T >= 1 && K >= 1 && K <= T && L >= 0 && L <= T - K;
-    srt_live* s = live_new(F, T, 4, args_ok ? K : (T >= 1 ? T : 1), args_ok ? L : 0);
+    srt_live* s = live_new(F, T, 4, args_ok ? K : (T >= 1 ? T : 1), args_ok ? L : 0, 4);
     if (!s) { stream_fail(who, "out of host memory"); return; }
     msr->impl = s;
     if (sampleRate) { s->rate = true; s->fs = sampleRate; s->maxBlock = maxBlock >= 1 ? maxBlock : 1; }     // a muted rate instance still writes inSampleCount samples per call
@@ -552,24 +608,80 @@ void Spleeter4StemsProcessSamples(Spleeter4Stems* msr, const float* inLeft, cons
 }
 
 // ---- C API (include/spleeterrt_amd.h)
-int srtLiveCreate(const srt_config* cfg, int hops_per_run, int lookahead, const void* const* h_coeff, srt_live** out)
+// One body behind srtLiveCreate, srtLiveCreateRate and srtLiveCreateEx; `who` names the caller in every message.  rate: a rate instance (sample_rate, max_block).
+// o: srtLiveCreateEx's options (never null; all zero for the two older calls).  Every argument is checked before any HIP call.
+namespace {
+bool gain_finite(const float* g, int n) { for (int i = 0; i < n; ++i) if (!isfinite(g[i])) return false; return true; }
+
+int live_create(const srt_config* cfg, int hops_per_run, int lookahead, bool rate, const srt_live_opts& o, const void* const* h_coeff, srt_live** out, const char* who)
 {
-    if (!cfg || !h_coeff || !out) return srt_set_error(-1, "%s", "srtLiveCreate: null argument");
+    if (!cfg || !h_coeff || !out) return srt_set_error(-1, "%s: null argument", who);
     *out = nullptr;
-    if (const int rc = srt_check_config(cfg, "srtLiveCreate")) return rc;             // srtCreate's own checks, before any HIP call
-    if (cfg->max_tiles != 1) return srt_set_error(-1, "%s", "srtLiveCreate: max_tiles must be 1 (a run is one window)");
-    if (hops_per_run < 1 || hops_per_run > cfg->T) return srt_set_error(-1, "%s", "srtLiveCreate: hops_per_run must be in 1..T");
-    if (lookahead < 0 || lookahead > cfg->T - hops_per_run) return srt_set_error(-1, "%s", "srtLiveCreate: lookahead must be in 0..T-hops_per_run");
+    if (const int rc = srt_check_config(cfg, who)) return rc;             // srtCreate's own checks, before any HIP call
+    if (cfg->max_tiles != 1) return srt_set_error(-1, "%s: max_tiles must be 1 (a run is one window)", who);
+    if (hops_per_run < 1 || hops_per_run > cfg->T) return srt_set_error(-1, "%s: hops_per_run must be in 1..T", who);
+    if (lookahead < 0 || lookahead > cfg->T - hops_per_run) return srt_set_error(-1, "%s: lookahead must be in 0..T-hops_per_run", who);
+    SrtRsGeom gin, gout;
+    int A = 0;
+    if (rate) {
+        if (o.max_block < 1 || o.max_block > SRT_LIVE_MAX_BLOCK) return srt_set_error(-1, "%s: max_block must be in 1..65536", who);
+        if (const int rc = rate_geometry(o.sample_rate, hops_per_run, lookahead, who, &gin, &gout, &A)) return rc;
+    }
+    if (o.n_out < 0 || o.n_out > SRT_MAX_STEMS) return srt_set_error(-1, "%s: n_out must be in 0..SRT_MAX_STEMS (8)", who);
+    if (o.n_out > 0 && !o.h_gain) return srt_set_error(-1, "%s: null h_gain with n_out > 0", who);
+    if (o.n_out > 0 && !gain_finite(o.h_gain, o.n_out * (cfg->n_stems + 1))) return srt_set_error(-1, "%s: h_gain has an entry that is not finite", who);
+    if (o.mask_extension != SRT_MASK_EXT_CONSTANT && o.mask_extension != SRT_MASK_EXT_AVERAGE) return srt_set_error(-1, "%s: unknown mask_extension (SRT_MASK_EXT_CONSTANT or SRT_MASK_EXT_AVERAGE)", who);
     for (int k = 0; k < cfg->n_stems; ++k)
-        if (!h_coeff[k]) return srt_set_error(-1, "%s", "srtLiveCreate: null coefficient blob");
+        if (!h_coeff[k]) return srt_set_error(-1, "%s: null coefficient blob", who);
     SrtSetupLock setup;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return srt_set_error(-3, "%s", "srtLiveCreate: no HIP device (this library has no CPU path)");
-    srt_live* s = live_new(cfg->F, cfg->T, cfg->n_stems, hops_per_run, lookahead);
-    if (!s || !s->hostq) { live_free(s); return srt_set_error(-2, "%s", "srtLiveCreate: out of host memory"); }
-    if (const int rc = live_init(s, *cfg, h_coeff, "srtLiveCreate")) { live_free(s); return rc; }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return srt_set_error(-3, "%s: no HIP device (this library has no CPU path)", who);
+    const int S = cfg->n_stems;
+    srt_live* s = live_new(cfg->F, cfg->T, S, hops_per_run, lookahead, o.n_out > 0 ? o.n_out : S);
+    if (!s || !s->hostq) { live_free(s); return srt_set_error(-2, "%s: out of host memory", who); }
+    s->nOut = o.n_out;
+    s->ext = o.mask_extension == SRT_MASK_EXT_AVERAGE;
+    s->combine = s->nOut > 0 || s->ext;                                       // neither: the launches of srtLiveCreate, untouched
+    if (s->nOut > 0) for (int m = 0; m < s->nOut; ++m) memcpy(s->G[m], o.h_gain + (size_t)m * (S + 1), (S + 1) * sizeof(float));
+    else for (int m = 0; m < S; ++m) s->G[m][m] = 1.0f;                       // the extension alone: every stem through the identity (a one-hot chain gives g_s exactly)
+    if (rate) {
+        s->rate = true; s->fs = o.sample_rate; s->maxBlock = o.max_block; s->A = A;
+        if (o.sample_rate == 44100) s->nq = (o.max_block + OUTPUTSEG - 1) / OUTPUTSEG + 2;     // only the 44.1 kHz path queues segments on the host
+    }
+    int rc = live_init(s, *cfg, h_coeff, who);
+    if (rc == 0 && rate) rc = live_rate_init(s, gin, gout, who);
+    if (rc) { live_free(s); return rc; }
     *out = s;
     return 0;
+}
+}  // namespace
+
+int srtLiveCreate(const srt_config* cfg, int hops_per_run, int lookahead, const void* const* h_coeff, srt_live** out)
+{
+    srt_live_opts o; memset(&o, 0, sizeof o);
+    return live_create(cfg, hops_per_run, lookahead, false, o, h_coeff, out, "srtLiveCreate");
+}
+
+int srtLiveCreateEx(const srt_config* cfg, int hops_per_run, int lookahead, const srt_live_opts* opts, const void* const* h_coeff, srt_live** out)
+{
+    srt_live_opts o; memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    return live_create(cfg, hops_per_run, lookahead, o.sample_rate != 0, o, h_coeff, out, "srtLiveCreateEx");
+}
+
+int srtLiveSetMix(srt_live* s, const float* h_gain)
+{
+    if (!s) return srt_set_error(-1, "%s", "srtLiveSetMix: null argument");
+    if (s->nOut == 0) return srt_set_error(-1, "%s", "srtLiveSetMix: the instance was created with n_out = 0 (the number of outputs is fixed at creation)");
+    if (!h_gain) return srt_set_error(-1, "%s", "srtLiveSetMix: null h_gain");
+    if (!gain_finite(h_gain, s->nOut * (s->S + 1))) return srt_set_error(-1, "%s", "srtLiveSetMix: h_gain has an entry that is not finite");
+    for (int m = 0; m < s->nOut; ++m) memcpy(s->G[m], h_gain + (size_t)m * (s->S + 1), (s->S + 1) * sizeof(float));     // host state only: the next hop's launch carries it
+    return 0;
+}
+
+int srtLiveOutputs(const srt_live* s)
+{
+    return s ? s->P : 0;
 }
 
 int srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead)
@@ -583,37 +695,15 @@ int srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead)
 
 int srtLiveCreateRate(const srt_config* cfg, int hops_per_run, int lookahead, int sample_rate, int max_block, const void* const* h_coeff, srt_live** out)
 {
-    const char* who = "srtLiveCreateRate";
-    if (!cfg || !h_coeff || !out) return srt_set_error(-1, "%s", "srtLiveCreateRate: null argument");
-    *out = nullptr;
-    if (const int rc = srt_check_config(cfg, who)) return rc;
-    if (cfg->max_tiles != 1) return srt_set_error(-1, "%s", "srtLiveCreateRate: max_tiles must be 1 (a run is one window)");
-    if (hops_per_run < 1 || hops_per_run > cfg->T) return srt_set_error(-1, "%s", "srtLiveCreateRate: hops_per_run must be in 1..T");
-    if (lookahead < 0 || lookahead > cfg->T - hops_per_run) return srt_set_error(-1, "%s", "srtLiveCreateRate: lookahead must be in 0..T-hops_per_run");
-    if (max_block < 1 || max_block > SRT_LIVE_MAX_BLOCK) return srt_set_error(-1, "%s", "srtLiveCreateRate: max_block must be in 1..65536");
-    SrtRsGeom gin, gout;
-    int A = 0;
-    if (const int rc = rate_geometry(sample_rate, hops_per_run, lookahead, who, &gin, &gout, &A)) return rc;
-    for (int k = 0; k < cfg->n_stems; ++k)
-        if (!h_coeff[k]) return srt_set_error(-1, "%s", "srtLiveCreateRate: null coefficient blob");
-    SrtSetupLock setup;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return srt_set_error(-3, "%s", "srtLiveCreateRate: no HIP device (this library has no CPU path)");
-    srt_live* s = live_new(cfg->F, cfg->T, cfg->n_stems, hops_per_run, lookahead);
-    if (!s || !s->hostq) { live_free(s); return srt_set_error(-2, "%s", "srtLiveCreateRate: out of host memory"); }
-    s->rate = true; s->fs = sample_rate; s->maxBlock = max_block; s->A = A;
-    if (sample_rate == 44100) s->nq = (max_block + OUTPUTSEG - 1) / OUTPUTSEG + 2;     // only the 44.1 kHz path queues segments on the host
-    int rc = live_init(s, *cfg, h_coeff, who);
-    if (rc == 0) rc = live_rate_init(s, gin, gout, who);
-    if (rc) { live_free(s); return rc; }
-    *out = s;
-    return 0;
+    srt_live_opts o; memset(&o, 0, sizeof o);
+    o.sample_rate = sample_rate; o.max_block = max_block;
+    return live_create(cfg, hops_per_run, lookahead, true, o, h_coeff, out, "srtLiveCreateRate");
 }
 
 int srtLiveProcess(srt_live* s, const float* inL, const float* inR, int n, float* const* out)
 {
     if (!s || n < 0 || (n > 0 && (!inL || !inR || !out))) return srt_set_error(-1, "%s", "srtLiveProcess: bad argument");
-    if (n > 0) for (int j = 0; j < 2 * s->S; ++j) if (!out[j]) return srt_set_error(-1, "%s", "srtLiveProcess: null output plane");
+    if (n > 0) for (int j = 0; j < 2 * s->P; ++j) if (!out[j]) return srt_set_error(-1, "%s", "srtLiveProcess: null output plane");
     return live_process(s, inL, inR, n, out);
 }
 
