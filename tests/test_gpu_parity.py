@@ -425,7 +425,9 @@ def test_fp16_c8_layers(oracle, coeffs, T, F, ntiles, modes):
     up1..up5 run on the DMA-fed kernels.  Every tensor of sampled instances (first, middle, last tile: the last one sits in a partly empty instance group of the deep
     layers) against (a) the SAME tile evaluated alone, which takes the planar kernels of srt_nn3.hip (same products, same order: fp16 rounding noise at most), and
     (b) the fp32 CPU oracle at the fp16 tolerance class of BASELINE configs[4] (masks <= 2e-2).  Geometries: F = 256 (one-pixel-high deep layers, everything a
-    partial tile), T = 192 / F = 768 (tile counts that are not powers of two), the bench's 1024 bins."""
+    partial tile), T = 192 / F = 768 (tile counts that are not powers of two), the bench's 1024 bins.
+    Both sides of (a) are our own kernels: the planar kernels themselves, and every C8 layer, are held to a float64 reference of the layer's own stored inputs in
+    tests/test_fp16_layer_local.py."""
     import torch
     import spleeterrt_amd as srt
     S = len(modes)
