@@ -193,10 +193,13 @@ def enc_operand(raw, scale, shift, kind, cell):
 
 # ------------------------------------------------------------------------------------------- reference layers
 class Ref:
-    """float64 value of one layer, its allowance E, and whether the output is stored as a half"""
+    """float64 value of one layer, its allowance E, and whether the output is stored as a half.
+    u: the per-element unit of tests/fp32_layer_ref.py - the same allowance evaluated with ONE accumulated term (K = 1), so that z = (got - ref) / u measures an
+    error in roundings of the element's own accumulation scale; acc: the part of E that the accumulation contributes (K 2^-24 A, BN-scaled in the decoder), which
+    the Winograd kernels replace by the bound of their bilinear algorithm"""
 
-    def __init__(self, ref, E, half, share=0.0, sigma=None):
-        self.ref, self.E, self.half, self.share, self.sigma = ref, E, half, share, sigma
+    def __init__(self, ref, E, half, share=0.0, sigma=None, u=None, acc=None):
+        self.ref, self.E, self.half, self.share, self.sigma, self.u, self.acc = ref, E, half, share, sigma, u, acc
 
 
 def enc_ref(a, d, w, b, *, w_half=True, fp32_products=False, out_half=True):
@@ -207,6 +210,7 @@ def enc_ref(a, d, w, b, *, w_half=True, fp32_products=False, out_half=True):
     A = contract64("conv", np.abs(a), np.abs(w)) + np.abs(bb)
     K = n_terms("conv", a.shape[0]) + (1 if fp32_products else 0)
     E = (K + C_EPI) * EPS32 * A
+    u, acc = (1 + C_EPI) * EPS32 * A, K * EPS32 * A
     share, sigma = 0.0, None
     if d is not None:
         E = E + contract64("conv", d, np.abs(w))
@@ -215,7 +219,7 @@ def enc_ref(a, d, w, b, *, w_half=True, fp32_products=False, out_half=True):
             # operands known only up to d: the error's scale is no longer the output's own ulp.  Standard deviation of one element under operands spread evenly
             # over +-d and an evenly spread output rounding; check C then measures in these units (see LayerLocal.enc)
             sigma = np.sqrt(contract64("conv", d * d, w * w) / 3 + ulp16(ref) ** 2 / 12)
-    return Ref(ref, E, out_half, share, sigma)
+    return Ref(ref, E, out_half, share, sigma, u, acc)
 
 
 def dec_ref(x, w, b, scale, shift, kind, *, w_half=True, fp32_products=False, out_half=True):
@@ -228,8 +232,9 @@ def dec_ref(x, w, b, scale, shift, kind, *, w_half=True, fp32_products=False, ou
     ref = sc * v + sh
     K = n_terms("tconv", x.shape[0]) + (1 if fp32_products else 0)
     e_t = (K + 1) * EPS32 * A                                    # the activations' slopes are <= 1
-    E = np.abs(sc) * e_t + C_EPI * EPS32 * ((1.0 if kind == ELU else 0.0) + np.abs(v) + np.abs(sc * v) + np.abs(sh) + np.abs(ref))
-    return Ref(ref, E, out_half)
+    e_epi = C_EPI * EPS32 * ((1.0 if kind == ELU else 0.0) + np.abs(v) + np.abs(sc * v) + np.abs(sh) + np.abs(ref))
+    E = np.abs(sc) * e_t + e_epi
+    return Ref(ref, E, out_half, u=np.abs(sc) * (1 + 1) * EPS32 * A + e_epi, acc=np.abs(sc) * K * EPS32 * A)
 
 
 def head_ref(up6, w, b):
@@ -242,7 +247,7 @@ def head_ref(up6, w, b):
     A = contract64("head", np.abs(x), np.abs(w4)) + np.abs(bb)
     with np.errstate(over="ignore"):
         ref = 1.0 / (1.0 + np.exp(-pre))
-    return Ref(ref, (16 + 2) * EPS32 * A / 4 + 8 * EPS32, False)
+    return Ref(ref, (16 + 2) * EPS32 * A / 4 + 8 * EPS32, False, u=(1 + 2) * EPS32 * A / 4 + 8 * EPS32, acc=16 * EPS32 * A / 4)
 
 
 # ------------------------------------------------------------------------------------------- emulation of a correct kernel

@@ -31,8 +31,11 @@ def _rel_rms(a, b):
     return float(np.sqrt(np.mean((a - b) ** 2)) / (np.sqrt(np.mean(b ** 2)) + 1e-30))
 
 
-TAP_RMS_TOL = 2e-5          # every intermediate tensor, relative to its own RMS
-TAP_MAX_TOL = 1e-4          # ... and its worst single element relative to the tensor's peak: a handful of wrong border pixels in a
+# Twice what the chain measures over the 1717 tensors this file checks (worst rel-RMS 2.26e-6: up1 of 320 x 1984; worst max-abs / peak 4.17e-6: conv6 of 256 x 2048 x 5;
+# both figures hold the fp32 oracle's own accumulation error and every earlier layer's).  They were 2e-5 / 1e-4.  The arithmetic of a single layer is held
+# by tests/test_fp32_layer_local.py; this is the bound on what propagates.
+TAP_RMS_TOL = 4.6e-6        # every intermediate tensor, relative to its own RMS
+TAP_MAX_TOL = 8.4e-6        # ... and its worst single element relative to the tensor's peak: a handful of wrong border pixels in a
                             # multi-million-element tensor passes an RMS bound, it cannot pass this one
 
 
