@@ -24,7 +24,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-ENC_CH = ((2, 16), (16, 32), (32, 64), (64, 128), (128, 256), (256, 512))       # csrc/srt_engine.hip ENC_CH / DEC_CH
+ENC_CH = ((2, 16), (16, 32), (32, 64), (64, 128), (128, 256), (256, 512))       # csrc/srt_engine.h ENC_CH / DEC_CH
 DEC_CH = ((512, 256), (512, 128), (256, 64), (128, 32), (64, 16), (32, 1))
 TUNE_CANDIDATES = (512, 768, 1024, 1280, 1536, 2048)                            # c8_tuned's cands[]
 EDGES = ("whole", "single", "last1", "grid_odd")

@@ -15,7 +15,12 @@ batches their hops across instances - each owns its hop stream and its network s
 is about - every call of every instance, the worst one included, must stay under 5 ms (a fifth of the hop period: a host with its own DSP in the callback
 keeps the rest), ordinary hops p99 under 2 ms.  Back to back (an artificial burst no host produces: eight network batches collide with every instance's
 hops) p99 must stay under 5 ms and the single worst call under 10 ms (recorded as `worst_call_us`).  The numbers go to gpurun_out/r06_latency.json
-(copied to profiles/)."""
+(copied to profiles/).
+
+Known single-call outlier of the eight-instance burst (docs/LAB_NOTEBOOK.md 7, 8, 9): on a card shared with other jobs one call in some runs takes 10.3 - 12.3 ms
+(bound 10 ms) while p50 / p99 stay at 0.6 / 1.3 ms.  Bare harness, 8 runs per build on the same MI355X, builds alternating (section 9): the commit before the engine
+source was cut by concern had one such call (10 299 us, instance 7, hop 605), the commit after it none (worst 1 792 us); one whole-suite run of the later build failed
+here with 10 340 us on instance 0, another passed.  The bound stands; the cause is not found."""
 import json
 import os
 import subprocess
