@@ -161,7 +161,8 @@ SRT_API int  srtSetMaskExtension(srt_engine *e, int mode);
  * srtSetMix returns -1 with srtLastError() text (before any device work) for a null engine, n_out outside 0..SRT_MAX_STEMS, a null h_gain with n_out > 0, an
  * entry that is not finite, or the Wiener filter on; srtSetWiener(n > 0) returns -1 while the mix is on.
  * Refused with -1, a text that says "mix" and nothing launched or written while the mix is on: srtSeparateCli, srtSeparateCliHost[Io] (no stem axis),
- * srtIstftWiener, srtSeparateBatch, srtSeparateBatchWiener (follow-ups) and srtMultiSeparate*Host when any engine of the object has it on.  The live
+ * srtIstftWiener, srtSeparateBatchWiener (follow-ups), srtSeparateBatch[Overlap] (the batch takes the mix per track and per call: srtSeparateBatchMix)
+ * and srtMultiSeparate*Host when any engine of the object has it on.  The live
  * stream has the mix on its own handle (srtLiveCreateEx, srtLiveSetMix); the plugin surface (Spleeter4Stems*) writes every stem. */
 SRT_API int srtSetMix(srt_engine *e, int n_out, const float *h_gain);
 SRT_API int srtMixOutputs(const srt_engine *e);   /* n_out while on, 0 while off or for a null engine */
@@ -191,11 +192,32 @@ SRT_API int  srtSeparateBatch(srt_engine *e, int ntracks, const float *const *d_
  * SRT_MASK_EXT_AVERAGE srtCopyTensor("mask_ext") holds track k's rows from packed row tile0[k] * T (rows between a track's last row and its next tile boundary
  * are not written).
  * -1, with nothing launched or written, for everything srtSeparateBatch refuses except the engine's overlap setting, overlap_rows outside 0..T/2, more than
- * max_tiles overlapped packed tiles (srtBatchPlanOverlap counts them), the stem remix on, or the Wiener filter on; -5 when a stem's weights are not set.
+ * max_tiles overlapped packed tiles (srtBatchPlanOverlap counts them), the engine's stem remix on (srtSeparateBatchMix), or the Wiener filter on; -5 when a stem's weights are not set.
  * srtSeparateBatch keeps refusing while srtSetOverlap > 0, and srtSeparateBatchWiener keeps refusing an overlap. */
 SRT_API int  srtBatchPlanOverlap(const size_t *n, int ntracks, int T, int overlap_rows, size_t *tile0, size_t *total_tiles);
 SRT_API int  srtSeparateBatchOverlap(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
                                      const size_t *n, float *const *d_out, int overlap_rows);
+
+/* srtSeparateBatchOverlap with a stem remix per track: every track of a queue carries its own request - vocals only for one upload, karaoke at
+ * -3 dB for the next - so the matrix of srtSetMix is an argument per track here.  Tracks, packing (srtBatchPlanOverlap), track-table upload and slot ring as
+ * srtSeparateBatchOverlap; always eager, refused inside a stream capture; the only host wait is the one for the upload issued four calls earlier.
+ * overlap_rows (0..T/2), n_out and the matrices hold for this call: the engine's own srtSetOverlap and srtSetMix state is neither read nor changed, the call works
+ * with either on or off, and srtMixOutputs(e) is the same afterwards.
+ * 1 <= n_out <= SRT_MAX_STEMS, one number for the call: d_out[k] is [n_out][2][srtIstftLength(srtStftRows(n[k]))].  h_gain is host memory and is copied; track k's
+ *   matrix is [n_out][n_stems + 1], row-major in srtSetMix's layout, at h_gain + k * gain_stride.  gain_stride = 0: every track uses the one matrix at h_gain;
+ *   otherwise gain_stride >= n_out * (n_stems + 1).  The matrices go up in stream order beside the track table, into a device table the first such call allocates.
+ * Output m of track k is what srtSeparate writes for that track alone after srtSetOverlap(e, overlap_rows) and srtSetMix(e, n_out, G_k) - srtSetMix's chain
+ *   h = G_k[m][n_stems]; h = fmaf(G_k[m][s], g_s, h) for s ascending, over the same g_s (mask, cross-fade, ratio_mask; above F oob_weight[s] or the table value of
+ *   SRT_MASK_EXT_AVERAGE) - bit for bit with batch_invariant, up to the network's batch-dependent kernel choice otherwise.  The fp16 mode keeps its masks as floats
+ *   for this call, as with srtSetMix.
+ * n_out = 0: srtSeparateBatchOverlap(.., overlap_rows), launch for launch; h_gain and gain_stride are ignored.
+ * -1 with srtLastError() text that names srtSeparateBatchMix, and nothing launched or written, for everything srtSeparateBatchOverlap refuses except the engine's
+ * mix setting, n_out outside 0..SRT_MAX_STEMS, a null h_gain with n_out > 0, a non-zero gain_stride below n_out * (n_stems + 1), an entry that is not finite
+ * (the text names the track), or the Wiener filter on; -5 when a stem's weights are not set.
+ * Follow-ups: a per-track n_out, the mix under the Wiener filter (srtSeparateBatchWiener), graph capture of batch calls. */
+SRT_API int  srtSeparateBatchMix(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
+                                 const size_t *n, float *const *d_out, int overlap_rows,
+                                 int n_out, const float *h_gain, size_t gain_stride);
 
 /* A long HOST-resident stream through one GPU: cut into chunks of max_tiles tiles, upload / compute / download overlapped on
  * three HIP streams with double buffers, chunk overlaps (3072 samples) added on the device.  Geometry as srtSeparateEx.

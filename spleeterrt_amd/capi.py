@@ -90,6 +90,7 @@ def load_library():
     L.srtSeparateBatchWiener.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
     L.srtBatchPlanOverlap.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.srtSeparateBatchOverlap.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
+    L.srtSeparateBatchMix.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     L.srtSetGraphMode.argtypes = [vp, C.c_int]
     L.srtPrepareForward.argtypes = [vp, f32p, C.c_int, f32p]
     L.srtReleaseStaging.argtypes = [vp]
@@ -348,28 +349,46 @@ class Engine:
         self._chk(self.L.srtSeparate(self.h, _ptr(L), _ptr(R), n, _ptr(out)))
         return out
 
-    def separate_batch(self, tracks, outs=None, wiener=None, overlap=None):
+    def separate_batch(self, tracks, outs=None, wiener=None, overlap=None, mix=None):
         """many independent tracks: [(L, R)] CUDA float32 tensors -> [stems [S,2,rows_k*1024+3072]], each equal to separate(L, R) of that track.
         The list is cut in order into calls of at most max_tiles packed tiles (stream.pack_tracks); one srtSeparateBatch per call.
         wiener: None = the engine's own setting (set_wiener), 0 = no filter, 1..3 = the multichannel Wiener filter per track with that many iterations
         (one srtSeparateBatchWiener per call): each track as separate(L, R) on an engine with set_wiener(wiener).
         overlap: None = the engine's own setting (set_overlap), 0 = back-to-back tiles, 1..T/2 = overlapped tiles with cross-faded masks inside every track
         (one srtSeparateBatchOverlap per call, the list cut by overlapped tiles): each track as separate(L, R) on an engine with set_overlap(overlap).  The
-        filter and an overlap exclude each other."""
+        filter and an overlap exclude each other.
+        mix: None = the stems (the engine's set_mix is not read: the batch calls refuse while it is on); one [n_out, S + 1] matrix for all tracks, or a list of
+        one such matrix per track, all with the same n_out (set_mix's layout: the last column is the unmasked input) -> [mixes [n_out,2,rows_k*1024+3072]],
+        each equal to separate(L, R) of that track after set_mix(its matrix) and set_overlap(overlap) (one srtSeparateBatchMix per call, each with its own
+        tracks' matrices).  Not with the filter."""
         from . import stream
+        import numpy as np
         t = self.torch
         ns = [L.numel() for L, _ in tracks]
+        G, n_planes = None, self.S
+        if mix is not None:
+            try:
+                G = np.ascontiguousarray(mix, dtype=np.float32)
+            except ValueError:                                           # matrices of different shapes
+                G = np.zeros(0, np.float32)
+            if G.ndim == 2:
+                G = np.ascontiguousarray(np.broadcast_to(G, (len(tracks),) + G.shape))
+            if G.ndim != 3 or G.shape[0] != len(tracks) or G.shape[2] != self.S + 1 or not 1 <= G.shape[1] <= MAX_STEMS:
+                raise EngineError("separate_batch: mix must be [n_out, S + 1] or one such matrix per track with the same n_out (1 <= n_out <= %d)" % MAX_STEMS)
+            n_planes = G.shape[1]
         for L, R in tracks:
             assert L.is_cuda and R.is_cuda and L.dtype == t.float32 and R.dtype == t.float32 and R.numel() == L.numel()
         wiener = self.wiener if wiener is None else int(wiener)
         overlap = self.overlap if overlap is None else int(overlap)
         if overlap > 0 and wiener:
             raise EngineError("separate_batch: the Wiener filter is not available with overlapped tiles (overlap = %d, wiener = %d): pass overlap=0 or wiener=0" % (overlap, wiener))
+        if G is not None and wiener:
+            raise EngineError("separate_batch: the stem mix is not available with the Wiener filter (wiener = %d): pass wiener=0 or mix=None" % wiener)
         if outs is None:
-            outs = [t.empty((self.S, 2, self.L.srtIstftLength(self.L.srtStftRows(n))), device=self.device, dtype=t.float32) for n in ns]
+            outs = [t.empty((n_planes, 2, self.L.srtIstftLength(self.L.srtStftRows(n))), device=self.device, dtype=t.float32) for n in ns]
         assert len(outs) == len(tracks)
         for o, n in zip(outs, ns):
-            assert o.is_cuda and o.is_contiguous() and o.numel() >= self.S * 2 * self.L.srtIstftLength(self.L.srtStftRows(n))
+            assert o.is_cuda and o.is_contiguous() and o.numel() >= n_planes * 2 * self.L.srtIstftLength(self.L.srtStftRows(n))
         src = [(L.contiguous(), R.contiguous()) for L, R in tracks]      # (kept alive until the calls are issued; the stream orders any reuse)
         own, own_ov = self.wiener, self.overlap
         if own and not wiener:                                           # srtSeparateBatch refuses while the engine's filter is on: off for these calls
@@ -382,7 +401,10 @@ class Engine:
                 P = C.c_void_p * k
                 args = (self.h, k, P(*[src[i][0].data_ptr() for i in g.tracks]), P(*[src[i][1].data_ptr() for i in g.tracks]),
                         (C.c_size_t * k)(*[ns[i] for i in g.tracks]), P(*[outs[i].data_ptr() for i in g.tracks]))
-                if overlap > 0:
+                if G is not None:
+                    Gk = np.ascontiguousarray(G[list(g.tracks)])
+                    self._chk(self.L.srtSeparateBatchMix(*args, overlap, n_planes, Gk.ctypes.data_as(C.POINTER(C.c_float)), n_planes * (self.S + 1)))
+                elif overlap > 0:
                     self._chk(self.L.srtSeparateBatchOverlap(*args, overlap))
                 else:
                     self._chk(self.L.srtSeparateBatchWiener(*args, wiener) if wiener else self.L.srtSeparateBatch(*args))

@@ -42,6 +42,17 @@ static int ensure_batch(srt_engine* e)
     return 0;
 }
 
+// the per-track remix matrices (see srt_engine::bgtab): the device table and its pinned slots, allocated once, by the first srtSeparateBatchMix with n_out > 0
+static int ensure_batch_mix(srt_engine* e)
+{
+    if (e->bgtab && e->bgpin) return 0;
+    SrtSetupLock setup;
+    const size_t bytes = (size_t)e->cfg.max_tiles * SRT_BATCH_GAIN_FLOATS * sizeof(float);
+    if (!e->bgtab) HIPCHK(e->bwmem.alloc(&e->bgtab, bytes));
+    if (!e->bgpin) HIPCHK(e->bwmem.alloc(&e->bgpin, SRT_BATCH_SLOTS * bytes, true));
+    return 0;
+}
+
 // the per-track filter's workspace (see srt_engine::bwmem): sizes follow from the configuration, so it is allocated once, by the first srtSeparateBatchWiener
 static size_t batch_wiener_chunk_cap(const srt_engine* e) { return (size_t)e->cfg.max_tiles * e->cfg.T / 16 + e->cfg.max_tiles; }
 static size_t batch_wiener_track_floats(const srt_engine* e) { return (size_t)SRT_WIENER_MAX_ITERS * e->cfg.n_stems * e->cfg.F; }      // R: x 4, weight sums: x 1
@@ -66,9 +77,11 @@ static int ensure_batch_wiener(srt_engine* e)
 // srtSeparateBatchWiener, 0 for the others), the track table(s) and their upload from a pinned slot, the batched STFT and the network over the packed tiles.
 // overlap: -1 for the entry points that have no overlap argument (they refuse while the engine's own setting is on); >= 0: srtSeparateBatchOverlap's argument, which
 // holds for the call whatever the engine's setting says (0: the back-to-back plan and kernels)
+// mx: srtSeparateBatchMix's own arguments (null for the other entry points, which refuse while the engine's srtSetMix is on); n_out = 0: no remix in this call
 struct BatchCall { size_t total; SrtBatchGrid g; size_t ch_stride; int wchunks; };
+struct BatchMix { int n_out; const float* h_gain; size_t stride; };
 static int batch_forward(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
-                         int wiener, int overlap, BatchCall* bc)
+                         int wiener, int overlap, BatchCall* bc, const BatchMix* mx = nullptr)
 {
     if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "%s: need ntracks >= 1 and the four track arrays", who);
     const SrtSwitches sw = srt_read_switches();
@@ -81,7 +94,15 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
     if (overlap < 0 && e->overlap) return fail(-1, OVERLAP_REFUSED, who);     // srtBatchPlan has no overlap argument: srtSeparateBatchOverlap
     if (overlap > T / 2) return fail(-1, "%s: the overlap must be 0 .. T / 2 rows", who);
     const int O = overlap > 0 ? overlap : 0;
-    if (e->mix_out) return fail(-1, MIX_REFUSED, who);
+    if (!mx && e->mix_out) return wiener ? fail(-1, MIX_REFUSED, who)
+                                         : fail(-1, "%s: not available with the engine's stem remix on (srtSetMix): srtSeparateBatchMix takes the mix per track, or srtSetMix(e, 0, NULL) first", who);
+    const int n_out = mx ? mx->n_out : 0, gw = n_out * (S + 1);                // gw: floats of one track's matrix
+    if (n_out) {
+        if (!mx->h_gain) return fail(-1, "%s: null gain matrices", who);
+        if (mx->stride && mx->stride < (size_t)gw) return fail(-1, "%s: gain_stride must be 0 (one matrix for every track) or at least n_out * (n_stems + 1)", who);
+        for (int k = 0; k < (mx->stride ? ntracks : 1); ++k)
+            for (int i = 0; i < gw; ++i) if (!isfinite(mx->h_gain[k * mx->stride + i])) { snprintf(what, sizeof what, "%s: a gain of track %d is not finite", who, k); return fail(-1, "%s", what); }
+    }
     if (overlap >= 0 && e->wiener) return fail(-1, "%s: not available with the Wiener filter on (its kernels index masks by back-to-back tiles): srtSetWiener(e, 0) first", who);
     if (!wiener && e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
     size_t total = 0;
@@ -97,6 +118,7 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
     int rc = ensure_batch(e);
     if (rc) return rc;
     if (wiener && (rc = ensure_batch_wiener(e))) return rc;
+    if (n_out && (rc = ensure_batch_mix(e))) return rc;
     // the table goes up in stream order from a pinned slot; the slot's previous copy (SRT_BATCH_SLOTS calls ago) must have left it first
     const int slot = e->bslot;
     if (e->bused[slot]) HIPCHK(hipEventSynchronize(e->bev[slot]));
@@ -109,7 +131,8 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         t.tile0 = (int)tile0; t.ntiles = (int)overlap_tiles((size_t)t.rows, T, O); tile0 += t.ntiles;      // (O = 0: ceil(rows / T))
         t.out = d_out[k]; t.out_len = srtIstftLength(t.rows);
     }
-    if (srt_batch_geometry(h, ntracks, T, F, S, &bc->g)) return fail(-1, "%s: batch geometry out of range", who);
+    // (the inverse grid has one workgroup column per output of a remix, as srt_launch_istft's ncol; the STFT grid does not depend on the count)
+    if (srt_batch_geometry(h, ntracks, T, F, n_out ? n_out : S, &bc->g)) return fail(-1, "%s: batch geometry out of range", who);
     bc->wchunks = 0;
     SrtBatchWiener* hw = wiener ? e->bwpin + (size_t)slot * e->cfg.max_tiles : nullptr;
     if (wiener) {
@@ -118,6 +141,11 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
     }
     HIPCHK(hipMemcpyAsync(e->btab, h, (size_t)ntracks * sizeof(SrtBatchTrack), hipMemcpyHostToDevice, e->stream));
     if (wiener) HIPCHK(hipMemcpyAsync(e->bwtab, hw, (size_t)ntracks * sizeof(SrtBatchWiener), hipMemcpyHostToDevice, e->stream));
+    if (n_out) {                                               // the tracks' matrices, packed [ntracks][n_out][S + 1], from the same slot of the ring
+        float* hg = e->bgpin + (size_t)slot * e->cfg.max_tiles * SRT_BATCH_GAIN_FLOATS;
+        for (int k = 0; k < ntracks; ++k) memcpy(hg + (size_t)k * gw, mx->h_gain + k * mx->stride, (size_t)gw * sizeof(float));
+        HIPCHK(hipMemcpyAsync(e->bgtab, hg, (size_t)ntracks * gw * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    }
     HIPCHK(hipEventRecord(e->bev[slot], e->stream));
     e->bused[slot] = true; e->bslot = (slot + 1) % SRT_BATCH_SLOTS;
     bc->total = total;
@@ -130,15 +158,18 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         if (srt_launch_stft_batch(p, e->btab, ntracks, bc->g, e->stream, O)) return fail(-2, "batched stft launch failed");
     }
     // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue (never with the filter, which reads fp32 masks)
-    return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, !wiener && masks16_wanted(e, sw));
+    // (nor with a remix: the MIX kernels read float masks, as under srtSetMix)
+    return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, !wiener && !n_out && masks16_wanted(e, sw));
 }
 
 // srtSeparateBatch (overlap = -1) and srtSeparateBatchOverlap (overlap >= 0): the shared front, the gain table of the average mask extension, one batched inverse
-static int batch_separate(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap)
+// mx with n_out > 0 (srtSeparateBatchMix): the inverse writes n_out pairs per track, each the chain of the track's own matrix row (the device gain table)
+static int batch_separate(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap,
+                          const BatchMix* mx = nullptr)
 {
     DeviceScope ds(e->device);
     BatchCall bc;
-    int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, 0, overlap, &bc);
+    int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, 0, overlap, &bc, mx);
     if (rc) return rc;
     const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems, O = overlap > 0 ? overlap : 0;
     SrtIstftParams q; memset(&q, 0, sizeof q);
@@ -153,7 +184,10 @@ static int batch_separate(srt_engine* e, const char* who, int ntracks, const flo
         q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
     }
     TimerScope ts(e, "istft_batch");
-    if (srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
+    if (mx && mx->n_out) {
+        q.n_out = mx->n_out;
+        if (srt_launch_istft_batch_mix(q, e->btab, e->bgtab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
+    } else if (srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
     return 0;
 }
 
@@ -169,6 +203,19 @@ int srtSeparateBatchOverlap(srt_engine* e, int ntracks, const float* const* d_L,
     if (!e) return fail(-1, "srtSeparateBatchOverlap: null engine");
     if (overlap_rows < 0) return fail(-1, "srtSeparateBatchOverlap: the overlap must be 0 .. T / 2 rows");
     return batch_separate(e, "srtSeparateBatchOverlap", ntracks, d_L, d_R, n, d_out, overlap_rows);
+}
+
+// srtSeparateBatchOverlap with a stem remix per track: n_out outputs per track instead of n_stems, track k's matrix [n_out][n_stems + 1] at
+// h_gain + k * gain_stride (0: one matrix for all).  overlap_rows, n_out and the matrices hold for this call; the engine's srtSetOverlap / srtSetMix are neither
+// read nor changed.  n_out = 0: srtSeparateBatchOverlap
+int srtSeparateBatchMix(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap_rows,
+                        int n_out, const float* h_gain, size_t gain_stride)
+{
+    if (!e) return fail(-1, "srtSeparateBatchMix: null engine");
+    if (overlap_rows < 0) return fail(-1, "srtSeparateBatchMix: the overlap must be 0 .. T / 2 rows");
+    if (n_out < 0 || n_out > SRT_MAX_STEMS) return fail(-1, "srtSeparateBatchMix: n_out must be 0 (no remix) .. SRT_MAX_STEMS");
+    const BatchMix mx = { n_out, h_gain, n_out ? gain_stride : 0 };
+    return batch_separate(e, "srtSeparateBatchMix", ntracks, d_L, d_R, n, d_out, overlap_rows, &mx);
 }
 
 // srtSeparateBatch with the Wiener filter per track: the shared front (fp32 masks), `iterations` x (statistics + finalize) and the filter over the packed rows

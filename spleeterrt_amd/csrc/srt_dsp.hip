@@ -257,8 +257,12 @@ __device__ __forceinline__ float srt_ratio_of_ov(const float* __restrict__ rowb0
 // The stem loop is the OUTER one: a pass over the stems for the square sums (ratio only), a second one for the chain (its re-reads are cache hits) - one matrix
 // entry per stem (a uniform load) and no per-stem array.  hl / hr: the NB bins tid + 256 j of the two channels.
 // r0 / a0: stem 0's L row of the frame in its primary / previous tile (r0 null: no masks, g_s = 1; a0 read only when two); ratio: a run-time flag here.
-template <int NB, int JC>
-__device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const float* __restrict__ r0, const float* __restrict__ a0, bool two, float w, bool ratio, int m, int tid,
+// Where row m of the matrix comes from is the gain source `g`, g(s) = G[m][s]: the launch's own arguments (srtSetMix: one matrix per call), or a row of the
+// device table of a packed batch (srtSeparateBatchMix: one matrix per track).  Either way the address is workgroup-uniform and an entry is loaded where it is used.
+struct SrtMixArg { const SrtIstftParams& p; int m; __device__ __forceinline__ float operator()(int s) const { return p.mix[m][s]; } };
+struct SrtMixTab { const float* __restrict__ row; __device__ __forceinline__ float operator()(int s) const { return row[s]; } };
+template <int NB, int JC, class GS>
+__device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const GS& g, const float* __restrict__ r0, const float* __restrict__ a0, bool two, float w, bool ratio, int tid,
                                               float (&hl)[NB], float (&hr)[NB])
 {
     const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
@@ -275,7 +279,7 @@ __device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const flo
 #pragma unroll
         for (int i = 0; i < JC; ++i) { suml[i] = 0.0f; sumr[i] = 0.0f; }
 #pragma unroll
-        for (int i = 0; i < JC; ++i) if (j0 + i < NB) { hl[j0 + i] = p.mix[m][p.nstems]; hr[j0 + i] = hl[j0 + i]; }
+        for (int i = 0; i < JC; ++i) if (j0 + i < NB) { hl[j0 + i] = g(p.nstems); hr[j0 + i] = hl[j0 + i]; }
         if (r0 && ratio) {
             for (int s = 0; s < p.nstems; ++s) {
                 const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * sstride;
@@ -290,7 +294,7 @@ __device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const flo
             }
         }
         for (int s = 0; s < p.nstems; ++s) {
-            const float gm = p.mix[m][s];
+            const float gm = g(s);
             const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * sstride;
 #pragma unroll
             for (int i = 0; i < JC; ++i) {
@@ -310,10 +314,11 @@ __device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const flo
     }
 }
 // the same chain over one value per stem (workgroup-uniform): x[s * stride], s ascending - the constant weights of bins >= F, or a row of the extension's table
-__device__ __forceinline__ float srt_mix_chain(const SrtIstftParams& p, int m, const float* __restrict__ x, size_t stride)
+template <class GS>
+__device__ __forceinline__ float srt_mix_chain(const SrtIstftParams& p, const GS& g, const float* __restrict__ x, size_t stride)
 {
-    float h = p.mix[m][p.nstems];
-    for (int s = 0; s < p.nstems; ++s) h = fmaf(p.mix[m][s], x[(size_t)s * stride], h);
+    float h = g(p.nstems);
+    for (int s = 0; s < p.nstems; ++s) h = fmaf(g(s), x[(size_t)s * stride], h);
     return h;
 }
 
@@ -323,8 +328,17 @@ __device__ __forceinline__ float srt_mix_chain(const SrtIstftParams& p, int m, c
 // or one track of a packed batch (srt_istft_batch_kernel: spectrum and masks offset to the track's first packed row / tile, its own frames and output).
 // Everything else (stem count and stride, T, F, oob weights, tables) comes from the launch's SrtIstftParams.
 // ext: the signal's rows of the average mask extension's gain table (stem 0's; EXT instantiations only, see srt_mask_ext_kernel)
-struct IstftView { const float2* spec; const float* masks; float* out; size_t out_len; int frames; const float* ext; };
-__device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { IstftView v = { p.spec, p.masks, p.out, p.out_len, p.frames, p.ext }; return v; }
+// gain: row 0 of the signal's remix matrix [n_out][nstems + 1] in device memory (the GTAB instantiations only: a track of srtSeparateBatchMix)
+struct IstftView { const float2* spec; const float* masks; float* out; size_t out_len; int frames; const float* ext; const float* gain; };
+__device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { IstftView v = { p.spec, p.masks, p.out, p.out_len, p.frames, p.ext, nullptr }; return v; }
+
+// the gain source of output m of a MIX body (see srt_mix_gains)
+template <bool GTAB>
+__device__ __forceinline__ auto srt_mix_source(const SrtIstftParams& p, const IstftView& w, int m)
+{
+    if constexpr (GTAB) return SrtMixTab{ w.gain + (size_t)m * (p.nstems + 1) };
+    else return SrtMixArg{ p, m };
+}
 
 #define ISTFT_OLA_LDS_F2 (2 * FFT_SMEM_F2 + FFT_TWB_F2)   // two staging / exchange buffers + the pass-2 twiddles (one LDS object)
 // OV: overlapped network tiles (srt_ov_row): the mask row of a frame's primary tile is prefetched as always; inside an overlap the previous tile's row is
@@ -334,7 +348,8 @@ __device__ __forceinline__ IstftView istft_view(const SrtIstftParams& p) { Istft
 // MIX: stem remix (srt_mix_gains): `stem` is the OUTPUT index m; no mask row is prefetched (every stem's row is read in the prologue), RATIO = false (a run-time flag)
 // TRK (with OV): the view is a track of a packed batch - p.ntiles is the packed total there (the masks' stem stride), and srt_ov_row clamps the primary tile with the
 // track's own overlapped count, the argument ov_tiles (unused otherwise: a whole call's count is p.ntiles)
-template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false>
+// GTAB (with MIX): the matrix row is read from the view's device table (w.gain, SrtMixTab) instead of the launch arguments (p.mix, SrtMixArg)
+template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false, bool GTAB = false>
 __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0)
 {
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
@@ -346,7 +361,8 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
     const size_t tf = (size_t)p.T * p.F;
     const int nseg = w.frames + 3;
     const int s0 = run * G, s1 = min(s0 + G, nseg);
-    const float oob = MIX ? srt_mix_chain(p, stem, p.oob, 1) : p.oob[stem];   // bins >= F: "unaffectedWeight" (main.c:486-493)
+    const auto gsrc = srt_mix_source<GTAB>(p, w, stem);
+    const float oob = MIX ? srt_mix_chain(p, gsrc, p.oob, 1) : p.oob[stem];   // bins >= F: "unaffectedWeight" (main.c:486-493)
     const cf* spec = reinterpret_cast<const cf*>(w.spec);
     float* oL = w.out + (size_t)(stem * 2 + 0) * w.out_len;
     float* oR = w.out + (size_t)(stem * 2 + 1) * w.out_len;
@@ -440,8 +456,8 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
                 const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                 const float* r0 = has_mask ? w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F : nullptr;
                 const float* a0 = OV && has_mask ? r0 - 2 * tf + (size_t)(p.T - O) * p.F : r0;
-                srt_mix_gains<9, 3>(p, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, stem, tid, gl, gr);
-                if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, stem, ext + fu, p.ext_stem); eR = srt_mix_chain(p, stem, ext + fu + 1, p.ext_stem); }
+                srt_mix_gains<9, 3>(p, gsrc, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, tid, gl, gr);
+                if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, gsrc, ext + fu, p.ext_stem); eR = srt_mix_chain(p, gsrc, ext + fu + 1, p.ext_stem); }
             }
             const float xl = EXT ? eL : oob, xr = EXT ? eR : oob;              // bins >= F
 #pragma unroll
@@ -683,8 +699,8 @@ __global__ void __launch_bounds__(256, 3) srt_stft_ov_kernel(const SrtStftParams
 #define ISTFT_OLA3_LDS_F2 (FFT_SMEM_F2 + FFT_MIR_F2 + FFT_TWB_F2)
 // EXT: as istft_ola_run
 // MIX: as istft_ola_run (RATIO = M16 = false)
-// TRK: as istft_ola_run
-template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false>
+// TRK, GTAB: as istft_ola_run
+template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false, bool GTAB = false>
 __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0)
 {
     cf* sx = s_mem;
@@ -696,7 +712,8 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
     const size_t tf = (size_t)p.T * p.F;
     const int nseg = w.frames + 3;
     const int s0 = run * G, s1 = min(s0 + G, nseg);
-    const float oob = MIX ? srt_mix_chain(p, stem, p.oob, 1) : p.oob[stem];   // bins >= F: "unaffectedWeight" (main.c:486-493)
+    const auto gsrc = srt_mix_source<GTAB>(p, w, stem);
+    const float oob = MIX ? srt_mix_chain(p, gsrc, p.oob, 1) : p.oob[stem];   // bins >= F: "unaffectedWeight" (main.c:486-493)
     const cf* spec = reinterpret_cast<const cf*>(w.spec);
     float* oL = w.out + (size_t)(stem * 2 + 0) * w.out_len;
     float* oR = w.out + (size_t)(stem * 2 + 1) * w.out_len;
@@ -801,8 +818,8 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
                 const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                 const float* r0 = has_mask ? w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F : nullptr;
                 const float* a0 = OV && has_mask ? r0 - 2 * tf + (size_t)(p.T - O) * p.F : r0;
-                srt_mix_gains<NM, NM>(p, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, stem, tid, gl, gr);
-                if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, stem, ext + fu, p.ext_stem); eR = srt_mix_chain(p, stem, ext + fu + 1, p.ext_stem); }
+                srt_mix_gains<NM, NM>(p, gsrc, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, tid, gl, gr);
+                if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, gsrc, ext + fu, p.ext_stem); eR = srt_mix_chain(p, gsrc, ext + fu + 1, p.ext_stem); }
             }
             const float xl = EXT ? eL : oob, xr = EXT ? eR : oob;              // bins >= F
 #pragma unroll
@@ -1236,6 +1253,27 @@ __global__ void __launch_bounds__(256, OLA3 && !RATIO ? 3 : 2) srt_istft_batch_o
     else istft_ola_run<RATIO, true, EXT, false, true>(p, w, stem, run - tk.wg_istft, G, s_mem, O, tk.ntiles);
 }
 
+// Stem remix per track (srtSeparateBatchMix): the MIX bodies on a track's view.  The workgroup index is the OUTPUT m, fastest in the XCD order, so
+// the outputs of a run share its spectrum rows and every stem's mask rows in L2 (srt_istft_ola3_mix_kernel).  Track k's matrix is row k of the device table
+// `gains` [ntracks][n_out][nstems + 1], uploaded beside the track table: the bodies read row m of it entry by entry (SrtMixTab; k and m are workgroup-uniform, so
+// these are scalar loads), nothing of p.mix.  OV = false: the back-to-back view of srt_istft_batch_kernel (O and the track's tile count are unused); EXT as above.
+template <bool OLA3, bool OV, bool EXT>
+__global__ void __launch_bounds__(256, 2) srt_istft_batch_bus_kernel(const SrtIstftParams p, const SrtBatchTrack* __restrict__ tracks, int ntracks, int G, int O, const float* __restrict__ gains)
+{
+    const int pos = srt_xcd_order(gridDim.x), m = pos % p.n_out, run = pos / p.n_out;
+    __shared__ cf s_mem[OLA3 ? ISTFT_OLA3_LDS_F2 : ISTFT_OLA_LDS_F2];
+    const int k = srt_batch_track<true>(tracks, ntracks, run);
+    const SrtBatchTrack tk = tracks[k];
+    IstftView w;
+    w.spec = p.spec + (size_t)tk.tile0 * p.T * SRT_SPEC_LD;
+    w.masks = p.masks + (size_t)tk.tile0 * 2 * p.T * p.F;                   // (the launcher checks that masks are given: floats)
+    w.out = tk.out; w.out_len = tk.out_len; w.frames = tk.rows;
+    w.ext = EXT ? p.ext + (size_t)tk.tile0 * p.T * 2 : nullptr;
+    w.gain = gains + (size_t)k * p.n_out * (p.nstems + 1);
+    if constexpr (OLA3) istft_ola3_run<4, false, false, OV, EXT, true, true, true>(p, w, m, run - tk.wg_istft, G, s_mem, O, tk.ntiles);
+    else istft_ola_run<false, OV, EXT, true, true, true>(p, w, m, run - tk.wg_istft, G, s_mem, O, tk.ntiles);
+}
+
 // The gain table of the average mask extension for such a batch: one wave per (packed row, channel), as srt_mask_ext_kernel.  The row's track is the last one
 // with tile0 * T <= row (the wave index is made uniform first, so every probe of the table is a scalar load); the row is mapped with the TRACK's tile count, its
 // blend partner is read inside the track's tiles, and ext is written at the packed row.  Rows past the track's own (the rest of its last tile) are skipped.
@@ -1369,6 +1407,27 @@ int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_track
     } else if (p.F > 1024) SRT_LAUNCH((srt_istft_batch_kernel<false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     else if (p.masks16) SRT_LAUNCH((srt_istft_batch_kernel<true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
     else SRT_LAUNCH((srt_istft_batch_kernel<true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G);
+    return srt_launch_status();
+}
+
+// the stem remix per track: p.n_out outputs per track (g from srt_batch_geometry with n_out workgroup columns), track k's matrix at d_gains + k * n_out * (nstems + 1);
+// float masks are required, p.mix is not read.  The form follows F, the overlap and p.ext; ratio is a run-time flag of the MIX bodies
+int srt_launch_istft_batch_mix(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, const float* d_gains, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap)
+{
+    if (g.istft_runs <= 0 || overlap < 0 || overlap > p.T / 2 || !p.masks || p.masks16 || !d_gains) return -1;
+    if (p.n_out < 1 || p.n_out > SRT_MAX_STEMS || p.nstems < 1 || p.nstems > SRT_MAX_STEMS) return -1;
+    if (p.ext && p.ext_stem < (size_t)p.frames * 2) return -1;
+    const dim3 grid(g.istft_runs * p.n_out);
+    const int O = overlap;
+    if (p.F > 1024) {
+        if (O > 0 && p.ext) SRT_LAUNCH((srt_istft_batch_bus_kernel<false, true, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O, d_gains);
+        else if (O > 0) SRT_LAUNCH((srt_istft_batch_bus_kernel<false, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O, d_gains);
+        else if (p.ext) SRT_LAUNCH((srt_istft_batch_bus_kernel<false, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, 0, d_gains);
+        else SRT_LAUNCH((srt_istft_batch_bus_kernel<false, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, 0, d_gains);
+    } else if (O > 0 && p.ext) SRT_LAUNCH((srt_istft_batch_bus_kernel<true, true, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O, d_gains);
+    else if (O > 0) SRT_LAUNCH((srt_istft_batch_bus_kernel<true, true, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, O, d_gains);
+    else if (p.ext) SRT_LAUNCH((srt_istft_batch_bus_kernel<true, false, true>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, 0, d_gains);
+    else SRT_LAUNCH((srt_istft_batch_bus_kernel<true, false, false>), grid, dim3(256), 0, s, p, d_tracks, ntracks, g.G, 0, d_gains);
     return srt_launch_status();
 }
 

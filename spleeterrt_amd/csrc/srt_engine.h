@@ -54,6 +54,7 @@ struct ForwardRecord {
 // `sw`: the run-time switches of the call (SrtSwitches, srt_internal.h) - all of them decide what a forward records, so a flipped switch captures a new
 // graph instead of replaying the old form.  Keys are zeroed before they are filled and compared with memcmp.
 #define SRT_BATCH_SLOTS 4
+#define SRT_BATCH_GAIN_FLOATS (SRT_MAX_STEMS * (SRT_MAX_STEMS + 1))      // the largest remix matrix of one track (srtSeparateBatchMix)
 // `overlap`: the rows consecutive network tiles share (srtSetOverlap) - a sequence captured at one overlap is never replayed at another.
 // `mask_ext`: the rule for bins >= F (srtSetMaskExtension), for the same reason.
 // `mix_gen`: the generation of the stem remix matrix (srtSetMix bumps it; 0 while the mix is off) - a changed matrix never replays a graph captured with the old one
@@ -127,6 +128,9 @@ struct srt_engine {
     SrtMem bwmem;
     SrtBatchWiener* bwtab = nullptr; SrtBatchWiener* bwpin = nullptr;
     float* bwslab = nullptr; float* bwtabf = nullptr;
+    // ... with the stem remix per track (srtSeparateBatchMix): the device gain table, max_tiles matrices of SRT_BATCH_GAIN_FLOATS, and the same ring
+    // of pinned slots; a call uploads ntracks x [n_out][n_stems + 1] beside the track table.  Allocated by the first such call, owned by bwmem as well
+    float* bgtab = nullptr; float* bgpin = nullptr;
     // timing
     bool timing = false; std::vector<TimingEntry> tlog;
 };

@@ -249,6 +249,9 @@ int srt_batch_geometry(SrtBatchTrack* t, int ntracks, int T, int F, int nstems, 
 // srtOverlapTiles(rows, T, overlap); the overlap is an argument of its own, as in srt_launch_stft / srt_launch_istft.  0: the kernels as they always were
 int srt_launch_stft_batch(const SrtStftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap = 0);
 int srt_launch_istft_batch(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap = 0);
+// the stem remix per track (srtSeparateBatchMix): p.n_out outputs per track, g from srt_batch_geometry with n_out in place of nstems; track k's matrix
+// [n_out][nstems + 1] (srtSetMix's layout) at d_gains + k * n_out * (nstems + 1) in device memory.  p.masks: floats, required; p.mix is not read
+int srt_launch_istft_batch_mix(const SrtIstftParams& p, const SrtBatchTrack* d_tracks, const float* d_gains, int ntracks, const SrtBatchGrid& g, hipStream_t s, int overlap = 0);
 // the gain table of the average mask extension over the packed rows of such a batch (p.rows = p.ntiles * T packed rows; rows past a track's own are left alone)
 int srt_launch_mask_ext_batch(const SrtMaskExtParams& p, const SrtBatchTrack* d_tracks, int ntracks, hipStream_t s, int overlap);
 
