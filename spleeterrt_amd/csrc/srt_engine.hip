@@ -571,7 +571,11 @@ static int launch_decoder_layer(srt_engine* e, const SrtSwitches& sw, const Forw
         }
     }
     if (e->act16 && i < 5 && rc == 1) return fail(-4, "internal: fp16 activation storage but no fp16 kernel for a decoder layer");
-    if (rc == 1 && e->wino_u[i] && (!f.few || srt_wino_force())) rc = srt_launch_dec_wino(p, e->wino_u[i] + (size_t)f.s0 * e->wino_u_stem[i], e->wino_u_stem[i], sw, e->stream);
+    if (rc == 1 && e->wino_u[i] && (!f.few || srt_wino_force())) {
+        SrtSwitches swd = sw;
+        if (swd.wino_ac && (e->graph_mode || stream_capturing(e))) swd.wino_ac = 0;      // (as for up6 + head above: what a graph records stays what it was)
+        rc = srt_launch_dec_wino(p, e->wino_u[i] + (size_t)f.s0 * e->wino_u_stem[i], e->wino_u_stem[i], swd, e->stream);
+    }
     if (rc == 1 && e->cfg.impl == SRT_IMPL_MFMA) rc = srt_launch_dec2(p, e->stream);
     if (rc < 0) return fail(-2, "decoder launch failed");
     if (rc == 1 && srt_launch_dec(p, e->cfg.impl, e->stream)) return fail(-2, "decoder launch failed");

@@ -65,7 +65,8 @@ enum { SRT_ACT_LEAKY = 0, SRT_ACT_RELU = 1, SRT_ACT_ELU = 2 };
     X(c8_nr2,    "SPLEETERRT_C8_NR2",    1,  INT)           /* bit 0: two sub-tiles per wave in up2..up4; 0: one everywhere */ \
     X(c8_wres,   "SPLEETERRT_C8_WRES",   1,  INT)           /* the weight slab stays in LDS where a unit is one K chunk; 0: moved every step */ \
     X(c8_tune,   "SPLEETERRT_C8_TUNE",   1,  INT)           /* the first launch of a C8 layer shape measures its workgroup count; 0: table values, 2: and print the choice */ \
-    X(wino_ph,   "SPLEETERRT_WINO_PH",   7,  INT)           /* fp32 Winograd decoder (srt_nn4.hip), barrier phase offset per layer group: bit 0 up1, bit 1 up2..up4, bit 2 up5; 0: every wave meets the barrier at quad 0 */
+    X(wino_ph,   "SPLEETERRT_WINO_PH",   7,  INT)           /* fp32 Winograd decoder (srt_nn4.hip), barrier phase offset per layer group: bit 0 up1, bit 1 up2..up4, bit 2 up5; 0: every wave meets the barrier at quad 0 */ \
+    X(wino_ac,   "SPLEETERRT_WINO_AC",   2,  INT)           /* fp32 Winograd decoder, all-class form (one wave per SIMD owns the four parity classes of its blocks) per layer group: bit 0 up1, bit 1 up2..up4, bit 2 up5 (built for up2..up4 only: the other bits select nothing); taken only where the group's WINO_PH bit is set too; 0: the class-split kernels */
 enum { SRT_SW_FLAG, SRT_SW_INT, SRT_SW_INT_NONEMPTY };
 #define SRT_SW_FIELD(field, name, dflt, rule) int field;
 struct SrtSwitches { SRT_SWITCH_TABLE(SRT_SW_FIELD) };

@@ -552,9 +552,346 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino(const SrtConvParams p, co
 constexpr int wino32_piece_quad(int i, int nq, int dpw) { return i * nq / dpw; }                                    // the quad in which a wave issues its piece i of a K step (the K loop issues by this function)
 constexpr int wino32_early_pieces(int nq, int dpw, int qb) { int n = 0; for (int i = 0; i < dpw; ++i) n += (wino32_piece_quad(i, nq, dpw) < qb) ? 1 : 0; return n; }      // pieces of a K step issued in quads < qb
 static_assert(wino32_early_pieces(3, 4, 0) == 0 && wino32_early_pieces(3, 4, 1) == 2 && wino32_early_pieces(3, 4, 2) == 3 && wino32_early_pieces(3, 4, 3) == 4, "pieces of a 3-quad wave ahead of its barrier");
-template <int BA, int BB, int ABL = 0, int UR = 3, int D = UR - 1, int BPS = 1, int SB = 0, int EA = 0, int ST = 0, int CS = 0, int NI = 1, int PEEL = 0, int RB = 1, int PH = 0>   // PEEL 1: a unit's first K step starts from C = 0 instead of zeroed accumulators (measured slower here, faster in srt_dec_wino)
-__global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, const float* __restrict__ U, size_t u_stem, int tpw)
+// AC 1: the all-class form.  Since the 2-tap classes share the 3-tap class's transform points (wino_w1d), the 49 V values of a block are 16 distinct numbers:
+// here ONE wave owns all four classes of its 16 blocks and both M blocks - f32x4 acc[2][49], 392 registers, which fits one wave per SIMD (the 512-entry
+// register file of a lone wave) - and computes the 16 values once per K step from 4 patch rows, where the class-split waves compute 49 from 14.
+//   workgroup = 4 waves = 32 output channels x 64 blocks (4 x 16 blocks = 8 x 32 input pixels of one instance); wave g owns block row g
+//   K step    = 4 groups (row I of V) x 2 M blocks: 14 MFMAs per half (classes C11 + C10, and for I < 3 also C01 + C00: 98 per step), each MFMA taking its
+//               A fragment from the class's own place in the slab.  The A fragments of a half are read one half ahead, one float4 behind each class sub-run (those of the next step's first half
+//               from slab k+1, which therefore lands one rendezvous early); the patch rows of step k+1 are read one half ahead of the bursts that transform them.
+//   VALU      = one burst behind each group (SB): row transforms of patch k+1 (rows 0, 2 behind group 0; 1, 3 behind group 1) and row I of V for step k+1
+//   DMA       = 26 U pieces + 7 patch pieces (pitch 416 floats, 32 mod 64) per K step: wave w moves pieces w, w + 4, ... (9 of them; past the end the last one
+//               again).  Pieces i < 6 are U pieces for every wave, piece 6 is a U piece for waves 0-1 and a patch piece for waves 2-3 (scalar selects, no
+//               branch), pieces 7 and 8 are patch pieces.  Rings of UR = 4 (132 KiB), lead D = 3: at the step's one barrier a wave's last D - 2 steps of pieces
+//               may be in flight - never vmcnt(0) - and slab k+D / patch k+1+D go where slab k-1 / patch k lived (UR >= D + 1).
+//   units     = one continuous K stream (CS); a unit's first K step starts from C = 0.
+// Same MFMAs into every accumulator in the same channel order, from the same V expressions and U: bit-identical to the class-split form (tests/test_wino_allclass.py).
+// Epilogue: a lane holds its block's whole 4 x 4 output patch per channel and writes it as four aligned float4 rows.
+// Registers: 392 accumulators leave 120 for everything else; what was done to stay inside them is noted where it was done (no scratch, no spilled VGPR:
+// profiles/wino_allclass_kernel_resources.txt).  Measured -5 .. -7 % on up2..up4.
+//
+// The MFMA of the all-class form, from inline assembly: the compiler places the accumulators of a kernel's MFMAs either all in AGPRs or all in VGPRs, and 98 tiles
+// fit neither half of the register file (it rotated 37 tiles through v_accvgpr_read / _write every K step).  AG: the tile lives in AGPRs, otherwise in VGPRs
+// (wino32ac_in_agpr: 64 + 34 tiles, 256 + 136 registers).  FIRST: C = 0 (the tile's old value is dead, "=&": the result may not share registers with the operands).
+// The compiler does not know these are MFMAs, so what it would insert between an MFMA and a VALU read of its result stands in the kernel (wino32ac_mfma_drain).
+constexpr bool wino32ac_in_agpr(int mb, int x) { return mb == 0 || x < 15; }
+template <bool AG, bool FIRST> __device__ __forceinline__ void wino32ac_mfma(f32x4& c, float a, float b)
 {
+    if constexpr (AG && FIRST) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&a"(c) : "v"(a), "v"(b));
+    else if constexpr (AG) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+    else if constexpr (FIRST) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, 0" : "=&v"(c) : "v"(a), "v"(b));
+    else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
+}
+// behind the last MFMA of a unit, ahead of the first read of an accumulator: 32 wait states (the 8-pass MFMA's result needs 11 before a VALU read)
+__device__ __forceinline__ void wino32ac_mfma_drain() { __builtin_amdgcn_sched_barrier(0); asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); __builtin_amdgcn_sched_barrier(0); }
+constexpr int wino32ac_piece_half(int i, int dpw) { return i * 8 / dpw; }      // the half (group, M block) of a K step in which a wave issues its piece i
+template <int BA, int BB, int UR, int D>
+__device__ __forceinline__ void srt_dec_wino32_allclass(const SrtConvParams& p, const float* __restrict__ U, size_t u_stem, int tpw)
+{
+    static_assert(BA == 4 && BB == 16, "tile: one block row per wave");
+    constexpr int UB1 = 4 * 16 * WINO_LD, UBUF = 2 * UB1, NUP = 26;
+    constexpr int TH = 2 * BA, TW = 2 * BB;
+    constexpr int PRH = TH + 2, PROW = TW + 8, PR4 = PROW / 4;
+    constexpr int PCH0 = PRH * PROW;
+    constexpr int PCH = (PCH0 + 31) / 64 * 64 + 32;                          // channel pitch: 32 mod 64 floats
+    constexpr int NF4 = PCH, NPP = (NF4 + 63) / 64, PBUF = NPP * 256;
+    constexpr int NPIECE = NUP + NPP, DPW = (NPIECE + 3) / 4;                // DMA pieces per K step, per wave
+    constexpr int IFX = NUP / 4, NPV = DPW - IFX;                            // pieces i < IFX: U for every wave; i = IFX: U for waves < NUP - 4 IFX, patch for the rest; i > IFX: patch
+    static_assert(PCH % 64 == 32 && PCH >= PCH0 && NPIECE <= 4 * DPW && NPIECE > 4 * (DPW - 1), "patch pitch / piece map");
+    static_assert(4 * IFX < NUP && 4 * (IFX + 1) >= NUP && NPV >= 1, "piece map: exactly one piece index is a U piece for some waves and a patch piece for others");
+    static_assert(4 * (DPW - 1) - NUP < NPP && 3 + 4 * (DPW - 2) - NUP <= NPP - 1, "piece map: the patch pieces cover the patch buffer");
+    constexpr int VMW = (D - 2) * DPW;                                       // in flight at the barrier of step k: this wave's pieces of steps k-D+2 .. k-1; landed: slabs <= k+1, patches <= k+2
+    static_assert(D >= 3 && UR >= D + 1 && VMW >= DPW && VMW < 64, "rings: lead / depth / vmcnt range (no vmcnt(0) in the K loop)");
+    static_assert((UR * (UBUF + PBUF) + 96) * 4 <= 160 * 1024, "LDS");
+    __shared__ __attribute__((aligned(16))) float s_all[UR * UBUF + UR * PBUF];
+    __shared__ __attribute__((aligned(16))) float s_epi[96];
+    float* s_u = s_all;
+    float* s_p = s_all + UR * UBUF;
+
+    const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, kq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = wave;
+    const int flags = tpw >> 8;
+    tpw &= 255;
+    const int tilesX = (p.W + TW - 1) / TW, tilesY = (p.H + TH - 1) / TH;
+    const int MB2 = p.Cout / 32, MB = p.Cout / 16;
+    const int colrun = !(flags & 2) ? 1 : tilesY % tpw == 0 ? tpw : tpw % tilesY == 0 ? tilesY : 1;
+    const int nsp = tilesX * tilesY, upw = nsp * p.ntiles / tpw;
+    const int pos = srt_xcd_order(upw * MB2 * p.nstems);
+    const bool mfast = (flags & 4) != 0;
+    const int wsel = pos / upw, mblk2 = mfast ? pos % MB2 : wsel % MB2, stem = mfast ? pos / (MB2 * upw) : wsel / MB2, unit0 = (mfast ? (pos / MB2) % upw : pos % upw) * tpw;
+    const int m0 = mblk2 * 32;
+    if (tid < 32) {
+        const size_t ci = stem * p.coeff_stem + m0 + tid;
+        s_epi[tid] = p.bias[ci]; s_epi[32 + tid] = p.bnScale[ci]; s_epi[64 + tid] = p.bnShift[ci];
+    }
+    const int act_kind = srt_act_kind(p, stem);
+    const size_t hw = (size_t)p.H * p.W;
+    const float* up = U + stem * u_stem + (size_t)(2 * mblk2) * UB1;
+
+    const int ba = g, bb = l15;
+    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) float*)s_all;
+
+    // ---- DMA state.  U pieces i < IFX: global_load_lds.  Pieces IFX + j: one buffer_load ... lds each, U or patch by the wave-uniform is_patch(j)
+    // (the piece's place in the slab rides in the scalar base: one lane offset for all U pieces - registers are what this kernel is short of)
+    const unsigned dvoff = (unsigned)(lane * 16);
+    unsigned dm0[IFX];
+#pragma unroll
+    for (int i = 0; i < IFX; ++i) dm0[i] = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((wave + 4 * i) * 1024));
+    const bool flex_patch = wave >= NUP - 4 * IFX;                           // piece IFX of this wave is a patch piece
+    auto vpiece = [&](int j) __attribute__((always_inline)) { return min(wave + 4 * (IFX + j), NPIECE - 1); };
+    unsigned fm0[NPV];
+#pragma unroll
+    for (int j = 0; j < NPV; ++j) {
+        const int pc = vpiece(j);
+        fm0[j] = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(pc >= NUP ? UR * UBUF * 4 + (pc - NUP) * 1024 : pc * 1024));
+    }
+    constexpr unsigned OOR = 0x80000000u;
+    const unsigned nrec_p = (unsigned)min((size_t)0x7fffffff, (size_t)4 * p.srcA_tile);
+    // per-unit DMA state of the unit whose patches are being fetched (set again - a handful of integer divisions - when the stream moves on to the next unit, D + 1
+    // steps before the current one ends: a second copy kept ready would cost three registers): the patch bases (wave-uniform halves, pinned to SGPRs), the same for piece IFX (the U slab for the waves whose
+    // piece IFX is a U piece: every select in the K loop is then a 2-way select between two values, see srt_dec_wino32's dma_flex), and the lanes' offsets
+    struct UnitBase { unsigned alo, ahi, blo, bhi, falo, fahi, fblo, fbhi; };
+    UnitBase cu;
+    unsigned c_voff[NPV];
+    auto unit_voff = [&](int unit, int j) __attribute__((always_inline)) {
+        int sx_, sy_; wino_sp_xy(unit % nsp, tilesX, colrun, sx_, sy_);
+        const int tx0 = sx_ * TW, ty0 = sy_ * TH, pc = vpiece(j);
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                                         // (worked out again per unit: hoisted out of the unit loop these lane constants would cost registers the K loop does not have)
+        const int e = (pc - NUP) * 64 + ln;
+        const int c = e / (PCH / 4), rem = e % (PCH / 4);
+        const int jj = rem % PR4, row = rem / PR4;
+        const int gy = ty0 - 1 + row, gx = tx0 - 4 + 4 * jj;
+        const bool ok = e >= 0 && e < NF4 && rem < PCH0 / 4 && gy >= 0 && gy < p.H && gx >= 0 && gx + 3 < p.W;
+        const unsigned pvoff = ok ? 4u * (unsigned)((size_t)c * hw + (size_t)gy * p.W + gx) : OOR;
+        return pc >= NUP ? pvoff : (unsigned)(pc * 1024 + ln * 16);
+    };
+    auto unit_base = [&](int unit) __attribute__((always_inline)) {
+        const int tile0 = unit / nsp;
+        const size_t ba_ = (size_t)(p.srcA + stem * p.srcA_stem + tile0 * p.srcA_tile), bb_ = (size_t)(p.srcB + stem * p.srcB_stem + tile0 * p.srcB_tile), bu_ = (size_t)up;
+        UnitBase u;
+        u.alo = __builtin_amdgcn_readfirstlane((unsigned)ba_); u.ahi = __builtin_amdgcn_readfirstlane((unsigned)(ba_ >> 32));
+        u.blo = __builtin_amdgcn_readfirstlane((unsigned)bb_); u.bhi = __builtin_amdgcn_readfirstlane((unsigned)(bb_ >> 32));
+        u.falo = __builtin_amdgcn_readfirstlane(flex_patch ? (unsigned)ba_ : (unsigned)bu_); u.fahi = __builtin_amdgcn_readfirstlane(flex_patch ? (unsigned)(ba_ >> 32) : (unsigned)(bu_ >> 32));
+        u.fblo = __builtin_amdgcn_readfirstlane(flex_patch ? (unsigned)bb_ : (unsigned)bu_); u.fbhi = __builtin_amdgcn_readfirstlane(flex_patch ? (unsigned)(bb_ >> 32) : (unsigned)(bu_ >> 32));
+        return u;
+    };
+    auto unit_cur = [&](int unit) __attribute__((always_inline)) {
+        cu = unit_base(unit);
+        WinoFor<0, NPV>::run([&](auto jc) { c_voff[decltype(jc)::value] = unit_voff(unit, decltype(jc)::value); });
+    };
+    const int kA = p.CA / 4;
+    const unsigned kstep_bytes = (unsigned)(16 * hw), ustep_bytes = (unsigned)((size_t)MB * UB1 * 4);
+    auto dma_u = [&](int i, int ku, int ubuf) __attribute__((always_inline)) {
+        const float* src = up + (size_t)ku * MB * UB1 + (wave + 4 * i) * 256;
+        const unsigned dst = dm0[i] + (unsigned)ubuf * (unsigned)(UBUF * 4);
+        asm volatile("s_mov_b32 m0, %2\n\tglobal_load_lds_dwordx4 %0, %1" :: "v"(dvoff), "s"(src), "s"(dst) : "memory");
+    };
+    // piece IFX + j: U slab ku -> buffer ubuf | patch kp of the DMA state's unit -> slot pslot
+    auto dma_v = [&](auto jc, int ku, int ubuf, int kp, int pslot) __attribute__((always_inline)) {
+        constexpr int j = decltype(jc)::value;
+        const bool isp = j > 0 || flex_patch;                                // wave-uniform
+        const bool fromA = kp < kA;
+        unsigned lo, hi;
+        if constexpr (j == 0) { lo = fromA ? cu.falo : cu.fblo; hi = fromA ? cu.fahi : cu.fbhi; }
+        else { lo = fromA ? cu.alo : cu.blo; hi = fromA ? cu.ahi : cu.bhi; }
+        i32x4 rs;
+        rs.x = (int)lo; rs.y = (int)(hi & 0xffffu); rs.z = (int)(isp ? nrec_p : 0x7fffffffu); rs.w = 0x00020000;
+        const unsigned soff = isp ? (unsigned)(fromA ? kp : kp - kA) * kstep_bytes : (unsigned)ku * ustep_bytes;
+        const unsigned dst = fm0[j] + (isp ? (unsigned)pslot * (unsigned)(PBUF * 4) : (unsigned)ubuf * (unsigned)(UBUF * 4));
+        const unsigned voff = c_voff[j];
+        asm volatile("s_mov_b32 m0, %2\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" :: "v"(voff), "s"(rs), "s"(dst), "s"(soff) : "memory");
+    };
+    auto dma = [&](auto ic, int ku, int ubuf, int kp, int pslot) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        if constexpr (i < IFX) dma_u(i, ku, ubuf); else dma_v(std::integral_constant<int, i - IFX>{}, ku, ubuf, kp, pslot);
+    };
+    const int poff = kq * PCH + (2 * ba) * PROW + 2 * bb + 3;                // this lane's patch: rows +0..3, columns +0..3 (b0-1..b0+2)
+    const int aoff = (kq * 16 + l15) * WINO_LD;
+    const int nk = p.Cin / 4;
+    const int Wo = p.W << 1;
+    const size_t ohw = (size_t)(p.H << 1) * Wo;
+    float* obase; bool blk_ok;
+    auto set_out_unit = [&](int unit) __attribute__((always_inline)) {
+        int sx_, sy_; wino_sp_xy(unit % nsp, tilesX, colrun, sx_, sy_);
+        const int tile = unit / nsp, a0 = sy_ * TH + 2 * ba, b0 = sx_ * TW + 2 * bb;
+        blk_ok = tile < p.ntiles && a0 < p.H && b0 < p.W;
+        obase = p.outAct + stem * p.out_stem + (blk_ok ? tile : 0) * p.out_tile + (size_t)(blk_ok ? 2 * a0 : 0) * Wo + (blk_ok ? 2 * b0 : 0);
+    };
+
+    f32x4 acc[2][49];
+    float t3[4][4], v[16];
+    float2 xm[4], xl[4], xr[4];                                              // patch row r: columns (b0, b0+1) | (b0-2, b0-1) | (b0+2, b0+3)
+    auto read_row = [&](const float* pbuf, int r) __attribute__((always_inline)) {
+        const float* q = pbuf + poff + r * PROW;
+        xm[r] = *reinterpret_cast<const float2*>(q + 1);
+        xl[r] = *reinterpret_cast<const float2*>(q - 1);
+        xr[r] = *reinterpret_cast<const float2*>(q + 3);
+    };
+    auto rows = [&](int r) __attribute__((always_inline)) { wino_in3(xl[r].y, xm[r].x, xm[r].y, xr[r].x, t3[r]); };
+    auto refill = [&](auto ic) __attribute__((always_inline)) {              // row I of V from t3
+        constexpr int I = decltype(ic)::value;
+        v[4 * I] = wino_vpoint<I, 0>(t3); v[4 * I + 1] = wino_vpoint<I, 1>(t3); v[4 * I + 2] = wino_vpoint<I, 2>(t3); v[4 * I + 3] = wino_vpoint<I, 3>(t3);
+    };
+    // A fragments: float4 x of the lane's 52-float row of M block mb.  Group I needs 0+I (C11 row I), 4 + (3I .. 3I+2) / 4 (C10), and for I < 3
+    // 7+I (C01 row I), 10 + (3I .. 3I+2) / 4 (C00); the float4s it is the first to need:
+    float4 fa[2][13];
+    // float4 number C of the four that group I is the first to need (C: the class sub-run of a half behind which the next half's float4 is read), if there is one
+    auto load_a1 = [&](const float* ub, auto ic, auto mc, auto cc) __attribute__((always_inline)) {
+        constexpr int I = decltype(ic)::value, mb = decltype(mc)::value, C = decltype(cc)::value;
+        constexpr int x = C == 0 ? I : C == 1 ? 4 + I : C == 2 ? 7 + I : 10 + I;
+        if constexpr (C == 0 || I < 3) fa[mb][x] = *reinterpret_cast<const float4*>(ub + mb * UB1 + 4 * x);
+    };
+    auto load_a = [&](const float* ub, auto ic, auto mc) __attribute__((always_inline)) {
+        WinoFor<0, 4>::run([&](auto cc) { load_a1(ub, ic, mc, cc); });
+    };
+    auto f4c = [](const float4& a, int c) __attribute__((always_inline)) { return c == 0 ? a.x : c == 1 ? a.y : c == 2 ? a.z : a.w; };
+
+    int su = 0, sp1 = 1 % UR, sd = D % UR, sd1 = (D + 1) % UR;               // k % UR, (k+1) % UR, (k+D) % UR, (k+1+D) % UR of the running step count
+    auto kstep = [&](int k, int unit_n, auto fc) __attribute__((always_inline)) {      // unit_n: the workgroup's next unit (after the last one: that one again - valid addresses, unused data)
+        constexpr bool FIRST = decltype(fc)::value;
+        __builtin_amdgcn_s_waitcnt(wino_vmcnt(VMW));
+        __syncthreads();
+        if (k + 1 + D == nk) unit_cur(unit_n);
+        const int kd = k + D >= nk ? k + D - nk : k + D, kp = k + 1 + D >= nk ? k + 1 + D - nk : k + 1 + D;
+        const float* ub = s_u + su * UBUF + aoff;
+        const float* ubx = s_u + (su == UR - 1 ? 0 : su + 1) * UBUF + aoff;  // slab k+1
+        const float* pbuf = s_p + sp1 * PBUF;                                // patch k+1
+        WinoFor<0, 4>::run([&](auto ic) {
+            constexpr int I = decltype(ic)::value;
+            WinoFor<0, 2>::run([&](auto mc) {
+                constexpr int mb = decltype(mc)::value, h = 2 * I + mb;
+                // the next half's A fragments, one float4 behind each class sub-run of this half (into the registers that sub-run has just finished with; the last
+                // half of a step has two sub-runs for the four float4s of the next step's first half); the patch rows the next burst transforms
+                auto ahead = [&](auto cc) __attribute__((always_inline)) {
+                    if constexpr (mb == 0) load_a1(ub, ic, std::integral_constant<int, 1>{}, cc);
+                    else if constexpr (I < 3) load_a1(ub, std::integral_constant<int, I + 1>{}, std::integral_constant<int, 0>{}, cc);
+                    else load_a1(ubx, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, cc);
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                if constexpr (h == 0) { read_row(pbuf, 0); read_row(pbuf, 2); }
+                if constexpr (h == 2) { read_row(pbuf, 1); read_row(pbuf, 3); }
+                WinoFor<0, DPW>::run([&](auto pc) { if constexpr (wino32ac_piece_half(decltype(pc)::value, DPW) == h) dma(pc, kd, sd, kp, sd1); });
+                __builtin_amdgcn_sched_barrier(0);
+                WinoFor<0, 4>::run([&](auto jc) { constexpr int J = decltype(jc)::value, X = WINO_C11 + 4 * I + J;
+                    wino32ac_mfma<wino32ac_in_agpr(mb, X), FIRST>(acc[mb][X], f4c(fa[mb][I], J), v[4 * I + J]); });
+                ahead(std::integral_constant<int, 0>{});
+                WinoFor<0, 3>::run([&](auto jc) { constexpr int J = decltype(jc)::value, X = WINO_C10 + 3 * I + J;
+                    wino32ac_mfma<wino32ac_in_agpr(mb, X), FIRST>(acc[mb][X], f4c(fa[mb][4 + (3 * I + J) / 4], (3 * I + J) % 4), v[4 * I + J]); });
+                ahead(std::integral_constant<int, 1>{});
+                if constexpr (I == 3) { ahead(std::integral_constant<int, 2>{}); ahead(std::integral_constant<int, 3>{}); }
+                if constexpr (I < 3) {
+                    WinoFor<0, 4>::run([&](auto jc) { constexpr int J = decltype(jc)::value, X = WINO_C01 + 4 * I + J;
+                        wino32ac_mfma<wino32ac_in_agpr(mb, X), FIRST>(acc[mb][X], f4c(fa[mb][7 + I], J), v[4 * I + J]); });
+                    ahead(std::integral_constant<int, 2>{});
+                    WinoFor<0, 3>::run([&](auto jc) { constexpr int J = decltype(jc)::value, X = WINO_C00 + 3 * I + J;
+                        wino32ac_mfma<wino32ac_in_agpr(mb, X), FIRST>(acc[mb][X], f4c(fa[mb][10 + (3 * I + J) / 4], (3 * I + J) % 4), v[4 * I + J]); });
+                    ahead(std::integral_constant<int, 3>{});
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            // the group's one VALU burst: V of step k+1
+            if constexpr (I == 0) { rows(0); rows(2); }
+            if constexpr (I == 1) { rows(1); rows(3); }
+            refill(ic);
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        su = su == UR - 1 ? 0 : su + 1; sp1 = sp1 == UR - 1 ? 0 : sp1 + 1; sd = sd == UR - 1 ? 0 : sd + 1; sd1 = sd1 == UR - 1 ? 0 : sd1 + 1;
+    };
+
+    unit_cur(unit0);
+#pragma unroll
+    for (int j = 0; j < D; ++j)                                              // U slabs 0..D-1 -> buffers 0..D-1; patches 0..D-1 -> slots 0..D-1
+        WinoFor<0, DPW>::run([&](auto pc) { dma(pc, min(j, nk - 1), j, min(j, nk - 1), j); });
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                      // vmcnt(0): once per workgroup
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { read_row(s_p, r); rows(r); }
+    WinoFor<0, 4>::run(refill);
+    load_a(s_u + aoff, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+    // patch D -> slot D % UR: the patch pieces only.  From here on every wave issues exactly DPW DMA instructions per K step (what VMW counts on).
+    WinoFor<0, NPV>::run([&](auto jc) { if (decltype(jc)::value > 0 || flex_patch) dma_v(jc, 0, 0, min(D, nk - 1), D % UR); });
+
+    for (int t = 0; t < tpw; ++t) {
+        const int unit_n = unit0 + min(t + 1, tpw - 1);
+        kstep(0, unit_n, std::true_type{});
+        for (int k = 1; k < nk; ++k) kstep(k, unit_n, std::false_type{});
+        wino32ac_mfma_drain();
+        // ---- output transform + bias -> activation -> batch-norm: this lane's block, all four classes, channels m0 + 16 mb + 4 kq + r
+        set_out_unit(unit0 + t);
+        // (the activation kind is workgroup-uniform; the branch on it sits INSIDE the channel loop, around the 16 finished values of one channel, so that the code
+        //  that reads the accumulators exists once: with three copies of the whole epilogue the register allocator spilled accumulators)
+        int kind_ = act_kind;
+        asm volatile("" : "+s"(kind_));                                      // (the activation's constants are made here, per unit, not kept in registers through the K loop)
+        const SrtAct actp = srt_act_params(kind_, p.variant);
+        const int akind = srt_act_is_plain_elu(actp) ? 0 : actp.ue != 0.0f ? 1 : 2;
+        if (blk_ok) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) {
+                const float4 bi4 = *reinterpret_cast<const float4*>(&s_epi[16 * mb + 4 * kq]), sc4 = *reinterpret_cast<const float4*>(&s_epi[32 + 16 * mb + 4 * kq]),
+                             sf4 = *reinterpret_cast<const float4*>(&s_epi[64 + 16 * mb + 4 * kq]);
+                const float bi[4] = { bi4.x, bi4.y, bi4.z, bi4.w }, sc[4] = { sc4.x, sc4.y, sc4.z, sc4.w }, sf[4] = { sf4.x, sf4.y, sf4.z, sf4.w };
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    // (fenced class by class: the accumulators fill the register file, the scheduler must not gather the 49 values of a channel - let alone of
+                    //  several channels - ahead of the transforms that consume them)
+                    float y[2][2][2][2];                                     // [py][px][da][db]
+                    auto cls_out = [&](auto xc, auto nyc, auto nxc, float (&yy)[2][2]) __attribute__((always_inline)) {
+                        constexpr int X0 = decltype(xc)::value, NY = decltype(nyc)::value, NX = decltype(nxc)::value;
+                        __builtin_amdgcn_sched_barrier(0);
+                        float m[NY * NX];
+#pragma unroll
+                        for (int x = 0; x < NY * NX; ++x) m[x] = acc[mb][X0 + x][r];
+                        wino_out2d<NY, NX>(m, yy);
+                        __builtin_amdgcn_sched_barrier(0);
+                    };
+                    using I3 = std::integral_constant<int, 3>; using I4 = std::integral_constant<int, 4>;
+                    cls_out(std::integral_constant<int, WINO_C11>{}, I4{}, I4{}, y[1][1]);
+                    cls_out(std::integral_constant<int, WINO_C10>{}, I4{}, I3{}, y[1][0]);
+                    cls_out(std::integral_constant<int, WINO_C01>{}, I3{}, I4{}, y[0][1]);
+                    cls_out(std::integral_constant<int, WINO_C00>{}, I3{}, I3{}, y[0][0]);
+                    int ch = m0 + 16 * mb + 4 * kq + r;
+                    asm volatile("" : "+v"(ch));                             // (as in unit_voff: not hoisted out of the unit loop)
+                    float* oc = obase + (size_t)ch * ohw;
+                    auto emit = [&](auto act) __attribute__((always_inline)) {
+#pragma unroll
+                        for (int da = 0; da < 2; ++da)
+#pragma unroll
+                            for (int py = 0; py < 2; ++py) {
+                                // output row 2(a0+da)+py, columns 2(b0+db)+px: one float4 = (px0 db0, px1 db0, px0 db1, px1 db1)
+                                float4 e;
+                                e.x = act(y[py][0][da][0], bi[r], sc[r], sf[r]); e.y = act(y[py][1][da][0], bi[r], sc[r], sf[r]);
+                                e.z = act(y[py][0][da][1], bi[r], sc[r], sf[r]); e.w = act(y[py][1][da][1], bi[r], sc[r], sf[r]);
+                                *reinterpret_cast<float4*>(oc + (size_t)(2 * da + py) * Wo) = e;
+                            }
+                    };
+                    if (akind == 0) emit([&](float y_, float b, float s, float f) { return srt_dec_epilogue_elu(y_, b, s, f); });
+                    else if (akind == 1) emit([&](float y_, float b, float s, float f) { return srt_dec_epilogue(y_, b, s, f, actp); });
+                    else emit([&](float y_, float b, float s, float f) { return srt_dec_epilogue_lin(y_, b, s, f, actp.lin); });
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        if (t + 1 < tpw) {
+            // The next unit's first V and A fragments came out of the last K step's bursts and read-ahead; they are computed again here, from the same patch slot and
+            // slab (nothing overwrites either before this wave meets the next step's barrier), so that they do not stay live across the epilogue: beside the
+            // accumulators there is no room for them.
+            const float* pb0 = s_p + su * PBUF;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { read_row(pb0, r); rows(r); }
+            WinoFor<0, 4>::run(refill);
+            load_a(s_u + su * UBUF + aoff, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+        }
+    }
+}
+
+template <int BA, int BB, int ABL = 0, int UR = 3, int D = UR - 1, int BPS = 1, int SB = 0, int EA = 0, int ST = 0, int CS = 0, int NI = 1, int PEEL = 0, int RB = 1, int PH = 0, int AC = 0>   // PEEL 1: a unit's first K step starts from C = 0 instead of zeroed accumulators (measured slower here, faster in srt_dec_wino); AC 1: the all-class form above
+__global__ void __launch_bounds__(AC ? 256 : 512, 1) srt_dec_wino32(const SrtConvParams p, const float* __restrict__ U, size_t u_stem, int tpw)
+{
+    if constexpr (AC) {
+        static_assert(!AC || (ABL == 0 && BPS == 1 && SB == 1 && EA == 1 && CS == 1 && NI == 1 && PEEL == 1 && RB == 1 && PH == 0), "the all-class form: fenced bursts, early A reads, continuous stream, peeled first step, no phase offset (one wave per SIMD)");
+        srt_dec_wino32_allclass<BA, BB, UR, D>(p, U, u_stem, tpw);
+    } else {
     static_assert(UR >= 3 && UR <= 5 && D >= BPS + EA && UR >= D + BPS && !(CS && EA), "rings (5 x 31 KiB = 155 KiB of LDS)");
     static_assert(PH == 0 || (PH <= 2 && BPS == 1 && EA == 0 && CS == 1 && D >= 2 && UR >= D + 2), "phase offset: the high waves run their first PH quads ahead of the rendezvous (derived for the continuous K stream only)");
     static_assert(BA * BB * NI == 32 && (BA * BB) % 16 == 0, "tile");
@@ -879,6 +1216,7 @@ __global__ void __launch_bounds__(512, 1) srt_dec_wino32(const SrtConvParams p, 
     else if (cls == 1) body(std::integral_constant<int, 1>{});
     else if (cls == 2) body(std::integral_constant<int, 2>{});
     else body(std::integral_constant<int, 3>{});
+    }                                                                        // !AC
 }
 
 // ------------------------------------------------------------------------------------------- encoder layers in Winograd form
@@ -1332,6 +1670,9 @@ static int wino_mfast_bit(size_t ubytes, int mb2)
 // quad 1.  sw.wino_ph (SPLEETERRT_WINO_PH) picks it per layer group: bit 0 the two-instance form (up1 of 256-row tiles), bit 1 the one-instance form (up2..up4), bit 2 srt_dec_wino (up5);
 // 0 is the arrangement above.  Same MFMAs in the same order either way: the two forms are bit-identical (tests/test_wino_phase.py).
 #define SRT_WINO32_PHASED(BB, NI) 2, BB, 0, 5, 3, 1, 1, 0, 1, 1, NI, 0, 1, 1
+// ... and the all-class form (srt_dec_wino32's AC; sw.wino_ac, SPLEETERRT_WINO_AC, bit 1: up2..up4): 4 x 16 blocks, rings of four, lead 3.  Launched for a layer
+// group only where its wino_ph bit is set too; with the wino_ph bit clear the launcher keeps the unphased class-split kernel.  Bit-identical (tests/test_wino_allclass.py).
+#define SRT_WINO32_ALLCLASS 4, 16, 0, 4, 3, 1, 1, 1, 0, 1, 1, 1, 1, 0, 1
 #define SRT_WINO_RING 3
 #define SRT_WINO_PHASED 4, 16, 1, 0, 5, 0, 0, 1, 3, 2                        // srt_dec_wino (up5, sw.wino_ph bit 2): rings of five (100 KiB), lead 3, waves 4-7 meet the barrier in front of their group 2 of 4
 static int wino32_on()
@@ -1388,6 +1729,13 @@ int srt_launch_dec_wino(const SrtConvParams& p, const float* U, size_t u_stem, c
         if (wino_tune("decrb=") == 0) { SRT_LAUNCH((srt_dec_wino32<2, 16, 0, 3, 2, 1, 1, 0, 1, 1, 1, 0, 0>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32)); return 0; }      // round-4 patch reads (natural pitch, b32 outer columns)
 #undef W32
 #endif
+        if ((sw.wino_ac & 2) && (sw.wino_ph & 2) && p.H >= 8) {             // the all-class form: units of 8 x 32 inputs, one workgroup per CU
+            const long units_ac = (long)((p.W + 31) / 32) * ((p.H + 7) / 8) * p.ntiles, wgs_ac = units_ac * (p.Cout / 32) * p.nstems;
+            int tpw_ac = 1;
+            while (tpw_ac < 16 && wgs_ac / (2 * tpw_ac) >= 256 && units_ac % (2 * tpw_ac) == 0) tpw_ac *= 2;
+            SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_ALLCLASS>), dim3((unsigned)(wgs_ac / tpw_ac)), dim3(256), 0, s, p, U, u_stem, tpw_ac | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32));
+            return srt_launch_status();
+        }
         if (sw.wino_ph & 2) SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_PHASED(16, 1)>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32));
         else SRT_LAUNCH((srt_dec_wino32<SRT_WINO32_SHIPPED>), grid, dim3(512), 0, s, p, U, u_stem, tpw | wino_walk_bit() | wino_mfast_bit(u_stem * 4, p.Cout / 32));
         return srt_launch_status();
