@@ -291,6 +291,40 @@ SRT_API int  srtSetWiener(srt_engine *e, int iterations);
  * `iterations` 1..3 whatever srtSetWiener says; d_out as srtIstft.  srtCopyTensor(e, "wiener_cov", stem, iteration, h, 5F + 1) then returns R_j of
  * that iteration of the last filtered call as [F][4] (R00, R11, Re R01, Im R01), the weight sums sum_t v_j [F] (spectrum units) and a [1]. */
 SRT_API int  srtIstftWiener(srt_engine *e, const float *d_spec, size_t rows, const float *d_masks, int iterations, float *d_out);
+/* ---- the filter with overlapped tiles, the average mask extension and the stem remix, for a single signal.  srtSetWiener / srtIstftWiener
+ * refuse those three (see each of them); these two entry points take them as options that hold FOR THE CALL ONLY: the engine's srtSetWiener, srtSetOverlap,
+ * srtSetMaskExtension and srtSetMix state is neither read nor changed (srtMixOutputs and the overlap are the same afterwards), and the calls work with any of
+ * them on or off.  d_out is [n_out ? n_out : n_stems][2][srtIstftLength(rows)].
+ *   overlap_rows O > 0: d_masks (and the magnitudes srtSeparateWiener builds) are in srtSetOverlap's layout, srtOverlapTiles(rows, T, O) tiles.  The filter sees
+ *     ONE mask value per (stem, row, channel, bin): the blended value a + w (b - a) of srtSetOverlap's rule, formed by the inverse transform's own helper; that
+ *     value enters v = m |x| in the soft-mask start of every pass.  Every spectrum row enters the statistics exactly once, however many tiles hold it; the
+ *     window, a = max(1, max |x| / 10), the row chunks and the summation order depend on `rows` only, as in srtIstftWiener.
+ *   SRT_MASK_EXT_CONSTANT: stem j's bins >= F are oob_weight[j] * spectrum, as in srtIstftWiener (oob_weight = 0 is what official Spleeter's --mwf does).
+ *   SRT_MASK_EXT_AVERAGE: stem j's bins >= F of row r, channel c are e_j(r, c) * spectrum, e_j the table srtSetMaskExtension's kernel writes from the same masks
+ *     with the same overlap (no ratio); oob_weight is ignored.  A deliberate definition: the extension follows the NETWORK's (blended) mask, not the filter -
+ *     the filter's gain is a 2x2 matrix per bin and has no scalar mean.  The first such call allocates the engine's gain table if srtSetMaskExtension never did.
+ *   n_out > 0: h_gain is [n_out][n_stems + 1] in srtSetMix's layout, host memory, copied.  In band output m is formed per complex component as
+ *     h = G[m][n_stems] * s;  for j ascending: h = fmaf(G[m][j], y_j, h)     (y_j: stem j's filtered value; one rounded product, one fused multiply-add per stem);
+ *     above F it is h * s with h = G[m][n_stems]; h = fmaf(G[m][j], g_j, h), g_j = oob_weight[j] or e_j(r, c): srtSetMix's chain.  A one-hot row gives that
+ *     stem's bits.  Only n_out spectra are written and only n_out inverse transforms run.
+ * With overlap_rows = 0, SRT_MASK_EXT_CONSTANT and n_out = 0 both calls issue exactly the launches of srtIstftWiener / of srtSeparate under
+ * srtSetWiener(iterations): the same kernels, the same bits.  srtSeparateWiener: geometry as srtSeparate; one STFT in the overlapped layout, one forward over
+ * srtOverlapTiles(rows, T, O) tiles (fp32 masks in the fp16 mode too), then the body of srtIstftWienerEx.  Both always launch eagerly, in graph mode too (a
+ * graph key for the options is a follow-up); inside a caller's stream capture they return -1 when a workspace they need is not allocated yet.
+ * -1 with srtLastError() text that names the function, before any device work and with nothing written: a null argument or opts, iterations outside 1..3,
+ * overlap_rows outside 0..T/2, an unknown mask_extension, n_out outside 0..n_stems (the filter's spectrum workspace holds n_stems spectra), a null h_gain with
+ * n_out > 0, a gain that is not finite, ratio_mask set, more than max_tiles overlapped tiles, n < 4096; -5 when a stem's weights are not set (srtSeparateWiener).
+ * srtCopyTensor "wiener_cov" works afterwards as after srtIstftWiener, "mask_ext" after a call with the average extension.
+ * Follow-ups: the same options per track in srtSeparateBatchWiener, graph capture, n_out > n_stems, the filter folded into the inverse transform's prologue. */
+typedef struct srt_wiener_opts {
+    int iterations;       /* 1..3 */
+    int overlap_rows;     /* 0..T/2; masks / magnitudes in srtSetOverlap's layout, srtOverlapTiles(rows, T, O) tiles */
+    int mask_extension;   /* SRT_MASK_EXT_CONSTANT | SRT_MASK_EXT_AVERAGE */
+    int n_out;            /* 0: every stem; 1..n_stems: outputs of the mix */
+    const float *h_gain;  /* [n_out][n_stems + 1], srtSetMix's layout, host memory, copied */
+} srt_wiener_opts;
+SRT_API int  srtIstftWienerEx(srt_engine *e, const float *d_spec, size_t rows, const float *d_masks, const srt_wiener_opts *opts, float *d_out);
+SRT_API int  srtSeparateWiener(srt_engine *e, const float *d_L, const float *d_R, size_t n, const srt_wiener_opts *opts, float *d_out);
 /* srtSeparateBatch with the filter per track: arguments, layout, track table and packing as srtSeparateBatch (srtBatchPlan; d_out[k]:
  * [n_stems][2][srtIstftLength(srtStftRows(n[k]))]); `iterations` 1..3 whatever srtSetWiener says (the engine's setting may be on or off).  One batched STFT,
  * one srtForward over the packed tiles (fp32 masks, in the fp16 mode too), `iterations` x (statistics + finalize) and one filter pass over the packed rows,

@@ -29,6 +29,11 @@ class _LiveOpts(C.Structure):
     _fields_ = [("sample_rate", C.c_int), ("max_block", C.c_int), ("n_out", C.c_int), ("h_gain", C.POINTER(C.c_float)), ("mask_extension", C.c_int)]
 
 
+class _WienerOpts(C.Structure):
+    """srt_wiener_opts (include/spleeterrt_amd.h): the per-call options of srtIstftWienerEx / srtSeparateWiener"""
+    _fields_ = [("iterations", C.c_int), ("overlap_rows", C.c_int), ("mask_extension", C.c_int), ("n_out", C.c_int), ("h_gain", C.POINTER(C.c_float))]
+
+
 class Span(C.Structure):
     """srt_span (include/spleeterrt_amd.h): one rank's share of a stream, as srtRankSpan fills it."""
     _fields_ = [(k, C.c_size_t) for k in ("tile0", "tile1", "sample0", "nsamples", "frames", "rows", "out_offset")]
@@ -68,6 +73,8 @@ def load_library():
     L.srtOverlapTiles.restype = C.c_size_t
     L.srtOverlapTiles.argtypes = [C.c_size_t, C.c_int, C.c_int]
     L.srtIstftWiener.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_int, f32p]
+    L.srtIstftWienerEx.argtypes = [vp, f32p, C.c_size_t, f32p, C.POINTER(_WienerOpts), f32p]
+    L.srtSeparateWiener.argtypes = [vp, f32p, f32p, C.c_size_t, C.POINTER(_WienerOpts), f32p]
     L.srtSeparateCli.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.srtSeparateCliHost.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.srtSeparateHostStream.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp]
@@ -301,13 +308,66 @@ class Engine:
         from . import stream
         return stream.overlap_tiles(rows, self.T, self.overlap)
 
-    def istft_wiener(self, spec, masks, iterations=1):
-        """spec [2,rows,2052,2], fp32 masks [S,ntiles,2,T,F] -> Wiener-filtered stems [S,2,rows*1024+3072] (srtIstftWiener)"""
+    def _wiener_opts(self, who, iterations, overlap, mask_extension, mix):
+        """the per-call options of istft_wiener / separate_wiener as (srt_wiener_opts, the matrix it points into, outputs); shape and type errors raise here,
+        before any library call.  None: every option is off (the caller takes the entry point without options)."""
+        import numpy as np
+        m = {"constant": MASK_EXT_CONSTANT, "average": MASK_EXT_AVERAGE}.get(mask_extension, mask_extension) if isinstance(mask_extension, (str, int)) else None
+        if isinstance(m, bool) or m not in (MASK_EXT_CONSTANT, MASK_EXT_AVERAGE):
+            raise EngineError("%s: mask_extension must be \"constant\" or \"average\", not %r" % (who, mask_extension))
+        try:
+            it, ov = int(iterations), int(overlap)
+        except (TypeError, ValueError):
+            raise EngineError("%s: iterations and overlap must be integers, not %r and %r" % (who, iterations, overlap))
+        if not 1 <= it <= 3:
+            raise EngineError("%s: iterations must be 1..3, not %d" % (who, it))
+        if not 0 <= ov <= self.T // 2:
+            raise EngineError("%s: overlap must be 0 .. T / 2 = %d rows, not %d" % (who, self.T // 2, ov))
+        g = None
+        if mix is not None:
+            try:
+                g = np.ascontiguousarray(mix, np.float32)
+            except (TypeError, ValueError):
+                raise EngineError("%s: mix must be a real matrix [n_out, n_stems + 1]" % who)
+            if g.ndim != 2 or g.shape[1] != self.S + 1 or not 1 <= g.shape[0] <= self.S:
+                raise EngineError("%s: mix must be [n_out, n_stems + 1] = [1..%d, %d], not %r" % (who, self.S, self.S + 1, tuple(g.shape)))
+            if not np.isfinite(g).all():
+                raise EngineError("%s: every gain of mix must be finite" % who)
+        if ov == 0 and m == MASK_EXT_CONSTANT and g is None:
+            return None
+        o = _WienerOpts(it, ov, m, 0 if g is None else g.shape[0], None if g is None else g.ctypes.data_as(C.POINTER(C.c_float)))
+        return o, g, (self.S if g is None else g.shape[0])
+
+    def istft_wiener(self, spec, masks, iterations=1, overlap=0, mask_extension="constant", mix=None):
+        """spec [2,rows,2052,2], fp32 masks [S,ntiles,2,T,F] -> Wiener-filtered stems [S,2,rows*1024+3072] (srtIstftWiener).
+        overlap / mask_extension / mix: options of this call alone, whatever set_overlap / set_mask_extension / set_mix say (srtIstftWienerEx):
+        masks in the overlapped layout [S, tiles(rows, overlap), 2, T, F]; "average": bins >= F follow the (blended) masks' row means; mix [n_out, S + 1]
+        (set_mix's layout, n_out <= S): the result is [n_out, 2, ..], only those spectra are filtered out and inverted."""
+        opts = Engine._wiener_opts(self, "istft_wiener", iterations, overlap, mask_extension, mix)
         t = self.torch
         rows = spec.shape[1]
         assert masks.is_cuda and masks.dtype == t.float32 and masks.is_contiguous() and masks.shape[0] == self.S
-        out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
-        self._chk(self.L.srtIstftWiener(self.h, _ptr(spec.contiguous()), rows, _ptr(masks), int(iterations), _ptr(out)))
+        if opts is None:
+            out = t.empty((self.S, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
+            self._chk(self.L.srtIstftWiener(self.h, _ptr(spec.contiguous()), rows, _ptr(masks), int(iterations), _ptr(out)))
+            return out
+        o, _keep, planes = opts
+        out = t.empty((planes, 2, self.L.srtIstftLength(rows)), device=self.device, dtype=t.float32)
+        self._chk(self.L.srtIstftWienerEx(self.h, _ptr(spec.contiguous()), rows, _ptr(masks), C.byref(o), _ptr(out)))
+        return out
+
+    def separate_wiener(self, L, R, iterations=1, overlap=0, mask_extension="constant", mix=None, out=None):
+        """whole path with the Wiener filter and this call's own options (srtSeparateWiener; the options as istft_wiener's): planar PCM [n] x2 ->
+        [S, 2, rows*1024+3072], or [n_out, 2, ..] with a mix.  The engine's set_wiener / set_overlap / set_mask_extension / set_mix are neither read nor changed."""
+        opts = Engine._wiener_opts(self, "separate_wiener", iterations, overlap, mask_extension, mix)
+        t = self.torch
+        if opts is None:
+            opts = (_WienerOpts(int(iterations), 0, MASK_EXT_CONSTANT, 0, None), None, self.S)
+        o, _keep, planes = opts
+        n = L.numel()
+        if out is None:
+            out = t.empty((planes, 2, self.L.srtIstftLength(self.L.srtStftRows(n))), device=self.device, dtype=t.float32)
+        self._chk(self.L.srtSeparateWiener(self.h, _ptr(L), _ptr(R), n, C.byref(o), _ptr(out)))
         return out
 
     def wiener_cov(self, stem, iteration, track=0):

@@ -16,6 +16,7 @@
 // sample is written once (see srt_istft_ola_kernel).
 #include "srt_internal.h"
 #include "srt_device.h"
+#include "srt_overlap.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -210,27 +211,8 @@ __device__ __forceinline__ float srt_ratio_of(float own, const float* __restrict
     return (mine + e1) / (sum + eps);
 }
 
-// Overlapped network tiles (srtSetOverlap): consecutive tiles of a signal share O rows, stride S = T - O, tile j covers rows [jS, jS + T).
-// Row f lives at row k of its primary tile j1 = min(f / S, ntiles - 1); when j1 > 0 and k < O it is row k + S of tile j1 - 1 as well, and its mask is
-// a + w (b - a) with a from tile j1 - 1, b from tile j1, w = (k + 1/2) / O.  f is workgroup-uniform wherever this is used: scalar arithmetic.
-struct OvRow { int j1, k; bool two; float w; };
-__device__ __forceinline__ OvRow srt_ov_row(int f, int T, int O, int ntiles)
-{
-    const int S = T - O;
-    OvRow r;
-    r.j1 = min(f / S, ntiles - 1);
-    r.k = f - r.j1 * S;
-    r.two = r.j1 > 0 && r.k < O;
-    r.w = ((float)r.k + 0.5f) / (float)O;
-    return r;
-}
-// the cross-fade, rounded step by step (contract(off)): equal masks stay exactly equal (b - a = 0), so an all-ones mask stays the identity
-__device__ __forceinline__ float srt_blend(float a, float b, float w)
-{
-    const float d = b - a;
-    const float t = w * d;
-    return a + t;
-}
+// Overlapped network tiles (srtSetOverlap): OvRow / srt_ov_row (a row's primary tile, offset and blend weight) and srt_blend (the cross-fade,
+// rounded step by step) live in srt_overlap.h, shared with the Wiener filter's option kernels.
 // srt_ratio_of on BLENDED masks: every stem's value - the workgroup's own included - is blended from the two tiles' rows first (rowb0 / rowa0: mask row of stem 0
 // in the primary / the previous tile; rowa0 is read only when two), then squared and summed as in srt_ratio_of.  The RATIO overlap instantiations do not prefetch
 // their own mask row (it is one of the rows read here; the registers it would be staged in are what the F > 1024 form spills): ratio = false returns the stem's own

@@ -301,6 +301,20 @@ struct SrtWienerParams {
 int srt_launch_wiener_stats(const SrtWienerParams& p, int pass, hipStream_t s);      // pass 1..n: statistics of the estimates after pass - 1 iterations
 int srt_launch_wiener_finalize(const SrtWienerParams& p, int pass, hipStream_t s);   // R tables of that pass (and a, pass 1)
 int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s);    // W_j x after `iters` iterations for every stem; bins >= F copied
+// The filter with per-call options (srtIstftWienerEx / srtSeparateWiener).  p as above, except that with overlap > 0 p.masks is in the
+// overlapped layout and p.ntiles = srtOverlapTiles(rows, T, overlap) (the masks' stem stride, and the count srt_ov_row clamps the primary tile with).
+struct SrtWienerOpt {
+    int overlap;                                 // rows consecutive network tiles share, 0: back-to-back tiles
+    const float* ext; size_t ext_stem;           // average mask extension: stem j's gain of bins >= F at ext[j * ext_stem + row * 2 + channel] (srt_launch_mask_ext); nullptr: oob
+    float oob[SRT_MAX_STEMS];                    // the constant rule: stem j's gain of bins >= F
+    int n_out;                                   // 0: every stem's spectrum; 1..nstems: the mixes, output m at p.out + m * p.out_stem
+    float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1]; // srtSetMix's layout: G[m][j] the gain of stem j in output m, G[m][nstems] the gain of the input
+};
+// the statistics pass on blended masks (overlap > 0 only: at 0 the kernel above runs); finalize is srt_launch_wiener_finalize
+int srt_launch_wiener_stats_ov(const SrtWienerParams& p, int overlap, int pass, hipStream_t s);
+// the filter with any option on: the FINAL spectrum of every bin 0..2048 - in band y_j or the mix of the y_j, above F the gain (q.oob, q.ext or their chain
+// through the matrix) times the input - of q.n_out outputs, or of every stem; the inverse transform that follows applies no gain
+int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q, int iters, hipStream_t s);
 // The filter per track of a packed batch (srtSeparateBatchWiener): a second device table beside SrtBatchTrack's, one row per track - the track's row chunks of
 // the statistics pass (wiener_issue's rule on the track's own rows) as a run [chunk0, chunk0 + nchunks) of the call's global chunk numbering.
 struct SrtBatchWiener { int chunk0, nchunks, rpc, tab; };     // tab: the track's slot in the per-track tables (its index in the call)

@@ -12,14 +12,15 @@ int srtRatioMask(srt_engine* e, float* d_masks, int ntiles)
 
 SrtDspTables tables_of(const srt_engine* e) { SrtDspTables t; t.preWin = e->preWin; t.postWin = e->postWin; t.twiddle = e->twiddle; return t; }
 
-int srtStftEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_spec, float* d_mag)
+// the transform behind srtStftEx with the overlap of the magnitude layout as an argument (ov: the engine's srtSetOverlap for srtStftEx, the call's own for srtSeparateWiener)
+static int stft_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_spec, float* d_mag, int ov)
 {
     if (!e || !d_L || !d_R || !d_spec) return fail(-1, "srtStft: null argument");
     DeviceScope ds(e->device);
     if (rows < 1 || frames > rows) return fail(-1, "srtStft: need 1 <= frames <= rows");
-    const int T = e->cfg.T, O = d_mag ? e->overlap : 0;
-    const size_t ntiles = tiles_of(e, rows);
-    if (d_mag && ntiles > (size_t)e->cfg.max_tiles) return fail(-1, e->overlap ? "srtStft: more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtStft: more than max_tiles * T rows");
+    const int T = e->cfg.T, O = d_mag ? ov : 0;
+    const size_t ntiles = overlap_tiles(rows, T, ov);
+    if (d_mag && ntiles > (size_t)e->cfg.max_tiles) return fail(-1, ov ? "srtStft: more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtStft: more than max_tiles * T rows");
     SrtStftParams p; memset(&p, 0, sizeof p);
     p.L = d_L; p.R = d_R; p.nsamples = n;
     p.frames_computed = (int)frames;
@@ -34,6 +35,12 @@ int srtStftEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_
     TimerScope ts(e, "stft");
     if (srt_launch_stft(p, e->stream, O, (int)ntiles)) return fail(-2, "stft launch failed");
     return 0;
+}
+
+int srtStftEx(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_spec, float* d_mag)
+{
+    if (!e) return fail(-1, "srtStft: null argument");
+    return stft_issue(e, d_L, d_R, n, frames, rows, d_spec, d_mag, e->overlap);
 }
 
 int srtStft(srt_engine* e, const float* d_L, const float* d_R, size_t n, float* d_spec, float* d_mag)
@@ -59,7 +66,8 @@ int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, i
 
 // inverse transform of `nstems` stems of one spectrum under their masks (nullptr: all-ones) into [nstems][2][srtIstftLength(rows)]; oob: per stem, the weight of bins >= F
 // mix (srtSetMix; only istft_issue sets it): d_out is [mix_out][2][len], output m the chain of e->mix[m] over the stems' gains
-static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out, bool mix = false)
+// ext_mode: the rule for bins >= F - the engine's own (srtSetMaskExtension) unless the caller names one (the Wiener option calls, whose options hold for the call only)
+static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out, bool mix = false, int ext_mode = -1)
 {
     DeviceScope ds(e->device);
     const int T = e->cfg.T;
@@ -68,7 +76,7 @@ static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const fl
     const int O = masks ? e->overlap : 0;               // (the single-stem callers - CLI flows, Wiener filter - refuse an overlap before they get here)
     p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = (int)(O ? tiles_of(e, rows) : (rows + T - 1) / T);
     p.T = T; p.F = e->cfg.F;
-    const bool ext = e->mask_ext == SRT_MASK_EXT_AVERAGE;      // (its single-stem callers - CLI flows, Wiener filter - refuse the mode before they get here)
+    const bool ext = (ext_mode < 0 ? e->mask_ext : ext_mode) == SRT_MASK_EXT_AVERAGE;      // (its single-stem callers - CLI flows, Wiener filter - refuse the mode before they get here)
     for (int s = 0; s < nstems; ++s) p.oob[s] = ext ? 1.0f : oob[s];     // the mean of an all-ones mask is 1 exactly: no table without masks
     p.ratio = ratio ? 1 : 0; p.masks16 = masks16 ? 1 : 0;
     p.frames_out = nullptr; p.out = d_out; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
@@ -83,7 +91,7 @@ static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const fl
     return 0;
 }
 // ONE stem's mask (or none) into a [2][len] destination
-static int istft_one(srt_engine* e, const float2* spec, size_t rows, const float* mask_stem, float oob, float* d_dst) { return istft_launch(e, spec, rows, mask_stem, 1, &oob, false, false, d_dst); }
+static int istft_one(srt_engine* e, const float2* spec, size_t rows, const float* mask_stem, float oob, float* d_dst, int ext_mode = -1) { return istft_launch(e, spec, rows, mask_stem, 1, &oob, false, false, d_dst, false, ext_mode); }
 static int istft_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out, bool ratio, bool masks16 = false)
 {
     if (!e || !d_spec || !d_out) return fail(-1, "srtIstft: null argument");
@@ -116,29 +124,119 @@ static int ensure_wiener_ws(srt_engine* e)
 
 // statistics passes (one stats + one finalize launch per iteration), the filter, then one inverse transform per stem on its filtered spectrum
 // (no masks: all-ones in band; bins >= F get oob_weight as with masks).  The statistics window is exactly the `rows` rows of this call.
-static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, int iters, float* d_out)
+// opt (srtIstftWienerEx / srtSeparateWiener): the call's own options, checked by wiener_opts_check - the engine's srtSetOverlap / srtSetMaskExtension /
+// srtSetMix state is not read then.  With every option off the launches are the ones of a call without `opt`; with an overlap the statistics run on blended masks
+// (srt_wiener_stats_ov_kernel), and with any option the filter writes final spectra (srt_wiener_filter_opt_kernel) of the n_out mixes or of every stem, which the
+// inverse transforms without a gain.  d_masks: [S][overlap_tiles(rows, T, overlap)][2][T][F].
+struct WienerCall { int overlap, ext, n_out; float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1]; };
+static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, int iters, float* d_out, const WienerCall* opt = nullptr)
 {
     const int T = e->cfg.T, S = e->cfg.n_stems, F = e->cfg.F;
+    const int O = opt ? opt->overlap : 0;
+    const bool plain = !opt || (!O && !opt->ext && !opt->n_out);
     SrtWienerParams w; memset(&w, 0, sizeof w);
     w.spec = (const float2*)d_spec; w.spec_ch_stride = rows * SRT_SPEC_LD; w.rows = (int)rows;
-    w.masks = d_masks; w.nstems = S; w.ntiles = (int)((rows + T - 1) / T); w.T = T; w.F = F;
+    w.masks = d_masks; w.nstems = S; w.ntiles = (int)overlap_tiles(rows, T, O); w.T = T; w.F = F;
     int nch = (int)((rows + 15) / 16); if (nch > SRT_WIENER_MAX_CHUNKS) nch = SRT_WIENER_MAX_CHUNKS;
     w.rpc = (int)((rows + nch - 1) / nch); w.nchunks = (int)((rows + w.rpc - 1) / w.rpc);
     w.slab = e->wslab; w.slab_max = e->wslab + (size_t)SRT_WIENER_MAX_CHUNKS * S * 4 * F;
     w.rtab = e->wtab; w.wsum = e->wtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4; w.scal = w.wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F;
     w.out = e->wspec; w.out_stem = 2 * rows * SRT_SPEC_LD;
     for (int pass = 1; pass <= iters; ++pass) {
-        { TimerScope ts(e, "wiener_stats"); if (srt_launch_wiener_stats(w, pass, e->stream)) return fail(-2, "Wiener statistics launch failed"); }
+        { TimerScope ts(e, "wiener_stats"); if (O ? srt_launch_wiener_stats_ov(w, O, pass, e->stream) : srt_launch_wiener_stats(w, pass, e->stream)) return fail(-2, "Wiener statistics launch failed"); }
         { TimerScope ts(e, "wiener_cov"); if (srt_launch_wiener_finalize(w, pass, e->stream)) return fail(-2, "Wiener finalize launch failed"); }
     }
-    { TimerScope ts(e, "wiener_filter"); if (srt_launch_wiener_filter(w, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
-    e->last.wiener_last = iters; e->last.wiener_tracks = 0;
     const size_t len = srtIstftLength(rows);
-    for (int j = 0; j < S; ++j) {
-        const int rc = istft_one(e, e->wspec + (size_t)j * w.out_stem, rows, nullptr, e->cfg.oob_weight[j], d_out + (size_t)j * 2 * len);
+    // (an option call names the constant rule for its mask-free inverse transforms: the engine's srtSetMaskExtension mode is not read)
+    const int ext_mode = opt ? SRT_MASK_EXT_CONSTANT : -1;
+    if (plain) {
+        { TimerScope ts(e, "wiener_filter"); if (srt_launch_wiener_filter(w, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
+        e->last.wiener_last = iters; e->last.wiener_tracks = 0;
+        for (int j = 0; j < S; ++j) {
+            const int rc = istft_one(e, e->wspec + (size_t)j * w.out_stem, rows, nullptr, e->cfg.oob_weight[j], d_out + (size_t)j * 2 * len, ext_mode);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    SrtWienerOpt q; memset(&q, 0, sizeof q);
+    q.overlap = O; q.n_out = opt->n_out;
+    memcpy(q.oob, e->cfg.oob_weight, sizeof q.oob);
+    memcpy(q.mix, opt->mix, sizeof q.mix);
+    if (opt->ext) {      // e_j(r, c): the table the inverse transform's own kernel writes from the same (blended) masks, ratio = 0
+        const int rc = mask_ext_issue(e, d_masks, 0, S, w.ntiles, (int)rows, 0, O);
+        if (rc) return rc;
+        q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
+    }
+    { TimerScope ts(e, "wiener_filter"); if (srt_launch_wiener_filter_opt(w, q, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
+    e->last.wiener_last = iters; e->last.wiener_tracks = 0;
+    for (int m = 0; m < (q.n_out ? q.n_out : S); ++m) {      // the spectra are final: no gain in the inverse
+        const int rc = istft_one(e, e->wspec + (size_t)m * w.out_stem, rows, nullptr, 1.0f, d_out + (size_t)m * 2 * len, ext_mode);
         if (rc) return rc;
     }
     return 0;
+}
+
+// the checks srtIstftWienerEx and srtSeparateWiener share (`who` names the caller): 0 with *c filled, or -1 with the error text set; no device work
+static int wiener_opts_check(const srt_engine* e, const char* who, const srt_wiener_opts* o, size_t rows, WienerCall* c)
+{
+    const int T = e->cfg.T, S = e->cfg.n_stems;
+    if (o->iterations < 1 || o->iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "%s: iterations must be 1..3", who);
+    if (o->overlap_rows < 0 || o->overlap_rows > T / 2) return fail(-1, "%s: overlap_rows must be 0 .. T / 2", who);
+    if (o->mask_extension != SRT_MASK_EXT_CONSTANT && o->mask_extension != SRT_MASK_EXT_AVERAGE) return fail(-1, "%s: mask_extension must be SRT_MASK_EXT_CONSTANT (0) or SRT_MASK_EXT_AVERAGE (1)", who);
+    if (o->n_out < 0 || o->n_out > S) return fail(-1, "%s: n_out must be 0 (every stem) .. n_stems (the filter's spectrum workspace holds n_stems spectra; more outputs are a follow-up)", who);
+    if (o->n_out && !o->h_gain) return fail(-1, "%s: null gain matrix with n_out > 0", who);
+    for (int i = 0; i < o->n_out * (S + 1); ++i) if (!isfinite(o->h_gain[i])) return fail(-1, "%s: every gain must be finite", who);
+    if (e->cfg.ratio_mask) return fail(-1, "%s: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)", who);
+    if (rows < 1 || overlap_tiles(rows, T, o->overlap_rows) > (size_t)e->cfg.max_tiles)
+        return fail(-1, o->overlap_rows ? "%s: the signal takes more than max_tiles tiles at this overlap (srtOverlapTiles)" : "%s: need 1 <= rows <= max_tiles * T", who);
+    memset(c, 0, sizeof *c);
+    c->overlap = o->overlap_rows; c->ext = o->mask_extension; c->n_out = o->n_out;
+    for (int m = 0; m < o->n_out; ++m) for (int s = 0; s <= S; ++s) c->mix[m][s] = o->h_gain[m * (S + 1) + s];
+    return 0;
+}
+
+// the workspaces of an option call: the filter's, and with the average extension the engine's gain table (srtSetMaskExtension's, same size, kept until srtDestroy)
+static int ensure_wiener_opts_ws(srt_engine* e, const char* who, const WienerCall& c)
+{
+    const int rc = ensure_wiener_ws(e);
+    if (rc) return rc;
+    if (c.ext && !e->ext) {
+        if (stream_capturing(e)) return fail(-1, "%s: the mask extension's gain table is not allocated yet (srtSetMaskExtension, or one call outside the capture)", who);
+        SrtSetupLock setup;
+        HIPCHK(hipMalloc((void**)&e->ext, (size_t)e->cfg.n_stems * e->rows_cap * 2 * sizeof(float)));
+    }
+    return 0;
+}
+
+int srtIstftWienerEx(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, const srt_wiener_opts* opts, float* d_out)
+{
+    if (!e || !d_spec || !d_masks || !opts || !d_out) return fail(-1, "srtIstftWienerEx: null argument");
+    DeviceScope ds(e->device);
+    WienerCall c;
+    int rc = wiener_opts_check(e, "srtIstftWienerEx", opts, rows, &c);
+    if (rc) return rc;
+    if ((rc = ensure_wiener_opts_ws(e, "srtIstftWienerEx", c))) return rc;
+    return wiener_issue(e, d_spec, rows, d_masks, opts->iterations, d_out, &c);
+}
+
+// srtSeparate's stages with the call's own options: one STFT in the overlapped layout, one forward over its tiles (fp32 masks in the fp16 mode too, as with
+// srtSetWiener), the filter.  Always eager: the graph cache has no key for the options.
+int srtSeparateWiener(srt_engine* e, const float* d_L, const float* d_R, size_t n, const srt_wiener_opts* opts, float* d_out)
+{
+    if (!e || !d_L || !d_R || !opts || !d_out) return fail(-1, "srtSeparateWiener: null argument");
+    if (n < SRT_FFT) return fail(-1, "srtSeparateWiener: need at least 4096 samples");
+    DeviceScope ds(e->device);
+    const size_t rows = srtStftRows(n), frames = srtStftFrames(n);
+    WienerCall c;
+    int rc = wiener_opts_check(e, "srtSeparateWiener", opts, rows, &c);
+    if (rc) return rc;
+    for (int s = 0; s < e->cfg.n_stems; ++s) if (!e->have_coeff[s]) return fail(-5, "srtSeparateWiener: weights not set for every stem");
+    if ((rc = ensure_wiener_opts_ws(e, "srtSeparateWiener", c))) return rc;
+    const SrtSwitches sw = srt_read_switches();
+    const size_t ntiles = overlap_tiles(rows, e->cfg.T, c.overlap);
+    if ((rc = stft_issue(e, d_L, d_R, n, frames, rows, (float*)e->spec, e->mag, c.overlap))) return rc;
+    if ((rc = forward_range(e, sw, e->mag, (int)ntiles, e->masks, 0, e->cfg.n_stems, false))) return rc;
+    return wiener_issue(e, (const float*)e->spec, rows, e->masks, opts->iterations, d_out, &c);
 }
 
 int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, int iterations, float* d_out)

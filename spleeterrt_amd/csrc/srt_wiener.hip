@@ -18,7 +18,10 @@
 //   srt_wiener_filter_kernel    the chain through all n iterations per (row, bin), writing every stem's filtered spectrum (bins >= F: the input
 //                               spectrum, to which the inverse transform applies oob_weight as for masks).
 // The 2 x 2 inverse is the closed form with det C = c00 c11 - |c01|^2 (real); C >= sqrt(eps) al^2 I keeps it away from zero, as in norbert.
+// With per-call options (overlapped tiles, the average mask extension, the stem remix: srtIstftWienerEx / srtSeparateWiener) srt_wiener_stats_ov_kernel and
+// srt_wiener_filter_opt_kernel at the end of this file take the places of the first and the third; with every option off the three above run as always.
 #include "srt_internal.h"
+#include "srt_overlap.h"
 #include <math.h>
 
 #define W_EPS      1.1920928955078125e-07f        // 2^-23: fp32 machine epsilon, norbert's default for complex64
@@ -46,7 +49,23 @@ __device__ __forceinline__ void w_start(float2 (&yl)[SRT_MAX_STEMS], float2 (&yr
     }
 }
 
+// |y_L|^2 + |y_R|^2 of one stem as the kernels of a plain call form it from w_iter's sum below: the first square, then one fused multiply-add per further
+// component, left to right.  Spelled out (contraction off, explicit fmaf) for the option kernels at the end of this file: there the vectoriser otherwise turns the
+// sum into packed products and separate adds in some instantiations and not in others, and the estimates differ in their last bits between kernels that have
+// to agree bit for bit (a one-hot remix and the stem; one tile with and without an overlap).
+#pragma clang fp contract(off)
+__device__ __forceinline__ float w_power(float2 a, float2 b)
+{
+    float t = a.x * a.x;
+    t = fmaf(a.y, a.y, t);
+    t = fmaf(b.x, b.x, t);
+    return fmaf(b.y, b.y, t);
+}
+#pragma clang fp contract(fast)
+
 // one EM iteration at (row, bin): R points at stem 0's entry of this bin in the iteration's table, stems F apart; delta = sqrt(eps) al^2
+// PIN (the option kernels): the stem's power through w_power; false: the statement as it always was, and the plain kernels' code with it
+template <bool PIN = false>
 __device__ __forceinline__ void w_iter(float2 (&yl)[SRT_MAX_STEMS], float2 (&yr)[SRT_MAX_STEMS], float2 sL, float2 sR,
                                        const float4* __restrict__ R, int F, float delta, int S)
 {
@@ -54,7 +73,8 @@ __device__ __forceinline__ void w_iter(float2 (&yl)[SRT_MAX_STEMS], float2 (&yr)
     float c00 = delta, c11 = delta, c01r = 0.0f, c01i = 0.0f;
 #pragma unroll
     for (int j = 0; j < SRT_MAX_STEMS; ++j) {
-        v[j] = 0.5f * (yl[j].x * yl[j].x + yl[j].y * yl[j].y + yr[j].x * yr[j].x + yr[j].y * yr[j].y);
+        if constexpr (PIN) v[j] = 0.5f * w_power(yl[j], yr[j]);
+        else v[j] = 0.5f * (yl[j].x * yl[j].x + yl[j].y * yl[j].y + yr[j].x * yr[j].x + yr[j].y * yr[j].y);
         if (j < S) {
             const float4 r = R[(size_t)j * F];
             c00 += v[j] * r.x; c11 += v[j] * r.y; c01r += v[j] * r.z; c01i += v[j] * r.w;
@@ -400,5 +420,215 @@ int srt_launch_wiener_filter_batch(const SrtWienerParams& p, const SrtBatchTrack
 {
     if (iters < 1 || iters > SRT_WIENER_MAX_ITERS || !w_batch_args_ok(p, ntracks) || p.rows / W_FILTER_ROWS > 65535 || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD) return -1;
     SRT_LAUNCH(srt_wiener_filter_batch_kernel, dim3(SRT_WIENER_BINBLK, p.rows / W_FILTER_ROWS), dim3(256), 0, s, p, d_tracks, d_wt, ntracks, iters);
+    return srt_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------- per-call options (srtIstftWienerEx / srtSeparateWiener)
+// Overlapped tiles, the average mask extension and the stem remix under the filter.  The kernels above are not touched: with every option off the entry
+// points launch them as always.  An overlap changes the one thing the filter reads of the network - the mask value of a (stem, row, channel, bin) becomes
+// the cross-faded value of the row's two tiles (srt_ov_row / srt_blend, srt_overlap.h: the inverse transform's own helpers) - and nothing else: a spectrum
+// row enters the statistics once however many tiles hold it, and the window, a, the row chunks and the order of every sum stay wiener_issue's.
+
+// w_start on mask VALUES (already fetched, and blended where the row lies in two tiles) instead of a mask pointer: the same statements in the same order
+__device__ __forceinline__ void w_start_v(float2 (&yl)[SRT_MAX_STEMS], float2 (&yr)[SRT_MAX_STEMS], float2 sL, float2 sR,
+                                          const float (&ml)[SRT_MAX_STEMS], const float (&mr)[SRT_MAX_STEMS], int S)
+{
+    const float aL = hypotf(sL.x, sL.y), aR = hypotf(sR.x, sR.y);
+    float vl[SRT_MAX_STEMS], vr[SRT_MAX_STEMS], suml = 0.0f, sumr = 0.0f;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        vl[j] = 0.0f; vr[j] = 0.0f;
+        if (j < S) { vl[j] = ml[j] * aL; vr[j] = mr[j] * aR; suml += vl[j]; sumr += vr[j]; }
+    }
+    const float il = 1.0f / (W_EPS_SOFT + suml), ir = 1.0f / (W_EPS_SOFT + sumr);
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        const float gl = vl[j] * il, gr = vr[j] * ir;
+        yl[j] = make_float2(gl * sL.x, gl * sL.y);
+        yr[j] = make_float2(gr * sR.x, gr * sR.y);
+    }
+}
+
+// the mask values of row t, bin k in the overlapped layout: the row's primary tile, cross-faded with row k + S of the previous tile inside an overlap.
+// t is workgroup-uniform (a loop counter from blockIdx), so srt_ov_row is scalar arithmetic and `two` a uniform branch: the second row is loaded only then.
+__device__ __forceinline__ void w_masks_ov(float (&ml)[SRT_MAX_STEMS], float (&mr)[SRT_MAX_STEMS], const SrtWienerParams& p, int O, int t, int k, int S)
+{
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const OvRow ov = srt_ov_row(t, p.T, O, p.ntiles);
+    const float* b = p.masks + (size_t)ov.j1 * 2 * tf + (size_t)ov.k * p.F + k;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        ml[j] = 0.0f; mr[j] = 0.0f;
+        if (j < S) { ml[j] = b[j * sstride]; mr[j] = b[j * sstride + tf]; }
+    }
+    if (ov.two) {
+        const float* a = b - 2 * tf + (size_t)(p.T - O) * p.F;
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S) { ml[j] = srt_blend(a[j * sstride], ml[j], ov.w); mr[j] = srt_blend(a[j * sstride + tf], mr[j], ov.w); }
+    }
+}
+
+// srt_wiener_stats_kernel with the mask fetch replaced (launched only with an overlap: at O = 0 that kernel runs, and the R tables are its own bit for bit)
+__global__ void __launch_bounds__(256) srt_wiener_stats_ov_kernel(const SrtWienerParams p, int O, int pass)
+{
+    __shared__ float red[4];
+    const int k = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, S = p.nstems;
+    const int r0 = c * p.rpc, r1 = min(r0 + p.rpc, p.rows);
+    const float al = (pass > 1 ? p.scal[0] : 1.0f) * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F, anyb = k < SRT_HALF;
+    const float2* sLp = p.spec + (anyb ? k : 0);
+    const float2* sRp = sLp + p.spec_ch_stride;
+    float acc[SRT_MAX_STEMS][4];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
+    float mx = 0.0f;
+    if (anyb) {
+        for (int t = r0; t < r1; ++t) {
+            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD];
+            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y)));
+            if (!inb) continue;
+            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS];
+            w_masks_ov(ml, mr, p, O, t, k, S);
+            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+            w_start_v(yl, yr, sL, sR, ml, mr, S);
+            for (int i = 0; i < pass - 1; ++i)
+                w_iter<true>(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y;
+                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y;
+                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      // y_L conj(y_R)
+                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y;
+            }
+        }
+    }
+    if (inb) {
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k] = acc[j][q];
+    }
+    if (pass == 1) {                                             // (block-uniform branch: every thread reaches the barriers)
+        mx = w_block_max(mx, red);
+        if (threadIdx.x == 0) p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] = mx;
+    }
+}
+
+// The remix of the filter's outputs (srt_mix_gains' / srt_mix_chain's arithmetic on filtered values): one rounded product and one fused multiply-add per stem,
+// nothing else contracted, so a one-hot row gives stem m's bits.  The matrix is read from the launch arguments where it is used (m is a uniform loop counter).
+#pragma clang fp contract(off)
+// in band, per complex component: h = G[m][S] s, then h = fmaf(G[m][j], y_j, h) for j ascending
+__device__ __forceinline__ float2 w_mix_inband(const SrtWienerOpt& q, int m, int S, float2 s, const float2 (&y)[SRT_MAX_STEMS])
+{
+    const float g = q.mix[m][S];
+    float hx = g * s.x, hy = g * s.y;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j)
+        if (j < S) { const float gj = q.mix[m][j]; hx = fmaf(gj, y[j].x, hx); hy = fmaf(gj, y[j].y, hy); }
+    return make_float2(hx, hy);
+}
+// above F: the gain h = G[m][S], then h = fmaf(G[m][j], g_j, h) for j ascending (g_j: stem j's gain of this row and channel)
+__device__ __forceinline__ float w_mix_gain(const SrtWienerOpt& q, int m, int S, const float (&g)[SRT_MAX_STEMS])
+{
+    float h = q.mix[m][S];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j)
+        if (j < S) h = fmaf(q.mix[m][j], g[j], h);
+    return h;
+}
+__device__ __forceinline__ float2 w_scale(float g, float2 s) { return make_float2(g * s.x, g * s.y); }
+#pragma clang fp contract(fast)
+
+// srt_wiener_filter_kernel for a call with any option on: one thread per bin, W_FILTER_ROWS rows per workgroup.  It writes the FINAL spectrum of every bin -
+// in band y_j (or, with a remix, the mixes of the y_j); above F the gain times the input, the gain being oob[j], the extension table's e_j(row, channel) (q.ext, a
+// run-time pointer; the address is workgroup-uniform: scalar loads) or, with a remix, their chain through the matrix - so the inverse transform behind it applies no
+// gain at all.  OV: the masks are in the overlapped layout (w_masks_ov); else they are fetched as srt_wiener_filter_kernel does.
+// The remix is a RUN-TIME branch (q.n_out, workgroup-uniform), not a second instantiation: a one-hot row must give the bits of the stem, and that holds by
+// construction only when the mixes and the stems come out of one compiled copy of the chain - compiled apart, the two copies differed in which products and sums
+// became fused multiply-adds, and the y_j in their last bits.
+template <bool OV>
+__global__ void __launch_bounds__(256) srt_wiener_filter_opt_kernel(const SrtWienerParams p, const SrtWienerOpt q, int iters)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x, S = p.nstems;
+    if (k >= SRT_HALF) return;
+    const int r0 = blockIdx.y * W_FILTER_ROWS, r1 = min(r0 + W_FILTER_ROWS, p.rows);
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf, och = p.out_stem / 2;
+    const float al = p.scal[0] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F;
+    for (int t = r0; t < r1; ++t) {
+        const size_t o = (size_t)t * SRT_SPEC_LD + k;
+        const float2 sL = p.spec[o], sR = p.spec[p.spec_ch_stride + o];
+        if (!inb) {
+            float gl[SRT_MAX_STEMS], gr[SRT_MAX_STEMS];
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+                gl[j] = 0.0f; gr[j] = 0.0f;
+                if (j < S) {
+                    if (q.ext) { const float* e = q.ext + (size_t)j * q.ext_stem + (size_t)t * 2; gl[j] = e[0]; gr[j] = e[1]; }
+                    else { gl[j] = q.oob[j]; gr[j] = gl[j]; }
+                }
+            }
+            if (q.n_out) {
+                for (int m = 0; m < q.n_out; ++m) {
+                    p.out[m * p.out_stem + o] = w_scale(w_mix_gain(q, m, S, gl), sL);
+                    p.out[m * p.out_stem + och + o] = w_scale(w_mix_gain(q, m, S, gr), sR);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < SRT_MAX_STEMS; ++j)
+                    if (j < S) { p.out[j * p.out_stem + o] = w_scale(gl[j], sL); p.out[j * p.out_stem + och + o] = w_scale(gr[j], sR); }
+            }
+            continue;
+        }
+        float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+        if constexpr (OV) {
+            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS];
+            w_masks_ov(ml, mr, p, q.overlap, t, k, S);
+            w_start_v(yl, yr, sL, sR, ml, mr, S);
+        } else {
+            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;
+            w_start(yl, yr, sL, sR, m, sstride, tf, S);
+        }
+        for (int i = 0; i < iters; ++i)
+            w_iter<true>(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
+        if (q.n_out) {
+            for (int m = 0; m < q.n_out; ++m) {
+                p.out[m * p.out_stem + o] = w_mix_inband(q, m, S, sL, yl);
+                p.out[m * p.out_stem + och + o] = w_mix_inband(q, m, S, sR, yr);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j)
+                if (j < S) { p.out[j * p.out_stem + o] = yl[j]; p.out[j * p.out_stem + och + o] = yr[j]; }
+        }
+    }
+}
+
+// masks of p.ntiles tiles at this overlap cover rows 0 .. p.rows - 1 (srt_ov_row then stays inside the masks: row k < T of tile j1 < ntiles, and k + S < T of tile j1 - 1)
+static bool w_layout_ok(const SrtWienerParams& p, int overlap)
+{
+    if (p.T < 1 || p.ntiles < 1 || overlap < 0 || overlap > p.T / 2) return false;
+    return (size_t)(p.ntiles - 1) * (p.T - overlap) + p.T >= (size_t)p.rows;
+}
+
+int srt_launch_wiener_stats_ov(const SrtWienerParams& p, int overlap, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || p.nchunks < 1 || p.nchunks > SRT_WIENER_MAX_CHUNKS || p.nstems < 1 || p.nstems > SRT_MAX_STEMS ||
+        p.F < 1 || p.F > SRT_HALF - 1 || (size_t)p.nchunks * p.rpc < (size_t)p.rows || overlap < 1 || !w_layout_ok(p, overlap)) return -1;
+    const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
+    SRT_LAUNCH(srt_wiener_stats_ov_kernel, dim3(bx, p.nchunks), dim3(256), 0, s, p, overlap, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q, int iters, hipStream_t s)
+{
+    if (iters < 1 || iters > SRT_WIENER_MAX_ITERS || p.rows < 1 || p.nstems < 1 || p.nstems > SRT_MAX_STEMS || p.F < 1 || p.F > SRT_HALF - 1 ||
+        !w_layout_ok(p, q.overlap) || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD) return -1;
+    if (q.n_out < 0 || q.n_out > p.nstems || (q.ext && q.ext_stem < (size_t)p.rows * 2)) return -1;      // the spectrum workspace holds nstems spectra
+    const dim3 grid(SRT_WIENER_BINBLK, (p.rows + W_FILTER_ROWS - 1) / W_FILTER_ROWS), block(256);
+    if (q.overlap > 0) SRT_LAUNCH(srt_wiener_filter_opt_kernel<true>, grid, block, 0, s, p, q, iters);
+    else SRT_LAUNCH(srt_wiener_filter_opt_kernel<false>, grid, block, 0, s, p, q, iters);
     return srt_launch_status();
 }
