@@ -2,31 +2,32 @@
 #include "srt_engine.h"
 
 // ---- packed batch of independent tracks (srt_dsp.hip: srt_stft_batch_kernel / srt_istft_batch_kernel)
+// the plan of checked tracks: track k takes overlap_tiles(rows_k, T, O) packed tiles from tile0[k] on (O = 0: ceil(rows_k / T)); returns their sum
+static size_t plan_tiles(const size_t* n, int ntracks, int T, int O, size_t* tile0)
+{
+    size_t t = 0;
+    for (int k = 0; k < ntracks; ++k) {
+        if (tile0) tile0[k] = t;
+        t += overlap_tiles(srtStftRows(n[k]), T, O);
+    }
+    return t;
+}
+
 int srtBatchPlan(const size_t* n, int ntracks, int T, size_t* tile0, size_t* total_tiles)
 {
     if (!n || !total_tiles || ntracks < 1 || T < 1) return fail(-1, "srtBatchPlan: need ntracks >= 1, T >= 1, n and total_tiles");
     for (int k = 0; k < ntracks; ++k) if (n[k] < SRT_FFT) return fail(-1, "srtBatchPlan: every track needs at least 4096 samples");
-    size_t t = 0;
-    for (int k = 0; k < ntracks; ++k) {
-        if (tile0) tile0[k] = t;
-        t += (srtStftRows(n[k]) + T - 1) / T;
-    }
-    *total_tiles = t;
+    *total_tiles = plan_tiles(n, ntracks, T, 0, tile0);
     return 0;
 }
 
-// the same with overlapped tiles inside every track (srtSeparateBatchOverlap): track k takes overlap_tiles(rows_k, T, O) packed tiles; O = 0 is srtBatchPlan
+// the same with overlapped tiles inside every track (srtSeparateBatchOverlap); O = 0 is srtBatchPlan
 int srtBatchPlanOverlap(const size_t* n, int ntracks, int T, int overlap_rows, size_t* tile0, size_t* total_tiles)
 {
     if (!n || !total_tiles || ntracks < 1 || T < 1) return fail(-1, "srtBatchPlanOverlap: need ntracks >= 1, T >= 1, n and total_tiles");
-    if (overlap_rows < 0 || overlap_rows > T / 2) return fail(-1, "srtBatchPlanOverlap: the overlap must be 0 .. T / 2 rows");
+    if (!overlap_ok(overlap_rows, T)) return fail(-1, "srtBatchPlanOverlap: the overlap must be 0 .. T / 2 rows");
     for (int k = 0; k < ntracks; ++k) if (n[k] < SRT_FFT) return fail(-1, "srtBatchPlanOverlap: every track needs at least 4096 samples");
-    size_t t = 0;
-    for (int k = 0; k < ntracks; ++k) {
-        if (tile0) tile0[k] = t;
-        t += overlap_tiles(srtStftRows(n[k]), T, overlap_rows);
-    }
-    *total_tiles = t;
+    *total_tiles = plan_tiles(n, ntracks, T, overlap_rows, tile0);
     return 0;
 }
 
@@ -73,43 +74,37 @@ static int ensure_batch_wiener(srt_engine* e)
     return 0;
 }
 
-// What the batch entry points share, up to and including the forward: the argument checks (`who` names the entry point; wiener = the iterations of
-// srtSeparateBatchWiener, 0 for the others), the track table(s) and their upload from a pinned slot, the batched STFT and the network over the packed tiles.
-// overlap: -1 for the entry points that have no overlap argument (they refuse while the engine's own setting is on); >= 0: srtSeparateBatchOverlap's argument, which
-// holds for the call whatever the engine's setting says (0: the back-to-back plan and kernels)
-// mx: srtSeparateBatchMix's own arguments (null for the other entry points, which refuse while the engine's srtSetMix is on); n_out = 0: no remix in this call
-struct BatchCall { size_t total; SrtBatchGrid g; size_t ch_stride; int wchunks; };
-struct BatchMix { int n_out; const float* h_gain; size_t stride; };
-static int batch_forward(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
-                         int wiener, int overlap, BatchCall* bc, const BatchMix* mx = nullptr)
+// the track arrays of a batch call (`who` names the entry point): what every entry point checks before it looks at options
+static int batch_tracks_check(const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
 {
     if (ntracks < 1 || !d_L || !d_R || !n || !d_out) return fail(-1, "%s: need ntracks >= 1 and the four track arrays", who);
-    const SrtSwitches sw = srt_read_switches();
     char what[160];
     for (int k = 0; k < ntracks; ++k) {
         if (!d_L[k] || !d_R[k] || !d_out[k]) { snprintf(what, sizeof what, "%s: null pointer in track %d", who, k); return fail(-1, "%s", what); }
         if (n[k] < SRT_FFT) { snprintf(what, sizeof what, "%s: track %d has fewer than 4096 samples", who, k); return fail(-1, "%s", what); }
     }
-    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
-    if (overlap < 0 && e->overlap) return fail(-1, OVERLAP_REFUSED, who);     // srtBatchPlan has no overlap argument: srtSeparateBatchOverlap
-    if (overlap > T / 2) return fail(-1, "%s: the overlap must be 0 .. T / 2 rows", who);
-    const int O = overlap > 0 ? overlap : 0;
-    if (!mx && e->mix_out) return wiener ? fail(-1, MIX_REFUSED, who)
-                                         : fail(-1, "%s: not available with the engine's stem remix on (srtSetMix): srtSeparateBatchMix takes the mix per track, or srtSetMix(e, 0, NULL) first", who);
-    const int n_out = mx ? mx->n_out : 0, gw = n_out * (S + 1);                // gw: floats of one track's matrix
-    if (n_out) {
-        if (!mx->h_gain) return fail(-1, "%s: null gain matrices", who);
-        if (mx->stride && mx->stride < (size_t)gw) return fail(-1, "%s: gain_stride must be 0 (one matrix for every track) or at least n_out * (n_stems + 1)", who);
-        for (int k = 0; k < (mx->stride ? ntracks : 1); ++k)
-            for (int i = 0; i < gw; ++i) if (!isfinite(mx->h_gain[k * mx->stride + i])) { snprintf(what, sizeof what, "%s: a gain of track %d is not finite", who, k); return fail(-1, "%s", what); }
-    }
-    if (overlap >= 0 && e->wiener) return fail(-1, "%s: not available with the Wiener filter on (its kernels index masks by back-to-back tiles): srtSetWiener(e, 0) first", who);
-    if (!wiener && e->wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
-    size_t total = 0;
-    if (O ? srtBatchPlanOverlap(n, ntracks, T, O, nullptr, &total) : srtBatchPlan(n, ntracks, T, nullptr, &total)) return -1;
+    return 0;
+}
+
+static const char* const BATCH_OVERLAP_RANGE = "%s: the overlap must be 0 .. T / 2 rows";
+static const char* const BATCH_MIX_REFUSED = "%s: not available with the engine's stem remix on (srtSetMix): srtSeparateBatchMix takes the mix per track, or srtSetMix(e, 0, NULL) first";
+static const char* const BATCH_WIENER_REFUSED = "%s: not available with the Wiener filter on (its kernels index masks by back-to-back tiles): srtSetWiener(e, 0) first";
+
+// What the batch entry points share once their checks have passed, up to and including the forward: the plan of o.overlap against max_tiles, the track table(s)
+// and their upload from a pinned slot, the batched STFT and the network over the packed tiles.  o.wiener: the filter's second table.  o.n_out > 0: the tracks'
+// matrices [n_out][n_stems + 1] at h_gain + k * gain_stride (0: one for all) go up beside the track table (per track, so beside the record: o.mix stays unused).
+struct BatchCall { size_t total; SrtBatchGrid g; size_t ch_stride; int wchunks; };
+static int batch_forward(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
+                         const SepOpts& o, const float* h_gain, size_t gain_stride, BatchCall* bc)
+{
+    const SrtSwitches sw = srt_read_switches();
+    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems, O = o.overlap, wiener = o.wiener;
+    const int n_out = o.n_out, gw = n_out * (S + 1);                           // gw: floats of one track's matrix
+    const size_t total = plan_tiles(n, ntracks, T, O, nullptr);
     if (total > (size_t)e->cfg.max_tiles) {
-        if (O) snprintf(what, sizeof what, "%s: the tracks take %zu overlapped tiles, more than max_tiles (srtBatchPlanOverlap counts them; split the list into calls that fit)", who, total);
-        else snprintf(what, sizeof what, "%s: the tracks take %zu tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", who, total);
+        char what[160];
+        snprintf(what, sizeof what, O ? "%s: the tracks take %zu overlapped tiles, more than max_tiles (srtBatchPlanOverlap counts them; split the list into calls that fit)"
+                                      : "%s: the tracks take %zu tiles, more than max_tiles (split the list into calls that fit, as stream.pack_tracks does)", who, total);
         return fail(-1, "%s", what);
     }
     if (wiener && total * T / 16 > 65535) return fail(-1, "%s: more than 65535 blocks of 16 packed rows (the filter's grid)", who);
@@ -143,7 +138,7 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
     if (wiener) HIPCHK(hipMemcpyAsync(e->bwtab, hw, (size_t)ntracks * sizeof(SrtBatchWiener), hipMemcpyHostToDevice, e->stream));
     if (n_out) {                                               // the tracks' matrices, packed [ntracks][n_out][S + 1], from the same slot of the ring
         float* hg = e->bgpin + (size_t)slot * e->cfg.max_tiles * SRT_BATCH_GAIN_FLOATS;
-        for (int k = 0; k < ntracks; ++k) memcpy(hg + (size_t)k * gw, mx->h_gain + k * mx->stride, (size_t)gw * sizeof(float));
+        for (int k = 0; k < ntracks; ++k) memcpy(hg + (size_t)k * gw, h_gain + k * gain_stride, (size_t)gw * sizeof(float));
         HIPCHK(hipMemcpyAsync(e->bgtab, hg, (size_t)ntracks * gw * sizeof(float), hipMemcpyHostToDevice, e->stream));
     }
     HIPCHK(hipEventRecord(e->bev[slot], e->stream));
@@ -157,52 +152,85 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
         TimerScope ts(e, "stft_batch");
         if (srt_launch_stft_batch(p, e->btab, ntracks, bc->g, e->stream, O)) return fail(-2, "batched stft launch failed");
     }
-    // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue (never with the filter, which reads fp32 masks)
-    // (nor with a remix: the MIX kernels read float masks, as under srtSetMix)
-    return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, !wiener && !n_out && masks16_wanted(e, sw));
+    // the network over all packed tiles; the fp16 mode's half masks under the same rule as separate_issue (never with the filter, which reads fp32 masks, nor
+    // with a remix: the MIX kernels read float masks, as under srtSetMix)
+    return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, masks16_wanted(e, sw, o));
 }
 
-// srtSeparateBatch (overlap = -1) and srtSeparateBatchOverlap (overlap >= 0): the shared front, the gain table of the average mask extension, one batched inverse
-// mx with n_out > 0 (srtSeparateBatchMix): the inverse writes n_out pairs per track, each the chain of the track's own matrix row (the device gain table)
-static int batch_separate(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap,
-                          const BatchMix* mx = nullptr)
+// Every batch entry point behind its checks: the shared front, then ONE batched inverse - of the masked spectrum (the gain table of o.mask_ext first: every batch
+// call runs under the engine's srtSetMaskExtension; o.n_out > 0: n_out pairs per track, each the chain of the track's own matrix row in the device gain table), or
+// with o.wiener of the per-stem spectra the filter wrote: o.wiener x (statistics + finalize) and the filter over the packed rows with every track's own window, a
+// and tables (srt_wiener.hip)
+static int batch_separate(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
+                          const SepOpts& o, const float* h_gain, size_t gain_stride)
 {
     DeviceScope ds(e->device);
     BatchCall bc;
-    int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, 0, overlap, &bc, mx);
+    int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, o, h_gain, gain_stride, &bc);
     if (rc) return rc;
-    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems, O = overlap > 0 ? overlap : 0;
+    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems, O = o.overlap;
     SrtIstftParams q; memset(&q, 0, sizeof q);
-    q.spec = e->spec; q.spec_ch_stride = bc.ch_stride; q.frames = (int)(bc.total * T);
-    q.masks = e->masks; q.masks16 = e->last.masks16 ? 1 : 0; q.nstems = S; q.ntiles = (int)bc.total; q.T = T; q.F = F;
+    q.spec_ch_stride = bc.ch_stride; q.frames = (int)(bc.total * T); q.nstems = S; q.ntiles = (int)bc.total; q.T = T; q.F = F;
     for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
-    q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
     q.tab = tables_of(e);
-    if (e->mask_ext == SRT_MASK_EXT_AVERAGE) {                 // row-local: one table over the packed rows, each track reads its own (tile0 * T onwards)
+    if (o.wiener) {
+        const size_t cap = (size_t)e->cfg.max_tiles, tf = batch_wiener_track_floats(e);
+        SrtWienerParams w; memset(&w, 0, sizeof w);
+        w.spec = e->spec; w.spec_ch_stride = bc.ch_stride; w.rows = q.frames;
+        w.masks = e->masks; w.nstems = S; w.ntiles = (int)bc.total; w.T = T; w.F = F;
+        w.nchunks = bc.wchunks;
+        w.slab = e->bwslab; w.slab_max = e->bwslab + batch_wiener_chunk_cap(e) * S * 4 * F;
+        w.rtab = e->bwtabf; w.wsum = e->bwtabf + cap * tf * 4; w.scal = w.wsum + cap * tf;
+        w.out = e->wspec; w.out_stem = 2 * bc.ch_stride;
+        for (int pass = 1; pass <= o.wiener; ++pass) {
+            { TimerScope ts(e, "wiener_stats_batch"); if (srt_launch_wiener_stats_batch(w, e->btab, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener statistics launch failed"); }
+            { TimerScope ts(e, "wiener_cov_batch"); if (srt_launch_wiener_finalize_batch(w, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener finalize launch failed"); }
+        }
+        { TimerScope ts(e, "wiener_filter_batch"); if (srt_launch_wiener_filter_batch(w, e->btab, e->bwtab, ntracks, o.wiener, e->stream)) return fail(-2, "batched Wiener filter launch failed"); }
+        e->last.wiener_last = o.wiener; e->last.wiener_tracks = ntracks;
+        q.spec = e->wspec;
+        TimerScope ts(e, "istft_batch");
+        return srt_launch_istft_batch_spec(q, w.out_stem, e->btab, ntracks, bc.g, e->stream) ? fail(-2, "batched istft launch failed") : 0;
+    }
+    q.spec = e->spec; q.masks = e->masks; q.masks16 = e->last.masks16 ? 1 : 0;
+    q.ratio = e->cfg.ratio_mask ? 1 : 0;                       // normalised in the inverse kernel's prologue, as separate_issue does
+    if (o.mask_ext == SRT_MASK_EXT_AVERAGE) {                  // row-local: one table over the packed rows, each track reads its own (tile0 * T onwards)
         // (with an overlap a packed row's tile and blend partner depend on the track it lies in: the batch form of the table kernel)
         if ((rc = mask_ext_issue(e, q.masks, q.masks16, S, q.ntiles, q.frames, q.ratio, O, O ? e->btab : nullptr, ntracks))) return rc;
         q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
     }
+    q.n_out = o.n_out;
     TimerScope ts(e, "istft_batch");
-    if (mx && mx->n_out) {
-        q.n_out = mx->n_out;
-        if (srt_launch_istft_batch_mix(q, e->btab, e->bgtab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
-    } else if (srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
+    if (o.n_out ? srt_launch_istft_batch_mix(q, e->btab, e->bgtab, ntracks, bc.g, e->stream, O) : srt_launch_istft_batch(q, e->btab, ntracks, bc.g, e->stream, O)) return fail(-2, "batched istft launch failed");
     return 0;
 }
 
 int srtSeparateBatch(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out)
 {
+    static const char* const who = "srtSeparateBatch";
     if (!e) return fail(-1, "srtSeparateBatch: null engine");
-    return batch_separate(e, "srtSeparateBatch", ntracks, d_L, d_R, n, d_out, -1);
+    if (const int rc = batch_tracks_check(who, ntracks, d_L, d_R, n, d_out)) return rc;
+    const SepOpts eng = engine_opts(e);
+    if (eng.overlap) return fail(-1, OVERLAP_REFUSED, who);    // srtBatchPlan has no overlap argument: srtSeparateBatchOverlap
+    if (eng.n_out) return fail(-1, BATCH_MIX_REFUSED, who);
+    if (eng.wiener) return fail(-1, "srtSeparateBatch: the Wiener filter's statistics would have to be per track (not supported): srtSetWiener(e, 0), or srtSeparate per track");
+    SepOpts o; o.mask_ext = eng.mask_ext;
+    return batch_separate(e, who, ntracks, d_L, d_R, n, d_out, o, nullptr, 0);
 }
 
 // srtSeparateBatch with overlapped tiles inside every track: overlap_rows holds for this call, the engine's own srtSetOverlap is neither read nor changed
 int srtSeparateBatchOverlap(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap_rows)
 {
+    static const char* const who = "srtSeparateBatchOverlap";
     if (!e) return fail(-1, "srtSeparateBatchOverlap: null engine");
     if (overlap_rows < 0) return fail(-1, "srtSeparateBatchOverlap: the overlap must be 0 .. T / 2 rows");
-    return batch_separate(e, "srtSeparateBatchOverlap", ntracks, d_L, d_R, n, d_out, overlap_rows);
+    if (const int rc = batch_tracks_check(who, ntracks, d_L, d_R, n, d_out)) return rc;
+    if (!overlap_ok(overlap_rows, e->cfg.T)) return fail(-1, BATCH_OVERLAP_RANGE, who);
+    const SepOpts eng = engine_opts(e);
+    if (eng.n_out) return fail(-1, BATCH_MIX_REFUSED, who);
+    if (eng.wiener) return fail(-1, BATCH_WIENER_REFUSED, who);
+    SepOpts o; o.overlap = overlap_rows; o.mask_ext = eng.mask_ext;
+    return batch_separate(e, who, ntracks, d_L, d_R, n, d_out, o, nullptr, 0);
 }
 
 // srtSeparateBatchOverlap with a stem remix per track: n_out outputs per track instead of n_stems, track k's matrix [n_out][n_stems + 1] at
@@ -211,47 +239,38 @@ int srtSeparateBatchOverlap(srt_engine* e, int ntracks, const float* const* d_L,
 int srtSeparateBatchMix(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int overlap_rows,
                         int n_out, const float* h_gain, size_t gain_stride)
 {
+    static const char* const who = "srtSeparateBatchMix";
     if (!e) return fail(-1, "srtSeparateBatchMix: null engine");
     if (overlap_rows < 0) return fail(-1, "srtSeparateBatchMix: the overlap must be 0 .. T / 2 rows");
     if (n_out < 0 || n_out > SRT_MAX_STEMS) return fail(-1, "srtSeparateBatchMix: n_out must be 0 (no remix) .. SRT_MAX_STEMS");
-    const BatchMix mx = { n_out, h_gain, n_out ? gain_stride : 0 };
-    return batch_separate(e, "srtSeparateBatchMix", ntracks, d_L, d_R, n, d_out, overlap_rows, &mx);
+    if (const int rc = batch_tracks_check(who, ntracks, d_L, d_R, n, d_out)) return rc;
+    if (!overlap_ok(overlap_rows, e->cfg.T)) return fail(-1, BATCH_OVERLAP_RANGE, who);
+    const int gw = n_out * (e->cfg.n_stems + 1);
+    if (!n_out) gain_stride = 0;
+    else {
+        if (!h_gain) return fail(-1, "%s: null gain matrices", who);
+        if (gain_stride && gain_stride < (size_t)gw) return fail(-1, "%s: gain_stride must be 0 (one matrix for every track) or at least n_out * (n_stems + 1)", who);
+        for (int k = 0; k < (gain_stride ? ntracks : 1); ++k)
+            if (!gain_finite(h_gain + k * gain_stride, gw)) { char what[160]; snprintf(what, sizeof what, "%s: a gain of track %d is not finite", who, k); return fail(-1, "%s", what); }
+    }
+    const SepOpts eng = engine_opts(e);
+    if (eng.wiener) return fail(-1, BATCH_WIENER_REFUSED, who);
+    SepOpts o; o.overlap = overlap_rows; o.mask_ext = eng.mask_ext; o.n_out = n_out;
+    return batch_separate(e, who, ntracks, d_L, d_R, n, d_out, o, h_gain, gain_stride);
 }
 
-// srtSeparateBatch with the Wiener filter per track: the shared front (fp32 masks), `iterations` x (statistics + finalize) and the filter over the packed rows
-// with every track's own window, a and tables (srt_wiener.hip), then ONE batched inverse of the per-stem filtered spectra
+// srtSeparateBatch with the Wiener filter per track: fp32 masks, every other option off
 int srtSeparateBatchWiener(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, int iterations)
 {
     static const char* const who = "srtSeparateBatchWiener";
     if (!e) return fail(-1, "srtSeparateBatchWiener: null engine");
-    DeviceScope ds(e->device);
     if (iterations < 1 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtSeparateBatchWiener: iterations must be 1..3");
     if (e->cfg.ratio_mask) return fail(-1, "srtSeparateBatchWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
-    if (e->mask_ext) return fail(-1, MASK_EXT_REFUSED, who);
-    BatchCall bc;
-    const int rc = batch_forward(e, who, ntracks, d_L, d_R, n, d_out, iterations, -1, &bc);
-    if (rc) return rc;
-    const int T = e->cfg.T, F = e->cfg.F, S = e->cfg.n_stems;
-    const size_t cap = (size_t)e->cfg.max_tiles, tf = batch_wiener_track_floats(e);
-    SrtWienerParams w; memset(&w, 0, sizeof w);
-    w.spec = e->spec; w.spec_ch_stride = bc.ch_stride; w.rows = (int)(bc.total * T);
-    w.masks = e->masks; w.nstems = S; w.ntiles = (int)bc.total; w.T = T; w.F = F;
-    w.nchunks = bc.wchunks;
-    w.slab = e->bwslab; w.slab_max = e->bwslab + batch_wiener_chunk_cap(e) * S * 4 * F;
-    w.rtab = e->bwtabf; w.wsum = e->bwtabf + cap * tf * 4; w.scal = w.wsum + cap * tf;
-    w.out = e->wspec; w.out_stem = 2 * bc.ch_stride;
-    for (int pass = 1; pass <= iterations; ++pass) {
-        { TimerScope ts(e, "wiener_stats_batch"); if (srt_launch_wiener_stats_batch(w, e->btab, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener statistics launch failed"); }
-        { TimerScope ts(e, "wiener_cov_batch"); if (srt_launch_wiener_finalize_batch(w, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener finalize launch failed"); }
-    }
-    { TimerScope ts(e, "wiener_filter_batch"); if (srt_launch_wiener_filter_batch(w, e->btab, e->bwtab, ntracks, iterations, e->stream)) return fail(-2, "batched Wiener filter launch failed"); }
-    e->last.wiener_last = iterations; e->last.wiener_tracks = ntracks;
-    SrtIstftParams q; memset(&q, 0, sizeof q);
-    q.spec = e->wspec; q.spec_ch_stride = bc.ch_stride; q.frames = (int)(bc.total * T);
-    q.nstems = S; q.ntiles = (int)bc.total; q.T = T; q.F = F;
-    for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = e->cfg.oob_weight[s];
-    q.tab = tables_of(e);
-    TimerScope ts(e, "istft_batch");
-    if (srt_launch_istft_batch_spec(q, w.out_stem, e->btab, ntracks, bc.g, e->stream)) return fail(-2, "batched istft launch failed");
-    return 0;
+    const SepOpts eng = engine_opts(e);
+    if (eng.mask_ext) return fail(-1, MASK_EXT_REFUSED, who);
+    if (const int rc = batch_tracks_check(who, ntracks, d_L, d_R, n, d_out)) return rc;
+    if (eng.overlap) return fail(-1, OVERLAP_REFUSED, who);
+    if (eng.n_out) return fail(-1, MIX_REFUSED, who);
+    SepOpts o; o.wiener = iterations;
+    return batch_separate(e, who, ntracks, d_L, d_R, n, d_out, o, nullptr, 0);
 }

@@ -2,6 +2,7 @@
 // the weight layout, the graph cache's types and the helpers those units call across files.  No other unit includes it.
 #pragma once
 #include "srt_internal.h"
+#include "srt_checks.h"
 #include "../../include/spleeterrt_amd.h"
 #include <math.h>
 #include <stdio.h>
@@ -55,10 +56,8 @@ struct ForwardRecord {
 // graph instead of replaying the old form.  Keys are zeroed before they are filled and compared with memcmp.
 #define SRT_BATCH_SLOTS 4
 #define SRT_BATCH_GAIN_FLOATS (SRT_MAX_STEMS * (SRT_MAX_STEMS + 1))      // the largest remix matrix of one track (srtSeparateBatchMix)
-// `overlap`: the rows consecutive network tiles share (srtSetOverlap) - a sequence captured at one overlap is never replayed at another.
-// `mask_ext`: the rule for bins >= F (srtSetMaskExtension), for the same reason.
-// `mix_gen`: the generation of the stem remix matrix (srtSetMix bumps it; 0 while the mix is off) - a changed matrix never replays a graph captured with the old one
-// (the matrix travels by value in the captured launch).
+// `wiener`, `overlap`, `mask_ext`, `mix_gen`: the call's options (graph_key_opts) - a sequence captured under one record is never replayed under another.  mix_gen is
+// the generation of the remix matrix (srtSetMix bumps it; 0 while the mix is off): the matrix travels by value in the captured launch.
 struct GraphKey { int kind; const void* p0; const void* p1; void* p2; size_t n, frames, rows; int ntiles, s0, ns, wiener; SrtSwitches sw; int overlap, mask_ext; unsigned mix_gen; };
 // left: e->last as the capture left it (an eager call in between may have changed it)
 struct GraphSlot { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; unsigned long used; ForwardRecord left; };
@@ -72,6 +71,18 @@ struct DeviceScope {
         if (hipGetDevice(&prev) == hipSuccess && prev != dev) sw = hipSetDevice(dev) == hipSuccess;
     }
     ~DeviceScope() { if (sw) hipSetDevice(prev); }
+};
+
+// The options of ONE separation call.  A public entry point resolves them once - engine_opts(e) where the call runs under the engine's setters, its
+// own arguments where it takes options (srtIstftWienerEx, srtSeparateWiener, srtSeparateBatchOverlap / Mix / Wiener) - refuses what it cannot run, and hands the record
+// down by reference: nothing below an entry point reads the engine's option fields.  SepOpts{} is every option off (the CLI flows, the filter's mask-free inverses).
+struct SepOpts {
+    int overlap = 0;                                   // rows two consecutive tiles of one signal share, 0: back-to-back tiles (the reference's cut)
+    int mask_ext = SRT_MASK_EXT_CONSTANT;              // the rule for bins >= F
+    int wiener = 0;                                    // EM iterations of the multichannel Wiener filter, 0: off
+    int n_out = 0;                                     // stem remix: > 0 - the inverse transform writes n_out pairs, pair m the chain of mix[m] over the stems' gains
+    float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1] = {};  // (a batch's per-track matrices travel beside the record)
+    unsigned mix_gen = 0;                              // the engine's count of the srtSetMix calls that switched the mix on: graph key only
 };
 
 struct srt_engine {
@@ -142,7 +153,6 @@ static const char* const MASK_EXT_REFUSED = "%s: not available with the average 
 // Overlapped network tiles, the one rule (mirrored by spleeterrt_amd/stream.py:overlap_tiles): stride S = T - O, tile j covers rows [jS, jS + T); one tile up
 // to T rows, else ceil((rows - O) / S) - every tile then owns a row no earlier tile covers, and the tiles cover all rows.  O = 0: ceil(rows / T).
 static inline size_t overlap_tiles(size_t rows, int T, int O) { return rows == 0 ? 0 : rows <= (size_t)T ? 1 : (rows - O + (T - O) - 1) / (T - O); }
-static inline size_t tiles_of(const srt_engine* e, size_t rows) { return overlap_tiles(rows, e->cfg.T, e->overlap); }     // network tiles of a signal of `rows` rows
 
 // element offset into an activation tensor whose elements are halves (act16) or floats
 static inline float* eoff(const srt_engine* e, float* base, size_t elems) { return (float*)((char*)base + elems * (e->act16 ? 2 : 4)); }
@@ -166,10 +176,14 @@ struct TimerScope {
 bool stream_capturing(const srt_engine* e);
 bool graph_prepare(srt_engine* e, bool valid, size_t ntiles, int kind, const SrtSwitches& sw, GraphKey* k);
 int forward_range(srt_engine* e, const SrtSwitches& sw, const float* d_mag, int ntiles, float* d_masks, int s0, int ns, bool masks16_req = false);
+SepOpts engine_opts(const srt_engine* e);
+void graph_key_opts(GraphKey* k, const SepOpts& o);
 // srt_separate.hip
 SrtDspTables tables_of(const srt_engine* e);
+int ensure_wiener_ws(srt_engine* e);
 int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks = nullptr, int ntracks = 0);
-bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw);
+bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw, const SepOpts& o);
+int separate_run(srt_engine* e, const SepOpts& o, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out);
 int cli_time_residual(srt_engine* e, const float* d_L, const float* d_R, size_t n, int stems, float* d_out, size_t len, size_t lo = 0, size_t hi = 0);
 int cli_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, int stems, float* d_out, bool residual_now);
 int cli_check(srt_engine* e, int stems);

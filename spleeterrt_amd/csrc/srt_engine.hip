@@ -69,14 +69,14 @@ size_t srtIstftLength(size_t rows) { return rows * SRT_HOP + (SRT_FFT - SRT_HOP)
 
 size_t srtOverlapTiles(size_t rows, int T, int overlap_rows)
 {
-    if (T < 1 || overlap_rows < 0 || overlap_rows > T / 2) { fail(-1, "srtOverlapTiles: need T >= 1 and 0 <= overlap <= T / 2"); return 0; }
+    if (T < 1 || !overlap_ok(overlap_rows, T)) { fail(-1, "srtOverlapTiles: need T >= 1 and 0 <= overlap <= T / 2"); return 0; }
     return overlap_tiles(rows, T, overlap_rows);
 }
 
 int srtSetOverlap(srt_engine* e, int overlap_rows)
 {
     if (!e) return fail(-1, "srtSetOverlap: null engine");
-    if (overlap_rows < 0 || overlap_rows > e->cfg.T / 2) return fail(-1, "srtSetOverlap: the overlap must be 0 (off) .. T / 2 rows");
+    if (!overlap_ok(overlap_rows, e->cfg.T)) return fail(-1, "srtSetOverlap: the overlap must be 0 (off) .. T / 2 rows");
     e->overlap = overlap_rows;
     return 0;
 }
@@ -88,7 +88,7 @@ int srtSetMix(srt_engine* e, int n_out, const float* h_gain)
     if (n_out < 0 || n_out > SRT_MAX_STEMS) return fail(-1, "srtSetMix: n_out must be 0 (off) .. SRT_MAX_STEMS");
     if (n_out && !h_gain) return fail(-1, "srtSetMix: null gain matrix");
     const int S = e->cfg.n_stems;
-    for (int i = 0; i < n_out * (S + 1); ++i) if (!isfinite(h_gain[i])) return fail(-1, "srtSetMix: every gain must be finite");
+    if (!gain_finite(h_gain, n_out * (S + 1))) return fail(-1, "srtSetMix: every gain must be finite");
     if (n_out && e->wiener) return fail(-1, "srtSetMix: the stem remix is not available with the Wiener filter on (the mix of filtered spectra is a follow-up, DESIGN.md 16): srtSetWiener(e, 0) first");
     memset(e->mix, 0, sizeof e->mix);
     for (int m = 0; m < n_out; ++m) for (int s = 0; s <= S; ++s) e->mix[m][s] = h_gain[m * (S + 1) + s];
@@ -102,7 +102,7 @@ int srt_engine_mix(const srt_engine* e) { return e->mix_out; }
 int srtSetMaskExtension(srt_engine* e, int mode)
 {
     if (!e) return fail(-1, "srtSetMaskExtension: null engine");
-    if (mode != SRT_MASK_EXT_CONSTANT && mode != SRT_MASK_EXT_AVERAGE) return fail(-1, "srtSetMaskExtension: the mode must be SRT_MASK_EXT_CONSTANT (0) or SRT_MASK_EXT_AVERAGE (1)");
+    if (!mask_ext_ok(mode)) return fail(-1, "srtSetMaskExtension: the mode must be SRT_MASK_EXT_CONSTANT (0) or SRT_MASK_EXT_AVERAGE (1)");
     if (mode && e->wiener) return fail(-1, "srtSetMaskExtension: not available with the Wiener filter on (its gains above F are a follow-up, DESIGN.md 15): srtSetWiener(e, 0) first");
     DeviceScope ds(e->device);
     if (mode && !e->ext) {                               // the gain table, once: never inside a capture, kept until srtDestroy (a captured graph holds its address)
@@ -113,6 +113,33 @@ int srtSetMaskExtension(srt_engine* e, int mode)
     e->mask_ext = mode;
     return 0;
 }
+
+int srtSetWiener(srt_engine* e, int iterations)
+{
+    if (!e) return fail(-1, "srtSetWiener: null engine");
+    if (iterations < 0 || iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "srtSetWiener: iterations must be 0 (off) or 1..3");
+    if (iterations && e->cfg.ratio_mask) return fail(-1, "srtSetWiener: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)");
+    if (iterations && e->mask_ext) return fail(-1, MASK_EXT_REFUSED, "srtSetWiener");
+    if (iterations && e->mix_out) return fail(-1, MIX_REFUSED, "srtSetWiener");
+    DeviceScope ds(e->device);
+    if (iterations) { const int rc = ensure_wiener_ws(e); if (rc) return rc; }
+    e->wiener = iterations;
+    return 0;
+}
+int srt_engine_wiener(const srt_engine* e) { return e->wiener; }
+
+// The engine's own options as a call's record: with the setters and accessors above, the only reader of these fields.  (The setters keep the filter apart from
+// the extension and the mix, so a record with wiener > 0 has both off.)
+SepOpts engine_opts(const srt_engine* e)
+{
+    SepOpts o;
+    o.overlap = e->overlap; o.mask_ext = e->mask_ext; o.wiener = e->wiener; o.n_out = e->mix_out; o.mix_gen = e->mix_gen;
+    memcpy(o.mix, e->mix, sizeof o.mix);
+    return o;
+}
+
+// the option fields of a graph key (GraphKey, srt_engine.h): a sequence captured under one record is never replayed under another; the generation counts only while the mix is on
+void graph_key_opts(GraphKey* k, const SepOpts& o) { k->wiener = o.wiener; k->overlap = o.overlap; k->mask_ext = o.mask_ext; k->mix_gen = o.n_out ? o.mix_gen : 0; }
 
 static void free_staging(srt_engine* e)
 {

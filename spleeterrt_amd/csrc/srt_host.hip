@@ -117,7 +117,7 @@ int srtSeparateCliHostIo(srt_engine* e, const void* h_in, const void* h_in2, siz
 // and the 3072-sample overlap between consecutive chunks is added on the device (srt_carry_kernel), so every output
 // sample crosses PCIe exactly once.  Geometry as srtSeparateEx (a tile range of a longer stream: rows = whole tiles,
 // frames = rows; the whole stream: rows = srtStftRows(n), frames = srtStftFrames(n)).
-// cli_stems = 0: the n_stems sub-networks on the same input (srtSeparateEx per chunk); 2 / 3: the CLI's flows (cli_issue per chunk)
+// cli_stems = 0: the n_stems sub-networks on the same input (separate_run per chunk, srtSeparateEx's body); 2 / 3: the CLI's flows (cli_issue per chunk)
 // seam (multi-device ranges, srt_multi.hip): h_out points at the range's first sample inside planes of seam.out_stride floats (the whole
 // stream's output length); with seam.h_tail the range's last 3072 samples - the overlap-add contribution that belongs to the NEXT range's
 // first samples - go to h_tail [planes][3072] instead of h_out; seam.head says a previous range will add its tail to this range's first
@@ -137,10 +137,11 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
     const float *h_L = (const float*)h_in, *h_R = (const float*)h_in2;
     float* h_out = (float*)h_out_;
     if (rows < 1 || frames > rows) return fail(-1, "srtSeparateHostStream: need 1 <= frames <= rows");
-    if (e->overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateHostStream");  // the blend would have to cross the chunk seams
-    if (e->wiener) return fail(-1, "srtSeparateHostStream: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)");
+    const SepOpts o = engine_opts(e);                   // once for the call: the refusals, the plane count and every chunk's separate_run
+    if (o.overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateHostStream");   // the blend would have to cross the chunk seams
+    if (o.wiener) return fail(-1, "srtSeparateHostStream: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)");
     DeviceScope ds(e->device);
-    const int S = cli_stems ? cli_stems : e->mix_out ? e->mix_out : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;     // pairs staged, carried, packed and downloaded: the outputs of a remix
+    const int S = cli_stems ? cli_stems : o.n_out ? o.n_out : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;     // pairs staged, carried, packed and downloaded: the outputs of a remix
     const size_t chunk_rows = (size_t)e->cfg.max_tiles * T, tail = SRT_FFT - SRT_HOP;
     const size_t nchunks = (rows + chunk_rows - 1) / chunk_rows, total_len = seam.out_stride ? seam.out_stride : srtIstftLength(rows);
     const size_t in_cap = chunk_rows * SRT_HOP + tail, out_cap = srtIstftLength(chunk_rows);
@@ -187,7 +188,7 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
             if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
         }
         rc = cli_stems ? cli_issue(e, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, crow, cli_stems, h.d_out[b], false)
-                       : srtSeparateEx(e, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, crow, h.d_out[b]);
+                       : separate_run(e, o, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, crow, h.d_out[b]);
         if (rc) break;
         if (srt_launch_carry(h.d_out[b], clen, NP, crow * SRT_HOP, h.d_carry, c == 0, c + 1 == nchunks, e->stream)) { rc = fail(-2, "carry launch failed"); break; }
         // CLI flows: the time-domain subtraction comes after the seam has been added (the planes now hold the stitched signals)

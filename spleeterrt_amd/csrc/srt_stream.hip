@@ -15,6 +15,7 @@
 // and every run is followed, on the network stream, by the extension's table for the K rows it serves.
 #include "srt_internal.h"
 #include "srt_rs.h"
+#include "srt_checks.h"
 #include "../../include/spleeterrt_amd.h"
 #include <math.h>
 #include <stdio.h>
@@ -611,8 +612,6 @@ void Spleeter4StemsProcessSamples(Spleeter4Stems* msr, const float* inLeft, cons
 // One body behind srtLiveCreate, srtLiveCreateRate and srtLiveCreateEx; `who` names the caller in every message.  rate: a rate instance (sample_rate, max_block).
 // o: srtLiveCreateEx's options (never null; all zero for the two older calls).  Every argument is checked before any HIP call.
 namespace {
-bool gain_finite(const float* g, int n) { for (int i = 0; i < n; ++i) if (!isfinite(g[i])) return false; return true; }
-
 int live_create(const srt_config* cfg, int hops_per_run, int lookahead, bool rate, const srt_live_opts& o, const void* const* h_coeff, srt_live** out, const char* who)
 {
     if (!cfg || !h_coeff || !out) return srt_set_error(-1, "%s: null argument", who);
