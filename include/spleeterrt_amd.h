@@ -214,7 +214,7 @@ SRT_API int  srtSeparateBatchOverlap(srt_engine *e, int ntracks, const float *co
  * -1 with srtLastError() text that names srtSeparateBatchMix, and nothing launched or written, for everything srtSeparateBatchOverlap refuses except the engine's
  * mix setting, n_out outside 0..SRT_MAX_STEMS, a null h_gain with n_out > 0, a non-zero gain_stride below n_out * (n_stems + 1), an entry that is not finite
  * (the text names the track), or the Wiener filter on; -5 when a stem's weights are not set.
- * Follow-ups: a per-track n_out, the mix under the Wiener filter (srtSeparateBatchWiener), graph capture of batch calls. */
+ * The mix under the Wiener filter per track: srtSeparateBatchWienerEx.  Follow-ups: a per-track n_out, graph capture of batch calls. */
 SRT_API int  srtSeparateBatchMix(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
                                  const size_t *n, float *const *d_out, int overlap_rows,
                                  int n_out, const float *h_gain, size_t gain_stride);
@@ -315,7 +315,8 @@ SRT_API int  srtIstftWiener(srt_engine *e, const float *d_spec, size_t rows, con
  * overlap_rows outside 0..T/2, an unknown mask_extension, n_out outside 0..n_stems (the filter's spectrum workspace holds n_stems spectra), a null h_gain with
  * n_out > 0, a gain that is not finite, ratio_mask set, more than max_tiles overlapped tiles, n < 4096; -5 when a stem's weights are not set (srtSeparateWiener).
  * srtCopyTensor "wiener_cov" works afterwards as after srtIstftWiener, "mask_ext" after a call with the average extension.
- * Follow-ups: the same options per track in srtSeparateBatchWiener, graph capture, n_out > n_stems, the filter folded into the inverse transform's prologue. */
+ * The same options per track of a packed batch: srtSeparateBatchWienerEx.  Follow-ups: graph capture, n_out > n_stems, the filter folded into the inverse
+ * transform's prologue. */
 typedef struct srt_wiener_opts {
     int iterations;       /* 1..3 */
     int overlap_rows;     /* 0..T/2; masks / magnitudes in srtSetOverlap's layout, srtOverlapTiles(rows, T, O) tiles */
@@ -338,6 +339,39 @@ SRT_API int  srtSeparateWiener(srt_engine *e, const float *d_L, const float *d_R
  * srtCopyTensor(e, "wiener_cov", stem, 4 * k + iteration, h, 5F + 1) then returns track k's tables (as after srtIstftWiener: R, weight sums, a). */
 SRT_API int  srtSeparateBatchWiener(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
                                     const size_t *n, float *const *d_out, int iterations);
+/* srtSeparateBatchWiener with srtSeparateWiener's options per call: the filter over a packed batch with overlapped tiles inside every track,
+ * the average mask extension and a stem remix per track.  Tracks, track-table upload and slot ring as srtSeparateBatchWiener; packing as srtBatchPlanOverlap(n,
+ * ntracks, T, overlap_rows, ..); d_out[k] is [n_out ? n_out : n_stems][2][srtIstftLength(srtStftRows(n[k]))] and nothing past those planes is written.  Always
+ * eager, refused inside a stream capture; the only host wait is the one for the upload issued four calls earlier.
+ * All five options hold for this call only: the engine's srtSetWiener, srtSetOverlap, srtSetMaskExtension and srtSetMix state is neither read nor changed, and
+ * the call works with any of them on or off (the one batch call that takes the rule for bins >= F from its arguments, not from srtSetMaskExtension).
+ * Output m of track k is what srtSeparateWiener(e, L_k, R_k, n_k, {iterations, overlap_rows, mask_extension, n_out, G_k}, out) writes for that track alone - bit
+ *   for bit with batch_invariant, up to the network's batch-dependent kernel choice otherwise.  Everything the filter derives from "the call" is the track's: the
+ *   statistics window is its own srtStftRows(n[k]) rows, each entering once however many of its tiles hold it; a is its own; its row chunks follow the single
+ *   call's rule; a blend partner is a tile of the same track; the table e_j(r, c) of SRT_MASK_EXT_AVERAGE comes from its own blended masks (no ratio).
+ *   h_gain is host memory and is copied; track k's matrix G_k is [n_out][n_stems + 1] in srtSetMix's layout at h_gain + k * gain_stride (srtSeparateBatchMix's
+ *   rule: gain_stride = 0 - one matrix for every track).  n_out is one number for the call, 1..n_stems (the filter's spectrum workspace holds n_stems spectra).
+ * With overlap_rows = 0, SRT_MASK_EXT_CONSTANT and n_out = 0 the call issues exactly the launches of srtSeparateBatchWiener(.., iterations): the same kernels,
+ * the same bits.  Otherwise: one batched STFT, one srtForward over the overlapped packed tiles (fp32 masks in the fp16 mode too), iterations x (statistics +
+ * finalize), the gain table with SRT_MASK_EXT_AVERAGE, one filter launch that writes final spectra, one batched inverse of n_out (or n_stems) spectra per track.
+ * -1 with srtLastError() text that names srtSeparateBatchWienerEx, before any device work and with nothing written: a null engine, opts or array or a null entry,
+ * everything srtSeparateBatch refuses of its track arrays, iterations outside 1..3, overlap_rows outside 0..T/2, an unknown mask_extension, n_out outside
+ * 0..n_stems, a null h_gain with n_out > 0, a non-zero gain_stride below n_out * (n_stems + 1), a gain that is not finite (the text names the track), ratio_mask
+ * set, more than max_tiles overlapped packed tiles (srtBatchPlanOverlap counts them), more than 65535 blocks of 16 packed rows, a call inside a stream capture;
+ * -5 when a stem's weights are not set.
+ * srtCopyTensor(e, "wiener_cov", stem, 4 * k + iteration, ..) works as after srtSeparateBatchWiener; after a call with the average extension
+ * srtCopyTensor(e, "mask_ext", ..) holds track k's rows from packed row tile0[k] * T, as after srtSeparateBatchOverlap.
+ * Follow-ups: a per-track overlap, iteration count or n_out, n_out > n_stems, graph capture of batch calls. */
+typedef struct srt_batch_wiener_opts {
+    int iterations;        /* 1..3 */
+    int overlap_rows;      /* 0..T/2, one value for the call (the packing depends on it: srtBatchPlanOverlap) */
+    int mask_extension;    /* SRT_MASK_EXT_CONSTANT | SRT_MASK_EXT_AVERAGE */
+    int n_out;             /* 0: every stem; 1..n_stems: outputs of the mix, one number for the call */
+    const float *h_gain;   /* track k's [n_out][n_stems + 1] at h_gain + k * gain_stride, host memory, copied (srtSeparateBatchMix's rule) */
+    size_t gain_stride;    /* 0: one matrix for every track; else >= n_out * (n_stems + 1) */
+} srt_batch_wiener_opts;
+SRT_API int  srtSeparateBatchWienerEx(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
+                                      const size_t *n, float *const *d_out, const srt_batch_wiener_opts *opts);
 
 /* ---- one node, several devices: the reference CLI's tile-range fan-out (Executable/main.c:544-673, `processMT`: spawnNthreads workers, each with
  * its own network instance and a contiguous tile range, one shared read-only weight blob) with a GPU where the reference has a CPU thread.

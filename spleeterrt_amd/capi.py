@@ -34,6 +34,12 @@ class _WienerOpts(C.Structure):
     _fields_ = [("iterations", C.c_int), ("overlap_rows", C.c_int), ("mask_extension", C.c_int), ("n_out", C.c_int), ("h_gain", C.POINTER(C.c_float))]
 
 
+class _BatchWienerOpts(C.Structure):
+    """srt_batch_wiener_opts (include/spleeterrt_amd.h): the per-call options of srtSeparateBatchWienerEx"""
+    _fields_ = [("iterations", C.c_int), ("overlap_rows", C.c_int), ("mask_extension", C.c_int), ("n_out", C.c_int), ("h_gain", C.POINTER(C.c_float)),
+                ("gain_stride", C.c_size_t)]
+
+
 class Span(C.Structure):
     """srt_span (include/spleeterrt_amd.h): one rank's share of a stream, as srtRankSpan fills it."""
     _fields_ = [(k, C.c_size_t) for k in ("tile0", "tile1", "sample0", "nsamples", "frames", "rows", "out_offset")]
@@ -97,6 +103,7 @@ def load_library():
     L.srtSeparateBatchWiener.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
     L.srtBatchPlanOverlap.argtypes = [C.POINTER(C.c_size_t), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.srtSeparateBatchOverlap.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int]
+    L.srtSeparateBatchWienerEx.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.POINTER(_BatchWienerOpts)]
     L.srtSeparateBatchMix.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(vp), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_size_t]
     L.srtSetGraphMode.argtypes = [vp, C.c_int]
     L.srtPrepareForward.argtypes = [vp, f32p, C.c_int, f32p]
@@ -473,6 +480,60 @@ class Engine:
                 self.set_wiener(own)
             if own_ov and not overlap:
                 self.set_overlap(own_ov)
+        return outs
+
+    def separate_batch_wiener(self, tracks, outs=None, iterations=1, overlap=0, mask_extension="constant", mix=None):
+        """many independent tracks through the Wiener filter with this call's own options (one srtSeparateBatchWienerEx per call):
+        [(L, R)] CUDA float32 tensors -> [stems [S,2,rows_k*1024+3072]] (with a mix: [n_out,2,..]), each equal to separate_wiener(L, R, iterations, overlap,
+        mask_extension, its matrix) of that track.  The list is cut in order by stream.pack_tracks(ns, T, max_tiles, overlap).  mix: one [n_out, S + 1]
+        matrix for all tracks, or one such matrix per track with the same n_out <= S; each call gets its own tracks' matrices.  The engine's set_wiener /
+        set_overlap / set_mask_extension / set_mix are neither read nor changed.  Argument errors raise EngineError before any library call."""
+        from . import stream
+        import numpy as np
+        who = "separate_batch_wiener"
+        m = {"constant": MASK_EXT_CONSTANT, "average": MASK_EXT_AVERAGE}.get(mask_extension, mask_extension) if isinstance(mask_extension, (str, int)) else None
+        if isinstance(m, bool) or m not in (MASK_EXT_CONSTANT, MASK_EXT_AVERAGE):
+            raise EngineError("%s: mask_extension must be \"constant\" or \"average\", not %r" % (who, mask_extension))
+        try:
+            it, ov = int(iterations), int(overlap)
+        except (TypeError, ValueError):
+            raise EngineError("%s: iterations and overlap must be integers, not %r and %r" % (who, iterations, overlap))
+        if not 1 <= it <= 3:
+            raise EngineError("%s: iterations must be 1..3, not %d" % (who, it))
+        if not 0 <= ov <= self.T // 2:
+            raise EngineError("%s: overlap must be 0 .. T / 2 = %d rows, not %d" % (who, self.T // 2, ov))
+        G, n_out = None, 0
+        if mix is not None:
+            shape = "%s: mix must be [n_out, n_stems + 1] or one such matrix per track with the same n_out (1 <= n_out <= %d)" % (who, self.S)
+            try:
+                G = np.ascontiguousarray(mix, dtype=np.float32)
+            except (TypeError, ValueError):                              # matrices of different shapes (two n_out), or no numbers at all
+                raise EngineError(shape)
+            if G.ndim == 2:
+                G = np.ascontiguousarray(np.broadcast_to(G, (len(tracks),) + G.shape))
+            if G.ndim != 3 or G.shape[0] != len(tracks) or G.shape[2] != self.S + 1 or not 1 <= G.shape[1] <= self.S:
+                raise EngineError(shape)
+            if not np.isfinite(G).all():
+                raise EngineError("%s: every gain of mix must be finite" % who)
+            n_out = G.shape[1]
+        t = self.torch
+        n_planes = n_out if n_out else self.S
+        ns = [L.numel() for L, _ in tracks]
+        for L, R in tracks:
+            assert L.is_cuda and R.is_cuda and L.dtype == t.float32 and R.dtype == t.float32 and R.numel() == L.numel()
+        if outs is None:
+            outs = [t.empty((n_planes, 2, self.L.srtIstftLength(self.L.srtStftRows(n))), device=self.device, dtype=t.float32) for n in ns]
+        assert len(outs) == len(tracks)
+        for o, n in zip(outs, ns):
+            assert o.is_cuda and o.is_contiguous() and o.numel() >= n_planes * 2 * self.L.srtIstftLength(self.L.srtStftRows(n))
+        src = [(L.contiguous(), R.contiguous()) for L, R in tracks]      # (kept alive until the calls are issued; the stream orders any reuse)
+        for g in stream.pack_tracks(ns, self.T, self.max_tiles, ov):
+            k = len(g.tracks)
+            P = C.c_void_p * k
+            Gk = None if G is None else np.ascontiguousarray(G[list(g.tracks)])
+            opts = _BatchWienerOpts(it, ov, m, n_out, None if Gk is None else Gk.ctypes.data_as(C.POINTER(C.c_float)), n_out * (self.S + 1))
+            self._chk(self.L.srtSeparateBatchWienerEx(self.h, k, P(*[src[i][0].data_ptr() for i in g.tracks]), P(*[src[i][1].data_ptr() for i in g.tracks]),
+                                                      (C.c_size_t * k)(*[ns[i] for i in g.tracks]), P(*[outs[i].data_ptr() for i in g.tracks]), C.byref(opts)))
         return outs
 
     def separate_cli(self, L, R, stems):

@@ -1,4 +1,4 @@
-// srt_batch.hip — the packed-batch entry points of the engine: the batch plans, the track tables, srtSeparateBatch / Overlap / Wiener (its private declarations: srt_engine.h).
+// srt_batch.hip — the packed-batch entry points of the engine: the batch plans, the track tables, srtSeparateBatch / Overlap / Mix / Wiener / WienerEx (its private declarations: srt_engine.h).
 #include "srt_engine.h"
 
 // ---- packed batch of independent tracks (srt_dsp.hip: srt_stft_batch_kernel / srt_istft_batch_kernel)
@@ -114,6 +114,7 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
     if (rc) return rc;
     if (wiener && (rc = ensure_batch_wiener(e))) return rc;
     if (n_out && (rc = ensure_batch_mix(e))) return rc;
+    if (wiener && o.mask_ext == SRT_MASK_EXT_AVERAGE && (rc = ensure_mask_ext_table(e, who))) return rc;      // (without the filter the table is srtSetMaskExtension's)
     // the table goes up in stream order from a pinned slot; the slot's previous copy (SRT_BATCH_SLOTS calls ago) must have left it first
     const int slot = e->bslot;
     if (e->bused[slot]) HIPCHK(hipEventSynchronize(e->bev[slot]));
@@ -157,10 +158,10 @@ static int batch_forward(srt_engine* e, const char* who, int ntracks, const floa
     return forward_range(e, sw, e->mag, (int)total, e->masks, 0, S, masks16_wanted(e, sw, o));
 }
 
-// Every batch entry point behind its checks: the shared front, then ONE batched inverse - of the masked spectrum (the gain table of o.mask_ext first: every batch
-// call runs under the engine's srtSetMaskExtension; o.n_out > 0: n_out pairs per track, each the chain of the track's own matrix row in the device gain table), or
+// Every batch entry point behind its checks: the shared front, then ONE batched inverse - of the masked spectrum (the gain table of o.mask_ext first: the engine's
+// srtSetMaskExtension, except in srtSeparateBatchWienerEx, which takes the rule from its arguments; o.n_out > 0: n_out pairs per track, each the chain of the track's own matrix row in the device gain table), or
 // with o.wiener of the per-stem spectra the filter wrote: o.wiener x (statistics + finalize) and the filter over the packed rows with every track's own window, a
-// and tables (srt_wiener.hip)
+// and tables (srt_wiener.hip); with o.overlap, the average extension or o.n_out under the filter the option kernels run and the spectra are final
 static int batch_separate(srt_engine* e, const char* who, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out,
                           const SepOpts& o, const float* h_gain, size_t gain_stride)
 {
@@ -182,11 +183,29 @@ static int batch_separate(srt_engine* e, const char* who, int ntracks, const flo
         w.slab = e->bwslab; w.slab_max = e->bwslab + batch_wiener_chunk_cap(e) * S * 4 * F;
         w.rtab = e->bwtabf; w.wsum = e->bwtabf + cap * tf * 4; w.scal = w.wsum + cap * tf;
         w.out = e->wspec; w.out_stem = 2 * bc.ch_stride;
+        // plain: srtSeparateBatchWiener's four launches as always.  With an option (srtSeparateBatchWienerEx) the statistics run on blended masks
+        // when O > 0, and the filter writes FINAL spectra of the n_out mixes or of every stem, which the batched inverse transforms without a gain
+        const bool average = o.mask_ext == SRT_MASK_EXT_AVERAGE, plain = !O && !average && !o.n_out;
         for (int pass = 1; pass <= o.wiener; ++pass) {
-            { TimerScope ts(e, "wiener_stats_batch"); if (srt_launch_wiener_stats_batch(w, e->btab, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener statistics launch failed"); }
+            { TimerScope ts(e, "wiener_stats_batch"); if (O ? srt_launch_wiener_stats_batch_ov(w, e->btab, e->bwtab, ntracks, O, pass, e->stream) : srt_launch_wiener_stats_batch(w, e->btab, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener statistics launch failed"); }
             { TimerScope ts(e, "wiener_cov_batch"); if (srt_launch_wiener_finalize_batch(w, e->bwtab, ntracks, pass, e->stream)) return fail(-2, "batched Wiener finalize launch failed"); }
         }
-        { TimerScope ts(e, "wiener_filter_batch"); if (srt_launch_wiener_filter_batch(w, e->btab, e->bwtab, ntracks, o.wiener, e->stream)) return fail(-2, "batched Wiener filter launch failed"); }
+        if (plain) {
+            TimerScope ts(e, "wiener_filter_batch");
+            if (srt_launch_wiener_filter_batch(w, e->btab, e->bwtab, ntracks, o.wiener, e->stream)) return fail(-2, "batched Wiener filter launch failed");
+        } else {
+            SrtBatchWienerOpt b; memset(&b, 0, sizeof b);
+            b.overlap = O; b.n_out = o.n_out; b.gains = o.n_out ? e->bgtab : nullptr;
+            memcpy(b.oob, e->cfg.oob_weight, sizeof b.oob);
+            if (average) {      // e_j(r, c) over the packed rows from the tracks' own (blended) masks, ratio = 0: the table wiener_issue takes, per track
+                if ((rc = mask_ext_issue(e, e->masks, 0, S, q.ntiles, q.frames, 0, O, O ? e->btab : nullptr, ntracks))) return rc;
+                b.ext = e->ext; b.ext_stem = e->rows_cap * 2;
+            }
+            TimerScope ts(e, "wiener_filter_batch");
+            if (srt_launch_wiener_filter_batch_opt(w, b, e->btab, e->bwtab, ntracks, o.wiener, e->stream)) return fail(-2, "batched Wiener filter launch failed");
+            q.nstems = o.n_out ? o.n_out : S;                  // the spectra to invert (bc.g has as many workgroup columns)
+            for (int s = 0; s < SRT_MAX_STEMS; ++s) q.oob[s] = 1.0f;
+        }
         e->last.wiener_last = o.wiener; e->last.wiener_tracks = ntracks;
         q.spec = e->wspec;
         TimerScope ts(e, "istft_batch");
@@ -273,4 +292,30 @@ int srtSeparateBatchWiener(srt_engine* e, int ntracks, const float* const* d_L, 
     if (eng.n_out) return fail(-1, MIX_REFUSED, who);
     SepOpts o; o.wiener = iterations;
     return batch_separate(e, who, ntracks, d_L, d_R, n, d_out, o, nullptr, 0);
+}
+
+// srtSeparateBatchWiener with the options of srtSeparateWiener per call: overlapped tiles inside every track, the rule for bins >= F and a stem
+// remix per track, all from the arguments - the engine's srtSetWiener / srtSetOverlap / srtSetMaskExtension / srtSetMix state is neither read nor changed
+int srtSeparateBatchWienerEx(srt_engine* e, int ntracks, const float* const* d_L, const float* const* d_R, const size_t* n, float* const* d_out, const srt_batch_wiener_opts* opts)
+{
+    static const char* const who = "srtSeparateBatchWienerEx";
+    if (!e) return fail(-1, "srtSeparateBatchWienerEx: null engine");
+    if (!opts) return fail(-1, "srtSeparateBatchWienerEx: null opts");
+    if (const int rc = batch_tracks_check(who, ntracks, d_L, d_R, n, d_out)) return rc;
+    const int S = e->cfg.n_stems, n_out = opts->n_out, gw = n_out * (S + 1);
+    if (opts->iterations < 1 || opts->iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "%s: iterations must be 1..3", who);
+    if (!overlap_ok(opts->overlap_rows, e->cfg.T)) return fail(-1, BATCH_OVERLAP_RANGE, who);
+    if (!mask_ext_ok(opts->mask_extension)) return fail(-1, "%s: mask_extension must be SRT_MASK_EXT_CONSTANT (0) or SRT_MASK_EXT_AVERAGE (1)", who);
+    if (n_out < 0 || n_out > S) return fail(-1, "%s: n_out must be 0 (every stem) .. n_stems (the filter's spectrum workspace holds n_stems spectra)", who);
+    size_t gain_stride = opts->gain_stride;
+    if (!n_out) gain_stride = 0;
+    else {
+        if (!opts->h_gain) return fail(-1, "%s: null gain matrices with n_out > 0", who);
+        if (gain_stride && gain_stride < (size_t)gw) return fail(-1, "%s: gain_stride must be 0 (one matrix for every track) or at least n_out * (n_stems + 1)", who);
+        for (int k = 0; k < (gain_stride ? ntracks : 1); ++k)
+            if (!gain_finite(opts->h_gain + k * gain_stride, gw)) { char what[160]; snprintf(what, sizeof what, "%s: a gain of track %d is not finite", who, k); return fail(-1, "%s", what); }
+    }
+    if (e->cfg.ratio_mask) return fail(-1, "%s: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)", who);
+    SepOpts o; o.wiener = opts->iterations; o.overlap = opts->overlap_rows; o.mask_ext = opts->mask_extension; o.n_out = n_out;
+    return batch_separate(e, who, ntracks, d_L, d_R, n, d_out, o, n_out ? opts->h_gain : nullptr, gain_stride);
 }

@@ -74,7 +74,7 @@ struct DeviceScope {
 };
 
 // The options of ONE separation call.  A public entry point resolves them once - engine_opts(e) where the call runs under the engine's setters, its
-// own arguments where it takes options (srtIstftWienerEx, srtSeparateWiener, srtSeparateBatchOverlap / Mix / Wiener) - refuses what it cannot run, and hands the record
+// own arguments where it takes options (srtIstftWienerEx, srtSeparateWiener, srtSeparateBatchOverlap / Mix / Wiener / WienerEx) - refuses what it cannot run, and hands the record
 // down by reference: nothing below an entry point reads the engine's option fields.  SepOpts{} is every option off (the CLI flows, the filter's mask-free inverses).
 struct SepOpts {
     int overlap = 0;                                   // rows two consecutive tiles of one signal share, 0: back-to-back tiles (the reference's cut)
@@ -181,6 +181,7 @@ void graph_key_opts(GraphKey* k, const SepOpts& o);
 // srt_separate.hip
 SrtDspTables tables_of(const srt_engine* e);
 int ensure_wiener_ws(srt_engine* e);
+int ensure_mask_ext_table(srt_engine* e, const char* who);
 int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks = nullptr, int ntracks = 0);
 bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw, const SepOpts& o);
 int separate_run(srt_engine* e, const SepOpts& o, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out);

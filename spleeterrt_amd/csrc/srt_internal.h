@@ -326,6 +326,19 @@ int srt_batch_wiener_geometry(const SrtBatchTrack* t, SrtBatchWiener* w, int ntr
 int srt_launch_wiener_stats_batch(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int pass, hipStream_t s);
 int srt_launch_wiener_finalize_batch(const SrtWienerParams& p, const SrtBatchWiener* d_wt, int ntracks, int pass, hipStream_t s);
 int srt_launch_wiener_filter_batch(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int iters, hipStream_t s);
+// The per-track filter with per-call options (srtSeparateBatchWienerEx): SrtWienerOpt's fields for a packed batch.  The matrices do not travel
+// by value - every track has its own - so the launch takes the device gain table (srt_launch_istft_batch_mix's d_gains); ext is indexed by packed row.
+struct SrtBatchWienerOpt {
+    int overlap;                                 // rows consecutive tiles of one track share (one value for the call: the packing depends on it), 0: back-to-back
+    const float* ext; size_t ext_stem;           // as SrtWienerOpt, written by srt_launch_mask_ext[_batch] over the packed rows; nullptr: oob
+    float oob[SRT_MAX_STEMS];
+    int n_out;                                   // 0: every stem's spectrum; 1..nstems: the mixes
+    const float* gains;                          // n_out > 0: track k's matrix [n_out][nstems + 1] at gains + k * n_out * (nstems + 1), device memory
+};
+// the statistics pass on blended masks per track (overlap > 0 only; the table's ntiles = srtOverlapTiles(rows, T, overlap)); finalize is srt_launch_wiener_finalize_batch
+int srt_launch_wiener_stats_batch_ov(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int overlap, int pass, hipStream_t s);
+// the filter with any option on: final spectra of q.n_out outputs, or of every stem, over the packed rows; the batched inverse behind it applies no gain
+int srt_launch_wiener_filter_batch_opt(const SrtWienerParams& p, const SrtBatchWienerOpt& q, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int iters, hipStream_t s);
 // batched inverse of per-stem spectra (the filter's output): stem s of every track reads p.spec + s * stem_stride (float2 elements) at its packed rows, no masks
 // (all-ones in band, p.oob[s] above F) - srt_launch_istft's single-stem, mask-free form for every (track, stem) in one launch
 int srt_launch_istft_batch_spec(const SrtIstftParams& p, size_t stem_stride, const SrtBatchTrack* d_tracks, int ntracks, const SrtBatchGrid& g, hipStream_t s);

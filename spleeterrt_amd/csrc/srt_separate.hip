@@ -180,16 +180,22 @@ static int wiener_opts_check(const srt_engine* e, const char* who, const srt_wie
 }
 
 // the workspaces of an option call: the filter's, and with the average extension the engine's gain table (srtSetMaskExtension's, same size, kept until srtDestroy)
+// (the gain table's piece on its own: srtSeparateBatchWienerEx has workspaces of its own but shares the table)
+// Calls on one engine are single-threaded by contract (the first test of e->ext is outside the lock, as everywhere); the table is tested again under the lock so that
+// a caller who breaks that rule cannot allocate it twice.  From batch_forward the capture branch is never taken: a batch call has refused a capture before it gets here.
+int ensure_mask_ext_table(srt_engine* e, const char* who)
+{
+    if (e->ext) return 0;
+    if (stream_capturing(e)) return fail(-1, "%s: the mask extension's gain table is not allocated yet (srtSetMaskExtension, or one call outside the capture)", who);
+    SrtSetupLock setup;
+    if (!e->ext) HIPCHK(hipMalloc((void**)&e->ext, (size_t)e->cfg.n_stems * e->rows_cap * 2 * sizeof(float)));
+    return 0;
+}
 static int ensure_wiener_opts_ws(srt_engine* e, const char* who, const SepOpts& c)
 {
     const int rc = ensure_wiener_ws(e);
     if (rc) return rc;
-    if (c.mask_ext && !e->ext) {
-        if (stream_capturing(e)) return fail(-1, "%s: the mask extension's gain table is not allocated yet (srtSetMaskExtension, or one call outside the capture)", who);
-        SrtSetupLock setup;
-        HIPCHK(hipMalloc((void**)&e->ext, (size_t)e->cfg.n_stems * e->rows_cap * 2 * sizeof(float)));
-    }
-    return 0;
+    return c.mask_ext ? ensure_mask_ext_table(e, who) : 0;
 }
 
 int srtIstftWienerEx(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, const srt_wiener_opts* opts, float* d_out)

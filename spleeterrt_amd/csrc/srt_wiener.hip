@@ -20,6 +20,7 @@
 // The 2 x 2 inverse is the closed form with det C = c00 c11 - |c01|^2 (real); C >= sqrt(eps) al^2 I keeps it away from zero, as in norbert.
 // With per-call options (overlapped tiles, the average mask extension, the stem remix: srtIstftWienerEx / srtSeparateWiener) srt_wiener_stats_ov_kernel and
 // srt_wiener_filter_opt_kernel at the end of this file take the places of the first and the third; with every option off the three above run as always.
+// Both families exist per track of a packed batch as well (srtSeparateBatchWiener: the plain three; srtSeparateBatchWienerEx: the option pair, at the very end).
 #include "srt_internal.h"
 #include "srt_overlap.h"
 #include <math.h>
@@ -630,5 +631,197 @@ int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q
     const dim3 grid(SRT_WIENER_BINBLK, (p.rows + W_FILTER_ROWS - 1) / W_FILTER_ROWS), block(256);
     if (q.overlap > 0) SRT_LAUNCH(srt_wiener_filter_opt_kernel<true>, grid, block, 0, s, p, q, iters);
     else SRT_LAUNCH(srt_wiener_filter_opt_kernel<false>, grid, block, 0, s, p, q, iters);
+    return srt_launch_status();
+}
+
+// ------------------------------------------------------------------------------------------- per-call options per track of a packed batch (srtSeparateBatchWienerEx)
+// The two option kernels above with "the call" replaced by "the track", as the batch kernels replace it in the plain ones: the in-track row walks the track's own
+// rows, srt_ov_row is clamped by the track's own tile count (a blend partner is a tile of the same track), the mask base is the track's first packed tile and
+// the stem stride the packed tile count.  Statistics, tables and a are indexed as in srt_wiener_stats_batch_kernel; finalize is srt_wiener_finalize_batch_kernel.
+
+// w_masks_ov with the stem stride and the clamp apart (there both come from p.ntiles): `masks` is the first tile of the view, `ntiles` the view's tile count;
+// the same statements in the same order
+__device__ __forceinline__ void w_masks_ov_view(float (&ml)[SRT_MAX_STEMS], float (&mr)[SRT_MAX_STEMS], const float* __restrict__ masks, int T, int F, size_t sstride,
+                                                int ntiles, int O, int t, int k, int S)
+{
+    const size_t tf = (size_t)T * F;
+    const OvRow ov = srt_ov_row(t, T, O, ntiles);
+    const float* b = masks + (size_t)ov.j1 * 2 * tf + (size_t)ov.k * F + k;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+        ml[j] = 0.0f; mr[j] = 0.0f;
+        if (j < S) { ml[j] = b[j * sstride]; mr[j] = b[j * sstride + tf]; }
+    }
+    if (ov.two) {
+        const float* a = b - 2 * tf + (size_t)(T - O) * F;
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S) { ml[j] = srt_blend(a[j * sstride], ml[j], ov.w); mr[j] = srt_blend(a[j * sstride + tf], mr[j], ov.w); }
+    }
+}
+
+// srt_wiener_stats_batch_kernel with the mask fetch replaced by the overlapped fetch on the track's view (launched only with an overlap); the chain and the
+// accumulation are srt_wiener_stats_ov_kernel's
+__global__ void __launch_bounds__(256) srt_wiener_stats_batch_ov_kernel(const SrtWienerParams p, const SrtBatchTrack* __restrict__ tracks,
+                                                                        const SrtBatchWiener* __restrict__ wt, int ntracks, int O, int pass)
+{
+    __shared__ float red[4];
+    const int k = blockIdx.x * 256 + threadIdx.x, c = blockIdx.y, S = p.nstems;
+    const int trk = w_chunk_track(wt, ntracks, c);
+    const SrtBatchWiener g = wt[trk];
+    const int rows = tracks[trk].rows, tile0 = tracks[trk].tile0, tiles = tracks[trk].ntiles;
+    const int r0 = (c - g.chunk0) * g.rpc, r1 = min(r0 + g.rpc, rows);           // rows of the TRACK
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const float* scal = p.scal + g.tab;
+    const float4* rtab = reinterpret_cast<const float4*>(p.rtab) + (size_t)g.tab * SRT_WIENER_MAX_ITERS * S * p.F;
+    const float al = (pass > 1 ? scal[0] : 1.0f) * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F, anyb = k < SRT_HALF;
+    const float2* sLp = p.spec + (size_t)tile0 * p.T * SRT_SPEC_LD + (anyb ? k : 0);       // the track's first packed row
+    const float2* sRp = sLp + p.spec_ch_stride;
+    const float* masks = p.masks + (size_t)tile0 * 2 * tf;                                 // ... and first packed tile
+    float acc[SRT_MAX_STEMS][4];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
+    float mx = 0.0f;
+    if (anyb) {
+        for (int t = r0; t < r1; ++t) {
+            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD];
+            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y)));
+            if (!inb) continue;
+            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS];
+            w_masks_ov_view(ml, mr, masks, p.T, p.F, sstride, tiles, O, t, k, S);
+            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+            w_start_v(yl, yr, sL, sR, ml, mr, S);
+            for (int i = 0; i < pass - 1; ++i)
+                w_iter<true>(yl, yr, sL, sR, rtab + (size_t)i * S * p.F + k, p.F, delta, S);
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y;
+                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y;
+                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      // y_L conj(y_R)
+                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y;
+            }
+        }
+    }
+    if (inb) {
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k] = acc[j][q];
+    }
+    if (pass == 1) {                                             // (block-uniform branch: every thread reaches the barriers)
+        mx = w_block_max(mx, red);
+        if (threadIdx.x == 0) p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] = mx;
+    }
+}
+
+// w_mix_inband / w_mix_gain on a matrix ROW in device memory (the track's, from the batch gain table: g[j] the gain of stem j, g[S] of the input) instead of the
+// launch arguments: the same statements in the same order.  The row's address is workgroup-uniform, so its entries are scalar loads.
+#pragma clang fp contract(off)
+__device__ __forceinline__ float2 w_mix_inband(const float* __restrict__ row, int S, float2 s, const float2 (&y)[SRT_MAX_STEMS])
+{
+    const float g = row[S];
+    float hx = g * s.x, hy = g * s.y;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j)
+        if (j < S) { const float gj = row[j]; hx = fmaf(gj, y[j].x, hx); hy = fmaf(gj, y[j].y, hy); }
+    return make_float2(hx, hy);
+}
+__device__ __forceinline__ float w_mix_gain(const float* __restrict__ row, int S, const float (&g)[SRT_MAX_STEMS])
+{
+    float h = row[S];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j)
+        if (j < S) h = fmaf(row[j], g[j], h);
+    return h;
+}
+#pragma clang fp contract(fast)
+
+// srt_wiener_filter_opt_kernel per track of a packed batch: blocks of W_FILTER_ROWS packed rows as in srt_wiener_filter_batch_kernel (a block lies in one tile,
+// hence in one track - rows_k <= ntiles_k * T holds with an overlap too; rows at or past the track's own are skipped), the FINAL spectrum of every bin of the
+// q.n_out mixes or of every stem as in the single-signal kernel.  The extension table is indexed by packed row; the remix reads the track's own matrix
+// q.gains + trk * n_out * (S + 1).  The remix stays a run-time branch inside one compiled copy per OV (see srt_wiener_filter_opt_kernel).
+template <bool OV>
+__global__ void __launch_bounds__(256) srt_wiener_filter_batch_opt_kernel(const SrtWienerParams p, const SrtBatchWienerOpt q, const SrtBatchTrack* __restrict__ tracks,
+                                                                          const SrtBatchWiener* __restrict__ wt, int ntracks, int iters)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x, S = p.nstems;
+    if (k >= SRT_HALF) return;
+    const int r0 = blockIdx.y * W_FILTER_ROWS;                                   // packed rows
+    const int trk = w_tile_track(tracks, ntracks, r0 / p.T);
+    const int tab = wt[trk].tab;
+    const int row0 = tracks[trk].tile0 * p.T;                                    // the track's first packed row
+    const int r1 = min(r0 + W_FILTER_ROWS, row0 + tracks[trk].rows);
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf, och = p.out_stem / 2;
+    const float4* rtab = reinterpret_cast<const float4*>(p.rtab) + (size_t)tab * SRT_WIENER_MAX_ITERS * S * p.F;
+    const float al = p.scal[tab] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const float* gains = q.gains + (size_t)trk * q.n_out * (S + 1);             // (not dereferenced with n_out = 0)
+    const bool inb = k < p.F;
+    for (int t = r0; t < r1; ++t) {
+        const size_t o = (size_t)t * SRT_SPEC_LD + k;
+        const float2 sL = p.spec[o], sR = p.spec[p.spec_ch_stride + o];
+        if (!inb) {
+            float gl[SRT_MAX_STEMS], gr[SRT_MAX_STEMS];
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
+                gl[j] = 0.0f; gr[j] = 0.0f;
+                if (j < S) {
+                    if (q.ext) { const float* e = q.ext + (size_t)j * q.ext_stem + (size_t)t * 2; gl[j] = e[0]; gr[j] = e[1]; }
+                    else { gl[j] = q.oob[j]; gr[j] = gl[j]; }
+                }
+            }
+            if (q.n_out) {
+                for (int m = 0; m < q.n_out; ++m) {
+                    p.out[m * p.out_stem + o] = w_scale(w_mix_gain(gains + m * (S + 1), S, gl), sL);
+                    p.out[m * p.out_stem + och + o] = w_scale(w_mix_gain(gains + m * (S + 1), S, gr), sR);
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < SRT_MAX_STEMS; ++j)
+                    if (j < S) { p.out[j * p.out_stem + o] = w_scale(gl[j], sL); p.out[j * p.out_stem + och + o] = w_scale(gr[j], sR); }
+            }
+            continue;
+        }
+        float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+        if constexpr (OV) {
+            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS];
+            w_masks_ov_view(ml, mr, p.masks + (size_t)tracks[trk].tile0 * 2 * tf, p.T, p.F, sstride, tracks[trk].ntiles, q.overlap, t - row0, k, S);
+            w_start_v(yl, yr, sL, sR, ml, mr, S);
+        } else {
+            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;      // packed tile = the track's first + the tile within it
+            w_start(yl, yr, sL, sR, m, sstride, tf, S);
+        }
+        for (int i = 0; i < iters; ++i)
+            w_iter<true>(yl, yr, sL, sR, rtab + (size_t)i * S * p.F + k, p.F, delta, S);
+        if (q.n_out) {
+            for (int m = 0; m < q.n_out; ++m) {
+                p.out[m * p.out_stem + o] = w_mix_inband(gains + m * (S + 1), S, sL, yl);
+                p.out[m * p.out_stem + och + o] = w_mix_inband(gains + m * (S + 1), S, sR, yr);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < SRT_MAX_STEMS; ++j)
+                if (j < S) { p.out[j * p.out_stem + o] = yl[j]; p.out[j * p.out_stem + och + o] = yr[j]; }
+        }
+    }
+}
+
+// (the table's ntiles / rows per track come from batch_forward's plan at the same overlap, so srt_ov_row stays inside the track's tiles: w_layout_ok per track)
+int srt_launch_wiener_stats_batch_ov(const SrtWienerParams& p, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int overlap, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || !w_batch_args_ok(p, ntracks) || overlap < 1 || overlap > p.T / 2) return -1;
+    const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
+    SRT_LAUNCH(srt_wiener_stats_batch_ov_kernel, dim3(bx, p.nchunks), dim3(256), 0, s, p, d_tracks, d_wt, ntracks, overlap, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_filter_batch_opt(const SrtWienerParams& p, const SrtBatchWienerOpt& q, const SrtBatchTrack* d_tracks, const SrtBatchWiener* d_wt, int ntracks, int iters, hipStream_t s)
+{
+    if (iters < 1 || iters > SRT_WIENER_MAX_ITERS || !w_batch_args_ok(p, ntracks) || p.rows / W_FILTER_ROWS > 65535 || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD) return -1;
+    if (q.overlap < 0 || q.overlap > p.T / 2 || q.n_out < 0 || q.n_out > p.nstems || (q.n_out && !q.gains) || (q.ext && q.ext_stem < (size_t)p.rows * 2)) return -1;
+    const dim3 grid(SRT_WIENER_BINBLK, p.rows / W_FILTER_ROWS), block(256);
+    if (q.overlap > 0) SRT_LAUNCH(srt_wiener_filter_batch_opt_kernel<true>, grid, block, 0, s, p, q, d_tracks, d_wt, ntracks, iters);
+    else SRT_LAUNCH(srt_wiener_filter_batch_opt_kernel<false>, grid, block, 0, s, p, q, d_tracks, d_wt, ntracks, iters);
     return srt_launch_status();
 }
