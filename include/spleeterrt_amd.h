@@ -273,7 +273,8 @@ SRT_API int  srtSetGraphMode(srt_engine *e, int enable);
  * that the first real call (on a real-time audio thread) is a plain graph launch.  Runs the networks once: d_masks is overwritten.
  * The drop-in layers call it from their Init functions for every buffer pair they will use. */
 SRT_API int  srtPrepareForward(srt_engine *e, const float *d_mag, int ntiles, float *d_masks);
-/* free the grow-only device staging of the host-buffer entry points (srtSeparateHostStream*, srtSeparateCliHost); the next such call re-allocates */
+/* free the grow-only device staging of the host-buffer entry points (srtSeparateHostStream*, srtSeparateCliHost, srtSeparateHostWiener and its store); the
+ * next such call re-allocates */
 SRT_API int  srtReleaseStaging(srt_engine *e);
 
 /* ---- multichannel Wiener filter: official Spleeter's `separate --mwf` post-processing, norbert.wiener(v, x, n) with its defaults (soft-mask start,
@@ -284,8 +285,8 @@ SRT_API int  srtReleaseStaging(srt_engine *e);
  * srtSetWiener: 0 = off (the default; nothing changes), 1..3 = iterations (Spleeter's default is 1).  Allocates its workspace for max_tiles tiles now
  * (call it before capturing).  -1 with ratio_mask set or iterations outside 0..3.  While it is on, srtSeparate / srtSeparateEx apply it (srtSeparateEx:
  * the statistics window is the call's own `rows`, so a tile range of a longer stream is filtered with its own covariance), in the fp16 mode too (the
- * masks then stay fp32).  Refused with -1 because the statistics span the whole signal: srtSeparateHostStream* (chunks), srtSeparateCli* (no stem
- * axis either) and srtMultiSeparate* (ranges per device).  In graph mode the iteration count is part of the captured call's key. */
+ * masks then stay fp32).  Refused with -1 because the statistics span the whole signal: srtSeparateHostStream* (chunks; srtSeparateHostWiener is the filter
+ * over a host stream of any length), srtSeparateCli* (no stem axis either) and srtMultiSeparate* (ranges per device).  In graph mode the iteration count is part of the captured call's key. */
 SRT_API int  srtSetWiener(srt_engine *e, int iterations);
 /* the filter + inverse transform for a caller-given spectrum [2][rows][2052] (srtStft layout) and fp32 masks [n_stems][ntiles][2][T][F] of all stems,
  * `iterations` 1..3 whatever srtSetWiener says; d_out as srtIstft.  srtCopyTensor(e, "wiener_cov", stem, iteration, h, 5F + 1) then returns R_j of
@@ -372,6 +373,33 @@ typedef struct srt_batch_wiener_opts {
 } srt_batch_wiener_opts;
 SRT_API int  srtSeparateBatchWienerEx(srt_engine *e, int ntracks, const float *const *d_L, const float *const *d_R,
                                       const size_t *n, float *const *d_out, const srt_batch_wiener_opts *opts);
+/* ---- the filter over a HOST stream of any length: srtSeparateWiener for host-resident PCM that need not fit max_tiles tiles - the albums,
+ * DJ sets and hour-long streams srtSeparateHostStream* exists for, and which it refuses with the filter on.  Geometry: the whole stream (rows = srtStftRows(n),
+ * frames = srtStftFrames(n)).  h_in, h_in2, h_out, flags (SRT_HOST_PINNED | SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16) and h_clipped exactly as in
+ * srtSeparateHostStreamIo; h_out is [n_out ? n_out : n_stems][2][srtIstftLength(rows)] floats, or int16 [..][len][2] with the out flag, and nothing past those
+ * planes is written.  Synchronous, always eager, refused inside a stream capture.  Any n >= 4096 works, one piece (a signal that fits max_tiles) included.
+ * What it equals: srtSeparateWiener(e, L, R, n, opts, out) on an engine large enough to hold the signal.  The R tables, weight sums and a are that call's BIT FOR
+ *   BIT (with batch_invariant; up to the network's batch-dependent kernel choice otherwise): the stream is walked in pieces of max_tiles tiles, and a statistics
+ *   chunk that straddles a piece boundary continues its partial sum from the slab (srt_wiener_stats_seg_kernel), so every sum keeps the whole-signal launch's
+ *   order.  The samples agree up to the association of the overlap-add at the piece seams (the 3072-sample seam is added on the device as in
+ *   srtSeparateHostStream: 2e-6 of the peak); a signal of one piece gives srtSeparateWiener's bits.
+ * How: sweep A uploads each piece and writes its spectrum and fp32 masks (in the fp16 mode too) into a device store that holds them for the whole stream, with
+ *   statistics pass 1; passes 2..iterations walk the store (no network, no PCIe); sweep B filters, inverts and downloads piece by piece.  The store takes
+ *   2 * 2052 * 8 + n_stems * 2 * F * 4 bytes per row, the masks padded to the tile boundary (about 65 KB per row at 4 stems and F = 1024, roughly 10 GB per hour
+ *   of audio); it is grow-only and kept with the host staging, srtReleaseStaging frees it.  srtHostWienerBytes(cfg, n) returns its size - pure host arithmetic, no
+ *   device - so a caller can check first; 0 with srtLastError() text for a null or bad config or n < 4096.  If the store cannot be allocated the call returns -2,
+ *   the text names the bytes asked for, and the engine stays usable.
+ * opts hold for the call only: the engine's srtSetWiener, srtSetOverlap, srtSetMaskExtension and srtSetMix state is neither read nor changed, and the call works
+ *   with any of them on or off.  Honoured: iterations 1..3, mask_extension (both modes), n_out / h_gain (1..n_stems, srtSetMix's layout) - all row-local once the
+ *   tables exist.  Refused: overlap_rows must be 0 (-1, the text says "overlap"): the blend across piece seams is a follow-up.
+ * -1 with srtLastError() text that names srtSeparateHostWiener, before any device work and with nothing written: a null argument, unknown flag bits or
+ * SRT_HOST_IN_PCM16 with h_in2 != NULL, everything srtSeparateWiener refuses of its options except the max_tiles limit, ratio_mask set, n < 4096; -5 when a
+ * stem's weights are not set.  srtCopyTensor "wiener_cov" works afterwards as after srtSeparateWiener.
+ * srtSeparateHostStream*, srtSeparateCli* and srtMultiSeparate* keep refusing the engine's srtSetWiener.  Follow-ups: overlapped tiles across piece seams, the
+ * multi-device host, the CLI flows, n_out > n_stems, graph capture. */
+SRT_API int    srtSeparateHostWiener(srt_engine *e, const void *h_in, const void *h_in2, size_t n,
+                                     const srt_wiener_opts *opts, void *h_out, unsigned flags, unsigned long long *h_clipped);
+SRT_API size_t srtHostWienerBytes(const srt_config *cfg, size_t n);
 
 /* ---- one node, several devices: the reference CLI's tile-range fan-out (Executable/main.c:544-673, `processMT`: spawnNthreads workers, each with
  * its own network instance and a contiguous tile range, one shared read-only weight blob) with a GPU where the reference has a CPU thread.

@@ -81,6 +81,9 @@ def load_library():
     L.srtIstftWiener.argtypes = [vp, f32p, C.c_size_t, f32p, C.c_int, f32p]
     L.srtIstftWienerEx.argtypes = [vp, f32p, C.c_size_t, f32p, C.POINTER(_WienerOpts), f32p]
     L.srtSeparateWiener.argtypes = [vp, f32p, f32p, C.c_size_t, C.POINTER(_WienerOpts), f32p]
+    L.srtSeparateHostWiener.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(_WienerOpts), vp, C.c_uint, vp]
+    L.srtHostWienerBytes.restype = C.c_size_t
+    L.srtHostWienerBytes.argtypes = [C.POINTER(_Config), C.c_size_t]
     L.srtSeparateCli.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.srtSeparateCliHost.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.srtSeparateHostStream.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp]
@@ -186,6 +189,7 @@ class Engine:
         h = C.c_void_p()
         self._chk(self.L.srtCreate(C.byref(cfg), C.c_void_p(self.stream.cuda_stream), C.byref(h)))
         self.h = h
+        self._cfg = cfg
         self.wiener = 0
         self.overlap = 0
         if wiener:
@@ -643,6 +647,30 @@ class Engine:
         self._chk(self.L.srtSeparateHostStreamIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, frames, rows, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
 
+    def separate_host_wiener(self, pcm_or_LR, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False, overlap=0):
+        """separate_wiener for host PCM of any length (srtSeparateHostWiener): the stream is walked in pieces of max_tiles tiles, its spectrum and
+        masks are kept in a device store of host_wiener_bytes(n) bytes, and the R tables are those of one separate_wiener call over the whole signal, bit for bit.
+        Buffers as separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32; out_pcm16: int16 [outputs, len, 2] instead of float32 [outputs, 2, len];
+        pinned=True promises page-locked buffers.  iterations / mask_extension / mix: options of this call alone, as separate_wiener's; overlap must be 0 (the
+        blend across piece seams is a follow-up).  -> (out, clipped).  wiener_cov works afterwards; release_staging frees the store."""
+        try:
+            ov = int(overlap)
+        except (TypeError, ValueError):
+            raise EngineError("separate_host_wiener: overlap must be 0, not %r" % (overlap,))
+        if ov != 0:
+            raise EngineError("separate_host_wiener: overlap must be 0, not %d (overlapped tiles across piece seams are a follow-up)" % ov)
+        opts = Engine._wiener_opts(self, "separate_host_wiener", iterations, 0, mask_extension, mix)
+        if opts is None:
+            opts = (_WienerOpts(int(iterations), 0, MASK_EXT_CONSTANT, 0, None), None, self.S)
+        o, _keep_g, planes = opts
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, planes, None, out, pinned)
+        self._chk(self.L.srtSeparateHostWiener(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, C.byref(o), C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
+        return out, clipped
+
+    def host_wiener_bytes(self, n):
+        """bytes of the device store separate_host_wiener keeps for a stream of n samples on this engine (srtHostWienerBytes)"""
+        return host_wiener_bytes(n, self.F, self.T, self.S, self.max_tiles)
+
     def separate_cli_host_io(self, pcm_or_LR, stems, out_pcm16=False, out=None, pinned=False, keep_staging=False):
         """separate_cli_host with 16-bit PCM on either side (srtSeparateCliHostIo) -> (out, clipped) as separate_host_stream_io, `stems` outputs."""
         keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, stems, None, out, pinned)
@@ -706,6 +734,18 @@ class Engine:
         n = self._chk(self.L.srtGetTimingKernels(self.h, buf, len(buf)))
         ks = buf.value.decode().split(";")[:n]
         return [(name, k) for (name, _), k in zip(tim, ks)]
+
+
+def host_wiener_bytes(n, F, T, n_stems, max_tiles):
+    """srtHostWienerBytes: bytes of the device store srtSeparateHostWiener keeps for a stream of n samples - per spectrum row 2 * 2052 * 8 (the complex spectrum)
+    + n_stems * 2 * F * 4 (the fp32 masks, padded to the tile boundary).  Pure host arithmetic: works without a device.  Raises for a bad geometry or n < 4096."""
+    L = load_library()
+    cfg = _Config()
+    cfg.F, cfg.T, cfg.n_stems, cfg.max_tiles = int(F), int(T), int(n_stems), int(max_tiles)
+    b = L.srtHostWienerBytes(C.byref(cfg), int(n))
+    if not b:
+        raise EngineError("libspleeterrt_amd: %s" % L.srtLastError().decode())
+    return int(b)
 
 
 def live_latency(hops_per_run, lookahead):

@@ -36,6 +36,8 @@ struct HostStaging {
     int16_t* d_in16[2]; int16_t* d_out16[2];
     size_t in16_cap, out16_cap;                        // stereo frames (4 bytes)
     unsigned long long* d_clip;                        // [SRT_MAX_STEMS] clipped-sample counters, then the pack's workgroup counts
+    // srtSeparateHostWiener's store: every piece's spectrum and fp32 masks (host_wiener_layout, srt_host.hip), grow-only like the rest
+    char* d_wstore; size_t wstore_cap;                 // bytes
 };
 
 // What the last forward left behind, for the calls that come after it (srtCopyTensor's taps, the inverse transform of srtSeparate).  forward_range and
@@ -188,6 +190,16 @@ int separate_run(srt_engine* e, const SepOpts& o, const float* d_L, const float*
 int cli_time_residual(srt_engine* e, const float* d_L, const float* d_R, size_t n, int stems, float* d_out, size_t len, size_t lo = 0, size_t hi = 0);
 int cli_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, int stems, float* d_out, bool residual_now);
 int cli_check(srt_engine* e, int stems);
+// ... srtSeparateHostWiener's stages (srt_host.hip drives them): a piece is rows [row0, row0 + rows) of the signal, spectrum [2][rows][SRT_SPEC_LD] and fp32 masks
+// [n_stems][ntiles][2][T][F] in the device store
+struct HostWienerPiece { float2* spec; float* masks; size_t row0, rows; int ntiles; };
+int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n, SepOpts* o);
+int host_wiener_ws(srt_engine* e, const SepOpts& o);
+int host_wiener_analyse(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, const HostWienerPiece& pc);
+SrtWienerParams wiener_geometry(const srt_engine* e, size_t rows);
+int host_wiener_stats(srt_engine* e, const SrtWienerParams& w, const HostWienerPiece& pc, int pass);
+int host_wiener_finalize(srt_engine* e, const SrtWienerParams& w, int pass);
+int host_wiener_render(srt_engine* e, const SrtWienerParams& w, const SepOpts& o, const HostWienerPiece& pc, float* d_out);
 
 // Run `issue` (a function that only enqueues work on e->stream) through the graph cache when graph mode is on.  `valid` says
 // whether the arguments passed the entry point's checks: an invalid call is issued eagerly (it fails with its own error code and

@@ -1,4 +1,5 @@
-// srt_host.hip — the host-buffer entry points of the engine: the device staging, srtSeparateCliHost and the chunk pipeline of srtSeparateHostStream (its private declarations: srt_engine.h).
+// srt_host.hip — the host-buffer entry points of the engine: the device staging, srtSeparateCliHost, the chunk pipeline of srtSeparateHostStream and the two sweeps of
+// srtSeparateHostWiener (its private declarations: srt_engine.h).
 #include "srt_engine.h"
 
 // Grow-only device staging shared by the host-buffer entry points (kept in the engine, freed by srtDestroy).
@@ -246,4 +247,166 @@ int srtSeparateHostStreamIo(srt_engine* e, const void* h_in, const void* h_in2, 
 int srtSeparateHostStream(srt_engine* e, const float* h_L, const float* h_R, size_t n, size_t frames, size_t rows, float* h_out)
 {
     return srtSeparateHostStreamEx(e, h_L, h_R, n, frames, rows, h_out, 0);
+}
+
+// ------------------------------------------------------------------------------------------- the Wiener filter over a host stream of any length
+// The filter's statistics span the whole signal, so the stream is walked twice.  Sweep A is host_stream's upload pipeline: a piece (max_tiles tiles) goes up, its
+// STFT and fp32 masks are written into a device store that holds them for the WHOLE stream, and pass 1 of the statistics runs over it.  Passes 2.. walk the store
+// alone.  Sweep B filters one piece at a time into the engine's spectrum workspace, inverts it, adds the 3072-sample seam (srt_launch_carry) and sends the piece
+// down on host_stream's download pipeline.  Nothing crosses PCIe twice, and the network runs once.
+
+// the store: piece c at c * piece_bytes - its spectrum [2][crow][SRT_SPEC_LD] float2, then its masks [n_stems][tiles][2][T][F] floats - every piece but the last
+// full (crow = max_tiles * T), the last one with its own row and tile count
+struct HostWienerLayout { size_t piece_rows, npieces, piece_bytes, total; };
+static size_t wstore_spec_bytes(size_t crow) { return 2 * crow * SRT_SPEC_LD * sizeof(float2); }
+static size_t wstore_mask_bytes(const srt_config& cfg, size_t tiles) { return (size_t)cfg.n_stems * tiles * 2 * cfg.T * cfg.F * sizeof(float); }
+static HostWienerLayout host_wiener_layout(const srt_config& cfg, size_t rows)
+{
+    HostWienerLayout l;
+    l.piece_rows = (size_t)cfg.max_tiles * cfg.T;
+    l.npieces = (rows + l.piece_rows - 1) / l.piece_rows;
+    l.piece_bytes = wstore_spec_bytes(l.piece_rows) + wstore_mask_bytes(cfg, (size_t)cfg.max_tiles);
+    const size_t last = rows - (l.npieces - 1) * l.piece_rows;
+    l.total = (l.npieces - 1) * l.piece_bytes + wstore_spec_bytes(last) + wstore_mask_bytes(cfg, (last + cfg.T - 1) / cfg.T);
+    return l;
+}
+static HostWienerPiece host_wiener_piece(const srt_config& cfg, const HostWienerLayout& l, char* store, size_t rows, size_t c)
+{
+    HostWienerPiece pc;
+    pc.row0 = c * l.piece_rows;
+    pc.rows = pc.row0 + l.piece_rows < rows ? l.piece_rows : rows - pc.row0;
+    pc.ntiles = (int)((pc.rows + cfg.T - 1) / cfg.T);
+    pc.spec = (float2*)(store + c * l.piece_bytes);
+    pc.masks = (float*)(store + c * l.piece_bytes + wstore_spec_bytes(pc.rows));      // (a multiple of 16 bytes: the mask extension's kernel reads vectors)
+    return pc;
+}
+
+size_t srtHostWienerBytes(const srt_config* cfg, size_t n)
+{
+    if (!cfg) { fail(-1, "srtHostWienerBytes: null config"); return 0; }
+    if (srt_check_config(cfg, "srtHostWienerBytes")) return 0;
+    if (n < SRT_FFT) { fail(-1, "srtHostWienerBytes: need at least 4096 samples"); return 0; }
+    return host_wiener_layout(*cfg, srtStftRows(n)).total;
+}
+
+// grow-only like the rest of the staging (the streams exist: ensure_staging ran).  A failed allocation leaves the engine without a store and otherwise as it was.
+static int ensure_wstore(srt_engine* e, size_t bytes)
+{
+    HostStaging& h = e->hs;
+    if (bytes <= h.wstore_cap) return 0;
+    HIPCHK(hipStreamSynchronize(h.s_in)); HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipStreamSynchronize(h.s_out));
+    if (h.d_wstore) { hipFree(h.d_wstore); h.d_wstore = nullptr; h.wstore_cap = 0; }
+    const hipError_t er = hipMalloc((void**)&h.d_wstore, bytes);
+    if (er != hipSuccess) {
+        (void)hipGetLastError();
+        h.d_wstore = nullptr;
+        char what[160];
+        snprintf(what, sizeof what, "%zu bytes (%s)", bytes, hipGetErrorString(er));
+        return fail(-2, "srtSeparateHostWiener: HIP error allocating the device store of %s: srtHostWienerBytes gives its size; a shorter stream or fewer stems fit", what);
+    }
+    h.wstore_cap = bytes;
+    return 0;
+}
+
+int srtSeparateHostWiener(srt_engine* e, const void* h_in, const void* h_in2, size_t n, const srt_wiener_opts* opts, void* h_out_, unsigned flags, unsigned long long* h_clipped)
+{
+    const bool in16 = flags & SRT_HOST_IN_PCM16, out16 = flags & SRT_HOST_OUT_PCM16;
+    if (!e || !h_in || (!in16 && !h_in2) || !opts || !h_out_) return fail(-1, "srtSeparateHostWiener: null argument");
+    if (flags & ~SRT_HOST_FLAGS) return fail(-1, "srtSeparateHostWiener: unknown flag bits");
+    if (in16 && h_in2) return fail(-1, "srtSeparateHostWiener: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)");
+    DeviceScope ds(e->device);
+    SepOpts o;
+    int rc = host_wiener_check(e, opts, n, &o);
+    if (rc) return rc;
+    if (stream_capturing(e)) return fail(-1, "srtSeparateHostWiener: not available inside a stream capture (the call is synchronous and allocates)");
+    const size_t rows = srtStftRows(n), frames = srtStftFrames(n);
+    const int S = e->cfg.n_stems, NO = o.n_out ? o.n_out : S, NP = NO * 2, iters = o.wiener;      // NO pairs staged, carried, packed and downloaded
+    const HostWienerLayout l = host_wiener_layout(e->cfg, rows);
+    const size_t tail = SRT_FFT - SRT_HOP, total_len = srtIstftLength(rows);
+    const size_t in_cap = l.piece_rows * SRT_HOP + tail, out_cap = srtIstftLength(l.piece_rows);
+    if ((rc = host_wiener_ws(e, o))) return rc;
+    if ((rc = ensure_staging(e, 2 * in_cap, (size_t)NP * out_cap, (size_t)NP * tail, 2))) return rc;
+    if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? in_cap : 0, out16 ? (size_t)NO * out_cap : 0))) return rc;
+    if ((rc = ensure_wstore(e, l.total))) return rc;
+    HostStaging& h = e->hs;
+    if (h_clipped) memset(h_clipped, 0, (size_t)NO * sizeof *h_clipped);
+    unsigned long long* d_clip = out16 && h_clipped ? h.d_clip : nullptr;
+    if (d_clip) HIPCHK(hipMemsetAsync(d_clip, 0, (size_t)NO * sizeof *d_clip, e->stream));
+    bool pinL = false, pinR = false, pinO = false;                  // as host_stream: register the caller's buffers for the call unless they are pinned already
+    if (!(flags & SRT_HOST_PINNED)) {
+        pinL = hipHostRegister((void*)h_in, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;       // int16 [n][2] is n * 4 bytes too
+        pinR = !in16 && hipHostRegister((void*)h_in2, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;
+        pinO = hipHostRegister(h_out_, (size_t)NP * total_len * (out16 ? sizeof(int16_t) : sizeof(float)), hipHostRegisterDefault) == hipSuccess;
+        (void)hipGetLastError();
+    }
+    const float *h_L = (const float*)h_in, *h_R = (const float*)h_in2;
+    const SrtSwitches sw = srt_read_switches();
+    const SrtWienerParams w = wiener_geometry(e, rows);      // the chunks and the tables of the WHOLE signal
+    hipError_t er = hipSuccess;
+#define STEP(x) do { if (er == hipSuccess) er = (x); } while (0)
+    // sweep A: upload, unpack, STFT and networks into the store, statistics pass 1
+    for (size_t c = 0; c < l.npieces && er == hipSuccess && rc == 0; ++c) {
+        const int b = (int)(c & 1);
+        const HostWienerPiece pc = host_wiener_piece(e->cfg, l, h.d_wstore, rows, c);
+        const size_t row1 = pc.row0 + pc.rows;
+        const size_t s0 = pc.row0 * SRT_HOP, send = row1 * SRT_HOP + tail < n ? row1 * SRT_HOP + tail : n;
+        const size_t ns = send > s0 ? send - s0 : 0;
+        const size_t cfr = frames > pc.row0 ? (frames - pc.row0 < pc.rows ? frames - pc.row0 : pc.rows) : 0;
+        if (c >= 2) STEP(hipStreamWaitEvent(h.s_in, h.ev_cmp[b], 0));      // the input buffer is free once the transform that read it two pieces ago has finished
+        if (ns && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * s0, ns * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
+        else if (ns) {
+            STEP(hipMemcpyAsync(h.d_in[b], h_L + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
+            STEP(hipMemcpyAsync(h.d_in[b] + in_cap, h_R + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
+        }
+        STEP(hipEventRecord(h.ev_in[b], h.s_in));
+        STEP(hipStreamWaitEvent(e->stream, h.ev_in[b], 0));
+        if (er != hipSuccess) break;
+        if (in16 && ns) {
+            TimerScope ts(e, "pcm16_unpack");
+            if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
+        }
+        if ((rc = host_wiener_analyse(e, sw, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, pc))) break;
+        STEP(hipEventRecord(h.ev_cmp[b], e->stream));                       // (the networks read the magnitudes, not the PCM, but the event is one per piece)
+        if ((rc = host_wiener_stats(e, w, pc, 1))) break;
+    }
+    // the R tables: pass 1, then every further pass over the store (no network, no PCIe)
+    if (rc == 0 && er == hipSuccess) rc = host_wiener_finalize(e, w, 1);
+    for (int pass = 2; pass <= iters && rc == 0 && er == hipSuccess; ++pass) {
+        for (size_t c = 0; c < l.npieces && rc == 0; ++c) rc = host_wiener_stats(e, w, host_wiener_piece(e->cfg, l, h.d_wstore, rows, c), pass);
+        if (rc == 0) rc = host_wiener_finalize(e, w, pass);
+    }
+    // sweep B: filter, inverse transforms, seam, pack, download
+    for (size_t c = 0; c < l.npieces && er == hipSuccess && rc == 0; ++c) {
+        const int b = (int)(c & 1);
+        const HostWienerPiece pc = host_wiener_piece(e->cfg, l, h.d_wstore, rows, c);
+        const size_t s0 = pc.row0 * SRT_HOP, clen = srtIstftLength(pc.rows);
+        const bool last = c + 1 == l.npieces;
+        if (c >= 2) STEP(hipStreamWaitEvent(e->stream, h.ev_out[b], 0));    // the output buffer is free once the download of two pieces ago has drained it
+        if (er != hipSuccess) break;
+        if ((rc = host_wiener_render(e, w, o, pc, h.d_out[b]))) break;
+        if (srt_launch_carry(h.d_out[b], clen, NP, pc.rows * SRT_HOP, h.d_carry, c == 0, last, e->stream)) { rc = fail(-2, "carry launch failed"); break; }
+        const size_t take = last ? clen : pc.rows * SRT_HOP;
+        if (out16) {
+            TimerScope ts(e, "pcm16_pack");
+            if (srt_launch_pcm16_pack(h.d_out[b], clen, NO, take, h.d_out16[b], clen, d_clip, d_clip ? d_clip + SRT_MAX_STEMS : nullptr, e->stream)) { rc = fail(-2, "pcm16 pack launch failed"); break; }
+        }
+        STEP(hipEventRecord(h.ev_cmp[b], e->stream));
+        STEP(hipStreamWaitEvent(h.s_out, h.ev_cmp[b], 0));
+        if (out16) STEP(hipMemcpy2DAsync((int16_t*)h_out_ + 2 * s0, total_len * 2 * sizeof(int16_t), h.d_out16[b], clen * 2 * sizeof(int16_t), take * 2 * sizeof(int16_t), NO, hipMemcpyDeviceToHost, h.s_out));
+        else STEP(hipMemcpy2DAsync((float*)h_out_ + s0, total_len * sizeof(float), h.d_out[b], clen * sizeof(float), take * sizeof(float), NP, hipMemcpyDeviceToHost, h.s_out));
+        STEP(hipEventRecord(h.ev_out[b], h.s_out));
+    }
+#undef STEP
+    hipStreamSynchronize(h.s_in);
+    hipStreamSynchronize(e->stream);
+    hipStreamSynchronize(h.s_out);
+    if (rc == 0 && er == hipSuccess && d_clip) {      // once, after the last piece
+        er = hipMemcpyAsync(h_clipped, d_clip, (size_t)NO * sizeof *d_clip, hipMemcpyDeviceToHost, e->stream);
+        if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
+    }
+    if (rc == 0 && er != hipSuccess) rc = fail(-2, "HIP error: %s", hipGetErrorString(er));
+    if (pinL) hipHostUnregister((void*)h_in);
+    if (pinR) hipHostUnregister((void*)h_in2);
+    if (pinO) hipHostUnregister(h_out_);
+    return rc;
 }

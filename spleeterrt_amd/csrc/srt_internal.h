@@ -300,6 +300,10 @@ struct SrtWienerParams {
 };
 int srt_launch_wiener_stats(const SrtWienerParams& p, int pass, hipStream_t s);      // pass 1..n: statistics of the estimates after pass - 1 iterations
 int srt_launch_wiener_finalize(const SrtWienerParams& p, int pass, hipStream_t s);   // R tables of that pass (and a, pass 1)
+// srt_launch_wiener_stats for rows [row0, row0 + nrows) of a signal held one piece at a time (srtSeparateHostWiener): p.spec / spec_ch_stride / masks / ntiles are
+// the PIECE's (its row 0 is the signal's row0), p.rows / rpc / nchunks the whole signal's.  Chunks that straddle a piece boundary continue from their slab slots, so
+// after the pieces have been launched in row order on one stream the slab (and slab_max) holds what one srt_launch_wiener_stats over the signal leaves, bit for bit.
+int srt_launch_wiener_stats_seg(const SrtWienerParams& p, size_t row0, size_t nrows, int pass, hipStream_t s);
 int srt_launch_wiener_filter(const SrtWienerParams& p, int iters, hipStream_t s);    // W_j x after `iters` iterations for every stem; bins >= F copied
 // The filter with per-call options (srtIstftWienerEx / srtSeparateWiener).  p as above, except that with overlap > 0 p.masks is in the
 // overlapped layout and p.ntiles = srtOverlapTiles(rows, T, overlap) (the masks' stem stride, and the count srt_ov_row clamps the primary tile with).

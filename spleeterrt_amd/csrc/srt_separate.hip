@@ -118,35 +118,34 @@ int ensure_wiener_ws(srt_engine* e)
     return 0;
 }
 
-// statistics passes (one stats + one finalize launch per iteration), the filter, then one inverse transform per stem on its filtered spectrum
-// (no masks: all-ones in band; bins >= F get oob_weight as with masks).  The statistics window is exactly the `rows` rows of this call.
-// o: o.wiener iterations under the call's other options (DESIGN.md 9.1; off on the engine's own path, whose setters keep them apart from the filter).  With every
-// option off the filter writes per-stem spectra and the inverse applies oob_weight; with an overlap the statistics run on blended masks
-// (srt_wiener_stats_ov_kernel), and with any option the filter writes final spectra (srt_wiener_filter_opt_kernel) of the n_out mixes or of every stem, which the
-// inverse transforms without a gain.  d_masks: [S][overlap_tiles(rows, T, overlap)][2][T][F].
-static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out, const SepOpts& o)
+// the part of the launch arguments that depends on the engine and on the signal's row count alone: the row chunks of the statistics pass (at most
+// SRT_WIENER_MAX_CHUNKS, of at least 16 rows) and the workspaces.  The caller adds the spectrum, the masks and their tile count.
+SrtWienerParams wiener_geometry(const srt_engine* e, size_t rows)
 {
-    const int T = e->cfg.T, S = e->cfg.n_stems, F = e->cfg.F;
-    const int O = o.overlap, iters = o.wiener;
-    const bool ext = o.mask_ext == SRT_MASK_EXT_AVERAGE, plain = !O && !ext && !o.n_out;
+    const int S = e->cfg.n_stems, F = e->cfg.F;
     SrtWienerParams w; memset(&w, 0, sizeof w);
-    w.spec = (const float2*)d_spec; w.spec_ch_stride = rows * SRT_SPEC_LD; w.rows = (int)rows;
-    w.masks = d_masks; w.nstems = S; w.ntiles = (int)overlap_tiles(rows, T, O); w.T = T; w.F = F;
+    w.rows = (int)rows; w.nstems = S; w.T = e->cfg.T; w.F = F;
     int nch = (int)((rows + 15) / 16); if (nch > SRT_WIENER_MAX_CHUNKS) nch = SRT_WIENER_MAX_CHUNKS;
     w.rpc = (int)((rows + nch - 1) / nch); w.nchunks = (int)((rows + w.rpc - 1) / w.rpc);
     w.slab = e->wslab; w.slab_max = e->wslab + (size_t)SRT_WIENER_MAX_CHUNKS * S * 4 * F;
     w.rtab = e->wtab; w.wsum = e->wtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4; w.scal = w.wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F;
     w.out = e->wspec; w.out_stem = 2 * rows * SRT_SPEC_LD;
-    for (int pass = 1; pass <= iters; ++pass) {
-        { TimerScope ts(e, "wiener_stats"); if (O ? srt_launch_wiener_stats_ov(w, O, pass, e->stream) : srt_launch_wiener_stats(w, pass, e->stream)) return fail(-2, "Wiener statistics launch failed"); }
-        { TimerScope ts(e, "wiener_cov"); if (srt_launch_wiener_finalize(w, pass, e->stream)) return fail(-2, "Wiener finalize launch failed"); }
-    }
+    return w;
+}
+
+// the filter over w's rows (its spectrum, masks and tile count; the R tables and a are final) into the engine's spectrum workspace, then one inverse transform per
+// output: the second half of wiener_issue, and what srtSeparateHostWiener runs per piece
+static int wiener_render(srt_engine* e, const SrtWienerParams& w, float* d_out, const SepOpts& o)
+{
+    const int S = e->cfg.n_stems, O = o.overlap, iters = o.wiener;
+    const size_t rows = (size_t)w.rows;
+    const bool ext = o.mask_ext == SRT_MASK_EXT_AVERAGE, plain = !O && !ext && !o.n_out;
     SrtWienerOpt q; memset(&q, 0, sizeof q);
     q.overlap = O; q.n_out = o.n_out;
     memcpy(q.oob, e->cfg.oob_weight, sizeof q.oob);
     memcpy(q.mix, o.mix, sizeof q.mix);
     if (ext) {      // e_j(r, c): the table the inverse transform's own kernel writes from the same (blended) masks, ratio = 0
-        const int rc = mask_ext_issue(e, d_masks, 0, S, w.ntiles, (int)rows, 0, O);
+        const int rc = mask_ext_issue(e, w.masks, 0, S, w.ntiles, (int)rows, 0, O);
         if (rc) return rc;
         q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
     }
@@ -160,8 +159,28 @@ static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const f
     return 0;
 }
 
+// statistics passes (one stats + one finalize launch per iteration), the filter, then one inverse transform per stem on its filtered spectrum
+// (no masks: all-ones in band; bins >= F get oob_weight as with masks).  The statistics window is exactly the `rows` rows of this call.
+// o: o.wiener iterations under the call's other options (DESIGN.md 9.1; off on the engine's own path, whose setters keep them apart from the filter).  With every
+// option off the filter writes per-stem spectra and the inverse applies oob_weight; with an overlap the statistics run on blended masks
+// (srt_wiener_stats_ov_kernel), and with any option the filter writes final spectra (srt_wiener_filter_opt_kernel) of the n_out mixes or of every stem, which the
+// inverse transforms without a gain.  d_masks: [S][overlap_tiles(rows, T, overlap)][2][T][F].
+static int wiener_issue(srt_engine* e, const float* d_spec, size_t rows, const float* d_masks, float* d_out, const SepOpts& o)
+{
+    const int O = o.overlap, iters = o.wiener;
+    SrtWienerParams w = wiener_geometry(e, rows);
+    w.spec = (const float2*)d_spec; w.spec_ch_stride = rows * SRT_SPEC_LD;
+    w.masks = d_masks; w.ntiles = (int)overlap_tiles(rows, e->cfg.T, O);
+    for (int pass = 1; pass <= iters; ++pass) {
+        { TimerScope ts(e, "wiener_stats"); if (O ? srt_launch_wiener_stats_ov(w, O, pass, e->stream) : srt_launch_wiener_stats(w, pass, e->stream)) return fail(-2, "Wiener statistics launch failed"); }
+        { TimerScope ts(e, "wiener_cov"); if (srt_launch_wiener_finalize(w, pass, e->stream)) return fail(-2, "Wiener finalize launch failed"); }
+    }
+    return wiener_render(e, w, d_out, o);
+}
+
 // the checks srtIstftWienerEx and srtSeparateWiener share (`who` names the caller): 0 with the call's record in *c, or -1 with the error text set; no device work
-static int wiener_opts_check(const srt_engine* e, const char* who, const srt_wiener_opts* o, size_t rows, SepOpts* c)
+// any_rows (srtSeparateHostWiener, which holds one piece of max_tiles tiles at a time): no limit on the signal's tiles
+static int wiener_opts_check(const srt_engine* e, const char* who, const srt_wiener_opts* o, size_t rows, SepOpts* c, bool any_rows = false)
 {
     const int T = e->cfg.T, S = e->cfg.n_stems;
     if (o->iterations < 1 || o->iterations > SRT_WIENER_MAX_ITERS) return fail(-1, "%s: iterations must be 1..3", who);
@@ -171,7 +190,7 @@ static int wiener_opts_check(const srt_engine* e, const char* who, const srt_wie
     if (o->n_out && !o->h_gain) return fail(-1, "%s: null gain matrix with n_out > 0", who);
     if (!gain_finite(o->h_gain, o->n_out * (S + 1))) return fail(-1, "%s: every gain must be finite", who);
     if (e->cfg.ratio_mask) return fail(-1, "%s: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)", who);
-    if (rows < 1 || overlap_tiles(rows, T, o->overlap_rows) > (size_t)e->cfg.max_tiles)
+    if (rows < 1 || (!any_rows && overlap_tiles(rows, T, o->overlap_rows) > (size_t)e->cfg.max_tiles))
         return fail(-1, o->overlap_rows ? "%s: the signal takes more than max_tiles tiles at this overlap (srtOverlapTiles)" : "%s: need 1 <= rows <= max_tiles * T", who);
     *c = SepOpts{};
     c->wiener = o->iterations; c->overlap = o->overlap_rows; c->mask_ext = o->mask_extension; c->n_out = o->n_out;
@@ -223,6 +242,60 @@ int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float*
     if (rc) return rc;
     o.wiener = iterations;                                                  // whatever srtSetWiener says
     return wiener_issue(e, d_spec, rows, d_masks, d_out, o);
+}
+
+// ---- srtSeparateHostWiener's stages: srt_host.hip walks the stream piece by piece and owns the copies, the store and the events; what a piece
+// computes is issued here, beside the single-signal path it has to equal.  A piece is rows [row0, row0 + rows) of the signal, its spectrum and masks in the store.
+int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n, SepOpts* o)
+{
+    static const char* const who = "srtSeparateHostWiener";
+    if (opts->overlap_rows > 0) return fail(-1, "%s: overlap_rows must be 0 (the overlap blend across piece seams is a follow-up): srtSeparateWiener takes an overlap for a signal of up to max_tiles tiles", who);
+    if (n < SRT_FFT) return fail(-1, "%s: need at least 4096 samples", who);
+    const size_t rows = srtStftRows(n);
+    if (rows > (size_t)0x7fffffff - 4) return fail(-1, "%s: more than 2^31 rows", who);
+    int rc = wiener_opts_check(e, who, opts, rows, o, true);
+    if (rc) return rc;
+    for (int s = 0; s < e->cfg.n_stems; ++s) if (!e->have_coeff[s]) return fail(-5, "%s: weights not set for every stem", who);
+    return 0;
+}
+
+int host_wiener_ws(srt_engine* e, const SepOpts& o) { return ensure_wiener_opts_ws(e, "srtSeparateHostWiener", o); }
+
+// sweep A: the piece's PCM -> its spectrum and fp32 masks in the store (not the engine's own mask buffer, so the fp16 mode keeps floats as everywhere the filter runs)
+int host_wiener_analyse(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, const HostWienerPiece& pc)
+{
+    const int rc = stft_issue(e, d_L, d_R, n, frames, pc.rows, (float*)pc.spec, e->mag, SepOpts{});
+    if (rc) return rc;
+    return forward_range(e, sw, e->mag, pc.ntiles, pc.masks, 0, e->cfg.n_stems);
+}
+
+// w: wiener_geometry of the whole signal; the piece goes into a copy of it
+static SrtWienerParams piece_params(const SrtWienerParams& w, const HostWienerPiece& pc)
+{
+    SrtWienerParams p = w;
+    p.spec = pc.spec; p.spec_ch_stride = pc.rows * SRT_SPEC_LD; p.masks = pc.masks; p.ntiles = pc.ntiles;
+    return p;
+}
+
+// the piece's share of statistics pass `pass` (chunks that straddle a piece boundary continue in the slab: srt_wiener_stats_seg_kernel)
+int host_wiener_stats(srt_engine* e, const SrtWienerParams& w, const HostWienerPiece& pc, int pass)
+{
+    TimerScope ts(e, "wiener_stats");
+    return srt_launch_wiener_stats_seg(piece_params(w, pc), pc.row0, pc.rows, pass, e->stream) ? fail(-2, "Wiener statistics launch failed") : 0;
+}
+
+int host_wiener_finalize(srt_engine* e, const SrtWienerParams& w, int pass)
+{
+    TimerScope ts(e, "wiener_cov");
+    return srt_launch_wiener_finalize(w, pass, e->stream) ? fail(-2, "Wiener finalize launch failed") : 0;
+}
+
+// sweep B: the filter is row-local once the tables exist, so the piece is rendered as a signal of its own rows: wiener_issue's second half
+int host_wiener_render(srt_engine* e, const SrtWienerParams& w, const SepOpts& o, const HostWienerPiece& pc, float* d_out)
+{
+    SrtWienerParams p = piece_params(w, pc);
+    p.rows = (int)pc.rows; p.out_stem = 2 * pc.rows * SRT_SPEC_LD;
+    return wiener_render(e, p, d_out, o);
 }
 
 // fp16 mode: the masks between the head and the inverse transform - the engine's own buffer, never seen by a caller - are halves where both kernels take them

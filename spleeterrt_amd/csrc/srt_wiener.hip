@@ -108,6 +108,29 @@ __device__ __forceinline__ float w_block_max(float x, float* red)
     return x;
 }
 
+// The row walk of the statistics pass, rows [T0, T1) of p.spec / p.masks in row order: max |s| (pass 1) and, in band, the chain through pass - 1 iterations and the
+// four sums per stem, acc += term.  A macro, not a function: srt_wiener_stats_kernel and srt_wiener_stats_seg_kernel must agree bit for bit, so both hold THIS text,
+// and the first keeps the instruction stream it had when the loop stood in its body (as an inline function the same statements were scheduled differently there).
+// It uses the kernel's locals p, pass, k, S, inb, tf, sstride, delta, sLp, sRp, acc and mx.
+#define W_STATS_ROWS(T0, T1) \
+        for (int t = (T0); t < (T1); ++t) { \
+            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD]; \
+            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y))); \
+            if (!inb) continue; \
+            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k; \
+            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS]; \
+            w_start(yl, yr, sL, sR, m, sstride, tf, S); \
+            for (int i = 0; i < pass - 1; ++i) \
+                w_iter(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S); \
+            _Pragma("unroll") \
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) { \
+                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y; \
+                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y; \
+                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      /* y_L conj(y_R) */ \
+                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y; \
+            } \
+        }
+
 __global__ void __launch_bounds__(256) srt_wiener_stats_kernel(const SrtWienerParams p, int pass)
 {
     __shared__ float red[4];
@@ -123,23 +146,53 @@ __global__ void __launch_bounds__(256) srt_wiener_stats_kernel(const SrtWienerPa
     for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
     float mx = 0.0f;
     if (anyb) {
-        for (int t = r0; t < r1; ++t) {
-            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD];
-            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y)));
-            if (!inb) continue;
-            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;
-            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
-            w_start(yl, yr, sL, sR, m, sstride, tf, S);
-            for (int i = 0; i < pass - 1; ++i)
-                w_iter(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
+        W_STATS_ROWS(r0, r1)
+    }
+    if (inb) {
 #pragma unroll
-            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
-                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y;
-                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y;
-                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      // y_L conj(y_R)
-                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y;
-            }
-        }
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k] = acc[j][q];
+    }
+    if (pass == 1) {                                             // (block-uniform branch: every thread reaches the barriers)
+        mx = w_block_max(mx, red);
+        if (threadIdx.x == 0) p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] = mx;
+    }
+}
+
+// srt_wiener_stats_kernel for rows [row0, row1) of a signal of p.rows rows whose spectrum and masks are resident one PIECE at a time (srtSeparateHostWiener,
+// DESIGN.md 9.3): p.spec / p.spec_ch_stride / p.masks / p.ntiles describe the piece (row row0 of the signal is row 0 of the piece), p.rows / p.rpc / p.nchunks the
+// whole signal.  Grid (bin blocks, the global chunks that intersect the piece), chunk c = c0 + blockIdx.y walks [max(c rpc, row0), min((c + 1) rpc, rows, row1)).
+// A chunk an earlier piece began (c rpc < row0) continues: its accumulators start from the slab slots that piece's launch stored - and in pass 1 the running
+// maximum from its slab_max entry - and go back to the same slots, so after the last piece a slot holds acc += term over the chunk's rows in row order, the
+// sequence the whole-signal launch runs in registers.  No atomics: one workgroup owns a (chunk, bin block) per launch, and the launches of consecutive pieces
+// are ordered on the compute stream.
+__global__ void __launch_bounds__(256) srt_wiener_stats_seg_kernel(const SrtWienerParams p, int row0, int row1, int c0, int pass)
+{
+    __shared__ float red[4];
+    const int k = blockIdx.x * 256 + threadIdx.x, c = c0 + blockIdx.y, S = p.nstems;
+    const int g0 = c * p.rpc;                                                    // the chunk's first row in the signal
+    const int r0 = max(g0, row0) - row0, r1 = min(min(g0 + p.rpc, p.rows), row1) - row0;      // rows of the PIECE
+    const bool cont = g0 < row0;                                                 // (workgroup-uniform)
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const float al = (pass > 1 ? p.scal[0] : 1.0f) * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F, anyb = k < SRT_HALF;
+    const float2* sLp = p.spec + (anyb ? k : 0);
+    const float2* sRp = sLp + p.spec_ch_stride;
+    float acc[SRT_MAX_STEMS][4];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
+    if (cont && inb) {
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[j][q] = p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k];
+    }
+    float mx = pass == 1 && cont ? p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] : 0.0f;
+    if (anyb) {
+        W_STATS_ROWS(r0, r1)
     }
     if (inb) {
 #pragma unroll
@@ -216,6 +269,19 @@ int srt_launch_wiener_stats(const SrtWienerParams& p, int pass, hipStream_t s)
         p.F < 1 || p.F > SRT_HALF - 1 || (size_t)p.nchunks * p.rpc < (size_t)p.rows || (size_t)p.ntiles * p.T < (size_t)p.rows) return -1;
     const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
     SRT_LAUNCH(srt_wiener_stats_kernel, dim3(bx, p.nchunks), dim3(256), 0, s, p, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_stats_seg(const SrtWienerParams& p, size_t row0, size_t nrows, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || p.nchunks < 1 || p.nchunks > SRT_WIENER_MAX_CHUNKS || p.nstems < 1 || p.nstems > SRT_MAX_STEMS ||
+        p.F < 1 || p.F > SRT_HALF - 1 || p.rpc < 1 || p.rows < 1 || (size_t)p.nchunks * p.rpc < (size_t)p.rows) return -1;
+    // the piece lies inside the signal, its masks and spectrum hold its rows, and every chunk it touches has a slab slot
+    if (nrows < 1 || row0 + nrows > (size_t)p.rows || p.T < 1 || p.ntiles < 1 || (size_t)p.ntiles * p.T < nrows || p.spec_ch_stride < nrows * SRT_SPEC_LD) return -1;
+    const int c0 = (int)(row0 / p.rpc), c1 = (int)((row0 + nrows - 1) / p.rpc);
+    if (c1 >= p.nchunks) return -1;
+    const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
+    SRT_LAUNCH(srt_wiener_stats_seg_kernel, dim3(bx, c1 - c0 + 1), dim3(256), 0, s, p, (int)row0, (int)(row0 + nrows), c0, pass);
     return srt_launch_status();
 }
 
