@@ -401,6 +401,34 @@ SRT_API int    srtSeparateHostWiener(srt_engine *e, const void *h_in, const void
                                      const srt_wiener_opts *opts, void *h_out, unsigned flags, unsigned long long *h_clipped);
 SRT_API size_t srtHostWienerBytes(const srt_config *cfg, size_t n);
 
+/* ---- overlapped network tiles over a HOST stream of any length: srtSeparate under srtSetOverlap(e, overlap_rows) for host-resident PCM that need
+ * not fit max_tiles overlapped tiles.  Geometry: the whole stream (rows = srtStftRows(n), frames = srtStftFrames(n)).  h_in, h_in2, h_out, flags (SRT_HOST_PINNED |
+ * SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16) and h_clipped exactly as in srtSeparateHostStreamIo; h_out is [n_out ? n_out : n_stems][2][srtIstftLength(rows)] floats, or
+ * int16 [..][len][2] with the out flag.  Synchronous and always eager.  Any n >= 4096 works, one piece included.
+ * overlap_rows (0..T/2) holds for this call only: the engine's srtSetOverlap is neither read nor changed, and the call works with it on or off.  Everything else
+ *   comes from the engine as in srtSeparateHostStreamIo: ratio_mask (blend, then normalise), srtSetMaskExtension in both modes, srtSetMix.  With overlap_rows > 0
+ *   the masks stay floats in the fp16 mode, as they do under srtSetMix.  overlap_rows = 0 is srtSeparateHostStreamIo(e, .., n, frames, rows, ..): the same
+ *   launches, the same bits.
+ * What it equals: srtSeparate on an engine large enough to hold the signal after srtSetOverlap(e, overlap_rows).  Every spectrum row gets the same gain, bit for
+ *   bit with batch_invariant (up to the network's batch-dependent kernel choice otherwise); the samples agree up to the association of the overlap-add at the
+ *   piece seams (2e-6 of the peak, as in srtSeparateHostStream); a signal of one piece gives srtSeparate's bits.
+ * How: the stream is walked in pieces of max_tiles overlapped tiles (srtHostOverlapPieces).  With S = T - O, piece p holds tiles [tile0, tile0 + tiles), owns -
+ *   inverts and downloads - the own_rows rows from row0 = tile0 * S, and analyses stft_rows >= own_rows rows from row0: its last tile reaches O rows into the next
+ *   piece, which are uploaded and transformed twice (O / (max_tiles * S) of the work).  Rows [0, O) of every later piece blend with rows [S, T) of the previous
+ *   piece's last tile, which a small kernel keeps in a carry of n_stems * 2 * O * F floats beside the host staging (grow-only, srtReleaseStaging frees it).
+ *   After a call with the average mask extension srtCopyTensor("mask_ext") holds the LAST piece's rows.
+ * srtHostOverlapPieces: the plan - pure host arithmetic, no device (like srtBatchPlanOverlap).  Returns the piece count and fills pieces[0 .. min(count,
+ *   max_pieces)) when pieces is not NULL; 0 for rows = 0; 0 with srtLastError() text for T < 1, overlap_rows outside 0..T/2 or max_tiles < 1.  overlap_rows = 0 is
+ *   the chunking of srtSeparateHostStream (max_tiles * T rows per piece, stft_rows = own_rows).
+ * -1 with srtLastError() text that names srtSeparateHostStreamOverlap, before any device work and with nothing written: a null argument, unknown flag bits,
+ * SRT_HOST_IN_PCM16 with h_in2 != NULL, n < 4096, overlap_rows outside 0..T/2, the Wiener filter on (the text says "Wiener"); -5 when a stem's weights are not set.
+ * srtSeparateHostStream*, srtSeparateCli*, srtMultiSeparate* and srtSeparateHostWiener keep their refusals.  Not built: an overlap in srtSeparateHostWiener, the CLI
+ * flows, multi-device ranges, a half-precision carry, graph capture. */
+typedef struct srt_host_piece { size_t tile0, tiles, row0, own_rows, stft_rows; } srt_host_piece;
+SRT_API size_t srtHostOverlapPieces(size_t rows, int T, int overlap_rows, int max_tiles, srt_host_piece *pieces, size_t max_pieces);
+SRT_API int    srtSeparateHostStreamOverlap(srt_engine *e, const void *h_in, const void *h_in2, size_t n, int overlap_rows,
+                                            void *h_out, unsigned flags, unsigned long long *h_clipped);
+
 /* ---- one node, several devices: the reference CLI's tile-range fan-out (Executable/main.c:544-673, `processMT`: spawnNthreads workers, each with
  * its own network instance and a contiguous tile range, one shared read-only weight blob) with a GPU where the reference has a CPU thread.
  * One engine per entry of `devices` (an index may repeat: several engines on one GPU), one host thread per engine while a call runs; weights are

@@ -90,6 +90,9 @@ def load_library():
     L.srtSeparateHostStreamEx.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_uint]
     L.srtSeparateHostStreamIo.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_uint, vp]
     L.srtSeparateCliHostIo.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_uint, vp]
+    L.srtSeparateHostStreamOverlap.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_uint, vp]
+    L.srtHostOverlapPieces.restype = C.c_size_t
+    L.srtHostOverlapPieces.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
     L.srtPcm16Unpack.argtypes = [vp, vp, C.c_size_t, vp, vp]
     L.srtPcm16Pack.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     for fn in (L.srtStftRows, L.srtStftFrames, L.srtIstftLength):
@@ -647,6 +650,24 @@ class Engine:
         self._chk(self.L.srtSeparateHostStreamIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, frames, rows, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
 
+    def separate_host_overlap(self, pcm_or_LR, overlap, out_pcm16=False, out=None, pinned=False):
+        """separate() under set_overlap(overlap) for host PCM of any length (srtSeparateHostStreamOverlap): the stream is walked in pieces of
+        max_tiles overlapped tiles (stream.host_overlap_pieces) and the mask blend crosses the piece seams through a small device carry.  overlap (0 .. T/2 rows)
+        holds for this call only - the engine's set_overlap is neither read nor changed; ratio_mask, the mask extension and the mix come from the engine.  Buffers as
+        separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32; out_pcm16: int16 [outputs, len, 2] instead of float32 [outputs, 2, len]; pinned=True
+        promises page-locked buffers.  overlap = 0 is separate_host_stream_io.  -> (out, clipped)."""
+        try:
+            ov = int(overlap)
+        except (TypeError, ValueError):
+            raise EngineError("separate_host_overlap: overlap must be an integer 0 .. T / 2, not %r" % (overlap,))
+        if ov != overlap or ov < 0 or ov > self.T // 2:
+            raise EngineError("separate_host_overlap: overlap must be an integer 0 .. T / 2 = %d, not %r" % (self.T // 2, overlap))
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, None, out, pinned)
+        if n < 4096:
+            raise EngineError("separate_host_overlap: need at least 4096 samples, not %d" % n)
+        self._chk(self.L.srtSeparateHostStreamOverlap(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, ov, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
+        return out, clipped
+
     def separate_host_wiener(self, pcm_or_LR, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False, overlap=0):
         """separate_wiener for host PCM of any length (srtSeparateHostWiener): the stream is walked in pieces of max_tiles tiles, its spectrum and
         masks are kept in a device store of host_wiener_bytes(n) bytes, and the R tables are those of one separate_wiener call over the whole signal, bit for bit.
@@ -734,6 +755,24 @@ class Engine:
         n = self._chk(self.L.srtGetTimingKernels(self.h, buf, len(buf)))
         ks = buf.value.decode().split(";")[:n]
         return [(name, k) for (name, _), k in zip(tim, ks)]
+
+
+class _HostPiece(C.Structure):
+    _fields_ = [(k, C.c_size_t) for k in ("tile0", "tiles", "row0", "own_rows", "stft_rows")]
+
+
+def host_overlap_pieces(rows, T, overlap, max_tiles):
+    """srtHostOverlapPieces: the piece plan of srtSeparateHostStreamOverlap as a list of dicts (tile0, tiles, row0, own_rows, stft_rows), from the library -
+    stream.host_overlap_pieces is the same arithmetic in Python.  Pure host arithmetic: works without a device.  Raises for bad arguments."""
+    L = load_library()
+    n = L.srtHostOverlapPieces(int(rows), int(T), int(overlap), int(max_tiles), None, 0)
+    if not n:
+        if int(rows) == 0 and int(T) >= 1 and 0 <= int(overlap) <= int(T) // 2 and int(max_tiles) >= 1:
+            return []
+        raise EngineError("libspleeterrt_amd: %s" % L.srtLastError().decode())
+    buf = (_HostPiece * n)()
+    L.srtHostOverlapPieces(int(rows), int(T), int(overlap), int(max_tiles), C.cast(buf, C.c_void_p), n)
+    return [dict((k, int(getattr(p, k))) for k, _ in _HostPiece._fields_) for p in buf]
 
 
 def host_wiener_bytes(n, F, T, n_stems, max_tiles):

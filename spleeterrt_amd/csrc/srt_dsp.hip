@@ -217,12 +217,16 @@ __device__ __forceinline__ float srt_ratio_of(float own, const float* __restrict
 // in the primary / the previous tile; rowa0 is read only when two), then squared and summed as in srt_ratio_of.  The RATIO overlap instantiations do not prefetch
 // their own mask row (it is one of the rows read here; the registers it would be staged in are what the F > 1024 form spills): ratio = false returns the stem's own
 // blended value.
+// SEAM: rowa0 may be a row of the mask seam carry (srt_ov_seam), whose stems lie astride floats apart; otherwise astride is unused (a's stems are sstride apart as b's).
+template <bool SEAM = false>
 __device__ __forceinline__ float srt_ratio_of_ov(const float* __restrict__ rowb0, const float* __restrict__ rowa0, bool two, float w,
-                                                 size_t sstride, int nstems, int stem, int k, bool ratio)
+                                                 size_t sstride, int nstems, int stem, int k, bool ratio, size_t astride = 0)
 {
     float sum = 0.0f, own = 0.0f;
     for (int s = 0; s < nstems; ++s) {
         float v = rowb0[(size_t)s * sstride + k];
+        if constexpr (SEAM) { if (two) v = srt_blend(rowa0[(size_t)s * astride + k], v, w); }
+        else
         if (two) v = srt_blend(rowa0[(size_t)s * sstride + k], v, w);
         const float sq = v * v;
         sum = sum + sq;
@@ -243,11 +247,13 @@ __device__ __forceinline__ float srt_ratio_of_ov(const float* __restrict__ rowb0
 // device table of a packed batch (srtSeparateBatchMix: one matrix per track).  Either way the address is workgroup-uniform and an entry is loaded where it is used.
 struct SrtMixArg { const SrtIstftParams& p; int m; __device__ __forceinline__ float operator()(int s) const { return p.mix[m][s]; } };
 struct SrtMixTab { const float* __restrict__ row; __device__ __forceinline__ float operator()(int s) const { return row[s]; } };
-template <int NB, int JC, class GS>
+// SEAM: a0 may be a row of the mask seam carry (srt_ov_seam): its stems lie astem floats apart and its channels ach; unused otherwise (a0 is a mask row like r0).
+template <int NB, int JC, class GS, bool SEAM = false>
 __device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const GS& g, const float* __restrict__ r0, const float* __restrict__ a0, bool two, float w, bool ratio, int tid,
-                                              float (&hl)[NB], float (&hr)[NB])
+                                              float (&hl)[NB], float (&hr)[NB], size_t astem = 0, size_t ach = 0)
 {
     const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
+    const size_t as = SEAM ? astem : sstride, ac = SEAM ? ach : tf;
     const float eps = 1e-10f, e1 = eps / (float)p.nstems;
     auto value = [&](const float* __restrict__ b, const float* __restrict__ a, int km) {
         float v = b[km];
@@ -264,12 +270,12 @@ __device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const GS&
         for (int i = 0; i < JC; ++i) if (j0 + i < NB) { hl[j0 + i] = g(p.nstems); hr[j0 + i] = hl[j0 + i]; }
         if (r0 && ratio) {
             for (int s = 0; s < p.nstems; ++s) {
-                const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * sstride;
+                const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * as;
 #pragma unroll
                 for (int i = 0; i < JC; ++i) {
                     if (j0 + i >= NB) continue;
                     const int km = min(min(tid + 256 * (j0 + i), 2048), p.F - 1);
-                    const float vl = value(b, a, km), vr = value(b + tf, a + tf, km);
+                    const float vl = value(b, a, km), vr = value(b + tf, a + ac, km);
                     const float ql = vl * vl, qr = vr * vr;
                     suml[i] = suml[i] + ql; sumr[i] = sumr[i] + qr;
                 }
@@ -277,14 +283,14 @@ __device__ __forceinline__ void srt_mix_gains(const SrtIstftParams& p, const GS&
         }
         for (int s = 0; s < p.nstems; ++s) {
             const float gm = g(s);
-            const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * sstride;
+            const float* b = r0 + (size_t)s * sstride; const float* a = a0 + (size_t)s * as;
 #pragma unroll
             for (int i = 0; i < JC; ++i) {
                 if (j0 + i >= NB) continue;
                 const int km = min(min(tid + 256 * (j0 + i), 2048), p.F - 1);
                 float vl = 1.0f, vr = 1.0f;
                 if (r0) {
-                    vl = value(b, a, km); vr = value(b + tf, a + tf, km);
+                    vl = value(b, a, km); vr = value(b + tf, a + ac, km);
                     if (ratio) {
                         const float ml = vl * vl, mr = vr * vr;
                         vl = (ml + e1) / (suml[i] + eps); vr = (mr + e1) / (sumr[i] + eps);
@@ -331,9 +337,13 @@ __device__ __forceinline__ auto srt_mix_source(const SrtIstftParams& p, const Is
 // TRK (with OV): the view is a track of a packed batch - p.ntiles is the packed total there (the masks' stem stride), and srt_ov_row clamps the primary tile with the
 // track's own overlapped count, the argument ov_tiles (unused otherwise: a whole call's count is p.ntiles)
 // GTAB (with MIX): the matrix row is read from the view's device table (w.gain, SrtMixTab) instead of the launch arguments (p.mix, SrtMixArg)
-template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false, bool GTAB = false>
-__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0)
+// SEAM (with OV): the signal is a piece of a longer stream (srtSeparateHostStreamOverlap) - rows [0, O) of its first tile (srt_ov_seam) take their
+// blend partner `a` from the mask seam carry `seam` [nstems][2][O][F], what the previous piece's last tile held in rows [S, T); every other row as OV.  The choice
+// of base and strides is workgroup-uniform (scalar); a null seam (the stream's first piece) leaves the OV behaviour
+template <bool RATIO, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false, bool GTAB = false, bool SEAM = false>
+__device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0, const float* seam = nullptr)
 {
+    static_assert(!SEAM || (OV && !TRK), "the seam carry belongs to one signal's overlapped tiles");
     cf* sx = s_mem;                                      // this frame's staging buffer (and its exchange 2)
     cf* sy = s_mem + FFT_SMEM_F2;                        // this frame's exchange 1; the roles swap every frame
     cf* s_twb = s_mem + 2 * FFT_SMEM_F2;
@@ -404,8 +414,24 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
             // staging into sx: its last readers (exchange 1 of the previous frame, when it was `sy`) all passed that frame's
             // second barrier; the first barrier below also orders the twiddle table written before the loop
             OvRow ov = { 0, 0, false, 0.0f };
+            // SEAM: whether the row's partner is a row of the carry, and then the carry's strides in place of the masks' (stem 0, L of row ov.k at seam + ov.k * F)
+            bool sm = false;
+            size_t a_stem = 0, a_ch = 0;
             if constexpr (OV) {
                 ov = srt_ov_row(f, p.T, O, TRK ? ov_tiles : p.ntiles);
+                if constexpr (SEAM) {
+                    asm volatile("" : "+s"(seam));       // the carry's lane addresses are formed per frame: hoisted out of the frame loop they would be 2 x NB more resident VGPRs
+                    sm = srt_ov_seam(ov, O, seam);
+                    a_ch = sm ? (size_t)O * p.F : tf; a_stem = sm ? 2 * (size_t)O * p.F : (size_t)p.ntiles * 2 * tf;
+                    if (!RATIO && !MIX && has_mask && (ov.two || sm)) {      // as below, a from the carry on the piece's first O rows
+                        const float* aL = sm ? seam + (size_t)stem * a_stem + (size_t)ov.k * p.F : w.masks + ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
+#pragma unroll
+                        for (int j = 0; j < 9; ++j) {
+                            const int km = min(min(tid + 256 * j, 2048), p.F - 1);
+                            gl[j] = srt_blend(aL[km], gl[j], ov.w); gr[j] = srt_blend(aL[a_ch + km], gr[j], ov.w);
+                        }
+                    }
+                } else
                 if (!RATIO && !MIX && has_mask && ov.two) {      // cross-fade of the two tiles' masks: a (row k + S of the previous tile) + w (b - a).  The a rows are read HERE,
                     // not with the prefetch (18 more staged registers spill at two workgroups per CU); the other workgroup of the CU covers the wait
                     const float* aL = w.masks + ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
@@ -420,10 +446,15 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
                 if (has_mask && (p.ratio || OV)) {       // normalise this frame's mask values across the stems (they arrived with the spectrum rows)
                     const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                     const float* r0 = w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F;
+                    if constexpr (SEAM) asm volatile("" : "+s"(r0));      // (the same for the mask rows: with two sets of lane addresses resident across the frame loop this form spills 16 dwords)
 #pragma unroll
                     for (int j = 0; j < 9; ++j) {
                         const int km = min(min(tid + 256 * j, 2048), p.F - 1);
-                        if constexpr (OV) {              // every stem's masks, this one's included, are blended the same way before the squares are summed
+                        if constexpr (SEAM) {            // as OV, a from the carry on the piece's first O rows
+                            const float* a0 = sm ? seam + (size_t)ov.k * p.F : r0 - 2 * tf + (size_t)(p.T - O) * p.F;
+                            gl[j] = srt_ratio_of_ov<true>(r0, a0, ov.two || sm, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0, a_stem);
+                            gr[j] = srt_ratio_of_ov<true>(r0 + tf, a0 + a_ch, ov.two || sm, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0, a_stem);
+                        } else if constexpr (OV) {       // every stem's masks, this one's included, are blended the same way before the squares are summed
                             const float* a0 = r0 - 2 * tf + (size_t)(p.T - O) * p.F;
                             gl[j] = srt_ratio_of_ov(r0, a0, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
                             gr[j] = srt_ratio_of_ov(r0 + tf, a0 + tf, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
@@ -438,6 +469,8 @@ __device__ __forceinline__ void istft_ola_run(const SrtIstftParams& p, const Ist
                 const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                 const float* r0 = has_mask ? w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F : nullptr;
                 const float* a0 = OV && has_mask ? r0 - 2 * tf + (size_t)(p.T - O) * p.F : r0;
+                if constexpr (SEAM) srt_mix_gains<9, 3, decltype(gsrc), true>(p, gsrc, r0, sm && has_mask ? seam + (size_t)ov.k * p.F : a0, ov.two || sm, ov.w, p.ratio && p.nstems > 1, tid, gl, gr, a_stem, a_ch);
+                else
                 srt_mix_gains<9, 3>(p, gsrc, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, tid, gl, gr);
                 if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, gsrc, ext + fu, p.ext_stem); eR = srt_mix_chain(p, gsrc, ext + fu + 1, p.ext_stem); }
             }
@@ -682,9 +715,11 @@ __global__ void __launch_bounds__(256, 3) srt_stft_ov_kernel(const SrtStftParams
 // EXT: as istft_ola_run
 // MIX: as istft_ola_run (RATIO = M16 = false)
 // TRK, GTAB: as istft_ola_run
-template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false, bool GTAB = false>
-__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0)
+// SEAM: as istft_ola_run (float masks: M16 = false)
+template <int NM, bool RATIO, bool M16, bool OV = false, bool EXT = false, bool MIX = false, bool TRK = false, bool GTAB = false, bool SEAM = false>
+__device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const IstftView& w, int stem, int run, int G, cf* s_mem, int O = 0, int ov_tiles = 0, const float* seam = nullptr)
 {
+    static_assert(!SEAM || (OV && !TRK && !M16), "the seam carry belongs to one signal's overlapped tiles and holds floats");
     cf* sx = s_mem;
     cf* mir = s_mem + FFT_SMEM_F2;
     cf* s_twb = mir + FFT_MIR_F2;
@@ -763,8 +798,23 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
             // thread's own transform inputs n2 = j; their partners 4096 - k go through `mir` to thread 256 - tid (slot 15 - j).
             cf v[16];
             OvRow ov = { 0, 0, false, 0.0f };
+            bool sm = false;                             // SEAM: as in istft_ola_run
+            size_t a_stem = 0, a_ch = 0;
             if constexpr (OV) {
                 ov = srt_ov_row(f, p.T, O, TRK ? ov_tiles : p.ntiles);
+                if constexpr (SEAM) {
+                    asm volatile("" : "+s"(seam));       // the carry's lane addresses are formed per frame: hoisted out of the frame loop they would be 2 x NB more resident VGPRs
+                    sm = srt_ov_seam(ov, O, seam);
+                    a_ch = sm ? (size_t)O * p.F : tf; a_stem = sm ? 2 * (size_t)O * p.F : (size_t)p.ntiles * 2 * tf;
+                    if (!RATIO && !MIX && has_mask && (ov.two || sm)) {      // as below, a from the carry on the piece's first O rows
+                        const float* aL = sm ? seam + (size_t)stem * a_stem + (size_t)ov.k * p.F : w.masks + ((size_t)(stem * p.ntiles + ov.j1 - 1) * 2) * tf + (size_t)(ov.k + p.T - O) * p.F;
+#pragma unroll
+                        for (int j = 0; j < NM; ++j) {
+                            const int km = min(tid + 256 * j, p.F - 1);
+                            gl[j] = srt_blend(aL[km], gl[j], ov.w); gr[j] = srt_blend(aL[a_ch + km], gr[j], ov.w);
+                        }
+                    }
+                } else
                 if (!RATIO && !MIX && has_mask && ov.two) {      // cross-fade of the two tiles' masks (halves are converted first): a (row k + S of the previous tile) + w (b - a).
                     // The a rows are read HERE, not with the prefetch: eight more staged registers do not fit the 168 of three workgroups per CU (9 dwords
                     // spilled when tried); the wait is covered by the CU's other workgroups and falls on O of every T - O frames only
@@ -785,7 +835,11 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
 #pragma unroll
                     for (int j = 0; j < NM; ++j) {
                         const int km = min(tid + 256 * j, p.F - 1);
-                        if constexpr (OV) {              // every stem's masks, this one's included, are blended the same way before the squares are summed
+                        if constexpr (SEAM) {            // as OV, a from the carry on the piece's first O rows
+                            const float* a0 = sm ? seam + (size_t)ov.k * p.F : r0 - 2 * tf + (size_t)(p.T - O) * p.F;
+                            gl[j] = srt_ratio_of_ov<true>(r0, a0, ov.two || sm, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0, a_stem);
+                            gr[j] = srt_ratio_of_ov<true>(r0 + tf, a0 + a_ch, ov.two || sm, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0, a_stem);
+                        } else if constexpr (OV) {       // every stem's masks, this one's included, are blended the same way before the squares are summed
                             const float* a0 = r0 - 2 * tf + (size_t)(p.T - O) * p.F;
                             gl[j] = srt_ratio_of_ov(r0, a0, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
                             gr[j] = srt_ratio_of_ov(r0 + tf, a0 + tf, ov.two, ov.w, (size_t)p.ntiles * 2 * tf, p.nstems, stem, km, p.ratio != 0);
@@ -800,6 +854,8 @@ __device__ __forceinline__ void istft_ola3_run(const SrtIstftParams& p, const Is
                 const int tile = OV ? ov.j1 : f / p.T, t = OV ? ov.k : f % p.T;
                 const float* r0 = has_mask ? w.masks + ((size_t)tile * 2) * tf + (size_t)t * p.F : nullptr;
                 const float* a0 = OV && has_mask ? r0 - 2 * tf + (size_t)(p.T - O) * p.F : r0;
+                if constexpr (SEAM) srt_mix_gains<NM, NM, decltype(gsrc), true>(p, gsrc, r0, sm && has_mask ? seam + (size_t)ov.k * p.F : a0, ov.two || sm, ov.w, p.ratio && p.nstems > 1, tid, gl, gr, a_stem, a_ch);
+                else
                 srt_mix_gains<NM, NM>(p, gsrc, r0, a0, OV && ov.two, ov.w, p.ratio && p.nstems > 1, tid, gl, gr);
                 if constexpr (EXT) { const size_t fu = (size_t)__builtin_amdgcn_readfirstlane(f) * 2; eL = srt_mix_chain(p, gsrc, ext + fu, p.ext_stem); eR = srt_mix_chain(p, gsrc, ext + fu + 1, p.ext_stem); }
             }
@@ -885,6 +941,37 @@ __global__ void __launch_bounds__(256, 2) srt_istft_ola_mix_kernel(const SrtIstf
     istft_ola_run<false, OV, EXT, true>(p, istft_view(p), m, run, G, s_mem, O);
 }
 
+// A piece of a longer stream under overlapped tiles (srtSeparateHostStreamOverlap): the overlap forms above with the SEAM bodies - the piece's
+// first O rows blend with the mask seam carry `seam` ([nstems][2][O][F] floats, srt_mask_seam_save_kernel).  Float masks only; the workgroups per CU of the OV siblings.
+template <int NM, bool RATIO, bool EXT>
+__global__ void __launch_bounds__(256, RATIO ? 2 : 3) srt_istft_ola3_seam_kernel(const SrtIstftParams p, int G, int O, const float* __restrict__ seam)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, RATIO, false, true, EXT, false, false, false, true>(p, istft_view(p), stem, run, G, s_mem, O, 0, seam);
+}
+template <bool RATIO, bool EXT>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_seam_kernel(const SrtIstftParams p, int G, int O, const float* __restrict__ seam)
+{
+    const int pos = srt_xcd_order(gridDim.x), stem = pos % p.nstems, run = pos / p.nstems;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<RATIO, true, EXT, false, false, false, true>(p, istft_view(p), stem, run, G, s_mem, O, 0, seam);
+}
+template <int NM, bool EXT>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola3_seam_bus_kernel(const SrtIstftParams p, int G, int O, const float* __restrict__ seam)
+{
+    const int pos = srt_xcd_order(gridDim.x), m = pos % p.n_out, run = pos / p.n_out;
+    __shared__ cf s_mem[ISTFT_OLA3_LDS_F2];
+    istft_ola3_run<NM, false, false, true, EXT, true, false, false, true>(p, istft_view(p), m, run, G, s_mem, O, 0, seam);
+}
+template <bool EXT>
+__global__ void __launch_bounds__(256, 2) srt_istft_ola_seam_bus_kernel(const SrtIstftParams p, int G, int O, const float* __restrict__ seam)
+{
+    const int pos = srt_xcd_order(gridDim.x), m = pos % p.n_out, run = pos / p.n_out;
+    __shared__ cf s_mem[ISTFT_OLA_LDS_F2];
+    istft_ola_run<false, true, EXT, true, false, false, true>(p, istft_view(p), m, run, G, s_mem, O, 0, seam);
+}
+
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_tiles)
 {
     // short signals (one tile, the real-time regime): fewer frames per workgroup so that the frames spread over the CUs
@@ -907,7 +994,7 @@ int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_t
     return srt_launch_status();
 }
 
-int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
+int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap, const float* seam)
 {
     if (p.frames <= 0) return 0;
     // overlapped tiles: p.ntiles tiles of stride T - O must cover every frame (the kernels index masks by srt_ov_row); without masks there is nothing to blend
@@ -933,7 +1020,24 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap)
     // one stem per workgroup: 32 accumulator + 54 prefetch registers + the FFT fit in 256 VGPRs at 2 workgroups per CU
     // F > 1024: eight mask registers per channel do not fit the 168-VGPR budget of the three-per-CU form (22 dwords would spill): the two-per-CU kernel
     if (p.ext && (!p.masks || p.ext_stem < (size_t)p.frames * 2)) return -1;      // the table holds [frames][2] gains per stem, derived from masks
-    if (p.n_out) {                                       // stem remix: the MIX forms by the same F rule (ratio is their run-time flag)
+    if (seam) {                                          // a piece of a longer stream: the SEAM forms, chosen as the overlap forms below are (float masks only)
+        if (O <= 0 || p.masks16) return -1;
+        const bool ratio = p.ratio && p.nstems > 1, big = p.F > 1024;
+        const dim3 grid(blocks * ncol), blk(256);
+        if (p.n_out) {
+            if (big) { if (p.ext) SRT_LAUNCH((srt_istft_ola_seam_bus_kernel<true>), grid, blk, 0, s, p, G, O, seam); else SRT_LAUNCH((srt_istft_ola_seam_bus_kernel<false>), grid, blk, 0, s, p, G, O, seam); }
+            else if (p.ext) SRT_LAUNCH((srt_istft_ola3_seam_bus_kernel<4, true>), grid, blk, 0, s, p, G, O, seam);
+            else SRT_LAUNCH((srt_istft_ola3_seam_bus_kernel<4, false>), grid, blk, 0, s, p, G, O, seam);
+        } else if (big) {
+            if (ratio) { if (p.ext) SRT_LAUNCH((srt_istft_ola_seam_kernel<true, true>), grid, blk, 0, s, p, G, O, seam); else SRT_LAUNCH((srt_istft_ola_seam_kernel<true, false>), grid, blk, 0, s, p, G, O, seam); }
+            else if (p.ext) SRT_LAUNCH((srt_istft_ola_seam_kernel<false, true>), grid, blk, 0, s, p, G, O, seam);
+            else SRT_LAUNCH((srt_istft_ola_seam_kernel<false, false>), grid, blk, 0, s, p, G, O, seam);
+        } else if (ratio) { if (p.ext) SRT_LAUNCH((srt_istft_ola3_seam_kernel<4, true, true>), grid, blk, 0, s, p, G, O, seam); else SRT_LAUNCH((srt_istft_ola3_seam_kernel<4, true, false>), grid, blk, 0, s, p, G, O, seam); }
+        else if (p.ext) SRT_LAUNCH((srt_istft_ola3_seam_kernel<4, false, true>), grid, blk, 0, s, p, G, O, seam);
+        else SRT_LAUNCH((srt_istft_ola3_seam_kernel<4, false, false>), grid, blk, 0, s, p, G, O, seam);
+        return srt_launch_status();
+    }
+    if (p.n_out) {                                      // stem remix: the MIX forms by the same F rule (ratio is their run-time flag)
         const dim3 grid(blocks * p.n_out);
         if (p.F > 1024) {
             if (O > 0 && p.ext) SRT_LAUNCH((srt_istft_ola_mix_kernel<true, true>), grid, dim3(256), 0, s, p, G, O);
@@ -1010,9 +1114,11 @@ __device__ __forceinline__ void srt_mask_load16(const float* __restrict__ masks,
 // nt: the tile count srt_ov_row clamps the primary tile with (OV only): p.ntiles for a whole call, the track's own in a packed batch (where p.ntiles is the packed
 // total, the stem stride)
 // TRK: the row belongs to a track of a packed batch - mo / eo: its first mask element (halves for M16) / its first float of a stem's table
-template <int NS, bool M16, bool RATIO, bool OV, bool TRK = false>
-__device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int O, int f, int c, int lane, int nt, size_t mo = 0, size_t eo = 0)
+// SEAM (with OV, float masks): the rows are a piece's of a longer stream - on its first O rows (srt_ov_seam) `a` comes from the mask seam carry, as in the inverse kernels
+template <int NS, bool M16, bool RATIO, bool OV, bool TRK = false, bool SEAM = false>
+__device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int O, int f, int c, int lane, int nt, size_t mo = 0, size_t eo = 0, const float* __restrict__ seam = nullptr)
 {
+    static_assert(!SEAM || (OV && !TRK && !M16), "the seam carry belongs to one signal's overlapped tiles and holds floats");
     constexpr int V = M16 ? 8 : 4;                      // mask values per 16-byte load
     const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf;
     int tile = f / p.T, t = f % p.T;
@@ -1021,6 +1127,9 @@ __device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int 
     size_t bo = ((size_t)tile * 2 + c) * tf + (size_t)t * p.F;                           // stem 0's row in the primary tile
     if constexpr (TRK) bo += mo;
     const size_t ao = ov.two ? bo - 2 * tf + (size_t)(p.T - O) * p.F : bo;              // ... and row k + S of the previous tile
+    const bool sm = SEAM && srt_ov_seam(ov, O, seam);                                   // ... or row k of the carry: its base, first element and stem stride
+    const float* __restrict__ const am = sm ? seam : p.masks;
+    const size_t so = sm ? ((size_t)c * O + ov.k) * p.F : ao, as = sm ? 2 * (size_t)O * p.F : sstride;
     float sum[NS];
 #pragma unroll
     for (int s = 0; s < NS; ++s) sum[s] = 0.0f;
@@ -1031,7 +1140,8 @@ __device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int 
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 srt_mask_load16<M16>(p.masks, (size_t)s * sstride + bo + k, b[s]);
-                if constexpr (TWO) srt_mask_load16<M16>(p.masks, (size_t)s * sstride + ao + k, a[s]);
+                if constexpr (TWO && SEAM) srt_mask_load16<M16>(am, (size_t)s * as + so + k, a[s]);
+                else if constexpr (TWO) srt_mask_load16<M16>(p.masks, (size_t)s * sstride + ao + k, a[s]);
                 else {
 #pragma unroll
                     for (int j = 0; j < V; ++j) a[s][j] = b[s][j];
@@ -1051,7 +1161,7 @@ __device__ __forceinline__ void srt_mask_ext_row(const SrtMaskExtParams& p, int 
             }
         }
     };
-    if (OV && ov.two) walk(std::true_type{}); else walk(std::false_type{});
+    if (OV && (ov.two || sm)) walk(std::true_type{}); else walk(std::false_type{});
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         float v = sum[s];
@@ -1078,10 +1188,28 @@ __global__ void __launch_bounds__(256) srt_mask_ext_kernel(const SrtMaskExtParam
     default: srt_mask_ext_row<8, M16, RATIO, OV>(p, O, f, c, lane, p.ntiles); break;
     }
 }
+// the table of a piece of a longer stream (srtSeparateHostStreamOverlap): the OV form with the SEAM rows
+template <bool RATIO>
+__global__ void __launch_bounds__(256) srt_mask_ext_seam_kernel(const SrtMaskExtParams p, int O, const float* __restrict__ seam)
+{
+    const int wave = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (wave >= p.rows * 2) return;
+    const int f = wave >> 1, c = wave & 1;
+    switch (p.nstems) {
+    case 1: srt_mask_ext_row<1, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    case 2: srt_mask_ext_row<2, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    case 3: srt_mask_ext_row<3, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    case 4: srt_mask_ext_row<4, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    case 5: srt_mask_ext_row<5, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    case 6: srt_mask_ext_row<6, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    case 7: srt_mask_ext_row<7, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    default: srt_mask_ext_row<8, false, RATIO, true, false, true>(p, O, f, c, lane, p.ntiles, 0, 0, seam); break;
+    }
+}
 #pragma clang fp contract(fast)
 
 // the form follows the inverse launchers' gates: ratio when p.ratio && p.nstems > 1, halves never with the ratio, the overlap only with O > 0
-int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap)
+int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap, const float* seam)
 {
     if (p.rows <= 0) return 0;
     static_assert(SRT_MAX_STEMS == 8, "srt_mask_ext_kernel dispatches on 1..8 stems");
@@ -1092,6 +1220,12 @@ int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap)
     const bool ratio = p.ratio && p.nstems > 1;
     if (p.masks16 && (ratio || p.F > 1024)) return -1;
     const dim3 grid((p.rows * 2 + 3) / 4), block(256);
+    if (seam) {                                          // a piece of a longer stream: 16-byte loads from the carry too
+        if (overlap <= 0 || p.masks16 || ((uintptr_t)seam & 15) != 0) return -1;
+        if (ratio) SRT_LAUNCH((srt_mask_ext_seam_kernel<true>), grid, block, 0, s, p, overlap, seam);
+        else SRT_LAUNCH((srt_mask_ext_seam_kernel<false>), grid, block, 0, s, p, overlap, seam);
+        return srt_launch_status();
+    }
     if (overlap > 0) {
         if (ratio) SRT_LAUNCH((srt_mask_ext_kernel<false, true, true>), grid, block, 0, s, p, overlap);
         else if (p.masks16) SRT_LAUNCH((srt_mask_ext_kernel<true, false, true>), grid, block, 0, s, p, overlap);
@@ -1508,6 +1642,26 @@ int srt_launch_carry(float* out, size_t plane_len, int nplanes, size_t tail, flo
 {
     if (first && last) return 0;
     SRT_LAUNCH(srt_carry_kernel, dim3((SRT_FFT - SRT_HOP) / 256, nplanes), dim3(256), 0, s, out, plane_len, tail, carry, first, last);
+    return srt_launch_status();
+}
+
+// The mask seam carry of overlapped tiles across the pieces of a long stream (srtSeparateHostStreamOverlap): the next piece's forward overwrites
+// the mask buffer, and rows [0, O) of its first tile blend with rows [S, T) of this piece's last tile - those O * F floats per (stem, channel), contiguous in the
+// tile, are copied out.  Bandwidth-bound: one 16-byte load and store per thread, blockIdx.y = stem * 2 + channel.
+__global__ void __launch_bounds__(256) srt_mask_seam_save_kernel(const float4* __restrict__ masks4, float4* __restrict__ seam4, size_t stem4, size_t tf4, size_t row4, unsigned n4)
+{
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    const int st = blockIdx.y >> 1, c = blockIdx.y & 1;
+    if (i < n4) seam4[(size_t)blockIdx.y * n4 + i] = masks4[(size_t)st * stem4 + (size_t)c * tf4 + row4 + i];
+}
+
+int srt_launch_mask_seam_save(const float* masks, int nstems, int ntiles, int T, int F, int overlap, float* seam, hipStream_t s)
+{
+    if (!masks || !seam || nstems < 1 || ntiles < 1 || overlap < 1 || overlap > T / 2 || F < 4 || F % 4) return -1;
+    if ((((uintptr_t)masks | (uintptr_t)seam) & 15) != 0) return -1;
+    const size_t tf4 = (size_t)T * F / 4, n4 = (size_t)overlap * F / 4;
+    const size_t row4 = (size_t)(ntiles - 1) * 2 * tf4 + (size_t)(T - overlap) * F / 4;                  // row S of the last tile, channel L
+    SRT_LAUNCH(srt_mask_seam_save_kernel, dim3((unsigned)((n4 + 255) / 256), nstems * 2), dim3(256), 0, s, (const float4*)masks, (float4*)seam, (size_t)ntiles * 2 * tf4, tf4, row4, (unsigned)n4);
     return srt_launch_status();
 }
 

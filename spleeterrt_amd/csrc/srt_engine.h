@@ -38,6 +38,8 @@ struct HostStaging {
     unsigned long long* d_clip;                        // [SRT_MAX_STEMS] clipped-sample counters, then the pack's workgroup counts
     // srtSeparateHostWiener's store: every piece's spectrum and fp32 masks (host_wiener_layout, srt_host.hip), grow-only like the rest
     char* d_wstore; size_t wstore_cap;                 // bytes
+    // srtSeparateHostStreamOverlap's mask seam carry [n_stems][2][O][F] (srt_mask_seam_save_kernel), grow-only like the rest
+    float* d_mseam; size_t mseam_cap;                  // floats
 };
 
 // What the last forward left behind, for the calls that come after it (srtCopyTensor's taps, the inverse transform of srtSeparate).  forward_range and
@@ -184,9 +186,13 @@ void graph_key_opts(GraphKey* k, const SepOpts& o);
 SrtDspTables tables_of(const srt_engine* e);
 int ensure_wiener_ws(srt_engine* e);
 int ensure_mask_ext_table(srt_engine* e, const char* who);
-int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks = nullptr, int ntracks = 0);
+int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks = nullptr, int ntracks = 0, const float* seam = nullptr);
 bool masks16_wanted(const srt_engine* e, const SrtSwitches& sw, const SepOpts& o);
 int separate_run(srt_engine* e, const SepOpts& o, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_out);
+// ... a piece of srtSeparateHostStreamOverlap's plan (srtHostOverlapPieces): `tiles` overlapped tiles over stft_rows spectrum rows, of which the piece owns (inverts)
+// the first own_rows; seam: the mask seam carry of the piece before it (nullptr: the stream's first piece)
+struct HostOvPiece { size_t tiles, own_rows, stft_rows; const float* seam; };
+int separate_piece(srt_engine* e, const SrtSwitches& sw, const SepOpts& o, const float* d_L, const float* d_R, size_t n, size_t frames, const HostOvPiece& pc, float* d_seam, float* d_out);
 int cli_time_residual(srt_engine* e, const float* d_L, const float* d_R, size_t n, int stems, float* d_out, size_t len, size_t lo = 0, size_t hi = 0);
 int cli_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, int stems, float* d_out, bool residual_now);
 int cli_check(srt_engine* e, int stems);

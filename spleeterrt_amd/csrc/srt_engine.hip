@@ -156,6 +156,7 @@ static void free_staging(srt_engine* e)
     if (h.d_carry) hipFree(h.d_carry);
     if (h.d_clip) hipFree(h.d_clip);
     if (h.d_wstore) hipFree(h.d_wstore);
+    if (h.d_mseam) hipFree(h.d_mseam);
     if (h.s_in) hipStreamDestroy(h.s_in);
     if (h.s_out) hipStreamDestroy(h.s_out);
     memset(&h, 0, sizeof h);

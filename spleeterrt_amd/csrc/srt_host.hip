@@ -63,8 +63,45 @@ static int ensure_staging16(srt_engine* e, size_t in_frames, size_t out_frames)
     return 0;
 }
 
+// srtSeparateHostStreamOverlap's mask seam carry, after ensure_staging: grow-only like the rest
+static int ensure_mask_seam(srt_engine* e, size_t floats)
+{
+    HostStaging& h = e->hs;
+    if (floats <= h.mseam_cap) return 0;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (h.d_mseam) { hipFree(h.d_mseam); h.d_mseam = nullptr; h.mseam_cap = 0; }
+    HIPCHK(hipMalloc((void**)&h.d_mseam, floats * sizeof(float)));
+    h.mseam_cap = floats;
+    return 0;
+}
+
+// Piece p of a stream of `rows` rows under overlap O on an engine of P = max_tiles (N = overlap_tiles(rows, T, O), p * P < N): tiles
+// [pP, min((p + 1) P, N)); it owns the rows whose primary tile is one of them - [pPS, (p + 1) PS), the last piece up to `rows` - and analyses the rows its tiles
+// cover, (tiles - 1) S + T from row0 (the last piece: what is left), O of them owned by the next piece.  O = 0: chunks of P * T rows.
+static srt_host_piece host_ov_piece(size_t rows, int T, int O, int P, size_t N, size_t p)
+{
+    const size_t S = (size_t)(T - O);
+    srt_host_piece pc;
+    pc.tile0 = p * P;
+    pc.tiles = N - pc.tile0 < (size_t)P ? N - pc.tile0 : (size_t)P;
+    pc.row0 = pc.tile0 * S;
+    pc.own_rows = pc.tile0 + pc.tiles == N ? rows - pc.row0 : pc.tiles * S;
+    const size_t span = (pc.tiles - 1) * S + T;
+    pc.stft_rows = rows - pc.row0 < span ? rows - pc.row0 : span;
+    return pc;
+}
+
+size_t srtHostOverlapPieces(size_t rows, int T, int overlap_rows, int max_tiles, srt_host_piece* pieces, size_t max_pieces)
+{
+    if (T < 1 || !overlap_ok(overlap_rows, T)) { fail(-1, "srtHostOverlapPieces: need T >= 1 and 0 <= overlap_rows <= T / 2"); return 0; }
+    if (max_tiles < 1) { fail(-1, "srtHostOverlapPieces: need max_tiles >= 1"); return 0; }
+    const size_t N = overlap_tiles(rows, T, overlap_rows), count = (N + max_tiles - 1) / max_tiles;
+    for (size_t p = 0; pieces && p < count && p < max_pieces; ++p) pieces[p] = host_ov_piece(rows, T, overlap_rows, max_tiles, N, p);
+    return count;
+}
+
 static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_t n, size_t frames, size_t rows, void* h_out, unsigned flags, int cli_stems,
-                       SrtSeam seam = SrtSeam{0, nullptr, false}, unsigned long long* h_clipped = nullptr);
+                       SrtSeam seam = SrtSeam{0, nullptr, false}, unsigned long long* h_clipped = nullptr, int call_overlap = -1);
 
 // Host-buffer form of srtSeparateCli for plain-C callers (the CLI harness): synchronous.  A file that fits the engine's capacity
 // (max_tiles tiles) is one resident batch: H2D, chain, D2H.  A longer one - any length, as the reference's tile loop over a
@@ -128,26 +165,39 @@ int srtSeparateCliHostIo(srt_engine* e, const void* h_in, const void* h_in2, siz
 // into d_in[b] on the compute stream (ev_cmp[b] releases both).  SRT_HOST_OUT_PCM16: h_out is int16 [planes / 2][total_len][2]; after the seam add (and the CLI
 // flows' subtraction) the samples this chunk downloads - each plane's [0, take) - are packed into d_out16[b], so every output sample is quantised and counted
 // once, and ev_cmp[b] is recorded after the pack.  h_clipped [stems]: the clipped samples of each stem (zero without the flag).
+// call_overlap >= 0: srtSeparateHostStreamOverlap - the call's own overlap in place of the engine's, which is then neither read nor refused.  The
+// chunks are the pieces of host_ov_piece: a piece uploads and analyses stft_rows rows, of which it inverts, stitches and downloads the first own_rows
+// (separate_piece); after every piece but the last the mask rows the next piece's first O rows blend with are kept (srt_mask_seam_save_kernel).  At 0 the pieces are
+// the chunks and every launch is the one the engine's path issues.
 static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_t n, size_t frames, size_t rows, void* h_out_, unsigned flags, int cli_stems, SrtSeam seam,
-                       unsigned long long* h_clipped)
+                       unsigned long long* h_clipped, int call_overlap)
 {
+    const char* const who = call_overlap >= 0 ? "srtSeparateHostStreamOverlap" : "srtSeparateHostStream";
     const bool in16 = flags & SRT_HOST_IN_PCM16, out16 = flags & SRT_HOST_OUT_PCM16;
-    if (!e || !h_in || (!in16 && !h_in2) || !h_out_) return fail(-1, "srtSeparateHostStream: null argument");
-    if (in16 && h_in2) return fail(-1, "srtSeparateHostStream: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)");
-    if ((in16 || out16) && seam.out_stride) return fail(-1, "srtSeparateHostStream: the 16-bit PCM forms do not apply to a tile range of a multi-device stream (the seam join adds floats on the host)");
+    if (!e || !h_in || (!in16 && !h_in2) || !h_out_) return fail(-1, "%s: null argument", who);
+    if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
+    if ((in16 || out16) && seam.out_stride) return fail(-1, "%s: the 16-bit PCM forms do not apply to a tile range of a multi-device stream (the seam join adds floats on the host)", who);
     const float *h_L = (const float*)h_in, *h_R = (const float*)h_in2;
     float* h_out = (float*)h_out_;
-    if (rows < 1 || frames > rows) return fail(-1, "srtSeparateHostStream: need 1 <= frames <= rows");
-    const SepOpts o = engine_opts(e);                   // once for the call: the refusals, the plane count and every chunk's separate_run
-    if (o.overlap) return fail(-1, OVERLAP_REFUSED, "srtSeparateHostStream");   // the blend would have to cross the chunk seams
-    if (o.wiener) return fail(-1, "srtSeparateHostStream: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)");
+    if (rows < 1 || frames > rows) return fail(-1, "%s: need 1 <= frames <= rows", who);
+    SepOpts o = engine_opts(e);                         // once for the call: the refusals, the plane count and every chunk's separate_run
+    if (call_overlap >= 0) {
+        if (!overlap_ok(call_overlap, e->cfg.T)) return fail(-1, "%s: overlap_rows must be 0 .. T / 2", who);
+        o.overlap = call_overlap;
+    } else if (o.overlap) return fail(-1, OVERLAP_REFUSED, who);   // the blend crosses the chunk seams: srtSeparateHostStreamOverlap carries it
+    if (o.wiener) return fail(-1, "%s: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): use srtSeparate, or srtSetWiener(e, 0)", who);
+    const int O = o.overlap;                            // > 0 only on srtSeparateHostStreamOverlap's path
+    if (call_overlap >= 0) for (int s = 0; s < e->cfg.n_stems; ++s) if (!e->have_coeff[s]) return fail(-5, "%s: weights not set for every stem", who);
     DeviceScope ds(e->device);
     const int S = cli_stems ? cli_stems : o.n_out ? o.n_out : e->cfg.n_stems, T = e->cfg.T, NP = S * 2;     // pairs staged, carried, packed and downloaded: the outputs of a remix
     const size_t chunk_rows = (size_t)e->cfg.max_tiles * T, tail = SRT_FFT - SRT_HOP;
-    const size_t nchunks = (rows + chunk_rows - 1) / chunk_rows, total_len = seam.out_stride ? seam.out_stride : srtIstftLength(rows);
+    const size_t ntiles_all = overlap_tiles(rows, T, O);
+    const size_t nchunks = (ntiles_all + e->cfg.max_tiles - 1) / e->cfg.max_tiles, total_len = seam.out_stride ? seam.out_stride : srtIstftLength(rows);
     const size_t in_cap = chunk_rows * SRT_HOP + tail, out_cap = srtIstftLength(chunk_rows);
     int rc = ensure_staging(e, 2 * in_cap, (size_t)NP * out_cap, (size_t)NP * tail, 2);
     if (rc) return rc;
+    if (O && nchunks > 1 && (rc = ensure_mask_seam(e, (size_t)e->cfg.n_stems * 2 * O * e->cfg.F))) return rc;
+    const SrtSwitches sw = srt_read_switches();
     if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? in_cap : 0, out16 ? (size_t)S * out_cap : 0))) return rc;
     HostStaging& h = e->hs;
     if (h_clipped) memset(h_clipped, 0, (size_t)S * sizeof *h_clipped);
@@ -167,10 +217,11 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
 #define STEP(x) do { if (er == hipSuccess) er = (x); } while (0)
     for (size_t c = 0; c < nchunks && er == hipSuccess && rc == 0; ++c) {
         const int b = (int)(c & 1);
-        const size_t row0 = c * chunk_rows, row1 = row0 + chunk_rows < rows ? row0 + chunk_rows : rows, crow = row1 - row0;
+        const srt_host_piece pc = host_ov_piece(rows, T, O, e->cfg.max_tiles, ntiles_all, c);
+        const size_t row0 = pc.row0, crow = pc.own_rows, row1 = row0 + pc.stft_rows;       // rows [row0, row1) go up and are analysed, the first crow of them come down
         const size_t s0 = row0 * SRT_HOP, send = row1 * SRT_HOP + tail < n ? row1 * SRT_HOP + tail : n;
         const size_t ns = send > s0 ? send - s0 : 0;
-        const size_t cfr = frames > row0 ? (frames - row0 < crow ? frames - row0 : crow) : 0;
+        const size_t cfr = frames > row0 ? (frames - row0 < pc.stft_rows ? frames - row0 : pc.stft_rows) : 0;
         const size_t clen = srtIstftLength(crow);
         // upload: the input buffer is free once the compute that read it two chunks ago has finished
         if (c >= 2) STEP(hipStreamWaitEvent(h.s_in, h.ev_cmp[b], 0));
@@ -188,6 +239,10 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
             TimerScope ts(e, "pcm16_unpack");
             if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
         }
+        if (O) {
+            const HostOvPiece hp = { pc.tiles, pc.own_rows, pc.stft_rows, c ? h.d_mseam : nullptr };
+            rc = separate_piece(e, sw, o, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, hp, c + 1 < nchunks ? h.d_mseam : nullptr, h.d_out[b]);
+        } else
         rc = cli_stems ? cli_issue(e, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, crow, cli_stems, h.d_out[b], false)
                        : separate_run(e, o, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, crow, h.d_out[b]);
         if (rc) break;
@@ -247,6 +302,17 @@ int srtSeparateHostStreamIo(srt_engine* e, const void* h_in, const void* h_in2, 
 int srtSeparateHostStream(srt_engine* e, const float* h_L, const float* h_R, size_t n, size_t frames, size_t rows, float* h_out)
 {
     return srtSeparateHostStreamEx(e, h_L, h_R, n, frames, rows, h_out, 0);
+}
+
+int srtSeparateHostStreamOverlap(srt_engine* e, const void* h_in, const void* h_in2, size_t n, int overlap_rows, void* h_out, unsigned flags, unsigned long long* h_clipped)
+{
+    static const char* const who = "srtSeparateHostStreamOverlap";
+    if (!e || !h_in || !h_out) return fail(-1, "%s: null argument", who);
+    if (flags & ~SRT_HOST_FLAGS) return fail(-1, "%s: unknown flag bits", who);
+    if (n < SRT_FFT) return fail(-1, "%s: need at least 4096 samples", who);
+    if (overlap_rows < 0) return fail(-1, "%s: overlap_rows must be 0 .. T / 2", who);
+    if (srtStftRows(n) > (size_t)0x7fffffff - 4) return fail(-1, "%s: more than 2^31 rows", who);
+    return host_stream(e, h_in, h_in2, n, srtStftFrames(n), srtStftRows(n), h_out, flags, 0, SrtSeam{0, nullptr, false}, h_clipped, overlap_rows);
 }
 
 // ------------------------------------------------------------------------------------------- the Wiener filter over a host stream of any length

@@ -230,11 +230,15 @@ struct SrtMaskExtParams {
     int ratio;                // as SrtIstftParams::ratio
     float* ext; size_t ext_stem;
 };
-int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap = 0);
+int srt_launch_mask_ext(const SrtMaskExtParams& p, hipStream_t s, int overlap = 0, const float* seam = nullptr);      // seam: as srt_launch_istft (the table of a piece)
 // overlap > 0 (srtSetOverlap): consecutive network tiles share `overlap` rows - p.mag / p.masks are in the overlapped layout of ov_tiles / p.ntiles =
 // srtOverlapTiles(rows) tiles and the kernels' overlap instantiations run; 0: the back-to-back layout and the kernels as they always were
 int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap = 0, int ov_tiles = 0);
-int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap = 0);
+// seam (with overlap > 0 and float masks): the signal is a piece of a longer stream and `seam` the mask seam carry [nstems][2][overlap][F] of the piece before it
+// (srt_launch_mask_seam_save) - the SEAM instantiations run, whose first `overlap` rows blend with the carry; nullptr: a whole signal, the kernels as they were
+int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap = 0, const float* seam = nullptr);
+// rows [T - overlap, T) of the last of ntiles tiles of every stem and channel of masks [nstems][ntiles][2][T][F] (floats) -> seam [nstems][2][overlap][F]
+int srt_launch_mask_seam_save(const float* masks, int nstems, int ntiles, int T, int F, int overlap, float* seam, hipStream_t s);
 // packed batch of independent tracks (srtSeparateBatch): one row of the device-resident track table per track
 struct SrtBatchTrack {
     const float* L; const float* R; size_t n;    // the track's PCM, n >= 4096 samples

@@ -18,6 +18,10 @@ __device__ __forceinline__ OvRow srt_ov_row(int f, int T, int O, int ntiles)
     r.w = ((float)r.k + 0.5f) / (float)O;
     return r;
 }
+// A piece of a longer stream (srtSeparateHostStreamOverlap): rows [0, O) of the piece's first tile have their partner in the PREVIOUS piece's last
+// tile, rows [S, T), which that piece left in the mask seam carry [nstems][2][O][F] (srt_mask_seam_save_kernel).  True for those rows when a carry is given; the
+// row then blends a = carry[stem][channel][k] with b = its own row under the same w.  Workgroup-uniform like everything above.
+__device__ __forceinline__ bool srt_ov_seam(const OvRow& r, int O, const float* seam) { return seam != nullptr && r.j1 == 0 && r.k < O; }
 // the cross-fade, rounded step by step (contract(off)): equal masks stay exactly equal (b - a = 0), so an all-ones mask stays the identity
 __device__ __forceinline__ float srt_blend(float a, float b, float w)
 {

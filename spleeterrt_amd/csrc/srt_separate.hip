@@ -13,13 +13,14 @@ int srtRatioMask(srt_engine* e, float* d_masks, int ntiles)
 SrtDspTables tables_of(const srt_engine* e) { SrtDspTables t; t.preWin = e->preWin; t.postWin = e->postWin; t.twiddle = e->twiddle; return t; }
 
 // the transform behind srtStftEx; of the call's options only o.overlap matters: the tile layout of the magnitudes
-static int stft_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_spec, float* d_mag, const SepOpts& o)
+// tiles: the tile count when the caller's plan gives it (a piece of srtSeparateHostStreamOverlap), 0: the signal's own, overlap_tiles(rows)
+static int stft_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_t frames, size_t rows, float* d_spec, float* d_mag, const SepOpts& o, size_t tiles = 0)
 {
     if (!e || !d_L || !d_R || !d_spec) return fail(-1, "srtStft: null argument");
     DeviceScope ds(e->device);
     if (rows < 1 || frames > rows) return fail(-1, "srtStft: need 1 <= frames <= rows");
     const int T = e->cfg.T, O = d_mag ? o.overlap : 0;
-    const size_t ntiles = overlap_tiles(rows, T, o.overlap);
+    const size_t ntiles = tiles ? tiles : overlap_tiles(rows, T, o.overlap);
     if (d_mag && ntiles > (size_t)e->cfg.max_tiles) return fail(-1, o.overlap ? "srtStft: more than max_tiles tiles at this overlap (srtOverlapTiles)" : "srtStft: more than max_tiles * T rows");
     SrtStftParams p; memset(&p, 0, sizeof p);
     p.L = d_L; p.R = d_R; p.nsamples = n;
@@ -48,14 +49,15 @@ int srtStft(srt_engine* e, const float* d_L, const float* d_R, size_t n, float* 
 // average mask extension: the gain table of the inverse transform that follows on the same stream, from the masks that transform will apply
 // (rows <= rows_cap: every caller has checked its tiles against max_tiles)
 // (tracks: a packed batch with overlapped tiles - rows = the packed rows, each mapped inside its own track: srt_launch_mask_ext_batch)
-int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks, int ntracks)
+// (seam: a piece of srtSeparateHostStreamOverlap - the mask seam carry its first O rows blend with, as in the inverse transform)
+int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, int ntiles, int rows, int ratio, int O, const SrtBatchTrack* tracks, int ntracks, const float* seam)
 {
     if (!e->ext || (size_t)rows > e->rows_cap || nstems != e->cfg.n_stems) return fail(-1, "mask extension: no gain table for this call (srtSetMaskExtension allocates it for n_stems x max_tiles * T rows)");
     SrtMaskExtParams m; memset(&m, 0, sizeof m);
     m.masks = masks; m.masks16 = masks16; m.nstems = nstems; m.ntiles = ntiles; m.T = e->cfg.T; m.F = e->cfg.F; m.rows = rows; m.ratio = ratio;
     m.ext = e->ext; m.ext_stem = e->rows_cap * 2;
     TimerScope ts(e, "mask_ext");
-    if (tracks ? srt_launch_mask_ext_batch(m, tracks, ntracks, e->stream, O) : srt_launch_mask_ext(m, e->stream, O)) return fail(-2, "mask extension launch failed (the masks must be 16-byte aligned)");
+    if (tracks ? srt_launch_mask_ext_batch(m, tracks, ntracks, e->stream, O) : srt_launch_mask_ext(m, e->stream, O, seam)) return fail(-2, "mask extension launch failed (the masks must be 16-byte aligned)");
     e->last.ext_rows = rows;
     return 0;
 }
@@ -63,14 +65,17 @@ int mask_ext_issue(srt_engine* e, const float* masks, int masks16, int nstems, i
 // inverse transform of `nstems` stems of one spectrum under their masks (nullptr: all-ones) into [nstems][2][srtIstftLength(rows)]; oob: per stem, the weight of bins >= F
 // o: the overlap of the masks' tiles, the rule for bins >= F, and with o.n_out > 0 the remix - d_out is then [n_out][2][len], output m the chain of o.mix[m] over the
 // stems' gains.  The single-stem callers (CLI flows, Wiener filter) pass SepOpts{}.
-static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out, const SepOpts& o)
+// pc: the signal is a piece of a longer stream (separate_piece) - `rows` are the rows it owns, the first of pc->stft_rows spectrum rows, under pc->tiles mask tiles
+// (not overlap_tiles(rows): the piece's last tile reaches into the next piece's rows), and pc->seam the carry its first O rows blend with
+static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const float* masks, int nstems, const float* oob, bool ratio, bool masks16, float* d_out, const SepOpts& o,
+                        const HostOvPiece* pc = nullptr)
 {
     DeviceScope ds(e->device);
     const int T = e->cfg.T;
     SrtIstftParams p; memset(&p, 0, sizeof p);
-    p.spec = spec; p.spec_ch_stride = rows * SRT_SPEC_LD;
+    p.spec = spec; p.spec_ch_stride = (pc ? pc->stft_rows : rows) * SRT_SPEC_LD;
     const int O = masks ? o.overlap : 0;
-    p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = (int)overlap_tiles(rows, T, O);      // (O = 0: ceil(rows / T))
+    p.frames = (int)rows; p.masks = masks; p.nstems = nstems; p.ntiles = pc ? (int)pc->tiles : (int)overlap_tiles(rows, T, O);      // (O = 0: ceil(rows / T))
     p.T = T; p.F = e->cfg.F;
     const bool ext = o.mask_ext == SRT_MASK_EXT_AVERAGE;
     for (int s = 0; s < nstems; ++s) p.oob[s] = ext ? 1.0f : oob[s];     // the mean of an all-ones mask is 1 exactly: no table without masks
@@ -78,12 +83,12 @@ static int istft_launch(srt_engine* e, const float2* spec, size_t rows, const fl
     p.frames_out = nullptr; p.out = d_out; p.out_len = srtIstftLength(rows); p.tab = tables_of(e);
     if (o.n_out) { p.n_out = o.n_out; memcpy(p.mix, o.mix, sizeof p.mix); }
     if (ext && masks) {
-        const int rc = mask_ext_issue(e, masks, p.masks16, nstems, p.ntiles, (int)rows, p.ratio, O);
+        const int rc = mask_ext_issue(e, masks, p.masks16, nstems, p.ntiles, (int)rows, p.ratio, O, nullptr, 0, pc ? pc->seam : nullptr);
         if (rc) return rc;
         p.ext = e->ext; p.ext_stem = e->rows_cap * 2;
     }
     TimerScope ts(e, "istft");
-    if (srt_launch_istft(p, e->stream, O)) return fail(-2, "istft launch failed");
+    if (srt_launch_istft(p, e->stream, O, pc ? pc->seam : nullptr)) return fail(-2, "istft launch failed");
     return 0;
 }
 // ONE stem's mask (or none) into a [2][len] destination, every option off
@@ -315,6 +320,21 @@ static int separate_issue(srt_engine* e, const SrtSwitches& sw, const SepOpts& o
     if (o.wiener) return wiener_issue(e, (const float*)e->spec, rows, e->masks, d_out, o);
     // ratio_mask: normalised across the stems inside the inverse kernel's prologue (srt_ratio_of, srt_dsp.hip) - e->masks keeps the raw sigmoid masks
     return istft_issue(e, (const float*)e->spec, rows, e->masks, d_out, e->cfg.ratio_mask != 0, e->last.masks16, o);
+}
+
+// One piece of srtSeparateHostStreamOverlap (srt_host.hip walks the plan and owns the copies): separate_issue's stages on the piece's geometry.
+// The STFT runs over pc.stft_rows rows into pc.tiles overlapped tiles, the forward over those tiles (float masks in every mode: the carry holds floats), the
+// inverse over the pc.own_rows rows the piece owns with pc.seam for its first O rows; then, unless the piece is the stream's last, rows [S, T) of its last tile
+// go into d_seam for the next piece (the stream is in order: the inverse has read the old carry by then).  o.overlap > 0, o.wiener = 0.
+int separate_piece(srt_engine* e, const SrtSwitches& sw, const SepOpts& o, const float* d_L, const float* d_R, size_t n, size_t frames, const HostOvPiece& pc, float* d_seam, float* d_out)
+{
+    int rc = stft_issue(e, d_L, d_R, n, frames, pc.stft_rows, (float*)e->spec, e->mag, o, pc.tiles);
+    if (rc) return rc;
+    if ((rc = forward_range(e, sw, e->mag, (int)pc.tiles, e->masks, 0, e->cfg.n_stems))) return rc;
+    if ((rc = istft_launch(e, e->spec, pc.own_rows, e->masks, e->cfg.n_stems, e->cfg.oob_weight, e->cfg.ratio_mask != 0, false, d_out, o, &pc))) return rc;
+    if (!d_seam) return 0;
+    TimerScope ts(e, "mask_seam");
+    return srt_launch_mask_seam_save(e->masks, e->cfg.n_stems, (int)pc.tiles, e->cfg.T, e->cfg.F, o.overlap, d_seam, e->stream) ? fail(-2, "mask seam save launch failed") : 0;
 }
 
 // srtSeparate with the call's own options (fp32 masks in the fp16 mode too, as with srtSetWiener).  Always eager: the graph cache has no key for an option call.

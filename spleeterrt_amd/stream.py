@@ -99,6 +99,23 @@ def overlap_tiles(rows, T, O):
     return 1 if rows <= T else (rows - O + S - 1) // S
 
 
+def host_overlap_pieces(rows, T, O, max_tiles):
+    """srtHostOverlapPieces: the pieces srtSeparateHostStreamOverlap walks a stream of `rows` spectrum rows in, a list of dicts tile0 / tiles /
+    row0 / own_rows / stft_rows.  With S = T - O and N = overlap_tiles(rows, T, O), piece p holds tiles [p max_tiles, min((p + 1) max_tiles, N)), owns the rows
+    whose primary tile is one of them - max_tiles * S from row0 = tile0 * S, the last piece up to `rows` - and analyses the rows its tiles cover,
+    (tiles - 1) S + T from row0 (the last piece: what is left): O of them are the next piece's.  O = 0 is the chunking of separate_host_stream."""
+    if max_tiles < 1:
+        raise ValueError("host_overlap_pieces: need max_tiles >= 1 (max_tiles = %d)" % max_tiles)
+    N, S = overlap_tiles(rows, T, O), T - O
+    pieces = []
+    for tile0 in range(0, N, max_tiles):
+        tiles = min(max_tiles, N - tile0)
+        row0 = tile0 * S
+        own = rows - row0 if tile0 + tiles == N else tiles * S
+        pieces.append(dict(tile0=tile0, tiles=tiles, row0=row0, own_rows=own, stft_rows=min(rows - row0, (tiles - 1) * S + T)))
+    return pieces
+
+
 def _refuse_overlap(engine):
     """The chunked and ranked paths cut a stream at back-to-back tile boundaries; with overlapped tiles the blend would have to cross those seams."""
     if getattr(engine, "overlap", 0):
