@@ -984,7 +984,8 @@ int srt_launch_stft(const SrtStftParams& p, hipStream_t s, int overlap, int ov_t
     }
     // (tests/test_dsp_float64.py holds every row to float64 at one shape per regime of this rule: rows = 37 -> fpb 1, 1025 -> 2 and 4099 -> 6 (both with a last
     // workgroup of one frame), 9000 -> 12.  Nothing reads this rule from the tests: launcher_fpb / launcher_G in that file restate it and this function's sibling below
-    // by hand, for the printed tags only.  Whoever changes a rule edits the restatement and moves the shapes, or the regimes lose their coverage with every test green.)
+    // by hand, for the printed tags only.  Whoever changes a rule edits the restatement and moves the shapes, or the regimes lose their coverage with every test green.
+    // tests/test_dsp_float64_forms.py runs srt_stft_ov_kernel at rows = 1025 and 4099 (fpb 2 and 6, O = 16) against this kernel's bits and the O = 0 magnitudes.)
     const int blocks = (p.rows_total + fpb - 1) / fpb;
     if (blocks <= 0) return 0;
     if (overlap > 0) {                                   // the rows of tile j are [j (T - O), j (T - O) + T): every row below rows_total must have a tile
@@ -1015,7 +1016,10 @@ int srt_launch_istft(const SrtIstftParams& p, hipStream_t s, int overlap, const 
     const int gmin = (size_t)nseg * ncol >= 4096 ? 13 : 5;          // short signals: shorter runs (more warm-up, but all CUs busy)
     if (G < gmin) G = gmin;
     // (tests/test_dsp_float64.py, every output hop against float64: frames 1..4 and 13..17, one stem -> G = 5 with nseg mod G taking every value; 1400 frames x 3 stems
-    // -> G = 13; 2100 x 5 -> G = 14, 755 workgroups; 4500 x 3 at F = 1088 -> G = 14 on the table kernel.  A change to this rule moves those shapes as well.)
+    // -> G = 13; 2100 x 5 -> G = 14, 755 workgroups; 4500 x 3 at F = 1088 -> G = 14 on the table kernel.  A change to this rule moves those shapes as well.
+    // tests/test_dsp_float64_forms.py, the OV / EXT / MIX / RATIO / SEAM forms below against float64: 145 and 157 frames x 3 stems (2 outputs of a remix) and 277
+    // frames in three pieces -> G = 5; one stem at O = 32, frames 4, 13..17 and 65..69 -> G = 5 with nseg mod G taking every value, with and without blended rows
+    // inside the runs; 1400 frames x 3 stems at O = 16 -> G = 13 in both families (48 mod 13 = 9: every phase of a tile seam inside a run).)
     const int blocks = (nseg + G - 1) / G;
     // one stem per workgroup: 32 accumulator + 54 prefetch registers + the FFT fit in 256 VGPRs at 2 workgroups per CU
     // F > 1024: eight mask registers per channel do not fit the 168-VGPR budget of the three-per-CU form (22 dwords would spill): the two-per-CU kernel

@@ -102,8 +102,13 @@ def mag_rows(mag):
 
 def gains(mask_rows, oob, nrows, F, dtype=np.float64, edge_at_f=False):
     """the gain of every bin of rows: the mask below F, the stem's out-of-band weight from F on (main.c:473-494).  mask_rows: [2][nrows][F] or None (all ones).
+    oob: the stem's scalar weight (rounded to fp32, as the engine holds it), or [2][nrows] gains per (channel, row).
     edge_at_f: the negative control that lets the mask reach bin F."""
-    g = np.full((2, nrows, HALF), np.float32(oob), dtype)
+    if np.ndim(oob) == 0:
+        g = np.full((2, nrows, HALF), np.float32(oob), dtype)
+    else:                                                  # one gain per (channel, row), taken as it is: a row of the average extension's table, or a chain over such rows
+        g = np.empty((2, nrows, HALF), dtype)
+        g[...] = np.asarray(oob).reshape(2, nrows, 1)
     g[:, :, :F] = 1.0 if mask_rows is None else mask_rows
     if edge_at_f and F < HALF:
         g[:, :, F] = g[:, :, F - 1]
@@ -397,16 +402,25 @@ def _hop_errors(x, segs, scale):
     return e, ech, np.flatnonzero(silent & ~(d.max(axis=0) == 0)), float(lvl.max())
 
 
-def istft_case(oracle, spec, masks, oob, T, F, got=None, masks64=None, chain=None, **perturb):
+def _oob_rows(o, c0, c1):
+    """an out-of-band gain for frames [c0, c1): the scalar as it is, or those columns of a [2][rows] array"""
+    return o if np.ndim(o) == 0 else np.asarray(o)[:, c0:c1]
+
+
+def istft_case(oracle, spec, masks, oob, T, F, got=None, masks64=None, chain=None, oob64=None, seam_hops=None, **perturb):
     """Errors of the fp32 oracle (and of a device result got [S][2][(rows + 3) * 1024]) against the float64 inverse of spec [2][rows][2052][2] under
     masks [S][ntiles][2][T][F] (None: all ones) and the out-of-band weights, per (stem, output hop).  The oracle multiplies in fp32, as the
     reference does (main.c:473-494); the float64 side uses masks64 where given (the ratio test), else the same masks.
+    oob: per stem a scalar weight or a [2][rows] array of gains per (channel, row) (gains); oob64: the float64 side's, where it differs (else oob).
+    seam_hops: output hops whose frames a chunked path adds in another association than one pass does (tests/test_dsp_float64_forms.py).  The device's
+    error on those hops - and on no other - is reduced by the derived term 3 x 2^-24 x (sum of the peaks of frames s - 3 .. s) / scale(s) before it is merged
+    (three fp32 additions in any order; from the float64 reference alone); res["seam"] lists (stem, hop, error before the reduction, term).
     chain = (L, R) instead of spec (the round trip): the float64 side inverts stft64 of the signal, the oracle its own stft of it.
     perturb: edge_at_f (gains), plus_at_2048 (istft_frames64) for the negative controls."""
     rows = stft_rows(chain[0].size) if chain is not None else spec.shape[1]
     S, nseg = len(oob), rows + 3
     names = HOP_NAMES + HOP_CH_NAMES
-    res = {"cpu": {k: Worst() for k in names}, "gpu": {k: Worst() for k in names}, "silent": 0, "cap": [0.0, 0.0], "level": 0.0}
+    res = {"cpu": {k: Worst() for k in names}, "gpu": {k: Worst() for k in names}, "silent": 0, "cap": [0.0, 0.0], "level": 0.0, "seam": []}
     edge = {k: v for k, v in perturb.items() if k == "edge_at_f"}
     pack = {k: v for k, v in perturb.items() if k == "plus_at_2048"}
     if got is not None:
@@ -422,8 +436,8 @@ def istft_case(oracle, spec, masks, oob, T, F, got=None, masks64=None, chain=Non
         s, s0, s1 = item
         m32, m64 = m32s[s], m64s[s]
         c0, c1 = max(s0 - 3, 0), min(s1, rows)                                   # the frames these hops are made of
-        g32 = gains(None if m32 is None else m32[:, c0:c1], oob[s], c1 - c0, F, np.float32)
-        g64 = gains(m64[:, c0:c1] if m64 is not None else None if m32 is None else m32[:, c0:c1], oob[s], c1 - c0, F, **edge)
+        g32 = gains(None if m32 is None else m32[:, c0:c1], _oob_rows(oob[s], c0, c1), c1 - c0, F, np.float32)
+        g64 = gains(m64[:, c0:c1] if m64 is not None else None if m32 is None else m32[:, c0:c1], _oob_rows((oob if oob64 is None else oob64)[s], c0, c1), c1 - c0, F, **edge)
         ore = np.zeros((2, c1 - c0, FFT), np.float32)
         oim = np.zeros((2, c1 - c0, FFT), np.float32)
         if chain is not None:
@@ -439,6 +453,13 @@ def istft_case(oracle, spec, masks, oob, T, F, got=None, masks64=None, chain=Non
         segs, scale = overlap_add64(hf)                                          # hops c0 .. c1 + 3 (the first three partial unless c0 = 0)
         lo, hi = s0 - c0, s1 - c0
         segs, scale = segs[:, lo:hi], scale[:, lo:hi]
+        term = np.zeros(s1 - s0)
+        if seam_hops is not None:
+            psum, peak = np.zeros(c1 - c0 + 3), np.abs(hf).max(axis=-1).max(axis=0)
+            for q in range(4):
+                psum[q:q + c1 - c0] += peak
+            at = np.array([h - s0 for h in seam_hops if s0 <= h < s1 and scale[:, h - s0].max() > 0], int)
+            term[at] = 3.0 * 2.0 ** -24 * psum[lo:hi][at] / scale.max(axis=0)[at]
         ore[:, :, :HALF] = cre * g32
         oim[:, :, :HALF] = cim * g32
         o = oracle.istft(ore, oim).reshape(2, c1 - c0 + 3, HOP)[:, lo:hi]        # frames are added in frame order: the hops from s0 on are complete
@@ -453,6 +474,9 @@ def istft_case(oracle, spec, masks, oob, T, F, got=None, masks64=None, chain=Non
         for who, x in sets:
             e, ech, bad, lvl = _hop_errors(x, segs, scale)
             assert who == "cpu" or not bad.size, "stem %d: output hops %s are not exactly zero where the reference is" % (s, (bad[:4] + s0).tolist())
+            if who == "gpu" and seam_hops is not None:
+                seam = [(s, int(h) + s0, float(e[h]), float(term[h])) for h in np.flatnonzero(term)]
+                e = e - term
             errs += [(who, "hop max", e), (who, "hop max/ch", ech)]
         with lock:
             for who, k, e in errs:
@@ -460,6 +484,8 @@ def istft_case(oracle, spec, masks, oob, T, F, got=None, masks64=None, chain=Non
             res["cap"] = [_worse(u, v) for u, v in zip(res["cap"], cap)]
             res["silent"] += int(silent.sum()) if s == 0 else 0
             res["level"] = max(res["level"], lvl)
+            if got is not None and seam_hops is not None:
+                res["seam"] += seam
     _run(piece, [(s, s0, s1) for s in range(S) for s0, s1 in _chunks(nseg, 4)])
     return res
 
@@ -670,7 +696,7 @@ def test_istft_per_channel_at_matched_levels(oracle, F):
     eng.close()
 
 
-def _inverse_check(oracle, tag, eng, spec, masks, oob, T, F, masks64=None, got=None, per_channel=False):
+def _inverse_check(oracle, tag, eng, spec, masks, oob, T, F, masks64=None, got=None, per_channel=False, oob64=None, seam_hops=None):
     import torch
     rows = spec.shape[1]
     if got is None:
@@ -678,7 +704,7 @@ def _inverse_check(oracle, tag, eng, spec, masks, oob, T, F, masks64=None, got=N
         got = eng.istft(torch.from_numpy(spec).cuda(), md).cpu().numpy()
     S = len(oob)
     assert got.shape == (S, 2, (rows + 3) * HOP)
-    res = istft_case(oracle, spec, masks, oob, T, F, got, masks64)
+    res = istft_case(oracle, spec, masks, oob, T, F, got, masks64, oob64=oob64, seam_hops=seam_hops)
     G = launcher_G(rows, S, F)
     extra = MARGIN * ola3_window_delta() if F <= 1024 else 0.0                   # only the kernel that rebuilds its window gets the window term
     tag = "istft %s F %d T %d S %d frames %d G %d %s" % (tag, F, T, S, rows, G, "masks" if masks is not None else "no masks")
