@@ -391,15 +391,41 @@ SRT_API int  srtSeparateBatchWienerEx(srt_engine *e, int ntracks, const float *c
  *   the text names the bytes asked for, and the engine stays usable.
  * opts hold for the call only: the engine's srtSetWiener, srtSetOverlap, srtSetMaskExtension and srtSetMix state is neither read nor changed, and the call works
  *   with any of them on or off.  Honoured: iterations 1..3, mask_extension (both modes), n_out / h_gain (1..n_stems, srtSetMix's layout) - all row-local once the
- *   tables exist.  Refused: overlap_rows must be 0 (-1, the text says "overlap"): the blend across piece seams is a follow-up.
+ *   tables exist.  Refused: overlap_rows must be 0 (-1, the text says "overlap"): srtSeparateHostWienerOverlap below is the entry point that takes one.
  * -1 with srtLastError() text that names srtSeparateHostWiener, before any device work and with nothing written: a null argument, unknown flag bits or
  * SRT_HOST_IN_PCM16 with h_in2 != NULL, everything srtSeparateWiener refuses of its options except the max_tiles limit, ratio_mask set, n < 4096; -5 when a
  * stem's weights are not set.  srtCopyTensor "wiener_cov" works afterwards as after srtSeparateWiener.
- * srtSeparateHostStream*, srtSeparateCli* and srtMultiSeparate* keep refusing the engine's srtSetWiener.  Follow-ups: overlapped tiles across piece seams, the
- * multi-device host, the CLI flows, n_out > n_stems, graph capture. */
+ * srtSeparateHostStream*, srtSeparateCli* and srtMultiSeparate* keep refusing the engine's srtSetWiener.  Follow-ups: the multi-device host, the CLI flows,
+ * n_out > n_stems, graph capture.  (Overlapped tiles across piece seams: built, srtSeparateHostWienerOverlap.) */
 SRT_API int    srtSeparateHostWiener(srt_engine *e, const void *h_in, const void *h_in2, size_t n,
                                      const srt_wiener_opts *opts, void *h_out, unsigned flags, unsigned long long *h_clipped);
 SRT_API size_t srtHostWienerBytes(const srt_config *cfg, size_t n);
+/* ---- the filter with overlapped tiles over a HOST stream of any length: srtSeparateHostWiener with opts->overlap_rows honoured (0..T/2) - the
+ * quality configuration (`--mwf` on overlapped tiles) on the path for albums and hour-long streams.  Buffers, flags, h_clipped, the output planes, the options
+ * honoured (iterations 1..3, both mask_extension modes, n_out / h_gain) and the rule that the engine's setter state is neither read nor changed are exactly
+ * srtSeparateHostWiener's.  Synchronous, always eager, refused inside a stream capture.  Any n >= 4096 works, one piece included.
+ * What it equals: srtSeparateWiener(e_big, L, R, n, opts, out) on an engine with max_tiles >= srtOverlapTiles(srtStftRows(n), T, overlap_rows).  The R tables,
+ *   weight sums and a are that call's BIT FOR BIT (with batch_invariant): every spectrum row enters the statistics exactly once, with the blended mask value
+ *   a + w (b - a) of srtSetOverlap's rule, in the whole-signal launch's summation order (the chunking depends on the row count alone).  Every row gets the same gain;
+ *   the samples agree up to the association of the overlap-add at the piece seams (2e-6 of the peak); a signal of one piece gives srtSeparateWiener's bits.
+ *   overlap_rows = 0 is srtSeparateHostWiener: the same launches, the same bits.
+ * How: the stream is walked in the pieces of srtHostOverlapPieces(rows, T, overlap_rows, max_tiles) on srtSeparateHostWiener's two-sweep schedule.  A piece
+ *   analyses stft_rows rows into the overlapped layout of its own tiles (its last tile reaches O rows into the next piece: those rows are uploaded and transformed
+ *   twice), but only the own_rows rows it owns enter the statistics, the filter, the inverse and the download.  Rows [0, O) of a later piece blend with rows [S, T)
+ *   of the previous piece's last tile, which sweep A copies into a carry of n_stems * 2 * O * F floats per piece boundary, kept in the store.
+ * The store (kept with the host staging, grow-only, srtReleaseStaging frees it) holds per piece its spectrum - the look-ahead rows included -, its fp32 masks and
+ *   its carry: with S = T - O, N = srtOverlapTiles(rows, T, O) and P = max_tiles, every piece but the last takes
+ *   2 * ((P - 1) S + T) * 2052 * 8 + n_stems * P * 2 * T * F * 4 + n_stems * 2 * O * F * 4 bytes, and the last one 2 * stft_rows * 2052 * 8 + n_stems * tiles * 2 * T * F * 4
+ *   (about T / S times srtHostWienerBytes).  srtHostWienerOverlapBytes(cfg, n, overlap_rows) returns the total - pure host arithmetic, no device; at
+ *   overlap_rows = 0 it is srtHostWienerBytes(cfg, n); 0 with srtLastError() text for a null or bad config, n < 4096 or overlap_rows outside 0..T/2.  If the
+ *   store cannot be allocated the call returns -2, the text names the bytes asked for, and the engine stays usable.
+ * -1 with srtLastError() text that names srtSeparateHostWienerOverlap, before any device work and with nothing written: everything srtSeparateHostWiener
+ * refuses except the overlap; overlap_rows outside 0..T/2 (the text says "overlap"); -5 when a stem's weights are not set.  After a call with the average mask
+ * extension srtCopyTensor("mask_ext") holds the LAST piece's owned rows.  Not built: the multi-device host, the CLI flows, n_out > n_stems, graph capture, a
+ * store of halves. */
+SRT_API int    srtSeparateHostWienerOverlap(srt_engine *e, const void *h_in, const void *h_in2, size_t n,
+                                            const srt_wiener_opts *opts, void *h_out, unsigned flags, unsigned long long *h_clipped);
+SRT_API size_t srtHostWienerOverlapBytes(const srt_config *cfg, size_t n, int overlap_rows);
 
 /* ---- overlapped network tiles over a HOST stream of any length: srtSeparate under srtSetOverlap(e, overlap_rows) for host-resident PCM that need
  * not fit max_tiles overlapped tiles.  Geometry: the whole stream (rows = srtStftRows(n), frames = srtStftFrames(n)).  h_in, h_in2, h_out, flags (SRT_HOST_PINNED |
@@ -422,7 +448,7 @@ SRT_API size_t srtHostWienerBytes(const srt_config *cfg, size_t n);
  *   the chunking of srtSeparateHostStream (max_tiles * T rows per piece, stft_rows = own_rows).
  * -1 with srtLastError() text that names srtSeparateHostStreamOverlap, before any device work and with nothing written: a null argument, unknown flag bits,
  * SRT_HOST_IN_PCM16 with h_in2 != NULL, n < 4096, overlap_rows outside 0..T/2, the Wiener filter on (the text says "Wiener"); -5 when a stem's weights are not set.
- * srtSeparateHostStream*, srtSeparateCli*, srtMultiSeparate* and srtSeparateHostWiener keep their refusals.  Not built: an overlap in srtSeparateHostWiener, the CLI
+ * srtSeparateHostStream*, srtSeparateCli*, srtMultiSeparate* and srtSeparateHostWiener keep their refusals (the filter under an overlap over a host stream: srtSeparateHostWienerOverlap).  Not built: the CLI
  * flows, multi-device ranges, a half-precision carry, graph capture. */
 typedef struct srt_host_piece { size_t tile0, tiles, row0, own_rows, stft_rows; } srt_host_piece;
 SRT_API size_t srtHostOverlapPieces(size_t rows, int T, int overlap_rows, int max_tiles, srt_host_piece *pieces, size_t max_pieces);

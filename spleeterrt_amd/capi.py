@@ -84,6 +84,9 @@ def load_library():
     L.srtSeparateHostWiener.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(_WienerOpts), vp, C.c_uint, vp]
     L.srtHostWienerBytes.restype = C.c_size_t
     L.srtHostWienerBytes.argtypes = [C.POINTER(_Config), C.c_size_t]
+    L.srtSeparateHostWienerOverlap.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(_WienerOpts), vp, C.c_uint, vp]
+    L.srtHostWienerOverlapBytes.restype = C.c_size_t
+    L.srtHostWienerOverlapBytes.argtypes = [C.POINTER(_Config), C.c_size_t, C.c_int]
     L.srtSeparateCli.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_int, f32p]
     L.srtSeparateCliHost.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp]
     L.srtSeparateHostStream.argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp]
@@ -672,14 +675,14 @@ class Engine:
         """separate_wiener for host PCM of any length (srtSeparateHostWiener): the stream is walked in pieces of max_tiles tiles, its spectrum and
         masks are kept in a device store of host_wiener_bytes(n) bytes, and the R tables are those of one separate_wiener call over the whole signal, bit for bit.
         Buffers as separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32; out_pcm16: int16 [outputs, len, 2] instead of float32 [outputs, 2, len];
-        pinned=True promises page-locked buffers.  iterations / mask_extension / mix: options of this call alone, as separate_wiener's; overlap must be 0 (the
-        blend across piece seams is a follow-up).  -> (out, clipped).  wiener_cov works afterwards; release_staging frees the store."""
+        pinned=True promises page-locked buffers.  iterations / mask_extension / mix: options of this call alone, as separate_wiener's; overlap must be 0
+        (separate_host_wiener_overlap takes one).  -> (out, clipped).  wiener_cov works afterwards; release_staging frees the store."""
         try:
             ov = int(overlap)
         except (TypeError, ValueError):
             raise EngineError("separate_host_wiener: overlap must be 0, not %r" % (overlap,))
         if ov != 0:
-            raise EngineError("separate_host_wiener: overlap must be 0, not %d (overlapped tiles across piece seams are a follow-up)" % ov)
+            raise EngineError("separate_host_wiener: overlap must be 0, not %d (separate_host_wiener_overlap takes overlapped tiles)" % ov)
         opts = Engine._wiener_opts(self, "separate_host_wiener", iterations, 0, mask_extension, mix)
         if opts is None:
             opts = (_WienerOpts(int(iterations), 0, MASK_EXT_CONSTANT, 0, None), None, self.S)
@@ -691,6 +694,32 @@ class Engine:
     def host_wiener_bytes(self, n):
         """bytes of the device store separate_host_wiener keeps for a stream of n samples on this engine (srtHostWienerBytes)"""
         return host_wiener_bytes(n, self.F, self.T, self.S, self.max_tiles)
+
+    def separate_host_wiener_overlap(self, pcm_or_LR, overlap, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False):
+        """separate_wiener(..., overlap=overlap) for host PCM of any length (srtSeparateHostWienerOverlap): the stream is walked in pieces of
+        max_tiles overlapped tiles (stream.host_overlap_pieces), spectrum, masks and one mask carry per piece boundary are kept in a device store of
+        host_wiener_overlap_bytes(n, overlap) bytes, and the R tables are those of one separate_wiener call over the whole signal, bit for bit.  overlap
+        (0 .. T/2 rows), iterations, mask_extension and mix are options of this call alone; buffers as separate_host_wiener.  overlap = 0 is
+        separate_host_wiener.  -> (out, clipped).  wiener_cov works afterwards; release_staging frees the store."""
+        try:
+            ov = int(overlap)
+        except (TypeError, ValueError):
+            raise EngineError("separate_host_wiener_overlap: overlap must be an integer 0 .. T / 2, not %r" % (overlap,))
+        if ov != overlap or ov < 0 or ov > self.T // 2:
+            raise EngineError("separate_host_wiener_overlap: overlap must be an integer 0 .. T / 2 = %d, not %r" % (self.T // 2, overlap))
+        opts = Engine._wiener_opts(self, "separate_host_wiener_overlap", iterations, ov, mask_extension, mix)
+        if opts is None:
+            opts = (_WienerOpts(int(iterations), 0, MASK_EXT_CONSTANT, 0, None), None, self.S)
+        o, _keep_g, planes = opts
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, planes, None, out, pinned)
+        if n < 4096:
+            raise EngineError("separate_host_wiener_overlap: need at least 4096 samples, not %d" % n)
+        self._chk(self.L.srtSeparateHostWienerOverlap(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, C.byref(o), C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
+        return out, clipped
+
+    def host_wiener_overlap_bytes(self, n, overlap):
+        """bytes of the device store separate_host_wiener_overlap keeps for a stream of n samples at this overlap on this engine (srtHostWienerOverlapBytes)"""
+        return host_wiener_overlap_bytes(n, self.F, self.T, self.S, self.max_tiles, overlap)
 
     def separate_cli_host_io(self, pcm_or_LR, stems, out_pcm16=False, out=None, pinned=False, keep_staging=False):
         """separate_cli_host with 16-bit PCM on either side (srtSeparateCliHostIo) -> (out, clipped) as separate_host_stream_io, `stems` outputs."""
@@ -782,6 +811,20 @@ def host_wiener_bytes(n, F, T, n_stems, max_tiles):
     cfg = _Config()
     cfg.F, cfg.T, cfg.n_stems, cfg.max_tiles = int(F), int(T), int(n_stems), int(max_tiles)
     b = L.srtHostWienerBytes(C.byref(cfg), int(n))
+    if not b:
+        raise EngineError("libspleeterrt_amd: %s" % L.srtLastError().decode())
+    return int(b)
+
+
+def host_wiener_overlap_bytes(n, F, T, n_stems, max_tiles, overlap):
+    """srtHostWienerOverlapBytes: bytes of the device store srtSeparateHostWienerOverlap keeps for a stream of n samples.  With S = T - overlap and P = max_tiles
+    every piece but the last takes 2 * ((P - 1) S + T) * 2052 * 8 (its spectrum, the look-ahead rows included) + n_stems * P * 2 * T * F * 4 (its fp32 masks)
+    + n_stems * 2 * overlap * F * 4 (the mask carry of its boundary); the last one its own rows and tiles and no carry.  overlap = 0: host_wiener_bytes.  Pure host
+    arithmetic: works without a device.  Raises for a bad geometry, n < 4096 or an overlap outside 0 .. T / 2."""
+    L = load_library()
+    cfg = _Config()
+    cfg.F, cfg.T, cfg.n_stems, cfg.max_tiles = int(F), int(T), int(n_stems), int(max_tiles)
+    b = L.srtHostWienerOverlapBytes(C.byref(cfg), int(n), int(overlap))
     if not b:
         raise EngineError("libspleeterrt_amd: %s" % L.srtLastError().decode())
     return int(b)

@@ -36,7 +36,7 @@ struct HostStaging {
     int16_t* d_in16[2]; int16_t* d_out16[2];
     size_t in16_cap, out16_cap;                        // stereo frames (4 bytes)
     unsigned long long* d_clip;                        // [SRT_MAX_STEMS] clipped-sample counters, then the pack's workgroup counts
-    // srtSeparateHostWiener's store: every piece's spectrum and fp32 masks (host_wiener_layout, srt_host.hip), grow-only like the rest
+    // srtSeparateHostWiener's / srtSeparateHostWienerOverlap's store: every piece's spectrum, fp32 masks and mask carry (host_wiener_layout, srt_host.hip), grow-only like the rest
     char* d_wstore; size_t wstore_cap;                 // bytes
     // srtSeparateHostStreamOverlap's mask seam carry [n_stems][2][O][F] (srt_mask_seam_save_kernel), grow-only like the rest
     float* d_mseam; size_t mseam_cap;                  // floats
@@ -198,12 +198,15 @@ int cli_issue(srt_engine* e, const float* d_L, const float* d_R, size_t n, size_
 int cli_check(srt_engine* e, int stems);
 // ... srtSeparateHostWiener's stages (srt_host.hip drives them): a piece is rows [row0, row0 + rows) of the signal, spectrum [2][rows][SRT_SPEC_LD] and fp32 masks
 // [n_stems][ntiles][2][T][F] in the device store
-struct HostWienerPiece { float2* spec; float* masks; size_t row0, rows; int ntiles; };
-int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n, SepOpts* o);
-int host_wiener_ws(srt_engine* e, const SepOpts& o);
-int host_wiener_analyse(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, const HostWienerPiece& pc);
+// ... and srtSeparateHostWienerOverlap's (ov / O > 0): `rows` are the rows the piece owns, the first of the stft_rows its spectrum holds and its ntiles overlapped tiles
+// cover; seam: the mask carry [n_stems][2][O][F] of the piece before it (nullptr: the first piece), seam_out: its own slot for the next (nullptr: the last piece).
+// Without an overlap stft_rows = rows and both are null.
+struct HostWienerPiece { float2* spec; float* masks; size_t row0, rows; int ntiles; size_t stft_rows; const float* seam; float* seam_out; };
+int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n, SepOpts* o, bool ov);
+int host_wiener_ws(srt_engine* e, const SepOpts& o, const char* who);
+int host_wiener_analyse(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, const HostWienerPiece& pc, int O);
 SrtWienerParams wiener_geometry(const srt_engine* e, size_t rows);
-int host_wiener_stats(srt_engine* e, const SrtWienerParams& w, const HostWienerPiece& pc, int pass);
+int host_wiener_stats(srt_engine* e, const SrtWienerParams& w, const HostWienerPiece& pc, int pass, int O);
 int host_wiener_finalize(srt_engine* e, const SrtWienerParams& w, int pass);
 int host_wiener_render(srt_engine* e, const SrtWienerParams& w, const SepOpts& o, const HostWienerPiece& pc, float* d_out);
 

@@ -1,5 +1,5 @@
 // srt_host.hip — the host-buffer entry points of the engine: the device staging, srtSeparateCliHost, the chunk pipeline of srtSeparateHostStream and the two sweeps of
-// srtSeparateHostWiener (its private declarations: srt_engine.h).
+// srtSeparateHostWiener / srtSeparateHostWienerOverlap (its private declarations: srt_engine.h).
 #include "srt_engine.h"
 
 // Grow-only device staging shared by the host-buffer entry points (kept in the engine, freed by srtDestroy).
@@ -321,29 +321,35 @@ int srtSeparateHostStreamOverlap(srt_engine* e, const void* h_in, const void* h_
 // alone.  Sweep B filters one piece at a time into the engine's spectrum workspace, inverts it, adds the 3072-sample seam (srt_launch_carry) and sends the piece
 // down on host_stream's download pipeline.  Nothing crosses PCIe twice, and the network runs once.
 
-// the store: piece c at c * piece_bytes - its spectrum [2][crow][SRT_SPEC_LD] float2, then its masks [n_stems][tiles][2][T][F] floats - every piece but the last
-// full (crow = max_tiles * T), the last one with its own row and tile count
-struct HostWienerLayout { size_t piece_rows, npieces, piece_bytes, total; };
+// the store: piece c at c * piece_bytes - its spectrum [2][stft_rows][SRT_SPEC_LD] float2, then its masks [n_stems][tiles][2][T][F] floats, then (under an overlap, every
+// piece but the last) its mask seam carry [n_stems][2][O][F] floats.  The pieces are host_ov_piece's: every piece but the last is full - max_tiles tiles over
+// (max_tiles - 1) (T - O) + T spectrum rows, O of them the look-ahead rows the next piece owns and holds again - the last one has its own row and tile count.
+// O = 0: max_tiles * T rows a piece and no carry, srtSeparateHostWiener's store.
+struct HostWienerLayout { size_t ntiles, npieces, piece_bytes, total; int O; };
 static size_t wstore_spec_bytes(size_t crow) { return 2 * crow * SRT_SPEC_LD * sizeof(float2); }
 static size_t wstore_mask_bytes(const srt_config& cfg, size_t tiles) { return (size_t)cfg.n_stems * tiles * 2 * cfg.T * cfg.F * sizeof(float); }
-static HostWienerLayout host_wiener_layout(const srt_config& cfg, size_t rows)
+static size_t wstore_seam_bytes(const srt_config& cfg, int O) { return (size_t)cfg.n_stems * 2 * O * cfg.F * sizeof(float); }
+static HostWienerLayout host_wiener_layout(const srt_config& cfg, size_t rows, int O)
 {
     HostWienerLayout l;
-    l.piece_rows = (size_t)cfg.max_tiles * cfg.T;
-    l.npieces = (rows + l.piece_rows - 1) / l.piece_rows;
-    l.piece_bytes = wstore_spec_bytes(l.piece_rows) + wstore_mask_bytes(cfg, (size_t)cfg.max_tiles);
-    const size_t last = rows - (l.npieces - 1) * l.piece_rows;
-    l.total = (l.npieces - 1) * l.piece_bytes + wstore_spec_bytes(last) + wstore_mask_bytes(cfg, (last + cfg.T - 1) / cfg.T);
+    l.O = O;
+    l.ntiles = overlap_tiles(rows, cfg.T, O);
+    l.npieces = (l.ntiles + cfg.max_tiles - 1) / cfg.max_tiles;
+    l.piece_bytes = wstore_spec_bytes((size_t)(cfg.max_tiles - 1) * (cfg.T - O) + cfg.T) + wstore_mask_bytes(cfg, (size_t)cfg.max_tiles) + wstore_seam_bytes(cfg, O);
+    const srt_host_piece last = host_ov_piece(rows, cfg.T, O, cfg.max_tiles, l.ntiles, l.npieces - 1);
+    l.total = (l.npieces - 1) * l.piece_bytes + wstore_spec_bytes(last.stft_rows) + wstore_mask_bytes(cfg, last.tiles);
     return l;
 }
 static HostWienerPiece host_wiener_piece(const srt_config& cfg, const HostWienerLayout& l, char* store, size_t rows, size_t c)
 {
+    const srt_host_piece hp = host_ov_piece(rows, cfg.T, l.O, cfg.max_tiles, l.ntiles, c);
     HostWienerPiece pc;
-    pc.row0 = c * l.piece_rows;
-    pc.rows = pc.row0 + l.piece_rows < rows ? l.piece_rows : rows - pc.row0;
-    pc.ntiles = (int)((pc.rows + cfg.T - 1) / cfg.T);
-    pc.spec = (float2*)(store + c * l.piece_bytes);
-    pc.masks = (float*)(store + c * l.piece_bytes + wstore_spec_bytes(pc.rows));      // (a multiple of 16 bytes: the mask extension's kernel reads vectors)
+    pc.row0 = hp.row0; pc.rows = hp.own_rows; pc.stft_rows = hp.stft_rows; pc.ntiles = (int)hp.tiles;
+    char* const base = store + c * l.piece_bytes;
+    pc.spec = (float2*)base;
+    pc.masks = (float*)(base + wstore_spec_bytes(pc.stft_rows));      // (a multiple of 16 bytes, as the carry behind it: the mask extension's kernel reads vectors)
+    pc.seam_out = l.O && c + 1 < l.npieces ? (float*)((char*)pc.masks + wstore_mask_bytes(cfg, hp.tiles)) : nullptr;
+    pc.seam = l.O && c ? (const float*)(base - wstore_seam_bytes(cfg, l.O)) : nullptr;      // the slot that closes the (full) piece before this one
     return pc;
 }
 
@@ -352,11 +358,20 @@ size_t srtHostWienerBytes(const srt_config* cfg, size_t n)
     if (!cfg) { fail(-1, "srtHostWienerBytes: null config"); return 0; }
     if (srt_check_config(cfg, "srtHostWienerBytes")) return 0;
     if (n < SRT_FFT) { fail(-1, "srtHostWienerBytes: need at least 4096 samples"); return 0; }
-    return host_wiener_layout(*cfg, srtStftRows(n)).total;
+    return host_wiener_layout(*cfg, srtStftRows(n), 0).total;
+}
+
+size_t srtHostWienerOverlapBytes(const srt_config* cfg, size_t n, int overlap_rows)
+{
+    if (!cfg) { fail(-1, "srtHostWienerOverlapBytes: null config"); return 0; }
+    if (srt_check_config(cfg, "srtHostWienerOverlapBytes")) return 0;
+    if (n < SRT_FFT) { fail(-1, "srtHostWienerOverlapBytes: need at least 4096 samples"); return 0; }
+    if (!overlap_ok(overlap_rows, cfg->T)) { fail(-1, "srtHostWienerOverlapBytes: overlap_rows must be 0 .. T / 2"); return 0; }
+    return host_wiener_layout(*cfg, srtStftRows(n), overlap_rows).total;
 }
 
 // grow-only like the rest of the staging (the streams exist: ensure_staging ran).  A failed allocation leaves the engine without a store and otherwise as it was.
-static int ensure_wstore(srt_engine* e, size_t bytes)
+static int ensure_wstore(srt_engine* e, size_t bytes, bool ov)
 {
     HostStaging& h = e->hs;
     if (bytes <= h.wstore_cap) return 0;
@@ -368,32 +383,40 @@ static int ensure_wstore(srt_engine* e, size_t bytes)
         h.d_wstore = nullptr;
         char what[160];
         snprintf(what, sizeof what, "%zu bytes (%s)", bytes, hipGetErrorString(er));
-        return fail(-2, "srtSeparateHostWiener: HIP error allocating the device store of %s: srtHostWienerBytes gives its size; a shorter stream or fewer stems fit", what);
+        return ov ? fail(-2, "srtSeparateHostWienerOverlap: HIP error allocating the device store of %s: srtHostWienerOverlapBytes gives its size; a shorter stream, a smaller overlap or fewer stems fit", what)
+                  : fail(-2, "srtSeparateHostWiener: HIP error allocating the device store of %s: srtHostWienerBytes gives its size; a shorter stream or fewer stems fit", what);
     }
     h.wstore_cap = bytes;
     return 0;
 }
 
-int srtSeparateHostWiener(srt_engine* e, const void* h_in, const void* h_in2, size_t n, const srt_wiener_opts* opts, void* h_out_, unsigned flags, unsigned long long* h_clipped)
+// ov: srtSeparateHostWienerOverlap - the call takes opts->overlap_rows and names itself in every text.  The pieces are host_ov_piece's under the call's
+// overlap O: a piece uploads and analyses stft_rows rows into the overlapped layout of its own tiles, and only the rows it owns enter the statistics, the filter, the
+// inverse and the download; the first O rows of a later piece blend with the carry the piece before it left in the store (srt_mask_seam_save_kernel).  At O = 0 the
+// pieces are max_tiles * T rows each and every launch is srtSeparateHostWiener's.
+static int host_wiener(srt_engine* e, const void* h_in, const void* h_in2, size_t n, const srt_wiener_opts* opts, void* h_out_, unsigned flags, unsigned long long* h_clipped, bool ov)
 {
+    const char* const who = ov ? "srtSeparateHostWienerOverlap" : "srtSeparateHostWiener";
     const bool in16 = flags & SRT_HOST_IN_PCM16, out16 = flags & SRT_HOST_OUT_PCM16;
-    if (!e || !h_in || (!in16 && !h_in2) || !opts || !h_out_) return fail(-1, "srtSeparateHostWiener: null argument");
-    if (flags & ~SRT_HOST_FLAGS) return fail(-1, "srtSeparateHostWiener: unknown flag bits");
-    if (in16 && h_in2) return fail(-1, "srtSeparateHostWiener: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)");
+    if (!e || !h_in || (!in16 && !h_in2) || !opts || !h_out_) return fail(-1, "%s: null argument", who);
+    if (flags & ~SRT_HOST_FLAGS) return fail(-1, "%s: unknown flag bits", who);
+    if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
     DeviceScope ds(e->device);
     SepOpts o;
-    int rc = host_wiener_check(e, opts, n, &o);
+    int rc = host_wiener_check(e, opts, n, &o, ov);
     if (rc) return rc;
-    if (stream_capturing(e)) return fail(-1, "srtSeparateHostWiener: not available inside a stream capture (the call is synchronous and allocates)");
+    if (stream_capturing(e)) return fail(-1, "%s: not available inside a stream capture (the call is synchronous and allocates)", who);
     const size_t rows = srtStftRows(n), frames = srtStftFrames(n);
-    const int S = e->cfg.n_stems, NO = o.n_out ? o.n_out : S, NP = NO * 2, iters = o.wiener;      // NO pairs staged, carried, packed and downloaded
-    const HostWienerLayout l = host_wiener_layout(e->cfg, rows);
+    const int S = e->cfg.n_stems, NO = o.n_out ? o.n_out : S, NP = NO * 2, iters = o.wiener, O = o.overlap;      // NO pairs staged, carried, packed and downloaded
+    const HostWienerLayout l = host_wiener_layout(e->cfg, rows, O);
     const size_t tail = SRT_FFT - SRT_HOP, total_len = srtIstftLength(rows);
-    const size_t in_cap = l.piece_rows * SRT_HOP + tail, out_cap = srtIstftLength(l.piece_rows);
-    if ((rc = host_wiener_ws(e, o))) return rc;
+    // a full piece analyses (max_tiles - 1) (T - O) + T rows; the LAST piece may own that many too (its last tile has no successor to hand its last O rows to)
+    const size_t span = (size_t)(e->cfg.max_tiles - 1) * (e->cfg.T - O) + e->cfg.T;
+    const size_t in_cap = span * SRT_HOP + tail, out_cap = srtIstftLength(span);
+    if ((rc = host_wiener_ws(e, o, who))) return rc;
     if ((rc = ensure_staging(e, 2 * in_cap, (size_t)NP * out_cap, (size_t)NP * tail, 2))) return rc;
     if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? in_cap : 0, out16 ? (size_t)NO * out_cap : 0))) return rc;
-    if ((rc = ensure_wstore(e, l.total))) return rc;
+    if ((rc = ensure_wstore(e, l.total, ov))) return rc;
     HostStaging& h = e->hs;
     if (h_clipped) memset(h_clipped, 0, (size_t)NO * sizeof *h_clipped);
     unsigned long long* d_clip = out16 && h_clipped ? h.d_clip : nullptr;
@@ -414,10 +437,10 @@ int srtSeparateHostWiener(srt_engine* e, const void* h_in, const void* h_in2, si
     for (size_t c = 0; c < l.npieces && er == hipSuccess && rc == 0; ++c) {
         const int b = (int)(c & 1);
         const HostWienerPiece pc = host_wiener_piece(e->cfg, l, h.d_wstore, rows, c);
-        const size_t row1 = pc.row0 + pc.rows;
+        const size_t row1 = pc.row0 + pc.stft_rows;                          // rows [row0, row1) go up and are analysed
         const size_t s0 = pc.row0 * SRT_HOP, send = row1 * SRT_HOP + tail < n ? row1 * SRT_HOP + tail : n;
         const size_t ns = send > s0 ? send - s0 : 0;
-        const size_t cfr = frames > pc.row0 ? (frames - pc.row0 < pc.rows ? frames - pc.row0 : pc.rows) : 0;
+        const size_t cfr = frames > pc.row0 ? (frames - pc.row0 < pc.stft_rows ? frames - pc.row0 : pc.stft_rows) : 0;
         if (c >= 2) STEP(hipStreamWaitEvent(h.s_in, h.ev_cmp[b], 0));      // the input buffer is free once the transform that read it two pieces ago has finished
         if (ns && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * s0, ns * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
         else if (ns) {
@@ -431,14 +454,14 @@ int srtSeparateHostWiener(srt_engine* e, const void* h_in, const void* h_in2, si
             TimerScope ts(e, "pcm16_unpack");
             if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
         }
-        if ((rc = host_wiener_analyse(e, sw, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, pc))) break;
+        if ((rc = host_wiener_analyse(e, sw, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, pc, O))) break;
         STEP(hipEventRecord(h.ev_cmp[b], e->stream));                       // (the networks read the magnitudes, not the PCM, but the event is one per piece)
-        if ((rc = host_wiener_stats(e, w, pc, 1))) break;
+        if ((rc = host_wiener_stats(e, w, pc, 1, O))) break;
     }
     // the R tables: pass 1, then every further pass over the store (no network, no PCIe)
     if (rc == 0 && er == hipSuccess) rc = host_wiener_finalize(e, w, 1);
     for (int pass = 2; pass <= iters && rc == 0 && er == hipSuccess; ++pass) {
-        for (size_t c = 0; c < l.npieces && rc == 0; ++c) rc = host_wiener_stats(e, w, host_wiener_piece(e->cfg, l, h.d_wstore, rows, c), pass);
+        for (size_t c = 0; c < l.npieces && rc == 0; ++c) rc = host_wiener_stats(e, w, host_wiener_piece(e->cfg, l, h.d_wstore, rows, c), pass, O);
         if (rc == 0) rc = host_wiener_finalize(e, w, pass);
     }
     // sweep B: filter, inverse transforms, seam, pack, download
@@ -475,4 +498,14 @@ int srtSeparateHostWiener(srt_engine* e, const void* h_in, const void* h_in2, si
     if (pinR) hipHostUnregister((void*)h_in2);
     if (pinO) hipHostUnregister(h_out_);
     return rc;
+}
+
+int srtSeparateHostWiener(srt_engine* e, const void* h_in, const void* h_in2, size_t n, const srt_wiener_opts* opts, void* h_out, unsigned flags, unsigned long long* h_clipped)
+{
+    return host_wiener(e, h_in, h_in2, n, opts, h_out, flags, h_clipped, false);
+}
+
+int srtSeparateHostWienerOverlap(srt_engine* e, const void* h_in, const void* h_in2, size_t n, const srt_wiener_opts* opts, void* h_out, unsigned flags, unsigned long long* h_clipped)
+{
+    return host_wiener(e, h_in, h_in2, n, opts, h_out, flags, h_clipped, true);
 }

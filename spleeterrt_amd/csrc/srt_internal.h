@@ -322,7 +322,13 @@ struct SrtWienerOpt {
 int srt_launch_wiener_stats_ov(const SrtWienerParams& p, int overlap, int pass, hipStream_t s);
 // the filter with any option on: the FINAL spectrum of every bin 0..2048 - in band y_j or the mix of the y_j, above F the gain (q.oob, q.ext or their chain
 // through the matrix) times the input - of q.n_out outputs, or of every stem; the inverse transform that follows applies no gain
-int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q, int iters, hipStream_t s);
+// seam (with q.overlap > 0): p describes the rows a piece of a longer stream owns (srtSeparateHostWienerOverlap) - p.rows of the p.spec_ch_stride / SRT_SPEC_LD rows its
+// spectrum holds, under p.ntiles tiles - and `seam` is the mask seam carry [nstems][2][overlap][F] of the piece before it; nullptr: a whole signal, or the stream's first piece
+int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q, int iters, hipStream_t s, const float* seam = nullptr);
+// srt_launch_wiener_stats_seg on a piece's overlapped tiles (overlap > 0): rows [row0, row0 + nrows) are the rows the piece owns, masks fetched as srt_launch_wiener_stats_ov
+// fetches them on piece-local rows, the first `overlap` of them blended with `seam` as above.  After the pieces in row order the slab holds what one
+// srt_launch_wiener_stats_ov over the signal leaves, bit for bit.
+int srt_launch_wiener_stats_seg_ov(const SrtWienerParams& p, int overlap, const float* seam, size_t row0, size_t nrows, int pass, hipStream_t s);
 // The filter per track of a packed batch (srtSeparateBatchWiener): a second device table beside SrtBatchTrack's, one row per track - the track's row chunks of
 // the statistics pass (wiener_issue's rule on the track's own rows) as a run [chunk0, chunk0 + nchunks) of the call's global chunk numbering.
 struct SrtBatchWiener { int chunk0, nchunks, rpc, tab; };     // tab: the track's slot in the per-track tables (its index in the call)

@@ -139,8 +139,9 @@ SrtWienerParams wiener_geometry(const srt_engine* e, size_t rows)
 }
 
 // the filter over w's rows (its spectrum, masks and tile count; the R tables and a are final) into the engine's spectrum workspace, then one inverse transform per
-// output: the second half of wiener_issue, and what srtSeparateHostWiener runs per piece
-static int wiener_render(srt_engine* e, const SrtWienerParams& w, float* d_out, const SepOpts& o)
+// output: the second half of wiener_issue, and what srtSeparateHostWiener / srtSeparateHostWienerOverlap run per piece
+// seam (a later piece under an overlap): w.rows are the rows the piece owns and `seam` the mask carry its first O rows blend with - in the gain table and in the filter
+static int wiener_render(srt_engine* e, const SrtWienerParams& w, float* d_out, const SepOpts& o, const float* seam = nullptr)
 {
     const int S = e->cfg.n_stems, O = o.overlap, iters = o.wiener;
     const size_t rows = (size_t)w.rows;
@@ -150,11 +151,11 @@ static int wiener_render(srt_engine* e, const SrtWienerParams& w, float* d_out, 
     memcpy(q.oob, e->cfg.oob_weight, sizeof q.oob);
     memcpy(q.mix, o.mix, sizeof q.mix);
     if (ext) {      // e_j(r, c): the table the inverse transform's own kernel writes from the same (blended) masks, ratio = 0
-        const int rc = mask_ext_issue(e, w.masks, 0, S, w.ntiles, (int)rows, 0, O);
+        const int rc = mask_ext_issue(e, w.masks, 0, S, w.ntiles, (int)rows, 0, O, nullptr, 0, seam);
         if (rc) return rc;
         q.ext = e->ext; q.ext_stem = e->rows_cap * 2;
     }
-    { TimerScope ts(e, "wiener_filter"); if (plain ? srt_launch_wiener_filter(w, iters, e->stream) : srt_launch_wiener_filter_opt(w, q, iters, e->stream)) return fail(-2, "Wiener filter launch failed"); }
+    { TimerScope ts(e, "wiener_filter"); if (plain ? srt_launch_wiener_filter(w, iters, e->stream) : srt_launch_wiener_filter_opt(w, q, iters, e->stream, seam)) return fail(-2, "Wiener filter launch failed"); }
     e->last.wiener_last = iters; e->last.wiener_tracks = 0;
     const size_t len = srtIstftLength(rows);
     for (int m = 0; m < (o.n_out ? o.n_out : S); ++m) {      // plain: stem m under its oob_weight; with an option the spectra are final: no gain in the inverse
@@ -251,10 +252,12 @@ int srtIstftWiener(srt_engine* e, const float* d_spec, size_t rows, const float*
 
 // ---- srtSeparateHostWiener's stages: srt_host.hip walks the stream piece by piece and owns the copies, the store and the events; what a piece
 // computes is issued here, beside the single-signal path it has to equal.  A piece is rows [row0, row0 + rows) of the signal, its spectrum and masks in the store.
-int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n, SepOpts* o)
+// srtSeparateHostWienerOverlap (ov = true) runs the same stages on the pieces of srtHostOverlapPieces: `rows` are then the rows a piece owns, the first
+// of the stft_rows its tiles cover, and its first O rows blend with the carry of the piece before it.
+int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n, SepOpts* o, bool ov)
 {
-    static const char* const who = "srtSeparateHostWiener";
-    if (opts->overlap_rows > 0) return fail(-1, "%s: overlap_rows must be 0 (the overlap blend across piece seams is a follow-up): srtSeparateWiener takes an overlap for a signal of up to max_tiles tiles", who);
+    const char* const who = ov ? "srtSeparateHostWienerOverlap" : "srtSeparateHostWiener";
+    if (!ov && opts->overlap_rows > 0) return fail(-1, "%s: overlap_rows must be 0: srtSeparateHostWienerOverlap takes an overlap for a stream of any length", who);
     if (n < SRT_FFT) return fail(-1, "%s: need at least 4096 samples", who);
     const size_t rows = srtStftRows(n);
     if (rows > (size_t)0x7fffffff - 4) return fail(-1, "%s: more than 2^31 rows", who);
@@ -264,29 +267,37 @@ int host_wiener_check(const srt_engine* e, const srt_wiener_opts* opts, size_t n
     return 0;
 }
 
-int host_wiener_ws(srt_engine* e, const SepOpts& o) { return ensure_wiener_opts_ws(e, "srtSeparateHostWiener", o); }
+int host_wiener_ws(srt_engine* e, const SepOpts& o, const char* who) { return ensure_wiener_opts_ws(e, who, o); }
 
 // sweep A: the piece's PCM -> its spectrum and fp32 masks in the store (not the engine's own mask buffer, so the fp16 mode keeps floats as everywhere the filter runs)
-int host_wiener_analyse(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, const HostWienerPiece& pc)
+// O > 0: the transform covers the piece's stft_rows rows in the overlapped layout of its own tiles, and unless the piece is the stream's last, rows [S, T) of its last
+// tile go into its carry slot for the next piece (pc.seam_out)
+int host_wiener_analyse(srt_engine* e, const SrtSwitches& sw, const float* d_L, const float* d_R, size_t n, size_t frames, const HostWienerPiece& pc, int O)
 {
-    const int rc = stft_issue(e, d_L, d_R, n, frames, pc.rows, (float*)pc.spec, e->mag, SepOpts{});
+    SepOpts so{}; so.overlap = O;
+    int rc = stft_issue(e, d_L, d_R, n, frames, pc.stft_rows, (float*)pc.spec, e->mag, so, O ? (size_t)pc.ntiles : 0);
     if (rc) return rc;
-    return forward_range(e, sw, e->mag, pc.ntiles, pc.masks, 0, e->cfg.n_stems);
+    if ((rc = forward_range(e, sw, e->mag, pc.ntiles, pc.masks, 0, e->cfg.n_stems)) || !pc.seam_out) return rc;
+    TimerScope ts(e, "mask_seam");
+    return srt_launch_mask_seam_save(pc.masks, e->cfg.n_stems, pc.ntiles, e->cfg.T, e->cfg.F, O, pc.seam_out, e->stream) ? fail(-2, "mask seam save launch failed") : 0;
 }
 
 // w: wiener_geometry of the whole signal; the piece goes into a copy of it
 static SrtWienerParams piece_params(const SrtWienerParams& w, const HostWienerPiece& pc)
 {
     SrtWienerParams p = w;
-    p.spec = pc.spec; p.spec_ch_stride = pc.rows * SRT_SPEC_LD; p.masks = pc.masks; p.ntiles = pc.ntiles;
+    p.spec = pc.spec; p.spec_ch_stride = pc.stft_rows * SRT_SPEC_LD; p.masks = pc.masks; p.ntiles = pc.ntiles;
     return p;
 }
 
 // the piece's share of statistics pass `pass` (chunks that straddle a piece boundary continue in the slab: srt_wiener_stats_seg_kernel)
-int host_wiener_stats(srt_engine* e, const SrtWienerParams& w, const HostWienerPiece& pc, int pass)
+// (O > 0: on the blended masks of the piece's overlapped tiles, srt_wiener_stats_seg_ov_kernel)
+int host_wiener_stats(srt_engine* e, const SrtWienerParams& w, const HostWienerPiece& pc, int pass, int O)
 {
     TimerScope ts(e, "wiener_stats");
-    return srt_launch_wiener_stats_seg(piece_params(w, pc), pc.row0, pc.rows, pass, e->stream) ? fail(-2, "Wiener statistics launch failed") : 0;
+    const SrtWienerParams p = piece_params(w, pc);
+    return (O ? srt_launch_wiener_stats_seg_ov(p, O, pc.seam, pc.row0, pc.rows, pass, e->stream) : srt_launch_wiener_stats_seg(p, pc.row0, pc.rows, pass, e->stream))
+               ? fail(-2, "Wiener statistics launch failed") : 0;
 }
 
 int host_wiener_finalize(srt_engine* e, const SrtWienerParams& w, int pass)
@@ -300,7 +311,7 @@ int host_wiener_render(srt_engine* e, const SrtWienerParams& w, const SepOpts& o
 {
     SrtWienerParams p = piece_params(w, pc);
     p.rows = (int)pc.rows; p.out_stem = 2 * pc.rows * SRT_SPEC_LD;
-    return wiener_render(e, p, d_out, o);
+    return wiener_render(e, p, d_out, o, pc.seam);
 }
 
 // fp16 mode: the masks between the head and the inverse transform - the engine's own buffer, never seen by a caller - are halves where both kernels take them

@@ -21,6 +21,9 @@
 // With per-call options (overlapped tiles, the average mask extension, the stem remix: srtIstftWienerEx / srtSeparateWiener) srt_wiener_stats_ov_kernel and
 // srt_wiener_filter_opt_kernel at the end of this file take the places of the first and the third; with every option off the three above run as always.
 // Both families exist per track of a packed batch as well (srtSeparateBatchWiener: the plain three; srtSeparateBatchWienerEx: the option pair, at the very end).
+// A host stream held one piece at a time has the statistics kernel in a segmented form (srtSeparateHostWiener: srt_wiener_stats_seg_kernel) and, on overlapped
+// tiles, the option pair in forms that blend a piece's first rows with the carry of the piece before (srtSeparateHostWienerOverlap: srt_wiener_stats_seg_ov_kernel,
+// srt_wiener_filter_seam_kernel).
 #include "srt_internal.h"
 #include "srt_overlap.h"
 #include <math.h>
@@ -536,6 +539,44 @@ __device__ __forceinline__ void w_masks_ov(float (&ml)[SRT_MAX_STEMS], float (&m
     }
 }
 
+// A piece of a longer stream (srtSeparateHostWienerOverlap): after w_masks_ov on the piece's own tiles, rows [0, O) of its first tile (srt_ov_seam)
+// blend with the mask seam carry [nstems][2][O][F] the previous piece left (srt_mask_seam_save_kernel) - a = carry[stem][channel][k], b = the row's own value, the
+// same w and the same srt_blend as inside one signal.  seam = nullptr (the stream's first piece) or any other row: nothing happens.  t is workgroup-uniform.
+__device__ __forceinline__ void w_masks_seam(float (&ml)[SRT_MAX_STEMS], float (&mr)[SRT_MAX_STEMS], const SrtWienerParams& p, int O, const float* __restrict__ seam, int t, int k, int S)
+{
+    const OvRow ov = srt_ov_row(t, p.T, O, p.ntiles);
+    if (!srt_ov_seam(ov, O, seam)) return;
+    const size_t a_ch = (size_t)O * p.F, a_stem = 2 * a_ch;
+    const float* a = seam + (size_t)ov.k * p.F + k;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j)
+        if (j < S) { ml[j] = srt_blend(a[j * a_stem], ml[j], ov.w); mr[j] = srt_blend(a[j * a_stem + a_ch], mr[j], ov.w); }
+}
+
+// W_STATS_ROWS on blended masks: the mask fetch is w_masks_ov, then SEAM_STMT (empty inside one signal; the seam blend of a piece), and the chain runs through
+// w_start_v / w_iter<true>.  A macro for the reason given at W_STATS_ROWS: srt_wiener_stats_ov_kernel and srt_wiener_stats_seg_ov_kernel must agree bit for bit, so
+// both hold THIS text.  It uses the kernel's locals p, O, pass, k, S, inb, delta, sLp, sRp, acc and mx.
+#define W_STATS_ROWS_OV(T0, T1, SEAM_STMT) \
+        for (int t = (T0); t < (T1); ++t) { \
+            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD]; \
+            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y))); \
+            if (!inb) continue; \
+            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS]; \
+            w_masks_ov(ml, mr, p, O, t, k, S); \
+            SEAM_STMT \
+            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS]; \
+            w_start_v(yl, yr, sL, sR, ml, mr, S); \
+            for (int i = 0; i < pass - 1; ++i) \
+                w_iter<true>(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S); \
+            _Pragma("unroll") \
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) { \
+                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y; \
+                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y; \
+                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      /* y_L conj(y_R) */ \
+                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y; \
+            } \
+        }
+
 // srt_wiener_stats_kernel with the mask fetch replaced (launched only with an overlap: at O = 0 that kernel runs, and the R tables are its own bit for bit)
 __global__ void __launch_bounds__(256) srt_wiener_stats_ov_kernel(const SrtWienerParams p, int O, int pass)
 {
@@ -551,24 +592,49 @@ __global__ void __launch_bounds__(256) srt_wiener_stats_ov_kernel(const SrtWiene
     for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
     float mx = 0.0f;
     if (anyb) {
-        for (int t = r0; t < r1; ++t) {
-            const float2 sL = sLp[(size_t)t * SRT_SPEC_LD], sR = sRp[(size_t)t * SRT_SPEC_LD];
-            if (pass == 1) mx = fmaxf(mx, fmaxf(hypotf(sL.x, sL.y), hypotf(sR.x, sR.y)));
-            if (!inb) continue;
-            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS];
-            w_masks_ov(ml, mr, p, O, t, k, S);
-            float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
-            w_start_v(yl, yr, sL, sR, ml, mr, S);
-            for (int i = 0; i < pass - 1; ++i)
-                w_iter<true>(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
+        W_STATS_ROWS_OV(r0, r1, )
+    }
+    if (inb) {
 #pragma unroll
-            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
-                acc[j][0] += yl[j].x * yl[j].x + yl[j].y * yl[j].y;
-                acc[j][1] += yr[j].x * yr[j].x + yr[j].y * yr[j].y;
-                acc[j][2] += yl[j].x * yr[j].x + yl[j].y * yr[j].y;      // y_L conj(y_R)
-                acc[j][3] += yl[j].y * yr[j].x - yl[j].x * yr[j].y;
-            }
-        }
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k] = acc[j][q];
+    }
+    if (pass == 1) {                                             // (block-uniform branch: every thread reaches the barriers)
+        mx = w_block_max(mx, red);
+        if (threadIdx.x == 0) p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] = mx;
+    }
+}
+
+// srt_wiener_stats_seg_kernel on the overlapped tiles of a PIECE (srtSeparateHostWienerOverlap): rows [row0, row1) of a signal of p.rows rows are the
+// rows the piece OWNS, the first of the rows its p.ntiles tiles cover (p.spec / p.spec_ch_stride / p.masks / p.ntiles describe the piece; row row0 of the signal is
+// its row 0).  The chunks, the continuation from and back into the slab and the ordering argument are srt_wiener_stats_seg_kernel's; the mask fetch is
+// srt_wiener_stats_ov_kernel's on piece-local rows, with the seam rule (w_masks_seam) for the first O rows of a later piece.  No atomics.
+__global__ void __launch_bounds__(256) srt_wiener_stats_seg_ov_kernel(const SrtWienerParams p, int O, const float* __restrict__ seam, int row0, int row1, int c0, int pass)
+{
+    __shared__ float red[4];
+    const int k = blockIdx.x * 256 + threadIdx.x, c = c0 + blockIdx.y, S = p.nstems;
+    const int g0 = c * p.rpc;                                                    // the chunk's first row in the signal
+    const int r0 = max(g0, row0) - row0, r1 = min(min(g0 + p.rpc, p.rows), row1) - row0;      // rows of the PIECE
+    const bool cont = g0 < row0;                                                 // (workgroup-uniform)
+    const float al = (pass > 1 ? p.scal[0] : 1.0f) * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    const bool inb = k < p.F, anyb = k < SRT_HALF;
+    const float2* sLp = p.spec + (anyb ? k : 0);
+    const float2* sRp = sLp + p.spec_ch_stride;
+    float acc[SRT_MAX_STEMS][4];
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j) { acc[j][0] = 0.0f; acc[j][1] = 0.0f; acc[j][2] = 0.0f; acc[j][3] = 0.0f; }
+    if (cont && inb) {
+#pragma unroll
+        for (int j = 0; j < SRT_MAX_STEMS; ++j)
+            if (j < S)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc[j][q] = p.slab[(((size_t)c * S + j) * 4 + q) * p.F + k];
+    }
+    float mx = pass == 1 && cont ? p.slab_max[c * SRT_WIENER_BINBLK + blockIdx.x] : 0.0f;
+    if (anyb) {
+        W_STATS_ROWS_OV(r0, r1, w_masks_seam(ml, mr, p, O, seam, t, k, S);)
     }
     if (inb) {
 #pragma unroll
@@ -615,62 +681,74 @@ __device__ __forceinline__ float2 w_scale(float g, float2 s) { return make_float
 // The remix is a RUN-TIME branch (q.n_out, workgroup-uniform), not a second instantiation: a one-hot row must give the bits of the stem, and that holds by
 // construction only when the mixes and the stems come out of one compiled copy of the chain - compiled apart, the two copies differed in which products and sums
 // became fused multiply-adds, and the y_j in their last bits.
+// The body is a macro for the reason given at W_STATS_ROWS: srt_wiener_filter_opt_kernel keeps the instruction stream it had when these statements stood in it, and
+// the seam kernel below holds the same text.  OVC: the masks are in the overlapped layout; SEAM_STMT: empty, or the seam blend of a piece's first O rows (w_masks_seam).
+// It uses the kernel's arguments p, q and iters.
+#define W_FILTER_OPT_ROWS(OVC, SEAM_STMT) \
+    const int k = blockIdx.x * 256 + threadIdx.x, S = p.nstems; \
+    if (k >= SRT_HALF) return; \
+    const int r0 = blockIdx.y * W_FILTER_ROWS, r1 = min(r0 + W_FILTER_ROWS, p.rows); \
+    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf, och = p.out_stem / 2; \
+    const float al = p.scal[0] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al; \
+    const bool inb = k < p.F; \
+    for (int t = r0; t < r1; ++t) { \
+        const size_t o = (size_t)t * SRT_SPEC_LD + k; \
+        const float2 sL = p.spec[o], sR = p.spec[p.spec_ch_stride + o]; \
+        if (!inb) { \
+            float gl[SRT_MAX_STEMS], gr[SRT_MAX_STEMS]; \
+            _Pragma("unroll") \
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) { \
+                gl[j] = 0.0f; gr[j] = 0.0f; \
+                if (j < S) { \
+                    if (q.ext) { const float* e = q.ext + (size_t)j * q.ext_stem + (size_t)t * 2; gl[j] = e[0]; gr[j] = e[1]; } \
+                    else { gl[j] = q.oob[j]; gr[j] = gl[j]; } \
+                } \
+            } \
+            if (q.n_out) { \
+                for (int m = 0; m < q.n_out; ++m) { \
+                    p.out[m * p.out_stem + o] = w_scale(w_mix_gain(q, m, S, gl), sL); \
+                    p.out[m * p.out_stem + och + o] = w_scale(w_mix_gain(q, m, S, gr), sR); \
+                } \
+            } else { \
+            _Pragma("unroll") \
+                for (int j = 0; j < SRT_MAX_STEMS; ++j) \
+                    if (j < S) { p.out[j * p.out_stem + o] = w_scale(gl[j], sL); p.out[j * p.out_stem + och + o] = w_scale(gr[j], sR); } \
+            } \
+            continue; \
+        } \
+        float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS]; \
+        if constexpr (OVC) { \
+            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS]; \
+            w_masks_ov(ml, mr, p, q.overlap, t, k, S); \
+            SEAM_STMT \
+            w_start_v(yl, yr, sL, sR, ml, mr, S); \
+        } else { \
+            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k; \
+            w_start(yl, yr, sL, sR, m, sstride, tf, S); \
+        } \
+        for (int i = 0; i < iters; ++i) \
+            w_iter<true>(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S); \
+        if (q.n_out) { \
+            for (int m = 0; m < q.n_out; ++m) { \
+                p.out[m * p.out_stem + o] = w_mix_inband(q, m, S, sL, yl); \
+                p.out[m * p.out_stem + och + o] = w_mix_inband(q, m, S, sR, yr); \
+            } \
+        } else { \
+            _Pragma("unroll") \
+            for (int j = 0; j < SRT_MAX_STEMS; ++j) \
+                if (j < S) { p.out[j * p.out_stem + o] = yl[j]; p.out[j * p.out_stem + och + o] = yr[j]; } \
+        } \
+    }
 template <bool OV>
 __global__ void __launch_bounds__(256) srt_wiener_filter_opt_kernel(const SrtWienerParams p, const SrtWienerOpt q, int iters)
 {
-    const int k = blockIdx.x * 256 + threadIdx.x, S = p.nstems;
-    if (k >= SRT_HALF) return;
-    const int r0 = blockIdx.y * W_FILTER_ROWS, r1 = min(r0 + W_FILTER_ROWS, p.rows);
-    const size_t tf = (size_t)p.T * p.F, sstride = (size_t)p.ntiles * 2 * tf, och = p.out_stem / 2;
-    const float al = p.scal[0] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
-    const bool inb = k < p.F;
-    for (int t = r0; t < r1; ++t) {
-        const size_t o = (size_t)t * SRT_SPEC_LD + k;
-        const float2 sL = p.spec[o], sR = p.spec[p.spec_ch_stride + o];
-        if (!inb) {
-            float gl[SRT_MAX_STEMS], gr[SRT_MAX_STEMS];
-#pragma unroll
-            for (int j = 0; j < SRT_MAX_STEMS; ++j) {
-                gl[j] = 0.0f; gr[j] = 0.0f;
-                if (j < S) {
-                    if (q.ext) { const float* e = q.ext + (size_t)j * q.ext_stem + (size_t)t * 2; gl[j] = e[0]; gr[j] = e[1]; }
-                    else { gl[j] = q.oob[j]; gr[j] = gl[j]; }
-                }
-            }
-            if (q.n_out) {
-                for (int m = 0; m < q.n_out; ++m) {
-                    p.out[m * p.out_stem + o] = w_scale(w_mix_gain(q, m, S, gl), sL);
-                    p.out[m * p.out_stem + och + o] = w_scale(w_mix_gain(q, m, S, gr), sR);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < SRT_MAX_STEMS; ++j)
-                    if (j < S) { p.out[j * p.out_stem + o] = w_scale(gl[j], sL); p.out[j * p.out_stem + och + o] = w_scale(gr[j], sR); }
-            }
-            continue;
-        }
-        float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
-        if constexpr (OV) {
-            float ml[SRT_MAX_STEMS], mr[SRT_MAX_STEMS];
-            w_masks_ov(ml, mr, p, q.overlap, t, k, S);
-            w_start_v(yl, yr, sL, sR, ml, mr, S);
-        } else {
-            const float* m = p.masks + (size_t)(t / p.T) * 2 * tf + (size_t)(t % p.T) * p.F + k;
-            w_start(yl, yr, sL, sR, m, sstride, tf, S);
-        }
-        for (int i = 0; i < iters; ++i)
-            w_iter<true>(yl, yr, sL, sR, reinterpret_cast<const float4*>(p.rtab) + (size_t)i * S * p.F + k, p.F, delta, S);
-        if (q.n_out) {
-            for (int m = 0; m < q.n_out; ++m) {
-                p.out[m * p.out_stem + o] = w_mix_inband(q, m, S, sL, yl);
-                p.out[m * p.out_stem + och + o] = w_mix_inband(q, m, S, sR, yr);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < SRT_MAX_STEMS; ++j)
-                if (j < S) { p.out[j * p.out_stem + o] = yl[j]; p.out[j * p.out_stem + och + o] = yr[j]; }
-        }
-    }
+    W_FILTER_OPT_ROWS(OV, )
+}
+// the overlapped form over the rows a piece of a longer stream owns (srtSeparateHostWienerOverlap): p.rows = those rows, p.ntiles the piece's tiles,
+// p.spec_ch_stride the rows its spectrum holds, `seam` the carry its first O rows blend with
+__global__ void __launch_bounds__(256) srt_wiener_filter_seam_kernel(const SrtWienerParams p, const SrtWienerOpt q, int iters, const float* __restrict__ seam)
+{
+    W_FILTER_OPT_ROWS(true, w_masks_seam(ml, mr, p, q.overlap, seam, t, k, S);)
 }
 
 // masks of p.ntiles tiles at this overlap cover rows 0 .. p.rows - 1 (srt_ov_row then stays inside the masks: row k < T of tile j1 < ntiles, and k + S < T of tile j1 - 1)
@@ -689,13 +767,30 @@ int srt_launch_wiener_stats_ov(const SrtWienerParams& p, int overlap, int pass, 
     return srt_launch_status();
 }
 
-int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q, int iters, hipStream_t s)
+int srt_launch_wiener_stats_seg_ov(const SrtWienerParams& p, int overlap, const float* seam, size_t row0, size_t nrows, int pass, hipStream_t s)
+{
+    if (pass < 1 || pass > SRT_WIENER_MAX_ITERS || p.nchunks < 1 || p.nchunks > SRT_WIENER_MAX_CHUNKS || p.nstems < 1 || p.nstems > SRT_MAX_STEMS ||
+        p.F < 1 || p.F > SRT_HALF - 1 || p.rpc < 1 || p.rows < 1 || (size_t)p.nchunks * p.rpc < (size_t)p.rows || overlap < 1) return -1;
+    // the piece's owned rows lie inside the signal, its tiles at this overlap cover them and its spectrum holds them, and every chunk it touches has a slab slot
+    if (nrows < 1 || row0 + nrows > (size_t)p.rows || p.T < 1 || p.ntiles < 1 || overlap > p.T / 2 || (size_t)(p.ntiles - 1) * (p.T - overlap) + p.T < nrows ||
+        p.spec_ch_stride < nrows * SRT_SPEC_LD) return -1;
+    const int c0 = (int)(row0 / p.rpc), c1 = (int)((row0 + nrows - 1) / p.rpc);
+    if (c1 >= p.nchunks) return -1;
+    const int bx = pass == 1 ? SRT_WIENER_BINBLK : (p.F + 255) / 256;      // pass 1 also covers the out-of-band bins for max |x|
+    SRT_LAUNCH(srt_wiener_stats_seg_ov_kernel, dim3(bx, c1 - c0 + 1), dim3(256), 0, s, p, overlap, seam, (int)row0, (int)(row0 + nrows), c0, pass);
+    return srt_launch_status();
+}
+
+int srt_launch_wiener_filter_opt(const SrtWienerParams& p, const SrtWienerOpt& q, int iters, hipStream_t s, const float* seam)
 {
     if (iters < 1 || iters > SRT_WIENER_MAX_ITERS || p.rows < 1 || p.nstems < 1 || p.nstems > SRT_MAX_STEMS || p.F < 1 || p.F > SRT_HALF - 1 ||
-        !w_layout_ok(p, q.overlap) || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD) return -1;
+        !w_layout_ok(p, q.overlap) || p.out_stem != 2 * (size_t)p.rows * SRT_SPEC_LD || p.spec_ch_stride < (size_t)p.rows * SRT_SPEC_LD) return -1;
     if (q.n_out < 0 || q.n_out > p.nstems || (q.ext && q.ext_stem < (size_t)p.rows * 2)) return -1;      // the spectrum workspace holds nstems spectra
     const dim3 grid(SRT_WIENER_BINBLK, (p.rows + W_FILTER_ROWS - 1) / W_FILTER_ROWS), block(256);
-    if (q.overlap > 0) SRT_LAUNCH(srt_wiener_filter_opt_kernel<true>, grid, block, 0, s, p, q, iters);
+    if (seam) {                                          // a later piece of a longer stream
+        if (q.overlap <= 0) return -1;
+        SRT_LAUNCH(srt_wiener_filter_seam_kernel, grid, block, 0, s, p, q, iters, seam);
+    } else if (q.overlap > 0) SRT_LAUNCH(srt_wiener_filter_opt_kernel<true>, grid, block, 0, s, p, q, iters);
     else SRT_LAUNCH(srt_wiener_filter_opt_kernel<false>, grid, block, 0, s, p, q, iters);
     return srt_launch_status();
 }
