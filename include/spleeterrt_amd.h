@@ -455,6 +455,42 @@ SRT_API size_t srtHostOverlapPieces(size_t rows, int T, int overlap_rows, int ma
 SRT_API int    srtSeparateHostStreamOverlap(srt_engine *e, const void *h_in, const void *h_in2, size_t n, int overlap_rows,
                                             void *h_out, unsigned flags, unsigned long long *h_clipped);
 
+/* ---- host streams at the caller's sample rate: srtSeparateHostStreamIo / srtSeparateHostStreamOverlap for host PCM at in_rate, outputs at
+ * out_rate (either may be 44100: no converter on that side).  Both conversions run on the device inside the chunk pipeline, with the built-in filter of
+ * srtResamplerCreate, so every sample, at either rate, crosses the bus once and the host holds no 44.1 kHz copy.  h_in, h_in2, flags (SRT_HOST_PINNED |
+ * SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16) and h_clipped as in srtSeparateHostStreamIo; n counts frames at in_rate.  overlap_rows as in
+ * srtSeparateHostStreamOverlap: it holds for the call only, the engine's srtSetOverlap is neither read nor changed.  ratio_mask, srtSetMaskExtension, srtSetMix
+ * and the precision come from the engine.  Synchronous and always eager.
+ * What it equals: with n44 = srtResampleLength(n, in_rate, 44100) (n at 44100) and x44 = srtResample of the input, y44 = srtSeparateHostStreamOverlap(e, x44, n44,
+ *   overlap_rows, ..) as floats, [outputs][2][len44], len44 = srtIstftLength(srtStftRows(n44)); output pair p is srtResample(44100 -> out_rate) of y44[p] taken as
+ *   a signal of len44 frames, all len_out = srtResampleLength(len44, 44100, out_rate) of its frames (len44 at 44100) - bit for bit, up to the sign of a zero.
+ *   srtHostRateLength returns len_out.  h_out is float [outputs][2][len_out], or int16 [outputs][len_out][2] with the out flag (srtPcm16Pack's rule, the clipped
+ *   counts in h_clipped).  Nothing is pre-shifted or trimmed: the transform's delay is the caller's, as with srtSeparateHostStream.  With both rates 44100 the call
+ *   is srtSeparateHostStreamOverlap, launch for launch.
+ * How: a piece of srtHostOverlapPieces analyses 44.1 kHz samples [s0, s0 + ns); the source frames their windows reach - [src0, src0 + src_len) - go up into a
+ *   staging buffer at in_rate and srtResampleSpans' kernel writes the piece's 44.1 kHz input (a few hundred halo frames per piece go up twice).  Behind the seam
+ *   add the piece has finalised samples [fin0, fin1) of every plane; it emits output frames [out0, out1), those whose last weighted tap lies before fin1, from a
+ *   carry of the 2 H - 1 samples before fin0 (H = srtResampleHorizon(44100, out_rate)) and its own planes - one launch for all pairs - then packs and downloads.
+ *   Staging and carry are grow-only beside the host staging (srtReleaseStaging frees them); the filter of a rate pair is built at the first call that needs it
+ *   and kept until srtDestroy.  Timer names: rate_in, rate_out.
+ * srtHostRatePieces: the plan, pure host arithmetic, no device.  Returns the piece count and fills pieces[0 .. min(count, max_pieces)) when pieces is not NULL; 0
+ *   with srtLastError() text on a bad argument.
+ * -1 with srtLastError() text that names srtSeparateHostStreamRate, before any device work and with nothing written: a null argument, unknown flag bits,
+ * SRT_HOST_IN_PCM16 with h_in2 != NULL, a rate outside 8000..384000 Hz, n44 < 4096, overlap_rows outside 0..T/2, the Wiener filter on (the text says "Wiener"), a
+ * rate pair whose window does not fit LDS (none does with the built-in filter: the check guards a future table); -5 when a stem's weights are not set.
+ * Not built: the CLI flows, multi-device ranges, the Wiener stream forms, a caller's table, explicit frames / rows. */
+typedef struct srt_host_rate_piece {
+    size_t src0, src_len;           /* source frames at in_rate the piece uploads (in_rate 44100: s0, ns) */
+    size_t s0, ns;                  /* 44.1 kHz samples the piece analyses */
+    size_t fin0, fin1;              /* 44.1 kHz output samples the piece finalises, per plane */
+    size_t out0, out1;              /* output frames at out_rate the piece emits (out_rate 44100: fin0, fin1) */
+} srt_host_rate_piece;
+SRT_API size_t srtHostRateLength(size_t n, int in_rate, int out_rate);   /* frames per output plane; 0 on a bad argument; pure arithmetic */
+SRT_API size_t srtHostRatePieces(const srt_config *cfg, size_t n, int in_rate, int out_rate, int overlap_rows,
+                                 srt_host_rate_piece *pieces, size_t max_pieces);
+SRT_API int    srtSeparateHostStreamRate(srt_engine *e, const void *h_in, const void *h_in2, size_t n, int in_rate, int out_rate,
+                                         int overlap_rows, void *h_out, unsigned flags, unsigned long long *h_clipped);
+
 /* ---- one node, several devices: the reference CLI's tile-range fan-out (Executable/main.c:544-673, `processMT`: spawnNthreads workers, each with
  * its own network instance and a contiguous tile range, one shared read-only weight blob) with a GPU where the reference has a CPU thread.
  * One engine per entry of `devices` (an index may repeat: several engines on one GPU), one host thread per engine while a call runs; weights are
@@ -507,6 +543,21 @@ SRT_API int  srtResamplerDestroy(srt_resampler *r);
  * (d_R may equal d_L: mono; d_Ro may then equal d_Lo).  A frame's value depends on its index only: any split of a range gives the same bits. */
 SRT_API int  srtResample(srt_resampler *r, const float *d_L, const float *d_R, size_t n_in,
                          size_t out0, size_t n_out, float *d_Lo, float *d_Ro);
+/* The same frames from a window of the stream (a chunk pipeline holds a span of the signal plus a few hundred frames of history, not the whole input):
+ * frames [out0, out0 + n_out) of the converted stream of a signal of n_in frames, of which the device holds two consecutive spans:
+ * frames [a0, a0 + a_len) at d_a and [a0 + a_len, a0 + a_len + b_len) at d_b (b_len may be 0; a0 may be negative).
+ * `pairs` stereo pairs (1..SRT_MAX_STEMS): pair p's L at d_x + 2p * x_stride, its R at d_x + (2p + 1) * x_stride (x_stride >= x_len).
+ * Output pair p's L at d_out + 2p * out_stride, R at + (2p + 1) * out_stride, frame out0 at index 0.
+ * Frames outside [0, n_in) are zero, as in srtResample.  One launch computes every pair, and the pairs share each weight load (where `pairs` windows
+ * of 64 frames do not fit 64 KiB of LDS: one pair per workgroup, a grid dimension over the pairs).
+ * -1 before any launch when a requested frame has a weighted tap on a frame of [0, n_in) that neither span holds; taps 0 .. 2 H - 1 of a frame's window,
+ * H = srtResampleHorizon, count as weighted (input frames floor(j * fs_in / fs_out) - H + 1 .. + H).  Also -1: a null resampler or buffer, pairs out of range, a
+ * stride below its length, out0 + n_out above 2^44.
+ * Asynchronous on the resampler's stream, capturable.
+ * Every frame has the bits srtResample gives it. */
+SRT_API int  srtResampleSpans(srt_resampler *r, int pairs, const float *d_a, size_t a_stride, long long a0, size_t a_len,
+                              const float *d_b, size_t b_stride, size_t b_len, size_t n_in,
+                              size_t out0, size_t n_out, float *d_out, size_t out_stride);
 /* host buffers, synchronous, the whole stream: h_Lo / h_Ro hold srtResampleLength(n_in, fs_in, fs_out) frames */
 SRT_API int  srtResampleHost(srt_resampler *r, const float *h_L, const float *h_R, size_t n_in,
                              float *h_Lo, float *h_Ro);

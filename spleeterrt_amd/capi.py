@@ -96,6 +96,11 @@ def load_library():
     L.srtSeparateHostStreamOverlap.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, vp, C.c_uint, vp]
     L.srtHostOverlapPieces.restype = C.c_size_t
     L.srtHostOverlapPieces.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
+    L.srtSeparateHostStreamRate.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_uint, vp]
+    L.srtHostRateLength.restype = C.c_size_t
+    L.srtHostRateLength.argtypes = [C.c_size_t, C.c_int, C.c_int]
+    L.srtHostRatePieces.restype = C.c_size_t
+    L.srtHostRatePieces.argtypes = [C.POINTER(_Config), C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
     L.srtPcm16Unpack.argtypes = [vp, vp, C.c_size_t, vp, vp]
     L.srtPcm16Pack.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
     for fn in (L.srtStftRows, L.srtStftFrames, L.srtIstftLength):
@@ -151,6 +156,7 @@ def load_library():
     L.srtResamplerDestroy.argtypes = [vp]
     L.srtResample.argtypes = [vp, f32p, f32p, C.c_size_t, C.c_size_t, C.c_size_t, f32p, f32p]
     L.srtResampleHost.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+    L.srtResampleSpans.argtypes = [vp, C.c_int, f32p, C.c_size_t, C.c_longlong, C.c_size_t, f32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, f32p, C.c_size_t]
     # the converter as a stream (csrc/srt_rsstream.hip)
     L.srtResampleHorizon.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     L.srtResampleComputable.restype = C.c_longlong
@@ -604,7 +610,7 @@ class Engine:
                                                  1 if pinned else 0))
         return out if ret is None else ret
 
-    def _host_io(self, pcm_or_LR, out_pcm16, nstems, rows, out, pinned):
+    def _host_io(self, pcm_or_LR, out_pcm16, nstems, rows, out, pinned, length=None):
         """host buffers of the *_io calls -> (keep-alive list, h_in, h_in2, n, h_out, flags, out object, clipped array).  Input by dtype: an int16 array or CPU
         tensor of shape [n, 2] is interleaved 16-bit PCM, anything else a pair (L, R) of float32 buffers."""
         import numpy as np
@@ -628,7 +634,7 @@ class Engine:
             assert n == nb
             keep = [a, b]
         rows = self.L.srtStftRows(n) if rows is None else rows
-        ln = self.L.srtIstftLength(rows)
+        ln = self.L.srtIstftLength(rows) if length is None else length      # length: frames per output plane where the call's rates decide it (separate_host_rate)
         shape, dtype = ((nstems, ln, 2), np.int16) if out_pcm16 else ((nstems, 2, ln), np.float32)
         if out_pcm16:
             flags |= HOST_OUT_PCM16
@@ -669,6 +675,31 @@ class Engine:
         if n < 4096:
             raise EngineError("separate_host_overlap: need at least 4096 samples, not %d" % n)
         self._chk(self.L.srtSeparateHostStreamOverlap(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, ov, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
+        return out, clipped
+
+    def host_rate_length(self, n, sample_rate, out_rate=None):
+        """srtHostRateLength: frames per output plane of separate_host_rate for n input frames at sample_rate (pure arithmetic).  Raises for bad arguments."""
+        ln = self.L.srtHostRateLength(int(n), int(sample_rate), int(sample_rate if out_rate is None else out_rate))
+        if not ln:
+            raise EngineError("libspleeterrt_amd: %s" % self.L.srtLastError().decode())
+        return ln
+
+    def separate_host_rate(self, pcm_or_LR, sample_rate, out_rate=None, overlap=0, out_pcm16=False, out=None, pinned=False):
+        """separate_host_stream_io / separate_host_overlap for host PCM at sample_rate with the outputs at out_rate (None: sample_rate; either may be 44100)
+        (srtSeparateHostStreamRate): both conversions run on the device inside the chunk pipeline, so every sample crosses the bus once at its own
+        rate.  Equals Resampler.resample_host to 44.1 kHz, separate_host_overlap, resample_host per output pair, bit for bit.  overlap (0 .. T/2 rows) holds for the
+        call only; ratio_mask, the mask extension and the mix come from the engine.  Buffers as separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32;
+        out float32 [outputs, 2, host_rate_length(n, ..)] or, with out_pcm16, int16 [outputs, length, 2].  -> (out, clipped)."""
+        try:
+            fs_in, fs_out, ov = int(sample_rate), int(sample_rate if out_rate is None else out_rate), int(overlap)
+        except (TypeError, ValueError):
+            raise EngineError("separate_host_rate: sample_rate, out_rate and overlap must be integers, not %r, %r, %r" % (sample_rate, out_rate, overlap))
+        if ov != overlap or ov < 0 or ov > self.T // 2:
+            raise EngineError("separate_host_rate: overlap must be an integer 0 .. T / 2 = %d, not %r" % (self.T // 2, overlap))
+        first = pcm_or_LR[0] if isinstance(pcm_or_LR, (tuple, list)) else pcm_or_LR        # (L, R) or int16 [n, 2]: n is the first axis either way
+        ln = self.host_rate_length(first.shape[0] if hasattr(first, "shape") else len(first), fs_in, fs_out)
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, 0, out, pinned, length=ln)
+        self._chk(self.L.srtSeparateHostStreamRate(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, fs_in, fs_out, ov, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
 
     def separate_host_wiener(self, pcm_or_LR, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False, overlap=0):
@@ -802,6 +833,34 @@ def host_overlap_pieces(rows, T, overlap, max_tiles):
     buf = (_HostPiece * n)()
     L.srtHostOverlapPieces(int(rows), int(T), int(overlap), int(max_tiles), C.cast(buf, C.c_void_p), n)
     return [dict((k, int(getattr(p, k))) for k, _ in _HostPiece._fields_) for p in buf]
+
+
+class _HostRatePiece(C.Structure):
+    _fields_ = [(k, C.c_size_t) for k in ("src0", "src_len", "s0", "ns", "fin0", "fin1", "out0", "out1")]
+
+
+def host_rate_pieces(n, in_rate, out_rate, T, overlap, max_tiles, F=1024):
+    """srtHostRatePieces: the piece plan of srtSeparateHostStreamRate for n frames at in_rate as a list of dicts (src0, src_len, s0, ns, fin0, fin1, out0, out1), from
+    the library - stream.host_rate_pieces is the same arithmetic in Python.  Pure host arithmetic: works without a device.  Raises for bad arguments."""
+    L = load_library()
+    cfg = _Config()
+    cfg.F, cfg.T, cfg.n_stems, cfg.max_tiles = int(F), int(T), 1, int(max_tiles)
+    args = (C.byref(cfg), int(n), int(in_rate), int(out_rate), int(overlap))
+    cnt = L.srtHostRatePieces(*args, None, 0)
+    if not cnt:
+        raise EngineError("libspleeterrt_amd: %s" % L.srtLastError().decode())
+    buf = (_HostRatePiece * cnt)()
+    L.srtHostRatePieces(*args, C.cast(buf, C.c_void_p), cnt)
+    return [dict((k, int(getattr(p, k))) for k, _ in _HostRatePiece._fields_) for p in buf]
+
+
+def host_rate_length(n, in_rate, out_rate):
+    """srtHostRateLength without an engine: frames per output plane; raises for bad arguments"""
+    L = load_library()
+    ln = L.srtHostRateLength(int(n), int(in_rate), int(out_rate))
+    if not ln:
+        raise EngineError("libspleeterrt_amd: %s" % L.srtLastError().decode())
+    return ln
 
 
 def host_wiener_bytes(n, F, T, n_stems, max_tiles):
@@ -998,6 +1057,30 @@ class Resampler:
             Ro = torch.empty(n_out, device=L.device, dtype=torch.float32)
         self._chk(self.L.srtResample(self.h, _ptr(L), _ptr(R), n, int(out0), int(n_out), _ptr(Lo), _ptr(Ro)))
         return Lo, Ro
+
+    def resample_spans(self, a, a0, b, n_in, out0, n_out, out=None):
+        """srtResampleSpans: output frames [out0, out0 + n_out) of the converted stream of a signal of n_in frames of which the device holds two consecutive spans.
+        a: CUDA float32 [2 * pairs, a_len], rows L0, R0, L1, R1, .. holding frames [a0, a0 + a_len) (a0 may be negative); b: the same for the frames behind them, or
+        None.  Rows may be views into a larger buffer (any row stride, unit column stride).  -> out [2 * pairs, n_out].  Every frame has resample()'s bits; raises
+        when a weighted tap of a requested frame falls on a frame of [0, n_in) that neither span holds."""
+        import torch
+
+        def span(t):
+            if t is None:
+                return None, 0, 0
+            assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[0] == planes
+            assert t.shape[1] == 0 or t.stride(1) == 1
+            return (_ptr(t) if t.shape[1] else None), (t.stride(0) if t.shape[0] > 1 else t.shape[1]), t.shape[1]
+        planes = a.shape[0]
+        assert planes % 2 == 0 and planes >= 2
+        pa, sa, la = span(a)
+        pb, sb, lb = span(b)
+        if out is None:
+            out = torch.empty((planes, int(n_out)), device=a.device, dtype=torch.float32)
+        po, so, lo = span(out)
+        assert lo == n_out
+        self._chk(self.L.srtResampleSpans(self.h, planes // 2, pa, sa, int(a0), la, pb, sb, lb, int(n_in), int(out0), int(n_out), po, so))
+        return out
 
     def resample_host(self, L, R):
         """numpy float32 [n] x2 -> (Lo, Ro) numpy, the whole stream (synchronous)"""

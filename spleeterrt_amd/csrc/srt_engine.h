@@ -3,11 +3,13 @@
 #pragma once
 #include "srt_internal.h"
 #include "srt_checks.h"
+#include "srt_rs.h"
 #include "../../include/spleeterrt_amd.h"
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <deque>
 #include <string>
 #include <vector>
 
@@ -40,6 +42,10 @@ struct HostStaging {
     char* d_wstore; size_t wstore_cap;                 // bytes
     // srtSeparateHostStreamOverlap's mask seam carry [n_stems][2][O][F] (srt_mask_seam_save_kernel), grow-only like the rest
     float* d_mseam; size_t mseam_cap;                  // floats
+    // srtSeparateHostStreamRate: a piece's source frames at in_rate (L, then R), its converted planes [pairs * 2][frames] at out_rate, and
+    // the rate carry [pairs * 2][2 LO + 1] of the last finalised 44.1 kHz samples; grow-only like the rest, each allocated only when a call converts on that side
+    float* d_rin[2]; float* d_rout[2]; float* d_rcarry;
+    size_t rin_cap, rout_cap, rcarry_cap;              // floats
 };
 
 // What the last forward left behind, for the calls that come after it (srtCopyTensor's taps, the inverse transform of srtSeparate).  forward_range and
@@ -146,6 +152,9 @@ struct srt_engine {
     // ... with the stem remix per track (srtSeparateBatchMix): the device gain table, max_tiles matrices of SRT_BATCH_GAIN_FLOATS, and the same ring
     // of pinned slots; a call uploads ntracks x [n_out][n_stems + 1] beside the track table.  Allocated by the first such call, owned by bwmem as well
     float* bgtab = nullptr; float* bgpin = nullptr;
+    // srtSeparateHostStreamRate's converters (built-in filter), one per rate pair, built at the first call that needs it and kept until srtDestroy
+    struct RateFilter { int fs_in, fs_out; SrtRsFilter f; };
+    std::deque<RateFilter> rate_filters;
     // timing
     bool timing = false; std::vector<TimingEntry> tlog;
 };

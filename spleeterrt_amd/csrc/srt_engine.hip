@@ -149,6 +149,8 @@ static void free_staging(srt_engine* e)
         if (h.d_out[b]) hipFree(h.d_out[b]);
         if (h.d_in16[b]) hipFree(h.d_in16[b]);
         if (h.d_out16[b]) hipFree(h.d_out16[b]);
+        if (h.d_rin[b]) hipFree(h.d_rin[b]);
+        if (h.d_rout[b]) hipFree(h.d_rout[b]);
         if (h.ev_in[b]) hipEventDestroy(h.ev_in[b]);
         if (h.ev_cmp[b]) hipEventDestroy(h.ev_cmp[b]);
         if (h.ev_out[b]) hipEventDestroy(h.ev_out[b]);
@@ -157,6 +159,7 @@ static void free_staging(srt_engine* e)
     if (h.d_clip) hipFree(h.d_clip);
     if (h.d_wstore) hipFree(h.d_wstore);
     if (h.d_mseam) hipFree(h.d_mseam);
+    if (h.d_rcarry) hipFree(h.d_rcarry);
     if (h.s_in) hipStreamDestroy(h.s_in);
     if (h.s_out) hipStreamDestroy(h.s_out);
     memset(&h, 0, sizeof h);
@@ -184,6 +187,8 @@ static void free_all(srt_engine* e)
     if (e->bpin) hipHostFree(e->bpin);
     for (hipEvent_t ev : e->bev) if (ev) hipEventDestroy(ev);
     for (auto& t : e->tlog) { hipEventDestroy(t.a); hipEventDestroy(t.b); }
+    for (auto& rf : e->rate_filters) srt_rs_filter_free(&rf.f);
+    e->rate_filters.clear();
 }
 
 int srt_check_config(const srt_config* cfg, const char* who)

@@ -1,5 +1,5 @@
-// srt_host.hip — the host-buffer entry points of the engine: the device staging, srtSeparateCliHost, the chunk pipeline of srtSeparateHostStream and the two sweeps of
-// srtSeparateHostWiener / srtSeparateHostWienerOverlap (its private declarations: srt_engine.h).
+// srt_host.hip — the host-buffer entry points of the engine: the device staging, srtSeparateCliHost, the chunk pipeline of srtSeparateHostStream (with the converters of
+// srtSeparateHostStreamRate at both ends of a piece) and the two sweeps of srtSeparateHostWiener / srtSeparateHostWienerOverlap (its private declarations: srt_engine.h).
 #include "srt_engine.h"
 
 // Grow-only device staging shared by the host-buffer entry points (kept in the engine, freed by srtDestroy).
@@ -100,8 +100,110 @@ size_t srtHostOverlapPieces(size_t rows, int T, int overlap_rows, int max_tiles,
     return count;
 }
 
+// srtSeparateHostStreamRate's side of host_stream, resolved by the entry point: h_in holds n_src frames at the caller's rate (host_stream's n is then
+// the 44.1 kHz length), fin / fout the converters of the two sides (nullptr: that side is at 44.1 kHz), len_out the frames of an output plane
+struct HostRate { size_t n_src; const SrtRsFilter* fin; const SrtRsFilter* fout; size_t len_out; };
+// ---- srtSeparateHostStreamRate's plan.  Piece `pc` of a 44.1 kHz stream of n44 samples (len44 per output plane) whose source holds n_src frames; gi / go: the
+// geometry of in_rate -> 44100 / 44100 -> out_rate, nullptr where that side is at 44.1 kHz.  The source window is every frame a window of 44.1 kHz frames [s0, s0 + ns) starts
+// or ends on, cut to [0, n_src); the output range ends at the last frame whose weighted taps lie before fin1 (srt_rs_computable), so the ranges of the pieces tile [0, len_out).
+static srt_host_rate_piece host_rate_piece(const srt_host_piece& pc, bool last, size_t n_src, size_t n44, size_t len44, size_t len_out, const SrtRsGeom* gi, const SrtRsGeom* go)
+{
+    const size_t tail = SRT_FFT - SRT_HOP, row1 = pc.row0 + pc.stft_rows;
+    srt_host_rate_piece r;
+    r.s0 = pc.row0 * SRT_HOP;
+    const size_t send = row1 * SRT_HOP + tail < n44 ? row1 * SRT_HOP + tail : n44;
+    r.ns = send > r.s0 ? send - r.s0 : 0;
+    r.src0 = r.s0; r.src_len = r.ns;
+    if (gi) {
+        long long lo = 0, hi = 0;
+        if (r.ns) {
+            lo = (long long)((unsigned __int128)r.s0 * gi->P / gi->Q) - gi->LO;
+            hi = (long long)((unsigned __int128)(send - 1) * gi->P / gi->Q) - gi->LO + gi->T4;
+            if (lo < 0) lo = 0;
+            if (hi > (long long)n_src) hi = (long long)n_src;
+            if (hi < lo) hi = lo;
+        }
+        r.src0 = (size_t)lo; r.src_len = (size_t)(hi - lo);
+    }
+    r.fin0 = r.s0; r.fin1 = last ? len44 : r.s0 + pc.own_rows * SRT_HOP;
+    r.out0 = r.fin0; r.out1 = r.fin1;
+    if (go) {
+        const size_t j0 = (size_t)srt_rs_computable(*go, (long long)r.fin0), j1 = (size_t)srt_rs_computable(*go, (long long)r.fin1);
+        r.out0 = j0 < len_out ? j0 : len_out;
+        r.out1 = last || j1 > len_out ? len_out : j1;
+    }
+    return r;
+}
+
+// rates, lengths and the two geometries of a call; 0, or -1 with the error set
+struct HostRateDims { size_t n44, rows, len44, len_out; bool cin, cout; SrtRsGeom gi, go; };
+static int host_rate_dims(size_t n, int in_rate, int out_rate, const char* who, HostRateDims* d)
+{
+    if (in_rate < SRT_RS_MIN_RATE || in_rate > SRT_RS_MAX_RATE || out_rate < SRT_RS_MIN_RATE || out_rate > SRT_RS_MAX_RATE) return fail(-1, "%s: sample rates must lie in 8000..384000 Hz", who);
+    d->cin = in_rate != 44100; d->cout = out_rate != 44100;
+    d->n44 = d->cin ? srtResampleLength(n, in_rate, 44100) : n;
+    if (d->n44 < SRT_FFT) return fail(-1, "%s: need at least 4096 samples at 44.1 kHz", who);
+    if (n > (size_t)1 << 42 || srtStftRows(d->n44) > (size_t)0x7fffffff - 4) return fail(-1, "%s: stream too long (more than 2^31 rows)", who);
+    d->rows = srtStftRows(d->n44);
+    d->len44 = srtIstftLength(d->rows);
+    d->len_out = d->cout ? srtResampleLength(d->len44, 44100, out_rate) : d->len44;
+    int B, np, wl;
+    if (d->cin && (srt_rs_geometry(in_rate, 44100, false, 0, 0, who, &d->gi) || srt_rs_spans_shape(d->gi, 1, &B, &np, &wl)))
+        return fail(-1, "%s: the input converter's window does not fit the LDS for this rate pair", who);
+    if (d->cout && (srt_rs_geometry(44100, out_rate, false, 0, 0, who, &d->go) || srt_rs_spans_shape(d->go, 1, &B, &np, &wl)))
+        return fail(-1, "%s: the output converter's window does not fit the LDS for this rate pair", who);
+    return 0;
+}
+
+size_t srtHostRateLength(size_t n, int in_rate, int out_rate)
+{
+    HostRateDims d;
+    return host_rate_dims(n, in_rate, out_rate, "srtHostRateLength", &d) ? 0 : d.len_out;
+}
+
+size_t srtHostRatePieces(const srt_config* cfg, size_t n, int in_rate, int out_rate, int overlap_rows, srt_host_rate_piece* pieces, size_t max_pieces)
+{
+    static const char* const who = "srtHostRatePieces";
+    if (!cfg) { fail(-1, "%s: null config", who); return 0; }
+    if (srt_check_config(cfg, who)) return 0;
+    HostRateDims d;
+    if (host_rate_dims(n, in_rate, out_rate, who, &d)) return 0;
+    if (!overlap_ok(overlap_rows, cfg->T)) { fail(-1, "%s: overlap_rows must be 0 .. T / 2", who); return 0; }
+    const size_t N = overlap_tiles(d.rows, cfg->T, overlap_rows), count = (N + cfg->max_tiles - 1) / cfg->max_tiles;
+    for (size_t p = 0; pieces && p < count && p < max_pieces; ++p)
+        pieces[p] = host_rate_piece(host_ov_piece(d.rows, cfg->T, overlap_rows, cfg->max_tiles, N, p), p + 1 == count, n, d.n44, d.len44, d.len_out, d.cin ? &d.gi : nullptr, d.cout ? &d.go : nullptr);
+    return count;
+}
+
+// the staging of the rate forms, after ensure_staging (streams exist): grow-only like the rest; 0 floats = not wanted by this call
+static int ensure_rate_staging(srt_engine* e, size_t in_floats, size_t out_floats, size_t carry_floats)
+{
+    HostStaging& h = e->hs;
+    if (in_floats > h.rin_cap || out_floats > h.rout_cap || carry_floats > h.rcarry_cap) {
+        HIPCHK(hipStreamSynchronize(h.s_in)); HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipStreamSynchronize(h.s_out));
+    }
+    for (int b = 0; b < 2; ++b) {
+        if (in_floats > h.rin_cap) {
+            if (h.d_rin[b]) { hipFree(h.d_rin[b]); h.d_rin[b] = nullptr; }
+            HIPCHK(hipMalloc((void**)&h.d_rin[b], in_floats * sizeof(float)));
+        }
+        if (out_floats > h.rout_cap) {
+            if (h.d_rout[b]) { hipFree(h.d_rout[b]); h.d_rout[b] = nullptr; }
+            HIPCHK(hipMalloc((void**)&h.d_rout[b], out_floats * sizeof(float)));
+        }
+    }
+    if (in_floats > h.rin_cap) h.rin_cap = in_floats;
+    if (out_floats > h.rout_cap) h.rout_cap = out_floats;
+    if (carry_floats > h.rcarry_cap) {
+        if (h.d_rcarry) { hipFree(h.d_rcarry); h.d_rcarry = nullptr; h.rcarry_cap = 0; }
+        HIPCHK(hipMalloc((void**)&h.d_rcarry, carry_floats * sizeof(float)));
+        h.rcarry_cap = carry_floats;
+    }
+    return 0;
+}
+
 static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_t n, size_t frames, size_t rows, void* h_out, unsigned flags, int cli_stems,
-                       SrtSeam seam = SrtSeam{0, nullptr, false}, unsigned long long* h_clipped = nullptr, int call_overlap = -1);
+                       SrtSeam seam = SrtSeam{0, nullptr, false}, unsigned long long* h_clipped = nullptr, int call_overlap = -1, const HostRate* rate = nullptr);
 
 // Host-buffer form of srtSeparateCli for plain-C callers (the CLI harness): synchronous.  A file that fits the engine's capacity
 // (max_tiles tiles) is one resident batch: H2D, chain, D2H.  A longer one - any length, as the reference's tile loop over a
@@ -169,10 +271,13 @@ int srtSeparateCliHostIo(srt_engine* e, const void* h_in, const void* h_in2, siz
 // chunks are the pieces of host_ov_piece: a piece uploads and analyses stft_rows rows, of which it inverts, stitches and downloads the first own_rows
 // (separate_piece); after every piece but the last the mask rows the next piece's first O rows blend with are kept (srt_mask_seam_save_kernel).  At 0 the pieces are
 // the chunks and every launch is the one the engine's path issues.
+// rate != nullptr: srtSeparateHostStreamRate.  With rate->fin a piece uploads the source frames host_rate_piece names into d_rin[b] (16-bit: d_in16[b],
+// unpacked into d_rin[b]) and the spans kernel writes d_in[b] in front of the transform; with rate->fout the spans kernel converts every pair behind the seam add - span A
+// the rate carry, span B the piece's planes - into d_rout[b], which the pack and the download then take in d_out[b]'s place.  Without either the launches are the ones above.
 static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_t n, size_t frames, size_t rows, void* h_out_, unsigned flags, int cli_stems, SrtSeam seam,
-                       unsigned long long* h_clipped, int call_overlap)
+                       unsigned long long* h_clipped, int call_overlap, const HostRate* rate)
 {
-    const char* const who = call_overlap >= 0 ? "srtSeparateHostStreamOverlap" : "srtSeparateHostStream";
+    const char* const who = rate ? "srtSeparateHostStreamRate" : call_overlap >= 0 ? "srtSeparateHostStreamOverlap" : "srtSeparateHostStream";
     const bool in16 = flags & SRT_HOST_IN_PCM16, out16 = flags & SRT_HOST_OUT_PCM16;
     if (!e || !h_in || (!in16 && !h_in2) || !h_out_) return fail(-1, "%s: null argument", who);
     if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
@@ -198,7 +303,20 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
     if (rc) return rc;
     if (O && nchunks > 1 && (rc = ensure_mask_seam(e, (size_t)e->cfg.n_stems * 2 * O * e->cfg.F))) return rc;
     const SrtSwitches sw = srt_read_switches();
-    if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? in_cap : 0, out16 ? (size_t)S * out_cap : 0))) return rc;
+    // the rate forms: the largest source window and the most output frames of a piece size the staging; the carry holds the 2 LO + 1 samples in front of a piece
+    const SrtRsFilter* const fin = rate ? rate->fin : nullptr;
+    const SrtRsFilter* const fout = rate ? rate->fout : nullptr;
+    const size_t n_host = rate ? rate->n_src : n, out_len = fout ? rate->len_out : total_len, K = fout ? 2 * (size_t)fout->g.LO + 1 : 0;
+    size_t rin_len = 0, rout_len = 0;
+    for (size_t c = 0; (fin || fout) && c < nchunks; ++c) {
+        const srt_host_piece pc = host_ov_piece(rows, T, O, e->cfg.max_tiles, ntiles_all, c);
+        const srt_host_rate_piece rp = host_rate_piece(pc, c + 1 == nchunks, n_host, n, total_len, out_len, fin ? &fin->g : nullptr, fout ? &fout->g : nullptr);
+        if (rp.src_len > rin_len) rin_len = rp.src_len;
+        if (rp.out1 - rp.out0 > rout_len) rout_len = rp.out1 - rp.out0;
+        if (fout && c + 1 < nchunks && rp.fin1 - rp.fin0 < K) return fail(-1, "%s: a piece finalises fewer samples than the output converter's history", who);
+    }
+    if ((fin || fout) && (rc = ensure_rate_staging(e, fin ? 2 * rin_len : 0, fout ? (size_t)NP * rout_len : 0, (size_t)NP * K))) return rc;
+    if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? (fin && rin_len > in_cap ? rin_len : in_cap) : 0, out16 ? (size_t)S * (fout && rout_len > out_cap ? rout_len : out_cap) : 0))) return rc;
     HostStaging& h = e->hs;
     if (h_clipped) memset(h_clipped, 0, (size_t)S * sizeof *h_clipped);
     unsigned long long* d_clip = out16 && h_clipped ? h.d_clip : nullptr;
@@ -208,9 +326,9 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
     // registered for the duration of the call (if that fails the copies still work, staged by the runtime).
     bool pinL = false, pinR = false, pinO = false;
     if (!(flags & SRT_HOST_PINNED)) {
-        pinL = hipHostRegister((void*)h_in, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;       // int16 [n][2] is n * 4 bytes too
-        pinR = !in16 && hipHostRegister((void*)h_R, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;
-        pinO = !seam.out_stride && hipHostRegister((void*)h_out, (size_t)NP * total_len * (out16 ? sizeof(int16_t) : sizeof(float)), hipHostRegisterDefault) == hipSuccess;
+        pinL = hipHostRegister((void*)h_in, n_host * sizeof(float), hipHostRegisterDefault) == hipSuccess;       // int16 [n][2] is n * 4 bytes too
+        pinR = !in16 && hipHostRegister((void*)h_R, n_host * sizeof(float), hipHostRegisterDefault) == hipSuccess;
+        pinO = !seam.out_stride && hipHostRegister((void*)h_out, (size_t)NP * out_len * (out16 ? sizeof(int16_t) : sizeof(float)), hipHostRegisterDefault) == hipSuccess;
         (void)hipGetLastError();
     }
     hipError_t er = hipSuccess;
@@ -223,9 +341,16 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
         const size_t ns = send > s0 ? send - s0 : 0;
         const size_t cfr = frames > row0 ? (frames - row0 < pc.stft_rows ? frames - row0 : pc.stft_rows) : 0;
         const size_t clen = srtIstftLength(crow);
+        const srt_host_rate_piece rp = host_rate_piece(pc, c + 1 == nchunks, n_host, n, total_len, out_len, fin ? &fin->g : nullptr, fout ? &fout->g : nullptr);
         // upload: the input buffer is free once the compute that read it two chunks ago has finished
         if (c >= 2) STEP(hipStreamWaitEvent(h.s_in, h.ev_cmp[b], 0));
-        if (ns && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * s0, ns * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
+        if (fin) {                                          // the source window, at the caller's rate
+            if (rp.src_len && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * rp.src0, rp.src_len * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
+            else if (rp.src_len) {
+                STEP(hipMemcpyAsync(h.d_rin[b], h_L + rp.src0, rp.src_len * sizeof(float), hipMemcpyHostToDevice, h.s_in));
+                STEP(hipMemcpyAsync(h.d_rin[b] + rin_len, h_R + rp.src0, rp.src_len * sizeof(float), hipMemcpyHostToDevice, h.s_in));
+            }
+        } else if (ns && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * s0, ns * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
         else if (ns) {
             STEP(hipMemcpyAsync(h.d_in[b], h_L + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
             STEP(hipMemcpyAsync(h.d_in[b] + in_cap, h_R + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
@@ -235,9 +360,17 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
         STEP(hipStreamWaitEvent(e->stream, h.ev_in[b], 0));
         if (c >= 2) STEP(hipStreamWaitEvent(e->stream, h.ev_out[b], 0));
         if (er != hipSuccess) break;
-        if (in16 && ns) {
+        if (in16 && fin && rp.src_len) {
+            TimerScope ts(e, "pcm16_unpack");
+            if (srt_launch_pcm16_unpack(h.d_in16[b], rp.src_len, h.d_rin[b], h.d_rin[b] + rin_len, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
+        } else if (in16 && ns && !fin) {
             TimerScope ts(e, "pcm16_unpack");
             if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
+        }
+        if (fin && ns) {                                    // the piece's 44.1 kHz samples [s0, s0 + ns) from the source window: one span, one pair
+            TimerScope ts(e, "rate_in");
+            const SrtRsSpans sp = { 1, h.d_rin[b], rin_len, (long long)rp.src0, rp.src_len, nullptr, 0, 0, n_host, s0, ns, h.d_in[b], in_cap };
+            if ((rc = srt_rs_spans_launch(*fin, sp, e->stream, who))) break;
         }
         if (O) {
             const HostOvPiece hp = { pc.tiles, pc.own_rows, pc.stft_rows, c ? h.d_mseam : nullptr };
@@ -254,14 +387,34 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
             if (hi > lo && (rc = cli_time_residual(e, h.d_in[b], h.d_in[b] + in_cap, ns, cli_stems, h.d_out[b], clen, lo, hi))) break;
         }
         const size_t take = c + 1 == nchunks && !to_tail ? clen : crow * SRT_HOP;
-        if (out16) {
+        const size_t nj = rp.out1 - rp.out0;
+        if (fout) {
+            // output frames [out0, out1) of every pair in one launch: span A the carry (samples [fin0 - K, fin0); before the first piece nothing of it is read - those
+            // positions are negative), span B the samples this piece has finalised, [fin0, fin0 + take)
+            if (nj) {
+                TimerScope ts(e, "rate_out");
+                const SrtRsSpans sp = { S, h.d_rcarry, K, (long long)rp.fin0 - (long long)K, K, h.d_out[b], clen, take, total_len, rp.out0, nj, h.d_rout[b], rout_len };
+                if ((rc = srt_rs_spans_launch(*fout, sp, e->stream, who))) break;
+            }
+            // then the piece's last K finalised samples become the carry (ordered behind the launch that read it)
+            if (c + 1 < nchunks) STEP(hipMemcpy2DAsync(h.d_rcarry, K * sizeof(float), h.d_out[b] + take - K, clen * sizeof(float), K * sizeof(float), NP, hipMemcpyDeviceToDevice, e->stream));
+            if (er != hipSuccess) break;
+        }
+        if (out16 && fout && nj) {
+            TimerScope ts(e, "pcm16_pack");
+            if (srt_launch_pcm16_pack(h.d_rout[b], rout_len, S, nj, h.d_out16[b], rout_len, d_clip, d_clip ? d_clip + SRT_MAX_STEMS : nullptr, e->stream)) { rc = fail(-2, "pcm16 pack launch failed"); break; }
+        } else if (out16 && !fout) {
             TimerScope ts(e, "pcm16_pack");
             if (srt_launch_pcm16_pack(h.d_out[b], clen, S, take, h.d_out16[b], clen, d_clip, d_clip ? d_clip + SRT_MAX_STEMS : nullptr, e->stream)) { rc = fail(-2, "pcm16 pack launch failed"); break; }
         }
         STEP(hipEventRecord(h.ev_cmp[b], e->stream));
         // download: every plane's [0, crow*1024) (+ the final 3072 on the last chunk) lands at its place in h_out
         STEP(hipStreamWaitEvent(h.s_out, h.ev_cmp[b], 0));
-        if (out16) STEP(hipMemcpy2DAsync((int16_t*)h_out_ + 2 * s0, total_len * 2 * sizeof(int16_t), h.d_out16[b], clen * 2 * sizeof(int16_t), take * 2 * sizeof(int16_t), S, hipMemcpyDeviceToHost, h.s_out));
+        if (fout) {                                         // the converted planes: frames [out0, out1) of planes of out_len, one contiguous copy per plane (a pitched 2-D
+                                                            // copy of this size slowed the next piece's first kernels and the copy itself: DESIGN.md 8.1)
+            for (int p = 0; nj && out16 && p < S; ++p) STEP(hipMemcpyAsync((int16_t*)h_out_ + 2 * ((size_t)p * out_len + rp.out0), h.d_out16[b] + 2 * (size_t)p * rout_len, nj * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, h.s_out));
+            for (int p = 0; nj && !out16 && p < NP; ++p) STEP(hipMemcpyAsync(h_out + (size_t)p * out_len + rp.out0, h.d_rout[b] + (size_t)p * rout_len, nj * sizeof(float), hipMemcpyDeviceToHost, h.s_out));
+        } else if (out16) STEP(hipMemcpy2DAsync((int16_t*)h_out_ + 2 * s0, total_len * 2 * sizeof(int16_t), h.d_out16[b], clen * 2 * sizeof(int16_t), take * 2 * sizeof(int16_t), S, hipMemcpyDeviceToHost, h.s_out));
         else STEP(hipMemcpy2DAsync(h_out + s0, total_len * sizeof(float), h.d_out[b], clen * sizeof(float), take * sizeof(float), NP, hipMemcpyDeviceToHost, h.s_out));
         if (to_tail) STEP(hipMemcpy2DAsync(seam.h_tail, tail * sizeof(float), h.d_out[b] + crow * SRT_HOP, clen * sizeof(float), tail * sizeof(float), NP, hipMemcpyDeviceToHost, h.s_out));
         STEP(hipEventRecord(h.ev_out[b], h.s_out));
@@ -313,6 +466,40 @@ int srtSeparateHostStreamOverlap(srt_engine* e, const void* h_in, const void* h_
     if (overlap_rows < 0) return fail(-1, "%s: overlap_rows must be 0 .. T / 2", who);
     if (srtStftRows(n) > (size_t)0x7fffffff - 4) return fail(-1, "%s: more than 2^31 rows", who);
     return host_stream(e, h_in, h_in2, n, srtStftFrames(n), srtStftRows(n), h_out, flags, 0, SrtSeam{0, nullptr, false}, h_clipped, overlap_rows);
+}
+
+// the engine's converter of a rate pair (built-in filter): built on the first call that needs it, kept until srtDestroy
+static int rate_filter(srt_engine* e, int fs_in, int fs_out, const SrtRsGeom& g, const char* who, const SrtRsFilter** out)
+{
+    for (const auto& rf : e->rate_filters) if (rf.fs_in == fs_in && rf.fs_out == fs_out) { *out = &rf.f; return 0; }
+    srt_engine::RateFilter rf;
+    rf.fs_in = fs_in; rf.fs_out = fs_out;
+    if (const int rc = srt_rs_filter_create(g, nullptr, 0, e->stream, who, &rf.f)) return rc;
+    e->rate_filters.push_back(rf);                              // (a deque: the filters handed out earlier stay where they are)
+    *out = &e->rate_filters.back().f;
+    return 0;
+}
+
+int srtSeparateHostStreamRate(srt_engine* e, const void* h_in, const void* h_in2, size_t n, int in_rate, int out_rate, int overlap_rows, void* h_out, unsigned flags,
+                              unsigned long long* h_clipped)
+{
+    static const char* const who = "srtSeparateHostStreamRate";
+    const bool in16 = flags & SRT_HOST_IN_PCM16;
+    if (!e || !h_in || !h_out || (!in16 && !h_in2)) return fail(-1, "%s: null argument", who);
+    if (flags & ~SRT_HOST_FLAGS) return fail(-1, "%s: unknown flag bits", who);
+    if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
+    HostRateDims d;
+    if (const int rc = host_rate_dims(n, in_rate, out_rate, who, &d)) return rc;
+    if (!overlap_ok(overlap_rows, e->cfg.T)) return fail(-1, "%s: overlap_rows must be 0 .. T / 2", who);
+    if (engine_opts(e).wiener) return fail(-1, "%s: the Wiener filter's statistics span the whole signal (chunks would each get their own covariance): srtSetWiener(e, 0) first", who);
+    for (int s = 0; s < e->cfg.n_stems; ++s) if (!e->have_coeff[s]) return fail(-5, "%s: weights not set for every stem", who);
+    HostRate rate = { n, nullptr, nullptr, d.len_out };
+    {
+        DeviceScope ds(e->device);
+        if (d.cin) if (const int rc = rate_filter(e, in_rate, 44100, d.gi, who, &rate.fin)) return rc;
+        if (d.cout) if (const int rc = rate_filter(e, 44100, out_rate, d.go, who, &rate.fout)) return rc;
+    }
+    return host_stream(e, h_in, h_in2, d.n44, srtStftFrames(d.n44), d.rows, h_out, flags, 0, SrtSeam{0, nullptr, false}, h_clipped, overlap_rows, &rate);
 }
 
 // ------------------------------------------------------------------------------------------- the Wiener filter over a host stream of any length

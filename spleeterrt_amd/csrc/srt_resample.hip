@@ -91,6 +91,92 @@ __global__ __launch_bounds__(256) void srt_resample_kernel(SrtRsArgs a)
     }
 }
 
+// The same frames from two consecutive spans of the stream instead of the whole resident input (srtResampleSpans): stream position s is a.A[s - a0] inside
+// [a0, a0 + aLen), a.Bs[s - a0 - aLen] inside the aLen .. aLen + bLen behind it, and 0.0f anywhere else - outside [0, nIn) as above, and where no span holds the
+// position, which the host allows for zero-weight taps only (never memory nobody wrote: 0 x NaN is NaN).  NP stereo pairs share every weight: the workgroup stages NP
+// windows (pair p's at win + p * winLen) and each 16-byte weight load (or rs_weight evaluation) feeds NP dot products.  Per pair the weights, the order of the
+// FMAs and the final l0 + l1 are srt_resample_kernel's, so a frame has srtResample's bits.  blockIdx.y selects the first pair of the workgroup (NP = 1 grids).
+struct SrtRsSpanArgs {
+    SrtRsGeom g;
+    const float* table; const float4* bank;
+    const float* A; long long aStride, a0, aLen;
+    const float* Bs; long long bStride, bLen;
+    long long nIn;
+    float* out; long long outStride;
+    long long out0, outEnd;
+    int B, opt, winLen;
+    long long stepI, stepR, stepM;
+};
+
+template <bool ONFLY, int NP>
+__global__ __launch_bounds__(256) void srt_resample_spans_kernel(SrtRsSpanArgs a)
+{
+    extern __shared__ float2 win[];
+    const SrtRsGeom& g = a.g;
+    const int p0 = blockIdx.y * NP;
+    const long long n0 = a.out0 + (long long)blockIdx.x * a.B;
+    const long long nEnd = min(n0 + (long long)a.B, a.outEnd);
+    const long long i0 = n0 * g.P / g.Q, s0 = i0 - g.LO;
+    const int W = (int)((nEnd - 1) * g.P / g.Q - i0) + g.T4;   // <= winLen: the host sized the LDS for that
+    for (int j = threadIdx.x; j < W; j += blockDim.x) {
+        const long long s = s0 + j, ua = s - a.a0, ub = ua - a.aLen;
+        const bool live = s >= 0 && s < a.nIn, inA = live && ua >= 0 && ua < a.aLen, inB = live && ub >= 0 && ub < a.bLen;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            float2 v = make_float2(0.0f, 0.0f);
+            if (inA) { const float* x = a.A + (long long)(2 * (p0 + p)) * a.aStride + ua; v.x = x[0]; v.y = x[a.aStride]; }
+            else if (inB) { const float* x = a.Bs + (long long)(2 * (p0 + p)) * a.bStride + ub; v.x = x[0]; v.y = x[a.bStride]; }
+            win[p * a.winLen + j] = v;
+        }
+    }
+    __syncthreads();
+    long long n = n0 + threadIdx.x;
+    if (n >= nEnd) return;
+    long long pos = n * g.P, i = pos / g.Q, r = pos - i * g.Q, m = n % g.Q;
+    for (int k = 0; k < a.opt && n < nEnd; ++k) {
+        const float2* x = win + (i - i0);
+        float l0[NP], r0[NP], l1[NP], r1[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) l0[p] = r0[p] = l1[p] = r1[p] = 0.0f;
+        if (ONFLY) {
+            const long long start = rs_start(g, m);
+            for (int t = 0; t < g.T4; t += 4) {
+                const float w0 = rs_weight(g, a.table, start, t), w1 = rs_weight(g, a.table, start, t + 1);
+                const float w2 = rs_weight(g, a.table, start, t + 2), w3 = rs_weight(g, a.table, start, t + 3);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const float2* xp = x + p * a.winLen;
+                    const float2 x0 = xp[t], x1 = xp[t + 1], x2 = xp[t + 2], x3 = xp[t + 3];
+                    l0[p] = fmaf(w0, x0.x, l0[p]); r0[p] = fmaf(w0, x0.y, r0[p]); l1[p] = fmaf(w1, x1.x, l1[p]); r1[p] = fmaf(w1, x1.y, r1[p]);
+                    l0[p] = fmaf(w2, x2.x, l0[p]); r0[p] = fmaf(w2, x2.y, r0[p]); l1[p] = fmaf(w3, x3.x, l1[p]); r1[p] = fmaf(w3, x3.y, r1[p]);
+                }
+            }
+        } else {
+            const float4* wp = a.bank + m;
+            for (int t = 0; t < g.T4; t += 4) {
+                const float4 w = wp[(long long)(t >> 2) * g.Q];
+#pragma unroll
+                for (int p = 0; p < NP; ++p) {
+                    const float2* xp = x + p * a.winLen;
+                    const float2 x0 = xp[t], x1 = xp[t + 1], x2 = xp[t + 2], x3 = xp[t + 3];
+                    l0[p] = fmaf(w.x, x0.x, l0[p]); r0[p] = fmaf(w.x, x0.y, r0[p]); l1[p] = fmaf(w.y, x1.x, l1[p]); r1[p] = fmaf(w.y, x1.y, r1[p]);
+                    l0[p] = fmaf(w.z, x2.x, l0[p]); r0[p] = fmaf(w.z, x2.y, r0[p]); l1[p] = fmaf(w.w, x3.x, l1[p]); r1[p] = fmaf(w.w, x3.y, r1[p]);
+                }
+            }
+        }
+        const long long o = n - a.out0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            float* y = a.out + (long long)(2 * (p0 + p)) * a.outStride + o;
+            y[0] = l0[p] + l1[p];
+            y[a.outStride] = r0[p] + r1[p];
+        }
+        n += blockDim.x; i += a.stepI; r += a.stepR; m += a.stepM;
+        if (r >= g.Q) { r -= g.Q; ++i; }
+        if (m >= g.Q) m -= g.Q;
+    }
+}
+
 struct srt_resampler {
     int fs_in, fs_out, device, onfly;
     SrtRsGeom g;
@@ -243,6 +329,83 @@ int srtResample(srt_resampler* s, const float* d_L, const float* d_R, size_t n_i
     else SRT_LAUNCH(srt_resample_kernel<false>, dim3((unsigned)nb), dim3(s->threads), s->ldsBytes, s->stream, a);
     if (srt_launch_status()) return rs_fail(-2, "srtResample: kernel launch failed%s", "");
     return 0;
+}
+
+// Launch shape of the spans kernel: every pair of a frame block in one workgroup where `pairs` windows of B >= 64 frames fit the LDS budget (B shrinks as in
+// srtResamplerCreate), else one pair per workgroup and a second grid dimension over the pairs.  -1: not even one pair's window of 64 frames fits.
+int srt_rs_spans_shape(const SrtRsGeom& g, int pairs, int* B_out, int* per_wg, int* win_len)
+{
+    auto window = [&](int b) { return (size_t)(((long long)(b - 1) * g.P) / g.Q + 1 + g.T4); };
+    for (int np = pairs; ; np = 1) {
+        int B = 1024;
+        while (B > 64 && np * window(B) * sizeof(float2) > SRT_RS_LDS_BYTES) B >>= 1;
+        if (np * window(B) * sizeof(float2) <= SRT_RS_LDS_BYTES) { *B_out = B; *per_wg = np; *win_len = (int)window(B); return 0; }
+        if (np == 1) return -1;
+    }
+}
+
+template <bool ONFLY>
+static void spans_launch_np(int np, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const SrtRsSpanArgs& a)
+{
+    switch (np) {
+    case 1: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 1>), grid, block, lds, stream, a); break;
+    case 2: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 2>), grid, block, lds, stream, a); break;
+    case 3: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 3>), grid, block, lds, stream, a); break;
+    case 4: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 4>), grid, block, lds, stream, a); break;
+    case 5: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 5>), grid, block, lds, stream, a); break;
+    case 6: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 6>), grid, block, lds, stream, a); break;
+    case 7: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 7>), grid, block, lds, stream, a); break;
+    default: SRT_LAUNCH((srt_resample_spans_kernel<ONFLY, 8>), grid, block, lds, stream, a); break;
+    }
+}
+
+// Checks, then one launch on `stream`.  Taps 0 .. 2 LO + 1 of a frame's window count as weighted (srtResampleHorizon's view: the two outermost may have a zero
+// weight at some phases); the taps that pad the window to T4 never do.
+int srt_rs_spans_launch(const SrtRsFilter& f, const SrtRsSpans& s, hipStream_t stream, const char* who)
+{
+    const SrtRsGeom& g = f.g;
+    if (s.pairs < 1 || s.pairs > SRT_MAX_STEMS) return rs_fail_who(-1, who, "pairs must be 1..SRT_MAX_STEMS");
+    if (s.n_out == 0) return 0;
+    if ((s.a_len && !s.a) || (s.b_len && !s.b) || !s.out) return rs_fail_who(-1, who, "null buffer");
+    if (s.a_len > s.a_stride || s.b_len > s.b_stride || s.n_out > s.out_stride) return rs_fail_who(-1, who, "a plane stride is shorter than its span");
+    const size_t big = (size_t)1 << 44;
+    if (s.out0 > big || s.n_out > big || s.out0 + s.n_out > big || s.n_in > ((size_t)1 << 62) || s.a_len > big || s.b_len > big || s.a0 > (long long)1 << 62 || s.a0 < -((long long)1 << 62))
+        return rs_fail_who(-1, who, "output range too large");
+    int B, np, winLen;
+    if (srt_rs_spans_shape(g, s.pairs, &B, &np, &winLen)) return rs_fail_who(-1, who, "filter too long for this rate pair (input window above 64 KiB)");
+    const unsigned long long nb = (s.n_out + B - 1) / B;
+    if (nb > 0x7fffffffull) return rs_fail_who(-1, who, "output range too large");
+    // the frames of [0, n_in) a weighted tap of the range falls on
+    const long long iFirst = (long long)s.out0 * g.P / g.Q, iLast = (long long)(s.out0 + s.n_out - 1) * g.P / g.Q;
+    const long long lo = iFirst - g.LO > 0 ? iFirst - g.LO : 0, hi = iLast + g.LO + 2 < (long long)s.n_in ? iLast + g.LO + 2 : (long long)s.n_in;
+    if (lo < hi && (lo < s.a0 || hi > s.a0 + (long long)s.a_len + (long long)s.b_len))
+        return rs_fail_who(-1, who, "a requested frame has a weighted tap on an input frame that neither span holds");
+    SrtRsSpanArgs a;
+    a.g = g; a.table = f.d_table; a.bank = (const float4*)f.d_bank;
+    a.A = s.a; a.aStride = (long long)s.a_stride; a.a0 = s.a0; a.aLen = (long long)s.a_len;
+    a.Bs = s.b; a.bStride = (long long)s.b_stride; a.bLen = (long long)s.b_len;
+    a.nIn = (long long)s.n_in; a.out = s.out; a.outStride = (long long)s.out_stride;
+    a.out0 = (long long)s.out0; a.outEnd = (long long)(s.out0 + s.n_out);
+    const int threads = B < 256 ? B : 256;
+    a.B = B; a.opt = B / threads; a.winLen = winLen;
+    const long long adv = (long long)threads * g.P;
+    a.stepI = adv / g.Q; a.stepR = adv % g.Q; a.stepM = threads % g.Q;
+    const dim3 grid((unsigned)nb, (unsigned)(s.pairs / np)), block(threads);
+    const size_t lds = (size_t)np * winLen * sizeof(float2);
+    if (f.onfly) spans_launch_np<true>(np, grid, block, lds, stream, a);
+    else spans_launch_np<false>(np, grid, block, lds, stream, a);
+    if (srt_launch_status()) return rs_fail_who(-2, who, "kernel launch failed");
+    return 0;
+}
+
+int srtResampleSpans(srt_resampler* s, int pairs, const float* d_a, size_t a_stride, long long a0, size_t a_len, const float* d_b, size_t b_stride, size_t b_len,
+                     size_t n_in, size_t out0, size_t n_out, float* d_out, size_t out_stride)
+{
+    if (!s) return rs_fail(-1, "srtResampleSpans: null resampler");
+    SrtRsFilter f;
+    f.g = s->g; f.onfly = s->onfly; f.d_table = s->d_table; f.d_bank = s->d_bank;
+    const SrtRsSpans sp = { pairs, d_a, a_stride, a0, a_len, d_b, b_stride, b_len, n_in, out0, n_out, d_out, out_stride };
+    return srt_rs_spans_launch(f, sp, s->stream, "srtResampleSpans");
 }
 
 int srtResampleHost(srt_resampler* s, const float* h_L, const float* h_R, size_t n_in, float* h_Lo, float* h_Ro)

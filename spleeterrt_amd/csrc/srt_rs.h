@@ -53,6 +53,19 @@ int srt_rs_geometry(int fs_in, int fs_out, bool has_table, int table_len, int in
 int srt_rs_filter_create(const SrtRsGeom& g, const float* h_table, int table_len, hipStream_t stream, const char* who, SrtRsFilter* f);
 void srt_rs_filter_free(SrtRsFilter* f);
 
+// ---- spans form (srtResampleSpans, and both ends of srtSeparateHostStreamRate's pieces): the arguments of the public call, on any filter and stream
+struct SrtRsSpans {
+    int pairs;
+    const float* a; size_t a_stride; long long a0; size_t a_len;
+    const float* b; size_t b_stride, b_len;
+    size_t n_in, out0, n_out;
+    float* out; size_t out_stride;
+};
+// frames per workgroup, pairs per workgroup (`pairs`, or 1 with a grid dimension over the pairs) and the LDS window of one pair in frames; -1: one pair does not fit
+int srt_rs_spans_shape(const SrtRsGeom& g, int pairs, int* B, int* per_wg, int* win_len);
+// every check of srtResampleSpans, then one launch: 0, -1 / -2 with srtLastError() = "<who>: ..."
+int srt_rs_spans_launch(const SrtRsFilter& f, const SrtRsSpans& s, hipStream_t stream, const char* who);
+
 // ---- streaming form (srt_rsstream.hip): the same frames computed from a device ring of past input plus the call's block
 // frames a stream that has received n_in input frames can compute: those whose last weighted tap floor(j P / Q) + H, H = LO + 1, has arrived
 static inline int srt_rs_horizon(const SrtRsGeom& g) { return g.LO + 1; }

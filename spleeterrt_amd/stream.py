@@ -116,6 +116,75 @@ def host_overlap_pieces(rows, T, O, max_tiles):
     return pieces
 
 
+def rs_geometry(fs_in, fs_out, table_len=22438, index_inc=491):
+    """The converter's geometry for a rate pair (csrc/srt_resample.hip:srt_rs_geometry; defaults: the built-in filter's layout): dict P, Q (the rates over their
+    gcd), LO (a frame at input position i + frac takes input frames i - LO .. i + LO + 1) and T4 (the window's taps, padded to a multiple of 4 with zero weights)."""
+    from math import gcd
+    g = gcd(fs_in, fs_out)
+    inc = int(round(index_inc * min(fs_out / fs_in, 1.0) * 4096.0))      # rint: halves to even, as round()
+    LO = ((table_len - 2) << 12) // inc
+    return dict(P=fs_in // g, Q=fs_out // g, LO=LO, T4=(2 * LO + 2 + 3) // 4 * 4)
+
+
+def rs_computable(geom, n_in):
+    """srtResampleComputable: output frames whose last weighted tap, floor(j P / Q) + LO + 1, lies before input frame n_in"""
+    a = n_in - (geom["LO"] + 1)
+    return 0 if a <= 0 else -(-a * geom["Q"] // geom["P"])
+
+
+def resample_length(n, fs_in, fs_out):
+    """srtResampleLength: ceil(n * (fs_out / fs_in)) in doubles, as the reference allocates"""
+    from math import ceil
+    return int(ceil(float(n) * (fs_out / float(fs_in))))
+
+
+def host_rate_length(n, in_rate, out_rate):
+    """srtHostRateLength: frames per output plane of srtSeparateHostStreamRate for n frames at in_rate"""
+    n44 = n if in_rate == 44100 else resample_length(n, in_rate, 44100)
+    len44 = stft_rows(n44) * 1024 + 3072
+    return len44 if out_rate == 44100 else resample_length(len44, 44100, out_rate)
+
+
+def host_rate_pieces(n, in_rate, out_rate, T, O, max_tiles):
+    """srtHostRatePieces: the pieces srtSeparateHostStreamRate walks n frames at in_rate in, a list of dicts.  Piece c of host_overlap_pieces over
+    the 44.1 kHz stream analyses samples [s0, s0 + ns) and finalises [fin0, fin1) of every output plane (fin1 = s0 + own_rows * 1024, the last piece to the end).
+    With (P, Q, LO, T4) of in_rate -> 44100 it uploads source frames [src0, src0 + src_len) = [max(0, floor(s0 P / Q) - LO), min(n, floor((s0 + ns - 1) P / Q) -
+    LO + T4)); with the geometry of 44100 -> out_rate it emits output frames [out0, out1), out = min(len_out, rs_computable(fin)), the last piece to len_out.  A
+    side at 44100 has no converter: src = (s0, ns), out = fin."""
+    for r in (in_rate, out_rate):
+        if r < 8000 or r > 384000:
+            raise ValueError("host_rate_pieces: sample rates must lie in 8000..384000 Hz (%d)" % r)
+    n44 = n if in_rate == 44100 else resample_length(n, in_rate, 44100)
+    if n44 < 4096:
+        raise ValueError("host_rate_pieces: need at least 4096 samples at 44.1 kHz (%d)" % n44)
+    rows = stft_rows(n44)
+    len44 = rows * 1024 + 3072
+    len_out = host_rate_length(n, in_rate, out_rate)
+    gi = rs_geometry(in_rate, 44100) if in_rate != 44100 else None
+    go = rs_geometry(44100, out_rate) if out_rate != 44100 else None
+    plan = host_overlap_pieces(rows, T, O, max_tiles)
+    pieces = []
+    for c, pc in enumerate(plan):
+        last = c + 1 == len(plan)
+        s0 = pc["row0"] * 1024
+        send = min((pc["row0"] + pc["stft_rows"]) * 1024 + 3072, n44)
+        ns = max(send - s0, 0)
+        src0, src_len = s0, ns
+        if gi:
+            lo = hi = 0
+            if ns:
+                lo = max(s0 * gi["P"] // gi["Q"] - gi["LO"], 0)
+                hi = max(min((send - 1) * gi["P"] // gi["Q"] - gi["LO"] + gi["T4"], n), lo)
+            src0, src_len = lo, hi - lo
+        fin0, fin1 = s0, len44 if last else s0 + pc["own_rows"] * 1024
+        out0, out1 = fin0, fin1
+        if go:
+            out0 = min(rs_computable(go, fin0), len_out)
+            out1 = len_out if last else min(rs_computable(go, fin1), len_out)
+        pieces.append(dict(src0=src0, src_len=src_len, s0=s0, ns=ns, fin0=fin0, fin1=fin1, out0=out0, out1=out1))
+    return pieces
+
+
 def _refuse_overlap(engine):
     """The chunked and ranked paths cut a stream at back-to-back tile boundaries; with overlapped tiles the blend would have to cross those seams."""
     if getattr(engine, "overlap", 0):
