@@ -593,7 +593,7 @@ SRT_API int  srtResamplerStreamDestroy(srt_resampler_stream *r);
  * separation quality falls as L approaches 0.
  * srtLiveCreate: current device; cfg honours F, T, n_stems, stem_mode, oob_weight, variant, impl, precision, ratio_mask, batch_invariant; max_tiles
  * must be 1; h_coeff: n_stems spleeterCoeff blobs (copied).  Every argument is checked before any HIP call (-1 with srtLastError() text).  Init does
- * all allocation, graph capture and the pre-warm of the hop path; the Wiener filter is never on.
+ * all allocation, graph capture and the pre-warm of the hop path; the Wiener filter is off (srtLiveCreateWiener below turns it on).
  * srtLiveProcess: n samples per channel in, up to n samples written to each of the 2*n_stems planar outputs (stem-major L/R pairs), with the
  * reference's accounting (Spleeter4StemsProcessSamples): one 1024-sample segment per completed hop, a two-segment queue, the queue emitting from the
  * call that completes the first hop and never more than the call's n.  Returns the count written (0..n), negative on a bad argument.  Never
@@ -646,6 +646,29 @@ SRT_API int srtLiveCreateEx(const srt_config *cfg, int hops_per_run, int lookahe
                             const void *const *h_coeff, srt_live **out);
 SRT_API int srtLiveSetMix(srt_live *s, const float *h_gain);   /* same n_out as at creation; holds from the next hop processed */
 SRT_API int srtLiveOutputs(const srt_live *s);                 /* stereo pairs a call writes: n_out while the mix is on, else n_stems; 0 for NULL */
+/* The multichannel Wiener filter (srtSetWiener's --mwf) in the live hop path.  srtLiveCreateWiener is srtLiveCreateEx plus `iterations` = n,
+ * 0..3, fixed at creation; 0 is srtLiveCreateEx(cfg, K, L, opts, ..): the same launches, the same bits.  With n > 0 the statistics window of a run is its network
+ * window: run r, which ends at hop h_r, leaves the tables srtIstftWiener(e, X_r, T, M_r, n, ..) leaves as "wiener_cov", bit for bit - X_r [2][T][2052] the
+ * spectrum rows of frames h_r-T+1 .. h_r as the live forward transform stores them, oldest first, zero for frames before 0; M_r [S][2][T][F] the masks the run
+ * wrote (floats in every precision) - by the same kernels, chunks and row order.  Frame g, synthesised at hop g + D from the run whose window holds it at row
+ * p = T-1-(h_r-g) (the schedule above, unchanged), takes for k < F stem j's spectrum y_j from the filter's chain on (s_L, s_R, M_r[:, :, p, k]) - the soft-mask
+ * start, then n EM iterations with run r's tables and a - and for k >= F oob_weight[j] * s, or e_j(c) * s under SRT_MASK_EXT_AVERAGE (the extension follows the
+ * mask, not the filter).  With opts->n_out > 0 output m is, per complex component, h = G[m][S] * s; h = fmaf(G[m][j], y_j, h) for j ascending (srtIstftWienerEx's
+ * chain) in band and srtLiveCreateEx's gain chain times s above F; srtLiveSetMix works as there, and a one-hot row equals that stem of the instance without a
+ * mix bit for bit.  Before the first run is joined the tables are zero and a = 1; only zero spectra are synthesised then, and the chain gives exactly 0.
+ * Everything srtLiveCreateEx honours holds (rate instances, the mix, the extension, the engine's precision), as do its accounting, srtLiveLatency, the D silent
+ * hops and the failure policy; Init does every allocation, the workspace set-up and the pre-warm of every kernel, srtLiveProcess still never allocates or captures.
+ * -1 with srtLastError() text, before any HIP call: everything srtLiveCreateEx refuses, iterations outside 0..3, ratio_mask set with iterations > 0 (both
+ * are the post-processing of the masks).  srtLiveWiener: the iterations, 0 while off or for NULL.
+ * srtLiveCopyTensor: debug read-back of the run launched last (it waits for both of the instance's streams: not for the audio thread).  *run_hop (may be NULL)
+ * receives that run's h_r; while no run has been launched it receives -1, nothing is written and 0 is returned.  "wiener_cov": index = the iteration 1..n,
+ * 5 F + 1 floats as srtCopyTensor's (R [F][4], the weight sums [F], a); "wiener_spec": the gathered window [2][T][2052] complex, 2 * T * 2052 * 2 floats;
+ * "masks": the stem's [2][T][F].  Returns the float count; -1 for a null handle, name or buffer, an unknown name, a stem outside the stems, an index outside
+ * the iterations, a buffer that is too small, "wiener_*" on an instance without the filter. */
+SRT_API int srtLiveCreateWiener(const srt_config *cfg, int hops_per_run, int lookahead, const srt_live_opts *opts /* may be NULL */,
+                                int iterations, const void *const *h_coeff, srt_live **out);
+SRT_API int srtLiveWiener(const srt_live *s);      /* iterations, 0 while off or for NULL */
+SRT_API int srtLiveCopyTensor(srt_live *s, const char *name, int stem, int index, float *h_dst, size_t max_floats, long long *run_hop);
 
 /* debug / measurement */
 SRT_API int  srtCopyTensor(srt_engine *e, const char *name, int stem, int tile, float *h_dst, size_t max_floats); /* "conv1".."conv6","act1".."act5","up1".."up6";

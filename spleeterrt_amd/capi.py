@@ -149,6 +149,9 @@ def load_library():
     L.srtLiveCreateEx.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, C.POINTER(_LiveOpts), C.POINTER(vp), C.POINTER(vp)]
     L.srtLiveSetMix.argtypes = [vp, vp]
     L.srtLiveOutputs.argtypes = [vp]
+    L.srtLiveCreateWiener.argtypes = [C.POINTER(_Config), C.c_int, C.c_int, C.POINTER(_LiveOpts), C.c_int, C.POINTER(vp), C.POINTER(vp)]
+    L.srtLiveWiener.argtypes = [vp]
+    L.srtLiveCopyTensor.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, vp, C.c_size_t, C.POINTER(C.c_longlong)]
     # sample-rate converter (csrc/srt_resample.hip)
     L.srtResampleLength.restype = C.c_size_t
     L.srtResampleLength.argtypes = [C.c_size_t, C.c_int, C.c_int]
@@ -911,11 +914,13 @@ class Live:
     the delay is the constant `latency` whatever the call sizes; max_block is the largest slice a call is processed in.
     mix=G ([n_out][S + 1], srtSetMix's layout: the last column is the unmasked input) makes the calls write n_out stereo pairs, the mix of the stems formed
     inside the hop's inverse transform; set_mix replaces the values later.  mask_extension="average" lets the bins above F follow each
-    stem's mean mask instead of oob_weights.  Either one creates through srtLiveCreateEx (create_ex=True does so with no option set)."""
+    stem's mean mask instead of oob_weights.  Either one creates through srtLiveCreateEx (create_ex=True does so with no option set).
+    wiener=n (1..3) creates through srtLiveCreateWiener: the multichannel Wiener filter over each run's network window, applied inside the hop's inverse
+    transform; `wiener` returns the count and tensor() reads the last launched run's tables, window and masks back."""
 
     def __init__(self, F, T, stem_modes, oob_weights, variant, precision, hops_per_run, lookahead, coeffs, impl=IMPL_MFMA,
                  ratio_mask=False, batch_invariant=False, max_tiles=1, sample_rate=None, max_block=4096, mix=None, mask_extension="constant",
-                 create_ex=False):
+                 create_ex=False, wiener=0):
         import numpy as np
         self.L = load_library()
         self.S, self.F, self.T = len(stem_modes), F, T
@@ -933,7 +938,7 @@ class Live:
         h = C.c_void_p()
         self.sample_rate = None if sample_rate is None else int(sample_rate)
         ext = {"constant": MASK_EXT_CONSTANT, "average": MASK_EXT_AVERAGE}.get(mask_extension, mask_extension)
-        if mix is not None or ext != MASK_EXT_CONSTANT or create_ex:
+        if mix is not None or ext != MASK_EXT_CONSTANT or create_ex or int(wiener) > 0:
             o = _LiveOpts()
             if sample_rate is not None:
                 o.sample_rate, o.max_block = self.sample_rate, int(max_block)
@@ -941,7 +946,10 @@ class Live:
                 g = self._gain(mix, None)
                 o.n_out, o.h_gain = g.shape[0], g.ctypes.data_as(C.POINTER(C.c_float))
             o.mask_extension = int(ext)
-            self._chk(self.L.srtLiveCreateEx(C.byref(cfg), self.hops_per_run, self.lookahead, C.byref(o), ptrs, C.byref(h)))
+            if int(wiener) > 0:
+                self._chk(self.L.srtLiveCreateWiener(C.byref(cfg), self.hops_per_run, self.lookahead, C.byref(o), int(wiener), ptrs, C.byref(h)))
+            else:
+                self._chk(self.L.srtLiveCreateEx(C.byref(cfg), self.hops_per_run, self.lookahead, C.byref(o), ptrs, C.byref(h)))
         elif sample_rate is None:
             self._chk(self.L.srtLiveCreate(C.byref(cfg), self.hops_per_run, self.lookahead, ptrs, C.byref(h)))
         else:
@@ -964,6 +972,27 @@ class Live:
     def outputs(self):
         """stereo pairs a call writes (srtLiveOutputs): the mix's n_out, or the stem count while it is off"""
         return self.L.srtLiveOutputs(self.h)
+
+    @property
+    def wiener(self):
+        """iterations of the Wiener filter in the hop path (srtLiveWiener), 0 while off"""
+        return self.L.srtLiveWiener(self.h)
+
+    def tensor(self, name, stem=0, index=0):
+        """srtLiveCopyTensor: (array, run_hop) of the run launched last - "wiener_cov" (index = iteration 1..n; 5 F + 1 floats: R [F][4], weight sums [F], a),
+        "wiener_spec" (complex64 [2][T][2052]) or "masks" (the stem's [2][T][F]); (None, -1) while no run has been launched.  Waits for the instance's streams."""
+        import numpy as np
+        count = {"wiener_cov": 5 * self.F + 1, "wiener_spec": 2 * self.T * SPEC_LD * 2, "masks": 2 * self.T * self.F}.get(name, 1)
+        a = np.empty(count, np.float32)
+        hr = C.c_longlong(-2)
+        n = self._chk(self.L.srtLiveCopyTensor(self.h, name.encode(), int(stem), int(index), C.c_void_p(a.ctypes.data), a.size, C.byref(hr)))
+        if n == 0:
+            return None, int(hr.value)
+        if name == "wiener_spec":
+            return a.view(np.complex64).reshape(2, self.T, SPEC_LD), int(hr.value)
+        if name == "masks":
+            return a.reshape(2, self.T, self.F), int(hr.value)
+        return a, int(hr.value)
 
     def set_mix(self, G):
         """srtLiveSetMix: replace the matrix values (the same [n_out][S + 1]); holds from the next hop processed"""

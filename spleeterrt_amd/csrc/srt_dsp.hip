@@ -1959,6 +1959,130 @@ int srt_launch_live_combine_hop(const SrtLiveCombineHop& q, const SrtStreamHop& 
     return srt_launch_status();
 }
 
+// The hop inverse of a live stream with the Wiener filter (srtLiveCreateWiener): one workgroup per OUTPUT m, as the combining inverse.  The filter
+// is folded into the prologue: per bin k < F the thread loads s_L, s_R and the S mask values of both channels, runs the filter's chain for ALL stems - w_start,
+// then p.iters times w_iter on the joined run's R tables with delta = sqrt(eps) (a / 4096)^2, the statements the offline kernels run (srt_wiener_chain.h) - and
+// forms the output's spectrum per complex component,
+//   h = G[m][S] s;  for j = 0 .. S-1 ascending:  h = fmaf(G[m][j], y_j, h)
+// (srtIstftWienerEx's chain: one rounded product, one fused multiply-add per stem, nothing else contracted).  Above F the output is srt_live_combine_gains' gain
+// chain on oob / the extension's row (workgroup-uniform: computed once) times s: the extension follows the mask, not the filter.  Every output recomputes the chain
+// of every stem: one launch fewer on a hop that is bound by launch latency.  The nine bins are walked one after the other (no unrolling) so that yl / yr exist
+// once.  An instance without a mix launches this kernel with the identity, so a one-hot row and the stem come out of one compiled copy of the chain and agree
+// bit for bit.  Zero spectrum (the hops before the first join, silence): every y is exactly 0 and delta > 0 keeps the determinant positive - 0, never NaN.
+// Everything from the s_x packing on is srt_stream_inverse_body.
+#include "srt_wiener_chain.h"      // here, where the file's contraction state is the explicit `fast` the header leaves behind: the kernels above compile as they did
+#pragma clang fp contract(off)
+template <bool EXT>
+__device__ __forceinline__ void srt_live_wiener_oob(const SrtLiveWienerHop& p, int m, float& hl, float& hr)
+{
+    hl = hr = p.gain[m][p.nstems];
+    for (int s = 0; s < p.nstems; ++s) {
+        float ol = p.oob[s], orr = ol;
+        if constexpr (EXT) { ol = p.ext[(size_t)s * p.extStemStride]; orr = p.ext[(size_t)s * p.extStemStride + 1]; }
+        hl = fmaf(p.gain[m][s], ol, hl); hr = fmaf(p.gain[m][s], orr, hr);
+    }
+}
+__device__ __forceinline__ float2 srt_live_wiener_mix(const SrtLiveWienerHop& p, int m, int S, float2 s, const float2 (&y)[SRT_MAX_STEMS])
+{
+    const float g = p.gain[m][S];
+    float hx = g * s.x, hy = g * s.y;
+#pragma unroll
+    for (int j = 0; j < SRT_MAX_STEMS; ++j)
+        if (j < S) { const float gj = p.gain[m][j]; hx = fmaf(gj, y[j].x, hx); hy = fmaf(gj, y[j].y, hy); }
+    return make_float2(hx, hy);
+}
+#pragma clang fp contract(fast)
+
+template <bool EXT>
+__global__ void __launch_bounds__(256) srt_live_wiener_inverse_kernel(const SrtLiveWienerHop p)
+{
+    __shared__ cf s_tw[FFT_TW_F2];
+    __shared__ cf s_x[FFT_SMEM_F2];
+    const int tid = threadIdx.x, m = blockIdx.x, S = p.nstems;
+    fft_load_twiddles(s_tw, p.twiddle, tid);
+    const float2* specL = p.specRow;
+    const float2* specR = p.specRow + p.specChStride;
+    const float al = p.scal[0] * (1.0f / 4096.0f), delta = W_SQRT_EPS * al * al;
+    float ol, orr;
+    srt_live_wiener_oob<EXT>(p, m, ol, orr);
+#pragma unroll 1
+    for (int j = 0; j < 9; ++j) {
+        const int k = tid + 256 * j;
+        if (k <= 2048) {
+            const float2 sL = specL[k], sR = specR[k];
+            float reL, imL, reR, imR;
+            if (k < p.F) {
+                float2 yl[SRT_MAX_STEMS], yr[SRT_MAX_STEMS];
+                w_start(yl, yr, sL, sR, p.maskRow + k, p.maskStemStride, p.maskChStride, S);
+                for (int i = 0; i < p.iters; ++i)
+                    w_iter<true>(yl, yr, sL, sR, p.rtab + (size_t)i * S * p.F + k, p.F, delta, S);
+                const float2 hL = srt_live_wiener_mix(p, m, S, sL, yl), hR = srt_live_wiener_mix(p, m, S, sR, yr);
+                reL = hL.x; imL = hL.y; reR = hR.x; imR = hR.y;
+            } else { reL = sL.x * ol; imL = sL.y * ol; reR = sR.x * orr; imR = sR.y * orr; }
+            if (k == 0) s_x[0] = f2(reR, reL);
+            else if (k == 2048) s_x[2048] = f2(reR - imR, reL - imL);
+            else {
+                s_x[k] = f2(reR - imL, reL + imR);
+                s_x[4096 - k] = f2(reR + imL, reL - imR);
+            }
+        }
+    }
+    __syncthreads();
+    cf v[16];
+#pragma unroll
+    for (int n2 = 0; n2 < 16; ++n2) v[n2] = s_x[tid + 256 * n2];
+    __syncthreads();
+    fft4096(v, s_x, s_tw, tid);
+    float* ovL = p.overlap + (size_t)(2 * m) * 1024;
+    float* ovR = ovL + 1024;
+    const int os = 2 * p.n_out;
+#pragma unroll
+    for (int k2 = 8; k2 < 12; ++k2) {                                         // as srt_stream_inverse_body: k2 = 8..11 -> output, 12..15 -> kept half
+        const int i = tid + 256 * (k2 - 8);
+        const float w0 = p.synthesisWnd[i], w1 = p.synthesisWnd[i + 1024];
+        const cf y0 = v[FFT16_AT(k2)], y1 = v[FFT16_AT(k2 + 4)];
+        p.out[(size_t)i * os + 2 * m + 0] = ovL[i] + y0.y * w0;
+        p.out[(size_t)i * os + 2 * m + 1] = ovR[i] + y0.x * w0;
+        ovL[i] = y1.y * w1;
+        ovR[i] = y1.x * w1;
+    }
+}
+
+// q: the filtering inverse (n_out workgroups); p: the hop's SrtStreamHop, of which only the forward transform's fields are used
+int srt_launch_live_wiener_hop(const SrtLiveWienerHop& q, const SrtStreamHop& p, hipStream_t s)
+{
+    if (q.nstems < 1 || q.nstems > SRT_MAX_STEMS || q.n_out < 1 || q.n_out > SRT_MAX_STEMS || q.F < 1 || q.F > SRT_HALF - 1 ||
+        q.iters < 1 || q.iters > SRT_WIENER_MAX_ITERS || !q.rtab || !q.scal) return -1;
+    if (q.ext) SRT_LAUNCH((srt_live_wiener_inverse_kernel<true>), dim3(q.n_out), dim3(256), 0, s, q);
+    else SRT_LAUNCH((srt_live_wiener_inverse_kernel<false>), dim3(q.n_out), dim3(256), 0, s, q);
+    if (hipGetLastError() != hipSuccess) return -1;
+    SRT_LAUNCH(srt_stream_forward_kernel, dim3(1), dim3(256), 0, s, p);     // after the inverse has read the delayed row, as srt_launch_stream_hop
+    return srt_launch_status();
+}
+
+// Live spectrum-window gather (srtLiveCreateWiener): the spectrum ring holds frame g in row g mod R of each channel, R >= T; the statistics want the window's
+// oldest frame in row 0.  dst[c][i][:] = ring[c][(i + rot) mod R][:] for i < T, one workgroup per (row, 512 floats), 16-byte loads and stores (a row is
+// SRT_SPEC_LD complex values = 1026 float4).
+__global__ void __launch_bounds__(128) srt_live_spec_gather_kernel(const float4* __restrict__ ring, float4* __restrict__ dst, int T, int R, int rot)
+{
+    constexpr int LD4 = SRT_SPEC_LD / 2;
+    const int f = blockIdx.x * 128 + threadIdx.x;
+    if (f >= LD4) return;
+    const int row = blockIdx.y, c = row >= T ? 1 : 0, i = row - c * T;
+    int src = i + rot;
+    if (src >= R) src -= R;
+    dst[(size_t)row * LD4 + f] = ring[((size_t)c * R + src) * LD4 + f];
+}
+
+int srt_launch_live_spec_gather(const float2* ring, float2* dst, int T, int R, int rot, hipStream_t s)
+{
+    static_assert(SRT_SPEC_LD % 2 == 0, "a spectrum row is a whole number of float4");
+    if (T < 1 || R < T || rot < 0 || rot >= R) return -1;
+    SRT_LAUNCH(srt_live_spec_gather_kernel, dim3((SRT_SPEC_LD / 2 + 127) / 128, 2 * T), dim3(128), 0, s,
+               reinterpret_cast<const float4*>(ring), reinterpret_cast<float4*>(dst), T, R, rot);
+    return srt_launch_status();
+}
+
 // Live window gather (srt_stream.hip): the magnitude ring holds frame g in row g mod T of each channel; the network wants the
 // window's oldest frame in row 0.  dst[c][i][:] = ring[c][(i + rot) mod T][:], one workgroup per (row, 512 columns), 16-byte
 // loads and stores.  rot = 0 is a plain copy (the plugin's geometry, where every window starts at a multiple of T).

@@ -396,6 +396,27 @@ struct SrtLiveCombineHop {
 int srt_launch_live_combine_hop(const SrtLiveCombineHop& q, const SrtStreamHop& p, hipStream_t s);
 // Live window gather: dst[c][i] = ring[c][(i + rot) mod T] for the [2][T][F] magnitude ring (rows of F floats, F % 4 == 0)
 int srt_launch_live_gather(const float* ring, float* dst, int T, int F, int rot, hipStream_t s);
+// the hop inverse of a live stream with the Wiener filter (srtLiveCreateWiener): one workgroup per output; the prologue runs the filter's chain for
+// every stem at the thread's nine bins from the joined run's tables and forms the output's spectrum (in band the remix chain of the filtered stems, above F the
+// combining inverse's gain chain times the input)
+struct SrtLiveWienerHop {
+    const float2* specRow; size_t specChStride;                               // the DELAYED frame's row: L at specRow, R at specRow + specChStride
+    const float* maskRow; size_t maskStemStride, maskChStride;                // as SrtStreamHop
+    int F, nstems;
+    int n_out;                // outputs (workgroups), 1..SRT_MAX_STEMS
+    int iters;                // 1..SRT_WIENER_MAX_ITERS
+    const float4* rtab;       // the joined run's R tables [iters][nstems][F] (SrtWienerParams::rtab)
+    const float* scal;        // ... and its a (SrtWienerParams::scal)
+    float oob[SRT_MAX_STEMS];
+    const float* ext; size_t extStemStride;                                   // as SrtLiveCombineHop; nullptr: the constant rule
+    float gain[SRT_MAX_STEMS][SRT_MAX_STEMS + 1];                             // as SrtLiveCombineHop (without a mix: the identity)
+    float* overlap;           // [2*n_out][1024]
+    float* out;               // [1024][2*n_out] interleaved segment
+    const float* synthesisWnd; const float2* twiddle;
+};
+int srt_launch_live_wiener_hop(const SrtLiveWienerHop& q, const SrtStreamHop& p, hipStream_t s);      // p: the forward transform's fields, as srt_launch_live_combine_hop
+// Live spectrum-window gather: dst[c][i] = ring[c][(i + rot) mod R] for i < T, rows of SRT_SPEC_LD complex values; ring [2][R][SRT_SPEC_LD], dst [2][T][SRT_SPEC_LD], T <= R
+int srt_launch_live_spec_gather(const float2* ring, float2* dst, int T, int R, int rot, hipStream_t s);
 struct srt_config;
 // srtCreate's argument checks (no HIP call): 0, or the negative code with srtLastError() set and `who` naming the caller
 int srt_check_config(const srt_config* cfg, const char* who);

@@ -13,6 +13,9 @@
 // An instance of srtLiveCreateEx with a stem remix and / or the average mask extension writes P = n_out pairs instead of S: its hops run
 //   srt_live_combine_inverse_kernel x P outputs : frame h-D's spectrum x the chain over all S mask rows under the matrix in force
 // and every run is followed, on the network stream, by the extension's table for the K rows it serves.
+// An instance of srtLiveCreateWiener with iterations > 0 keeps a spectrum ring of max(D, T) rows; at a run's launch the window's spectrum rows are
+// gathered beside the magnitudes, the run is followed by the offline filter's statistics launches over that window into its table set, and the hops run
+//   srt_live_wiener_inverse_kernel x P outputs : the filter's chain for every stem from the joined run's masks and tables, folded into the inverse's prologue.
 #include "srt_internal.h"
 #include "srt_rs.h"
 #include "srt_checks.h"
@@ -59,7 +62,13 @@ struct srt_live {
     bool combine, ext;
     float G[SRT_MAX_STEMS][SRT_MAX_STEMS + 1];
     float* d_ext;
-    // device: input ring [2][4096], spectrum ring [2][D][SPEC_LD] (frame g at row g mod D), magnitude ring [2][T][F] (frame g at row g mod T),
+    // srtLiveCreateWiener.  W: the filter's iterations, 0: off (then nothing below exists and every launch is srtLiveCreateEx's).  R: rows of the
+    // spectrum ring, D without the filter, max(D, T) with it (the ring then holds a whole network window).  d_wspec: the window of the run launched last, gathered
+    // [2][T][SPEC_LD]; d_wslab: the statistics kernels' partial sums; d_wtab: the table sets [2 buffers][wtabF], buffer b written by the run that writes mask buffer b
+    int W, R;
+    float2* d_wspec; float* d_wslab; float* d_wtab;
+    size_t wtabF;
+    // device: input ring [2][4096], spectrum ring [2][R][SPEC_LD] (frame g at row g mod R; R = D unless the filter is on), magnitude ring [2][T][F] (frame g at row g mod T),
     // network window [2][T][F], masks [2 buffers][S][2][T][F], overlap [2P][1024], segment [1024][2P]
     float* d_ring; float2* d_spec; float* d_mag; float* d_tmp; float* d_masks; float* d_overlap; float* d_out;
     float *d_awin, *d_swin; float2* d_tw;
@@ -101,8 +110,8 @@ void asymmetric_window(std::vector<float>& an, std::vector<float>& sy)      // S
 
 float* masks_buf(const srt_live* s, int b) { return s->d_masks + (size_t)b * s->S * 2 * s->hw; }
 
-// the hop kernels' arguments for hop h: frame h is written to spectrum row h mod D and magnitude row h mod T after frame h-D has been
-// read from the same spectrum row under row T-1-(h_r-(h-D)) of the last joined run h_r
+// the hop kernels' arguments for hop h: frame h is written to spectrum row h mod R (R = D without the filter) and magnitude row h mod T after frame h-D
+// has been read - without the filter from the same spectrum row - under row T-1-(h_r-(h-D)) of the last joined run h_r
 SrtStreamHop hop_params(const srt_live* s, long long h)
 {
     SrtStreamHop p; memset(&p, 0, sizeof p);
@@ -110,7 +119,7 @@ SrtStreamHop hop_params(const srt_live* s, long long h)
     const long long g = h - s->D;
     const int prow = s->joinedHop >= 0 ? s->T - 1 - (int)(s->joinedHop - g) : s->T - 1 - s->L;     // before the first join: zero spectrum, unit masks
     p.ring = s->d_ring; p.inPos = (int)s->inPos;
-    p.specRow = s->d_spec + (size_t)(h % s->D) * rowF2; p.specChStride = (size_t)s->D * rowF2;
+    p.specRow = s->d_spec + (size_t)(h % s->R) * rowF2; p.specChStride = (size_t)s->R * rowF2;
     p.magRow = s->d_mag + (size_t)(h % s->T) * s->F; p.magChStride = s->hw;
     p.maskRow = masks_buf(s, s->joinedBuf) + (size_t)prow * s->F; p.maskStemStride = 2 * s->hw; p.maskChStride = s->hw;
     p.F = s->F; p.nstems = s->S;
@@ -137,11 +146,61 @@ SrtLiveCombineHop combine_params(const srt_live* s, const SrtStreamHop& p, long 
     return q;
 }
 
+// the statistics launches' arguments for the run that writes mask buffer b (a filter instance): srtIstftWiener's on (d_wspec, T rows, that buffer's masks) - one tile,
+// wiener_issue's chunk rule on rows = T - with the instance's own slab and table set b in the engine's table layout (R [iters][S][F][4], weight sums [iters][S][F], a)
+SrtWienerParams wiener_params(const srt_live* s, int b)
+{
+    const int S = s->S, F = s->F, T = s->T;
+    SrtWienerParams w; memset(&w, 0, sizeof w);
+    w.spec = s->d_wspec; w.spec_ch_stride = (size_t)T * SRT_SPEC_LD;
+    w.rows = T; w.masks = masks_buf(s, b); w.nstems = S; w.ntiles = 1; w.T = T; w.F = F;
+    int nch = (T + 15) / 16; if (nch > SRT_WIENER_MAX_CHUNKS) nch = SRT_WIENER_MAX_CHUNKS;
+    w.rpc = (T + nch - 1) / nch; w.nchunks = (T + w.rpc - 1) / w.rpc;
+    w.slab = s->d_wslab; w.slab_max = s->d_wslab + (size_t)w.nchunks * S * 4 * F;
+    w.rtab = s->d_wtab + (size_t)b * s->wtabF; w.wsum = w.rtab + (size_t)SRT_WIENER_MAX_ITERS * S * F * 4; w.scal = w.wsum + (size_t)SRT_WIENER_MAX_ITERS * S * F;
+    return w;
+}
+size_t wiener_slab_floats(int T, int S, int F)
+{
+    int nch = (T + 15) / 16; if (nch > SRT_WIENER_MAX_CHUNKS) nch = SRT_WIENER_MAX_CHUNKS;
+    return (size_t)nch * S * 4 * F + (size_t)nch * SRT_WIENER_BINBLK;
+}
+
+// the filtering inverse's arguments for hop h: frame h-D at ring row (h-D) mod R (rows of frames before 0 are still zero), its mask row and extension row as the
+// combining inverse takes them, the joined run's table set
+SrtLiveWienerHop wiener_hop_params(const srt_live* s, const SrtStreamHop& p, long long h)
+{
+    SrtLiveWienerHop q; memset(&q, 0, sizeof q);
+    const long long g = h - s->D;
+    const int f = s->joinedHop >= 0 ? s->K - 1 - (int)(s->joinedHop - g - s->L) : s->K - 1;
+    const SrtWienerParams w = wiener_params(s, s->joinedBuf);
+    q.specRow = s->d_spec + (size_t)(((g % s->R) + s->R) % s->R) * SRT_SPEC_LD; q.specChStride = p.specChStride;
+    q.maskRow = p.maskRow; q.maskStemStride = p.maskStemStride; q.maskChStride = p.maskChStride;
+    q.F = s->F; q.nstems = s->S; q.n_out = s->P; q.iters = s->W;
+    q.rtab = reinterpret_cast<const float4*>(w.rtab); q.scal = w.scal;
+    for (int k = 0; k < s->S; ++k) q.oob[k] = s->oob[k];
+    if (s->ext) { q.ext = s->d_ext + ((size_t)s->joinedBuf * s->S * s->K + f) * 2; q.extStemStride = (size_t)s->K * 2; }
+    memcpy(q.gain, s->G, sizeof q.gain);
+    q.overlap = s->d_overlap; q.out = p.out;
+    q.synthesisWnd = s->d_swin; q.twiddle = s->d_tw;
+    return q;
+}
+
 // one hop's kernels: the inverse of frame h-D (one workgroup per output pair) and the forward transform of frame h.  0, or -1: launch failed
 int launch_hop(const srt_live* s, const SrtStreamHop& p, long long h)
 {
+    if (s->W) return srt_launch_live_wiener_hop(wiener_hop_params(s, p, h), p, s->hop);
     if (!s->combine) return srt_launch_stream_hop(p, s->hop);
     return srt_launch_live_combine_hop(combine_params(s, p, h), p, s->hop);
+}
+
+// the R tables of the run that has just been queued into mask buffer b, on the network stream behind it: srtIstftWiener's launches over the gathered window
+int launch_wiener_tables(const srt_live* s, int b)
+{
+    const SrtWienerParams w = wiener_params(s, b);
+    for (int pass = 1; pass <= s->W; ++pass)
+        if (srt_launch_wiener_stats(w, pass, s->nn) || srt_launch_wiener_finalize(w, pass, s->nn)) return -1;
+    return 0;
 }
 
 // the average extension's table for the run that has just been queued into mask buffer b: srt_launch_mask_ext over the K rows T-L-K .. T-L-1 the run serves
@@ -167,11 +226,15 @@ bool hop_schedule(srt_live* s, long long h)
     }
     const int b = !s->runBuf;                                             // the buffer the joined run's predecessor wrote: its last reader was this hop
     if (srt_launch_live_gather(s->d_mag, s->d_tmp, s->T, s->F, (int)((h + 1) % s->T), s->hop)) { s->failed = true; return stream_fail("stream window", "kernel launch failed"); }   // replaces the "Prevent race condition" copy (:364-365)
+    // the filter's window: the spectrum rows of frames h-T+1 .. h, oldest first (frames before 0: ring rows nothing has written yet, zero).  One buffer: its last
+    // reader, the previous run's statistics, has been joined above
+    if (s->W && srt_launch_live_spec_gather(s->d_spec, s->d_wspec, s->T, s->R, (int)((((h + 1 - s->T) % s->R) + s->R) % s->R), s->hop)) { s->failed = true; return stream_fail("stream filter window", "kernel launch failed"); }
     HIPOK(hipEventRecord(s->evMag, s->hop), "stream flip");
     HIPOK(hipStreamWaitEvent(s->nn, s->evMag, 0), "stream flip");
     if (srtForward(s->eng, s->d_tmp, 1, masks_buf(s, b))) { s->failed = true; return stream_fail("stream networks", nullptr); }
     if (s->ratio && srtRatioMask(s->eng, masks_buf(s, b), 1)) { s->failed = true; return stream_fail("stream ratio mask", nullptr); }
     if (s->ext && launch_ext_table(s, b)) { s->failed = true; return stream_fail("stream mask extension", "kernel launch failed"); }
+    if (s->W && launch_wiener_tables(s, b)) { s->failed = true; return stream_fail("stream filter statistics", "kernel launch failed"); }
     HIPOK(hipEventRecord(s->evNN, s->nn), "stream flip");
     s->nnRunning = true; s->runHop = h; s->runBuf = b;
     return true;
@@ -215,6 +278,7 @@ srt_live* live_new(int F, int T, int S, int K, int L, int P)
     srt_live* s = new (std::nothrow) srt_live();           // value-initialised: every field zero
     if (!s) return nullptr;
     s->F = F; s->T = T; s->S = S; s->K = K; s->L = L; s->D = L + 2 * K; s->hw = (size_t)F * T;
+    s->R = s->D;
     s->P = P;
     s->needed = OUTPUTSEG;
     s->nq = 2;
@@ -268,7 +332,7 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     for (int k = 0; k < s->S; ++k)
         if (srtSetCoeffHost(s->eng, k, coeff[k])) { stream_fail(who, nullptr); return -2; }
     srtSetGraphMode(s->eng, 1);                           // the U-Nets run on the same buffers every K hops: replay one hipGraph per mask buffer
-    const size_t S = s->S, P = s->P, specF = 2 * (size_t)s->D * SRT_SPEC_LD * 2, maskF = 2 * S * 2 * s->hw;
+    const size_t S = s->S, P = s->P, specF = 2 * (size_t)s->R * SRT_SPEC_LD * 2, maskF = 2 * S * 2 * s->hw;
     INITTRY(s->mem.alloc(&s->d_ring, sizeof s->ring));
     INITTRY(s->mem.alloc(&s->d_spec, specF * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_mag, 2 * s->hw * sizeof(float)));
@@ -277,6 +341,13 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
     INITTRY(s->mem.alloc(&s->d_overlap, 2 * P * 1024 * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_out, OUTPUTSEG * 2 * P * sizeof(float)));
     if (s->ext) INITTRY(s->mem.alloc(&s->d_ext, 2 * S * s->K * 2 * sizeof(float)));
+    if (s->W) {
+        s->wtabF = (size_t)SRT_WIENER_MAX_ITERS * S * s->F * 5 + 4;
+        INITTRY(s->mem.alloc(&s->d_wspec, 2 * (size_t)s->T * SRT_SPEC_LD * sizeof(float2)));
+        INITTRY(s->mem.alloc(&s->d_wslab, wiener_slab_floats(s->T, s->S, s->F) * sizeof(float)));
+        INITTRY(s->mem.alloc(&s->d_wtab, 2 * s->wtabF * sizeof(float)));
+        INITTRY(hipMemset(s->d_wspec, 0, 2 * (size_t)s->T * SRT_SPEC_LD * sizeof(float2)));
+    }
     INITTRY(s->mem.alloc(&s->d_awin, FFTSIZE * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_swin, FFTSIZE * sizeof(float)));
     INITTRY(s->mem.alloc(&s->d_tw, FFTSIZE * sizeof(float2)));
@@ -311,6 +382,18 @@ int live_init(srt_live* s, const srt_config& cfg, const void* const* coeff, cons
         INITTRY(hipMemcpy(s->d_ext, one.data(), one.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     INITTRY(hipStreamSynchronize(nullptr));               // masks / windows / twiddles (null-stream copies) are in place before the first hop
+    if (s->W) {
+        // the filter's per-run launches load their code now: the window gather of the zero spectrum ring, then every statistics pass on it under the unit masks.
+        // Then both table sets start as the definition has them before the first join: R = 0, a = 1 (zero spectra only are synthesised until then)
+        if (srt_launch_live_spec_gather(s->d_spec, s->d_wspec, s->T, s->R, 0, s->hop)) { stream_fail(who, "filter window pre-warm: kernel launch failed"); return -2; }
+        INITTRY(hipStreamSynchronize(s->hop));
+        if (launch_wiener_tables(s, 0)) { stream_fail(who, "filter statistics pre-warm: kernel launch failed"); return -2; }
+        INITTRY(hipStreamSynchronize(s->nn));
+        INITTRY(hipMemset(s->d_wtab, 0, 2 * s->wtabF * sizeof(float)));
+        const float one = 1.0f;
+        for (int b = 0; b < 2; ++b) INITTRY(hipMemcpy(wiener_params(s, b).scal, &one, sizeof one, hipMemcpyHostToDevice));
+        INITTRY(hipStreamSynchronize(nullptr));
+    }
     // Pre-warm the per-hop path too: the first launch of the hop kernels loads their code, and eight plugin instances making their first call at
     // the same time queued behind each other for it - the slowest call of every instance was its FIRST one, 7.5 ms (round 6, host/rt_latency.c
     // `worst_hop`).  One hop on silence here, on this thread: zero ring, zero spectrum, unit masks - every buffer it writes stays zero; then one
@@ -612,7 +695,7 @@ void Spleeter4StemsProcessSamples(Spleeter4Stems* msr, const float* inLeft, cons
 // One body behind srtLiveCreate, srtLiveCreateRate and srtLiveCreateEx; `who` names the caller in every message.  rate: a rate instance (sample_rate, max_block).
 // o: srtLiveCreateEx's options (never null; all zero for the two older calls).  Every argument is checked before any HIP call.
 namespace {
-int live_create(const srt_config* cfg, int hops_per_run, int lookahead, bool rate, const srt_live_opts& o, const void* const* h_coeff, srt_live** out, const char* who)
+int live_create(const srt_config* cfg, int hops_per_run, int lookahead, bool rate, const srt_live_opts& o, const void* const* h_coeff, srt_live** out, const char* who, int iterations = 0)
 {
     if (!cfg || !h_coeff || !out) return srt_set_error(-1, "%s: null argument", who);
     *out = nullptr;
@@ -630,6 +713,8 @@ int live_create(const srt_config* cfg, int hops_per_run, int lookahead, bool rat
     if (o.n_out > 0 && !o.h_gain) return srt_set_error(-1, "%s: null h_gain with n_out > 0", who);
     if (o.n_out > 0 && !gain_finite(o.h_gain, o.n_out * (cfg->n_stems + 1))) return srt_set_error(-1, "%s: h_gain has an entry that is not finite", who);
     if (o.mask_extension != SRT_MASK_EXT_CONSTANT && o.mask_extension != SRT_MASK_EXT_AVERAGE) return srt_set_error(-1, "%s: unknown mask_extension (SRT_MASK_EXT_CONSTANT or SRT_MASK_EXT_AVERAGE)", who);
+    if (iterations < 0 || iterations > SRT_WIENER_MAX_ITERS) return srt_set_error(-1, "%s: iterations must be 0 (the filter off) .. 3", who);
+    if (iterations > 0 && cfg->ratio_mask) return srt_set_error(-1, "%s: the Wiener filter and ratio_mask exclude each other (both are the post-processing of the masks)", who);
     for (int k = 0; k < cfg->n_stems; ++k)
         if (!h_coeff[k]) return srt_set_error(-1, "%s: null coefficient blob", who);
     SrtSetupLock setup;
@@ -641,6 +726,8 @@ int live_create(const srt_config* cfg, int hops_per_run, int lookahead, bool rat
     s->nOut = o.n_out;
     s->ext = o.mask_extension == SRT_MASK_EXT_AVERAGE;
     s->combine = s->nOut > 0 || s->ext;                                       // neither: the launches of srtLiveCreate, untouched
+    s->W = iterations;
+    if (s->W && s->T > s->D) s->R = s->T;                                     // the filter's statistics read the whole window's spectrum rows
     if (s->nOut > 0) for (int m = 0; m < s->nOut; ++m) memcpy(s->G[m], o.h_gain + (size_t)m * (S + 1), (S + 1) * sizeof(float));
     else for (int m = 0; m < S; ++m) s->G[m][m] = 1.0f;                       // the extension alone: every stem through the identity (a one-hot chain gives g_s exactly)
     if (rate) {
@@ -681,6 +768,48 @@ int srtLiveSetMix(srt_live* s, const float* h_gain)
 int srtLiveOutputs(const srt_live* s)
 {
     return s ? s->P : 0;
+}
+
+int srtLiveCreateWiener(const srt_config* cfg, int hops_per_run, int lookahead, const srt_live_opts* opts, int iterations, const void* const* h_coeff, srt_live** out)
+{
+    srt_live_opts o; memset(&o, 0, sizeof o);
+    if (opts) o = *opts;
+    return live_create(cfg, hops_per_run, lookahead, o.sample_rate != 0, o, h_coeff, out, "srtLiveCreateWiener", iterations);
+}
+
+int srtLiveWiener(const srt_live* s)
+{
+    return s ? s->W : 0;
+}
+
+// debug read-back of the run launched last (not for the audio thread: both streams are drained).  Every argument is checked before any HIP call.
+int srtLiveCopyTensor(srt_live* s, const char* name, int stem, int index, float* h_dst, size_t max_floats, long long* run_hop)
+{
+    if (!s || !name || !h_dst) return srt_set_error(-1, "%s", "srtLiveCopyTensor: null argument");
+    const size_t F = (size_t)s->F;
+    const bool cov = !strcmp(name, "wiener_cov"), spec = !strcmp(name, "wiener_spec"), masks = !strcmp(name, "masks");
+    if (!cov && !spec && !masks) return srt_set_error(-1, "srtLiveCopyTensor: unknown tensor %s (wiener_cov, wiener_spec, masks)", name);
+    if ((cov || spec) && !s->W) return srt_set_error(-1, "srtLiveCopyTensor: %s needs an instance of srtLiveCreateWiener with iterations > 0", name);
+    if ((cov || masks) && (stem < 0 || stem >= s->S)) return srt_set_error(-1, "srtLiveCopyTensor: %s needs a stem in 0..n_stems-1", name);
+    if (cov && (index < 1 || index > s->W)) return srt_set_error(-1, "%s", "srtLiveCopyTensor: wiener_cov needs 1 <= index (the iteration) <= the instance's iterations");
+    const size_t count = cov ? 5 * F + 1 : spec ? 2 * (size_t)s->T * SRT_SPEC_LD * 2 : 2 * s->hw;
+    if (count > max_floats) return srt_set_error(-1, "%s", "srtLiveCopyTensor: destination too small");
+    if (s->failed) return srt_set_error(-1, "%s", "srtLiveCopyTensor: the instance is muted (an earlier device call failed)");
+    if (run_hop) *run_hop = s->runHop;
+    if (s->runHop < 0) return 0;
+#define COPYTRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) return srt_set_error(-2, "srtLiveCopyTensor: %s", hipGetErrorString(_e)); } while (0)
+    COPYTRY(hipStreamSynchronize(s->hop));
+    COPYTRY(hipStreamSynchronize(s->nn));
+    if (cov) {                                                               // srtCopyTensor("wiener_cov")'s layout: R [F][4], the weight sums [F], a
+        const SrtWienerParams w = wiener_params(s, s->runBuf);
+        const size_t o = ((size_t)(index - 1) * s->S + stem) * F;
+        COPYTRY(hipMemcpy(h_dst, w.rtab + o * 4, F * 4 * sizeof(float), hipMemcpyDeviceToHost));
+        COPYTRY(hipMemcpy(h_dst + 4 * F, w.wsum + o, F * sizeof(float), hipMemcpyDeviceToHost));
+        COPYTRY(hipMemcpy(h_dst + 5 * F, w.scal, sizeof(float), hipMemcpyDeviceToHost));
+    } else if (spec) COPYTRY(hipMemcpy(h_dst, s->d_wspec, count * sizeof(float), hipMemcpyDeviceToHost));
+    else COPYTRY(hipMemcpy(h_dst, masks_buf(s, s->runBuf) + (size_t)stem * 2 * s->hw, count * sizeof(float), hipMemcpyDeviceToHost));
+#undef COPYTRY
+    return (int)count;
 }
 
 int srtLiveRateLatency(int sample_rate, int hops_per_run, int lookahead)
