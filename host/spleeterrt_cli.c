@@ -27,6 +27,10 @@
  *   (srtSeparateCliHostIo, SRT_HOST_OUT_PCM16: q = rint(x * 32768) clamped, half the download) and go to the files as they are; a file with clipped
  *   samples is reported.  Single-engine path only (refused with several workers, and with SPLEETERRT_RESAMPLE=source on input that needs converting
  *   back).  Unset or 32: the float32 outputs.
+ *   $SPLEETERRT_OUT_BITS=24 writes packed 24-bit PCM outputs (format 1, block align 6; SRT_HOST_OUT_PCM24: q = rint(x * 2^23) clamped, 3/4 of the download)
+ *   under the same restrictions and with the same report of clipped samples.
+ *   $SPLEETERRT_DITHER=<seed> with SPLEETERRT_OUT_BITS=16 adds TPDF dither to the 16-bit outputs (SRT_HOST_OUT_DITHER; <seed> is a 64-bit integer, the
+ *   same seed gives the same files); with any other SPLEETERRT_OUT_BITS it is refused.
  *
  * Out of scope here (SURVEY §2.1 #9,#11,#12): FLAC/MP3 decoding — the input must be a RIFF/WAVE file (PCM 8/16/24/32-bit
  * or float32, 1 or 2 channels).  The reference embeds its weights
@@ -127,17 +131,17 @@ static int write_wav(const char *path, const float *L, const float *R, size_t fr
     return w == frames ? 0 : -1;
 }
 
-/* the call's 16-bit output as it stands: `frames` interleaved stereo frames -> 16-bit PCM stereo RIFF/WAVE at `rate` Hz */
-static int write_wav16(const char *path, const int16_t *il, size_t frames, uint32_t rate)
+/* the call's 16- or 24-bit output as it stands: `frames` interleaved stereo frames of `bits` bits -> PCM stereo RIFF/WAVE at `rate` Hz */
+static int write_wav_pcm(const char *path, const void *il, size_t frames, uint32_t rate, unsigned bits)
 {
     FILE *f = fopen(path, "wb");
     if (!f) { fprintf(stderr, "cannot write %s\n", path); return -1; }
-    const uint32_t data = (uint32_t)(frames * 4);
+    const uint32_t align = bits / 4, data = (uint32_t)(frames * align);       /* (an odd count of 6-byte frames is still an even count of bytes: no pad byte) */
     unsigned char h[44];
     memcpy(h, "RIFF", 4); memcpy(h + 8, "WAVEfmt ", 8); memcpy(h + 36, "data", 4);
-    PUT32(4, 36 + data); PUT32(16, 16); PUT16(20, 1); PUT16(22, 2); PUT32(24, rate); PUT32(28, rate * 4); PUT16(32, 4); PUT16(34, 16); PUT32(40, data);
+    PUT32(4, 36 + data); PUT32(16, 16); PUT16(20, 1); PUT16(22, 2); PUT32(24, rate); PUT32(28, rate * align); PUT16(32, align); PUT16(34, bits); PUT32(40, data);
     fwrite(h, 1, sizeof h, f);
-    const size_t w = fwrite(il, 4, frames, f);
+    const size_t w = fwrite(il, align, frames, f);
     fclose(f);
     return w == frames ? 0 : -1;
 }
@@ -173,10 +177,23 @@ int main(int argc, char **argv)
     }
 
     const char *ob = getenv("SPLEETERRT_OUT_BITS");
-    int out16 = 0;
+    int out_bits = 32;
     if (ob && *ob && strcmp(ob, "32")) {
-        if (!strcmp(ob, "16")) out16 = 1;
-        else { fprintf(stderr, "SPLEETERRT_OUT_BITS=%s: expected 16 or 32\n", ob); return -1; }
+        if (!strcmp(ob, "16")) out_bits = 16;
+        else if (!strcmp(ob, "24")) out_bits = 24;
+        else { fprintf(stderr, "SPLEETERRT_OUT_BITS=%s: expected 16, 24 or 32\n", ob); return -1; }
+    }
+    const int out_pcm = out_bits != 32;
+    /* $SPLEETERRT_DITHER=<seed>: TPDF dither on the 16-bit outputs */
+    const char *ds = getenv("SPLEETERRT_DITHER");
+    int dither = 0;
+    uint64_t dither_seed = 0;
+    if (ds && *ds) {
+        char *end = 0;
+        dither_seed = strtoull(ds, &end, 0);
+        if (!end || *end) { fprintf(stderr, "SPLEETERRT_DITHER=%s: expected an integer seed\n", ds); return -1; }
+        if (out_bits != 16) { fprintf(stderr, "SPLEETERRT_DITHER applies to 16-bit outputs only: set SPLEETERRT_OUT_BITS=16 (it is %d here), or unset SPLEETERRT_DITHER\n", out_bits); return -1; }
+        dither = 1;
     }
 
     float *pcm = 0; unsigned channels = 0, rate = 0;
@@ -185,7 +202,7 @@ int main(int argc, char **argv)
     if (rate != 44100 && !resample) { fprintf(stderr, "%s: %u Hz — only 44.1 kHz input is accepted (set SPLEETERRT_RESAMPLE=1 to convert it on the GPU)\n", argv[5], rate); return -1; }
     if (rate != 44100 && (rate < 8000 || rate > 384000)) { fprintf(stderr, "%s: %u Hz — the converter takes 8000..384000 Hz\n", argv[5], rate); return -1; }
     const int convert = rate != 44100;
-    if (out16 && convert && resample == 2) { fprintf(stderr, "SPLEETERRT_OUT_BITS=16 with SPLEETERRT_RESAMPLE=source: the stems are converted back as floats; write float32 outputs (unset SPLEETERRT_OUT_BITS)\n"); return -1; }
+    if (out_pcm && convert && resample == 2) { fprintf(stderr, "SPLEETERRT_OUT_BITS=%d with SPLEETERRT_RESAMPLE=source: the stems are converted back as floats; write float32 outputs (unset SPLEETERRT_OUT_BITS)\n", out_bits); return -1; }
     const size_t n44 = convert ? srtResampleLength(nframes, (int)rate, 44100) : nframes;       /* main.c:266 */
     const size_t nout = resample == 2 ? nframes : n44;                                          /* frames of every output file */
     /* the outputs are float32 stereo RIFF files: 8 bytes per frame under a 32-bit chunk size (main.c writes the same container) */
@@ -244,9 +261,9 @@ int main(int argc, char **argv)
     }
     const size_t per = (ntiles + (size_t)ndev - 1) / (size_t)ndev;       /* tiles of the largest range */
     cfg.variant = SRT_VARIANT_EXE; cfg.max_tiles = (int)(per < cap ? per : cap); cfg.impl = SRT_IMPL_MFMA; cfg.precision = SRT_PREC_F32;
-    if (out16 && (ndev > 1 || (dl && *dl))) { fprintf(stderr, "SPLEETERRT_OUT_BITS=16 is honoured on the single-engine path only (the multi-device join adds floats on the host): run one worker, or write float32 outputs\n"); return -1; }
+    if (out_pcm && (ndev > 1 || (dl && *dl))) { fprintf(stderr, "SPLEETERRT_OUT_BITS=%d is honoured on the single-engine path only (the multi-device join adds floats on the host): run one worker, or write float32 outputs\n", out_bits); return -1; }
     unsigned long long clipped[3] = { 0, 0, 0 };
-    void *out = malloc((size_t)stems * 2 * len * (out16 ? sizeof(int16_t) : sizeof(float)));      /* float [stems][2][len] | int16 [stems][len][2] */
+    void *out = malloc((size_t)stems * len * (size_t)(out_bits / 4));      /* float [stems][2][len] | int16 [stems][len][2] | uint8 [stems][len][2][3] */
     if (!out) { fprintf(stderr, "out of host memory (%zu output samples)\n", (size_t)stems * 2 * len); return -1; }
     if (ndev > 1 || (dl && *dl)) {
         srt_multi *m = 0;
@@ -266,7 +283,9 @@ int main(int argc, char **argv)
         if (srtSetCoeffFp16Host(e, 0, halfs) || srtSetCoeffFp16Host(e, 1, halfs + nhalf)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
         free(halfs);
         t0 = now();
-        if (out16 ? srtSeparateCliHostIo(e, inL, inR, finalSize, stems, out, SRT_HOST_OUT_PCM16, clipped) : srtSeparateCliHost(e, inL, inR, finalSize, stems, (float *)out)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+        const unsigned oflags = out_bits == 24 ? SRT_HOST_OUT_PCM24 : dither ? SRT_HOST_OUT_PCM16 | SRT_HOST_OUT_DITHER : SRT_HOST_OUT_PCM16;
+        if (dither && srtSetDitherSeed(e, dither_seed)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
+        if (out_pcm ? srtSeparateCliHostIo(e, inL, inR, finalSize, stems, out, oflags, clipped) : srtSeparateCliHost(e, inL, inR, finalSize, stems, (float *)out)) { fprintf(stderr, "%s\n", srtLastError()); return -1; }
         printf("Inference neural networks on the GPU takes %1.14lf sec (%zu tiles of %zu x %zu in chunks of %d, %d outputs)\n", now() - t0, ntiles, T, F, cfg.max_tiles, stems);
         srtReleaseStaging(e);                                          /* whole-file device copies of a one-shot program */
         srtDestroy(e);
@@ -286,8 +305,8 @@ int main(int argc, char **argv)
         char path[4096];
         t0 = now();
         snprintf(path, sizeof path, "%s_%s.wav", base_name(argv[5]), names[k]);
-        if (out16) {                                                   /* the stem's frames [4096, 4096 + nout) as the device packed them */
-            if (write_wav16(path, (const int16_t *)out + ((size_t)k * len + FFT) * 2, nout, 44100)) return -1;
+        if (out_pcm) {                                                 /* the stem's frames [4096, 4096 + nout) as the device packed them */
+            if (write_wav_pcm(path, (const unsigned char *)out + ((size_t)k * len + FFT) * (size_t)(out_bits / 4), nout, 44100, (unsigned)out_bits)) return -1;
             if (clipped[k]) printf("%s: %llu clipped sample(s)\n", path, clipped[k]);
             printf("Saving file -> %s takes %1.14lf sec\n", path, now() - t0);
             continue;

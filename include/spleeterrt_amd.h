@@ -262,6 +262,43 @@ SRT_API int  srtSeparateHostStreamIo(srt_engine *e, const void *h_in, const void
 SRT_API int  srtSeparateCliHostIo(srt_engine *e, const void *h_in, const void *h_in2, size_t n, int stems,
                                   void *h_out, unsigned flags, unsigned long long *h_clipped);
 
+/* ---- 24-bit PCM and dithered 16-bit output: the rest of the sample-format axis of the calls that take `flags`.
+ * 24-bit, packed: three bytes per sample, little-endian, two's complement, interleaved stereo (a WAV format-1 data chunk with block align 6).
+ *   Unpack: q is the sign-extended 24-bit integer, x = (float)q * 2^-23 (exact).  Pack: v = rint(x * 2^23), ties to even (the product is exact); NaN -> 0,
+ *   otherwise clamped to [-8388608, 8388607].  CLIPPED as the 16-bit rule defines it: v outside the range, or NaN (+1.0f clips, -1.0f does not).
+ * Dithered 16-bit: v = rint(x * 32768 + d) with d a TPDF (triangular probability density) value in (-1, 1) LSB; x * 32768 is exact, so the sum is rounded
+ *   once.  Clamp, NaN and the clip count are the 16-bit rule's, applied to the dithered v.  d depends on nothing but (seed, plane, i): plane = 2 * pair + channel
+ *   in output order, i the 64-bit index of the sample in its output plane for the whole call - so a stream gets the same noise whatever max_tiles, chunking or
+ *   piece plan cut it, and a run is reproducible.  All arithmetic below is uint32 with wrap-around:
+ *       mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *       k = mix32(lo32(seed) ^ mix32(hi32(seed) ^ mix32(plane + 0x9e3779b9)))
+ *       h = mix32(lo32(i) ^ mix32(hi32(i) ^ k))
+ *       a = mix32(h ^ 0x68bc21eb) >> 8;   b = mix32(h ^ 0x02e5be93) >> 8        (two 24-bit uniforms)
+ *       d = (float)((int)a - (int)b) * 2^-24                                     (exact)
+ *   Dither with 24-bit output is refused: above |x| = 2^-1 a float's own spacing is already the 24-bit LSB, so there is nothing below the LSB to decorrelate.
+ *   Noise shaping (sequential per channel) and 32-bit integer PCM are not provided.
+ * srtPcm24Unpack: d_in [n][2][3] bytes -> planar d_L [n], d_R [n].  srtPcm24Pack: as srtPcm16Pack, pair p -> d_out + p * out_stride * 6 as [count][2][3] bytes.
+ * srtPcm16PackDither: srtPcm16Pack with the dither; pair p's planes are 2 * (first_pair + p) and + 1, and sample 0 of the launch has plane index first_index
+ * (a caller that packs a long output in several launches passes each launch's offset and gets the bytes of one launch).
+ * All three: device pointers of any alignment (the 24-bit vector path wants 16-byte aligned bases, plane_stride % 4 == 0 and out_stride % 8 == 0), asynchronous
+ * on `stream`, capturable; -1 before any device work for a null pointer, pairs < 1, pairs > 65535, a stride below count, or first_pair < 0. */
+SRT_API int  srtPcm24Unpack(void *stream, const uint8_t *d_in, size_t n, float *d_L, float *d_R);
+SRT_API int  srtPcm24Pack(void *stream, const float *d_planes, size_t plane_stride, int pairs, size_t count, uint8_t *d_out, size_t out_stride,
+                          unsigned long long *d_clipped);
+SRT_API int  srtPcm16PackDither(void *stream, const float *d_planes, size_t plane_stride, int pairs, size_t count, int16_t *d_out, size_t out_stride,
+                                unsigned long long *d_clipped, uint64_t seed, int first_pair, uint64_t first_index);
+/* The flags of every call that takes `flags` (srtSeparateHostStreamIo / Overlap / Rate, srtSeparateHostWiener / WienerOverlap, srtSeparateCliHostIo):
+ * SRT_HOST_IN_PCM24: h_in is uint8 [n][2][3] and h_in2 must be NULL.  SRT_HOST_OUT_PCM24: h_out is uint8 [outputs][len][2][3]; h_clipped as for 16 bits.
+ * SRT_HOST_OUT_DITHER: with SRT_HOST_OUT_PCM16, the pack is srtPcm16PackDither under the engine's seed (srtSetDitherSeed), i running over the whole output.
+ * -1, with a text that names the function and before any device work: both IN formats, both OUT formats, SRT_HOST_OUT_DITHER without SRT_HOST_OUT_PCM16, any
+ * of these bits on a tile range of a multi-device stream.  Bit 8 and the bits from 128 up are unknown.  A call that sets none of the three issues exactly the
+ * launches it issued before they existed. */
+#define SRT_HOST_IN_PCM24   16u
+#define SRT_HOST_OUT_PCM24  32u
+#define SRT_HOST_OUT_DITHER 64u
+/* the seed of SRT_HOST_OUT_DITHER (default 0): read once per call into the call's resolved options */
+SRT_API int  srtSetDitherSeed(srt_engine *e, uint64_t seed);
+
 /* Low-latency callers that repeat the same call (same device pointers and sizes) over and over - the real-time plugin, the tile
  * API on one pair of buffers: with graph mode on, srtForward and srtSeparate / srtSeparateEx capture their launch sequence into
  * a hipGraph the first time an argument tuple is seen and replay it afterwards (one host call instead of ~25 launches; 4 cached

@@ -10,6 +10,7 @@ IMPL_MFMA, IMPL_NAIVE = 0, 1
 PREC_F32, PREC_F16, PREC_F16X2 = 0, 1, 2
 MASK_EXT_CONSTANT, MASK_EXT_AVERAGE = 0, 1                 # SRT_MASK_EXT_* (srtSetMaskExtension)
 HOST_PINNED, HOST_IN_PCM16, HOST_OUT_PCM16 = 1, 2, 4      # SRT_HOST_* (srtSeparateHostStreamIo / srtSeparateCliHostIo)
+HOST_IN_PCM24, HOST_OUT_PCM24, HOST_OUT_DITHER = 16, 32, 64   # ... 24-bit packed PCM and the dithered 16-bit output
 COEFF_FLOATS = 9822725
 SPEC_LD = 2052
 
@@ -103,6 +104,10 @@ def load_library():
     L.srtHostRatePieces.argtypes = [C.POINTER(_Config), C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]
     L.srtPcm16Unpack.argtypes = [vp, vp, C.c_size_t, vp, vp]
     L.srtPcm16Pack.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
+    L.srtPcm24Unpack.argtypes = [vp, vp, C.c_size_t, vp, vp]
+    L.srtPcm24Pack.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, C.c_size_t, vp]
+    L.srtPcm16PackDither.argtypes = [vp, vp, C.c_size_t, C.c_int, C.c_size_t, vp, C.c_size_t, vp, C.c_uint64, C.c_int, C.c_uint64]
+    L.srtSetDitherSeed.argtypes = [vp, C.c_uint64]
     for fn in (L.srtStftRows, L.srtStftFrames, L.srtIstftLength):
         fn.restype = C.c_size_t
         fn.argtypes = [C.c_size_t]
@@ -278,6 +283,10 @@ class Engine:
         assert masks.is_contiguous() and masks.shape[0] == self.S
         self._chk(self.L.srtRatioMask(self.h, _ptr(masks), masks.shape[1]))
         return masks
+
+    def set_dither_seed(self, seed):
+        """the seed of the dithered 16-bit output of the host paths (dither=True; srtSetDitherSeed): any 64-bit value, default 0"""
+        self._chk(self.L.srtSetDitherSeed(self.h, int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def set_wiener(self, iterations):
         """multichannel Wiener filter (Spleeter's --mwf) inside separate / separate_ex: 0 = off, 1..3 EM iterations (srtSetWiener)"""
@@ -613,9 +622,18 @@ class Engine:
                                                  1 if pinned else 0))
         return out if ret is None else ret
 
-    def _host_io(self, pcm_or_LR, out_pcm16, nstems, rows, out, pinned, length=None):
+    def _host_io(self, pcm_or_LR, out_pcm16, nstems, rows, out, pinned, length=None, out_bits=None, dither=False):
         """host buffers of the *_io calls -> (keep-alive list, h_in, h_in2, n, h_out, flags, out object, clipped array).  Input by dtype: an int16 array or CPU
-        tensor of shape [n, 2] is interleaved 16-bit PCM, anything else a pair (L, R) of float32 buffers."""
+        tensor of shape [n, 2] is interleaved 16-bit PCM, a uint8 one of shape [n, 2, 3] packed 24-bit PCM, anything else a pair (L, R) of float32 buffers.
+        out_bits: 32 (float32 [S, 2, len]), 24 (uint8 [S, len, 2, 3]) or 16 (int16 [S, len, 2]); out_pcm16=True means 16; dither: TPDF dither, 16-bit output only."""
+        if out_bits is None:
+            out_bits = 16 if out_pcm16 else 32
+        if out_bits not in (16, 24, 32):
+            raise ValueError("out_bits must be 16, 24 or 32, not %r" % (out_bits,))
+        if out_pcm16 and out_bits != 16:
+            raise ValueError("out_pcm16=True means out_bits=16, not %r" % (out_bits,))
+        if dither and out_bits != 16:
+            raise ValueError("dither=True applies to 16-bit output only (out_bits=16), not out_bits=%r" % (out_bits,))
         import numpy as np
         t = self.torch
 
@@ -627,7 +645,13 @@ class Engine:
             return a, a.ctypes.data, a.size
         flags = HOST_PINNED if pinned else 0
         is16 = not isinstance(pcm_or_LR, (tuple, list)) and str(pcm_or_LR.dtype) in ("int16", "torch.int16")
-        if is16:
+        is24 = not isinstance(pcm_or_LR, (tuple, list)) and str(pcm_or_LR.dtype) in ("uint8", "torch.uint8")
+        if is24:
+            assert len(pcm_or_LR.shape) == 3 and tuple(pcm_or_LR.shape[1:]) == (2, 3), "24-bit input is packed interleaved stereo [n, 2, 3]"
+            a, p_in, cnt = host(pcm_or_LR, np.uint8)
+            keep, p_in2, n = [a], None, cnt // 6
+            flags |= HOST_IN_PCM24
+        elif is16:
             assert len(pcm_or_LR.shape) == 2 and pcm_or_LR.shape[1] == 2, "16-bit input is interleaved stereo [n, 2]"
             a, p_in, cnt = host(pcm_or_LR, np.int16)
             keep, p_in2, n = [a], None, cnt // 2
@@ -638,9 +662,8 @@ class Engine:
             keep = [a, b]
         rows = self.L.srtStftRows(n) if rows is None else rows
         ln = self.L.srtIstftLength(rows) if length is None else length      # length: frames per output plane where the call's rates decide it (separate_host_rate)
-        shape, dtype = ((nstems, ln, 2), np.int16) if out_pcm16 else ((nstems, 2, ln), np.float32)
-        if out_pcm16:
-            flags |= HOST_OUT_PCM16
+        shape, dtype = {16: ((nstems, ln, 2), np.int16), 24: ((nstems, ln, 2, 3), np.uint8), 32: ((nstems, 2, ln), np.float32)}[out_bits]
+        flags |= {16: HOST_OUT_PCM16, 24: HOST_OUT_PCM24, 32: 0}[out_bits] | (HOST_OUT_DITHER if dither else 0)
         ret = None
         if out is None:
             if pinned:                                           # keep the promise for the output too
@@ -649,32 +672,34 @@ class Engine:
             else:
                 out = np.empty(shape, dtype)
         o, p_out, no = host(out, dtype)
-        assert no == shape[0] * shape[1] * shape[2]
+        assert no == int(np.prod(shape))
         clipped = np.zeros(nstems, np.uint64)
         return keep + [o], p_in, p_in2, n, rows, p_out, flags, (o if ret is None else ret), clipped
 
-    def separate_host_stream_io(self, pcm_or_LR, out_pcm16=False, frames=None, rows=None, out=None, pinned=False):
+    def separate_host_stream_io(self, pcm_or_LR, out_pcm16=False, frames=None, rows=None, out=None, pinned=False, out_bits=None, dither=False):
         """separate_host_stream with 16-bit PCM on either side (srtSeparateHostStreamIo; the conversion runs on the GPU, half the bytes cross the bus).
         pcm_or_LR: int16 [n, 2] interleaved stereo, or (L, R) float32; out_pcm16: stems as int16 [S, len, 2] (a WAV data chunk per stem) instead of float32
-        [S, 2, len].  -> (out, clipped): clipped uint64 [S], the samples per stem whose value before clamping lay outside [-32768, 32767] (zeros for float output)."""
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, rows, out, pinned)
+        [S, 2, len].  -> (out, clipped): clipped uint64 [S], the samples per stem whose value before clamping lay outside [-32768, 32767] (zeros for float output).
+        24 bits: a uint8 [n, 2, 3] input is packed 24-bit PCM; out_bits=24 gives uint8 [S, len, 2, 3]; out_bits=16 is out_pcm16=True, and dither=True
+        adds the TPDF dither of set_dither_seed to it (the noise does not depend on max_tiles)."""
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, rows, out, pinned, out_bits=out_bits, dither=dither)
         frames = self.L.srtStftFrames(n) if frames is None else frames
         self._chk(self.L.srtSeparateHostStreamIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, frames, rows, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
 
-    def separate_host_overlap(self, pcm_or_LR, overlap, out_pcm16=False, out=None, pinned=False):
+    def separate_host_overlap(self, pcm_or_LR, overlap, out_pcm16=False, out=None, pinned=False, out_bits=None, dither=False):
         """separate() under set_overlap(overlap) for host PCM of any length (srtSeparateHostStreamOverlap): the stream is walked in pieces of
         max_tiles overlapped tiles (stream.host_overlap_pieces) and the mask blend crosses the piece seams through a small device carry.  overlap (0 .. T/2 rows)
         holds for this call only - the engine's set_overlap is neither read nor changed; ratio_mask, the mask extension and the mix come from the engine.  Buffers as
         separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32; out_pcm16: int16 [outputs, len, 2] instead of float32 [outputs, 2, len]; pinned=True
-        promises page-locked buffers.  overlap = 0 is separate_host_stream_io.  -> (out, clipped)."""
+        promises page-locked buffers; out_bits / dither and a uint8 [n, 2, 3] input as there.  overlap = 0 is separate_host_stream_io.  -> (out, clipped)."""
         try:
             ov = int(overlap)
         except (TypeError, ValueError):
             raise EngineError("separate_host_overlap: overlap must be an integer 0 .. T / 2, not %r" % (overlap,))
         if ov != overlap or ov < 0 or ov > self.T // 2:
             raise EngineError("separate_host_overlap: overlap must be an integer 0 .. T / 2 = %d, not %r" % (self.T // 2, overlap))
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, None, out, pinned)
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, None, out, pinned, out_bits=out_bits, dither=dither)
         if n < 4096:
             raise EngineError("separate_host_overlap: need at least 4096 samples, not %d" % n)
         self._chk(self.L.srtSeparateHostStreamOverlap(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, ov, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
@@ -687,12 +712,13 @@ class Engine:
             raise EngineError("libspleeterrt_amd: %s" % self.L.srtLastError().decode())
         return ln
 
-    def separate_host_rate(self, pcm_or_LR, sample_rate, out_rate=None, overlap=0, out_pcm16=False, out=None, pinned=False):
+    def separate_host_rate(self, pcm_or_LR, sample_rate, out_rate=None, overlap=0, out_pcm16=False, out=None, pinned=False, out_bits=None, dither=False):
         """separate_host_stream_io / separate_host_overlap for host PCM at sample_rate with the outputs at out_rate (None: sample_rate; either may be 44100)
         (srtSeparateHostStreamRate): both conversions run on the device inside the chunk pipeline, so every sample crosses the bus once at its own
         rate.  Equals Resampler.resample_host to 44.1 kHz, separate_host_overlap, resample_host per output pair, bit for bit.  overlap (0 .. T/2 rows) holds for the
         call only; ratio_mask, the mask extension and the mix come from the engine.  Buffers as separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32;
-        out float32 [outputs, 2, host_rate_length(n, ..)] or, with out_pcm16, int16 [outputs, length, 2].  -> (out, clipped)."""
+        out float32 [outputs, 2, host_rate_length(n, ..)] or, with out_pcm16, int16 [outputs, length, 2]; out_bits / dither and a uint8 [n, 2, 3] input as there (the
+        dither's sample index runs over the converted output).  -> (out, clipped)."""
         try:
             fs_in, fs_out, ov = int(sample_rate), int(sample_rate if out_rate is None else out_rate), int(overlap)
         except (TypeError, ValueError):
@@ -701,15 +727,15 @@ class Engine:
             raise EngineError("separate_host_rate: overlap must be an integer 0 .. T / 2 = %d, not %r" % (self.T // 2, overlap))
         first = pcm_or_LR[0] if isinstance(pcm_or_LR, (tuple, list)) else pcm_or_LR        # (L, R) or int16 [n, 2]: n is the first axis either way
         ln = self.host_rate_length(first.shape[0] if hasattr(first, "shape") else len(first), fs_in, fs_out)
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, 0, out, pinned, length=ln)
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, self.outputs, 0, out, pinned, length=ln, out_bits=out_bits, dither=dither)
         self._chk(self.L.srtSeparateHostStreamRate(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, fs_in, fs_out, ov, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
 
-    def separate_host_wiener(self, pcm_or_LR, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False, overlap=0):
+    def separate_host_wiener(self, pcm_or_LR, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False, overlap=0, out_bits=None, dither=False):
         """separate_wiener for host PCM of any length (srtSeparateHostWiener): the stream is walked in pieces of max_tiles tiles, its spectrum and
         masks are kept in a device store of host_wiener_bytes(n) bytes, and the R tables are those of one separate_wiener call over the whole signal, bit for bit.
         Buffers as separate_host_stream_io: pcm_or_LR int16 [n, 2] or (L, R) float32; out_pcm16: int16 [outputs, len, 2] instead of float32 [outputs, 2, len];
-        pinned=True promises page-locked buffers.  iterations / mask_extension / mix: options of this call alone, as separate_wiener's; overlap must be 0
+        pinned=True promises page-locked buffers; out_bits / dither and a uint8 [n, 2, 3] input as there.  iterations / mask_extension / mix: options of this call alone, as separate_wiener's; overlap must be 0
         (separate_host_wiener_overlap takes one).  -> (out, clipped).  wiener_cov works afterwards; release_staging frees the store."""
         try:
             ov = int(overlap)
@@ -721,7 +747,7 @@ class Engine:
         if opts is None:
             opts = (_WienerOpts(int(iterations), 0, MASK_EXT_CONSTANT, 0, None), None, self.S)
         o, _keep_g, planes = opts
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, planes, None, out, pinned)
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, planes, None, out, pinned, out_bits=out_bits, dither=dither)
         self._chk(self.L.srtSeparateHostWiener(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, C.byref(o), C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         return out, clipped
 
@@ -729,7 +755,7 @@ class Engine:
         """bytes of the device store separate_host_wiener keeps for a stream of n samples on this engine (srtHostWienerBytes)"""
         return host_wiener_bytes(n, self.F, self.T, self.S, self.max_tiles)
 
-    def separate_host_wiener_overlap(self, pcm_or_LR, overlap, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False):
+    def separate_host_wiener_overlap(self, pcm_or_LR, overlap, iterations=1, mask_extension="constant", mix=None, out_pcm16=False, out=None, pinned=False, out_bits=None, dither=False):
         """separate_wiener(..., overlap=overlap) for host PCM of any length (srtSeparateHostWienerOverlap): the stream is walked in pieces of
         max_tiles overlapped tiles (stream.host_overlap_pieces), spectrum, masks and one mask carry per piece boundary are kept in a device store of
         host_wiener_overlap_bytes(n, overlap) bytes, and the R tables are those of one separate_wiener call over the whole signal, bit for bit.  overlap
@@ -745,7 +771,7 @@ class Engine:
         if opts is None:
             opts = (_WienerOpts(int(iterations), 0, MASK_EXT_CONSTANT, 0, None), None, self.S)
         o, _keep_g, planes = opts
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, planes, None, out, pinned)
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, planes, None, out, pinned, out_bits=out_bits, dither=dither)
         if n < 4096:
             raise EngineError("separate_host_wiener_overlap: need at least 4096 samples, not %d" % n)
         self._chk(self.L.srtSeparateHostWienerOverlap(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, C.byref(o), C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
@@ -755,9 +781,9 @@ class Engine:
         """bytes of the device store separate_host_wiener_overlap keeps for a stream of n samples at this overlap on this engine (srtHostWienerOverlapBytes)"""
         return host_wiener_overlap_bytes(n, self.F, self.T, self.S, self.max_tiles, overlap)
 
-    def separate_cli_host_io(self, pcm_or_LR, stems, out_pcm16=False, out=None, pinned=False, keep_staging=False):
-        """separate_cli_host with 16-bit PCM on either side (srtSeparateCliHostIo) -> (out, clipped) as separate_host_stream_io, `stems` outputs."""
-        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, stems, None, out, pinned)
+    def separate_cli_host_io(self, pcm_or_LR, stems, out_pcm16=False, out=None, pinned=False, keep_staging=False, out_bits=None, dither=False):
+        """separate_cli_host with 16- or 24-bit PCM on either side (srtSeparateCliHostIo) -> (out, clipped) as separate_host_stream_io, `stems` outputs."""
+        keep, p_in, p_in2, n, rows, p_out, flags, out, clipped = self._host_io(pcm_or_LR, out_pcm16, stems, None, out, pinned, out_bits=out_bits, dither=dither)
         try:
             self._chk(self.L.srtSeparateCliHostIo(self.h, C.c_void_p(p_in), C.c_void_p(p_in2), n, stems, C.c_void_p(p_out), flags, C.c_void_p(clipped.ctypes.data)))
         except EngineError:
@@ -1235,6 +1261,60 @@ def pcm16_pack(planes, clipped=None):
             clipped = torch.zeros(pairs, device=planes.device, dtype=torch.int64)
         assert clipped.is_cuda and clipped.dtype == torch.int64 and clipped.is_contiguous() and clipped.numel() == pairs
         rc = lib.srtPcm16Pack(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(planes), count, pairs, count, _ptr(out), count, _ptr(clipped))
+    if rc < 0:
+        raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (lib.srtLastError().decode(), rc))
+    return out, clipped
+
+
+def pcm24_unpack(t):
+    """uint8 CUDA tensor [n, 2, 3] (packed 24-bit interleaved stereo, little-endian) -> (L, R) float32 [n], x = q / 2^23 (srtPcm24Unpack, on the tensor's device
+    and the current stream)"""
+    import torch
+    assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 3 and tuple(t.shape[1:]) == (2, 3)
+    lib = load_library()
+    t = t.contiguous()
+    with torch.cuda.device(t.device):
+        out = torch.empty((2, t.shape[0]), device=t.device, dtype=torch.float32)
+        rc = lib.srtPcm24Unpack(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(t), t.shape[0], _ptr(out[0]), _ptr(out[1]))
+    if rc < 0:
+        raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (lib.srtLastError().decode(), rc))
+    return out[0], out[1]
+
+
+def pcm24_pack(planes, clipped=None):
+    """float32 CUDA tensor [pairs, 2, count] (planar stereo pairs) -> (uint8 [pairs, count, 2, 3], clipped int64 [pairs]); q = clamp(rint(x * 2^23)), NaN -> 0
+    (srtPcm24Pack).  clipped: an int64 CUDA tensor [pairs] the counts are ADDED to (default: zeros)."""
+    import torch
+    assert planes.is_cuda and planes.dtype == torch.float32 and planes.dim() == 3 and planes.shape[1] == 2
+    lib = load_library()
+    planes = planes.contiguous()
+    pairs, count = planes.shape[0], planes.shape[2]
+    with torch.cuda.device(planes.device):
+        out = torch.empty((pairs, count, 2, 3), device=planes.device, dtype=torch.uint8)
+        if clipped is None:
+            clipped = torch.zeros(pairs, device=planes.device, dtype=torch.int64)
+        assert clipped.is_cuda and clipped.dtype == torch.int64 and clipped.is_contiguous() and clipped.numel() == pairs
+        rc = lib.srtPcm24Pack(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(planes), count, pairs, count, _ptr(out), count, _ptr(clipped))
+    if rc < 0:
+        raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (lib.srtLastError().decode(), rc))
+    return out, clipped
+
+
+def pcm16_pack_dither(planes, seed=0, first_pair=0, first_index=0, clipped=None):
+    """pcm16_pack with TPDF dither: q = clamp(rint(x * 32768 + d)), d of (seed, 2 * (first_pair + pair) + channel, first_index + sample) (srtPcm16PackDither;
+    DESIGN.md §14.1) -> (int16 [pairs, count, 2], clipped int64 [pairs])."""
+    import torch
+    assert planes.is_cuda and planes.dtype == torch.float32 and planes.dim() == 3 and planes.shape[1] == 2
+    lib = load_library()
+    planes = planes.contiguous()
+    pairs, count = planes.shape[0], planes.shape[2]
+    with torch.cuda.device(planes.device):
+        out = torch.empty((pairs, count, 2), device=planes.device, dtype=torch.int16)
+        if clipped is None:
+            clipped = torch.zeros(pairs, device=planes.device, dtype=torch.int64)
+        assert clipped.is_cuda and clipped.dtype == torch.int64 and clipped.is_contiguous() and clipped.numel() == pairs
+        rc = lib.srtPcm16PackDither(C.c_void_p(torch.cuda.current_stream().cuda_stream), _ptr(planes), count, pairs, count, _ptr(out), count, _ptr(clipped),
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_pair), int(first_index))
     if rc < 0:
         raise EngineError("libspleeterrt_amd: %s (rc=%d)" % (lib.srtLastError().decode(), rc))
     return out, clipped

@@ -34,9 +34,9 @@ struct HostStaging {
     hipStream_t s_in, s_out;
     hipEvent_t ev_in[2], ev_cmp[2], ev_out[2];
     bool ready;
-    // 16-bit PCM forms (SRT_HOST_IN_PCM16 / SRT_HOST_OUT_PCM16, srt_pcm.hip): allocated only when a call asks for them
-    int16_t* d_in16[2]; int16_t* d_out16[2];
-    size_t in16_cap, out16_cap;                        // stereo frames (4 bytes)
+    // integer PCM forms (SRT_HOST_IN_PCM16 / _PCM24, SRT_HOST_OUT_PCM16 / _PCM24, srt_pcm.hip): one set for every format, allocated only when a call asks for one
+    void* d_inq[2]; void* d_outq[2];
+    size_t inq_cap, outq_cap;                          // bytes
     unsigned long long* d_clip;                        // [SRT_MAX_STEMS] clipped-sample counters, then the pack's workgroup counts
     // srtSeparateHostWiener's / srtSeparateHostWienerOverlap's store: every piece's spectrum, fp32 masks and mask carry (host_wiener_layout, srt_host.hip), grow-only like the rest
     char* d_wstore; size_t wstore_cap;                 // bytes
@@ -93,6 +93,7 @@ struct SepOpts {
     int n_out = 0;                                     // stem remix: > 0 - the inverse transform writes n_out pairs, pair m the chain of mix[m] over the stems' gains
     float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1] = {};  // (a batch's per-track matrices travel beside the record)
     unsigned mix_gen = 0;                              // the engine's count of the srtSetMix calls that switched the mix on: graph key only
+    unsigned long long dither_seed = 0;                // SRT_HOST_OUT_DITHER's seed (srtSetDitherSeed): read by the host paths' pack alone
 };
 
 struct srt_engine {
@@ -138,6 +139,7 @@ struct srt_engine {
     // of mix[m] over the stems' gains; mix_gen counts the calls that switched it on (the graph key)
     int mix_out = 0; unsigned mix_gen = 0;
     float mix[SRT_MAX_STEMS][SRT_MAX_STEMS + 1] = {};
+    unsigned long long dither_seed = 0;                // srtSetDitherSeed
     // packed batches of tracks (srtSeparateBatch): the device track table (max_tiles rows: every track takes at least one tile) and a ring of pinned
     // host slots it is uploaded from, each reused only after the copy from it issued SRT_BATCH_SLOTS calls earlier has completed (bev)
     SrtBatchTrack* btab = nullptr; SrtBatchTrack* bpin = nullptr;

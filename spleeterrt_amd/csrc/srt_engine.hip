@@ -128,12 +128,20 @@ int srtSetWiener(srt_engine* e, int iterations)
 }
 int srt_engine_wiener(const srt_engine* e) { return e->wiener; }
 
+int srtSetDitherSeed(srt_engine* e, uint64_t seed)
+{
+    if (!e) return fail(-1, "srtSetDitherSeed: null engine");
+    e->dither_seed = seed;
+    return 0;
+}
+
 // The engine's own options as a call's record: with the setters and accessors above, the only reader of these fields.  (The setters keep the filter apart from
 // the extension and the mix, so a record with wiener > 0 has both off.)
 SepOpts engine_opts(const srt_engine* e)
 {
     SepOpts o;
     o.overlap = e->overlap; o.mask_ext = e->mask_ext; o.wiener = e->wiener; o.n_out = e->mix_out; o.mix_gen = e->mix_gen;
+    o.dither_seed = e->dither_seed;
     memcpy(o.mix, e->mix, sizeof o.mix);
     return o;
 }
@@ -147,8 +155,8 @@ static void free_staging(srt_engine* e)
     for (int b = 0; b < 2; ++b) {
         if (h.d_in[b]) hipFree(h.d_in[b]);
         if (h.d_out[b]) hipFree(h.d_out[b]);
-        if (h.d_in16[b]) hipFree(h.d_in16[b]);
-        if (h.d_out16[b]) hipFree(h.d_out16[b]);
+        if (h.d_inq[b]) hipFree(h.d_inq[b]);
+        if (h.d_outq[b]) hipFree(h.d_outq[b]);
         if (h.d_rin[b]) hipFree(h.d_rin[b]);
         if (h.d_rout[b]) hipFree(h.d_rout[b]);
         if (h.ev_in[b]) hipEventDestroy(h.ev_in[b]);

@@ -40,26 +40,27 @@ static int ensure_staging(srt_engine* e, size_t in_floats, size_t out_floats, si
     return 0;
 }
 
-// The 16-bit staging of the PCM16 flags, after ensure_staging (streams exist): grow-only like the float buffers; 0 frames = not wanted by this call.
-static int ensure_staging16(srt_engine* e, size_t in_frames, size_t out_frames)
+// The integer staging of the PCM flags (16- and 24-bit share it), after ensure_staging (streams exist): grow-only like the float buffers; 0 bytes = not wanted
+// by this call.
+static int ensure_staging_pcm(srt_engine* e, size_t in_bytes, size_t out_bytes)
 {
     HostStaging& h = e->hs;
-    if (in_frames > h.in16_cap || out_frames > h.out16_cap) {
+    if (in_bytes > h.inq_cap || out_bytes > h.outq_cap) {
         HIPCHK(hipStreamSynchronize(h.s_in)); HIPCHK(hipStreamSynchronize(e->stream)); HIPCHK(hipStreamSynchronize(h.s_out));
     }
     for (int b = 0; b < 2; ++b) {
-        if (in_frames > h.in16_cap) {
-            if (h.d_in16[b]) { hipFree(h.d_in16[b]); h.d_in16[b] = nullptr; }
-            HIPCHK(hipMalloc((void**)&h.d_in16[b], in_frames * 2 * sizeof(int16_t)));
+        if (in_bytes > h.inq_cap) {
+            if (h.d_inq[b]) { hipFree(h.d_inq[b]); h.d_inq[b] = nullptr; }
+            HIPCHK(hipMalloc(&h.d_inq[b], in_bytes));
         }
-        if (out_frames > h.out16_cap) {
-            if (h.d_out16[b]) { hipFree(h.d_out16[b]); h.d_out16[b] = nullptr; }
-            HIPCHK(hipMalloc((void**)&h.d_out16[b], out_frames * 2 * sizeof(int16_t)));
+        if (out_bytes > h.outq_cap) {
+            if (h.d_outq[b]) { hipFree(h.d_outq[b]); h.d_outq[b] = nullptr; }
+            HIPCHK(hipMalloc(&h.d_outq[b], out_bytes));
         }
     }
-    if (in_frames > h.in16_cap) h.in16_cap = in_frames;
-    if (out_frames > h.out16_cap) h.out16_cap = out_frames;
-    if (out_frames && !h.d_clip) HIPCHK(hipMalloc((void**)&h.d_clip, (SRT_MAX_STEMS + srt_pcm16_pack_scratch(SRT_MAX_STEMS)) * sizeof(unsigned long long)));
+    if (in_bytes > h.inq_cap) h.inq_cap = in_bytes;
+    if (out_bytes > h.outq_cap) h.outq_cap = out_bytes;
+    if (out_bytes && !h.d_clip) HIPCHK(hipMalloc((void**)&h.d_clip, (SRT_MAX_STEMS + srt_pcm16_pack_scratch(SRT_MAX_STEMS)) * sizeof(unsigned long long)));
     return 0;
 }
 
@@ -202,6 +203,48 @@ static int ensure_rate_staging(srt_engine* e, size_t in_floats, size_t out_float
     return 0;
 }
 
+// The sample formats of a call's flags.  in_bytes / out_bytes: bytes of a stereo frame in the caller's buffers (8: floats, two planes of 4).
+struct HostFmt {
+    int in_bits, out_bits; bool dither;
+    bool pcm_in() const { return in_bits != 32; }
+    bool pcm_out() const { return out_bits != 32; }
+    size_t in_bytes() const { return (size_t)in_bits / 4; }
+    size_t out_bytes() const { return (size_t)out_bits / 4; }
+};
+static const unsigned SRT_HOST_FLAGS = SRT_HOST_PINNED | SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16 | SRT_HOST_IN_PCM24 | SRT_HOST_OUT_PCM24 | SRT_HOST_OUT_DITHER;
+// 0, or -1 with the error set: nothing has touched the device
+static int host_fmt(unsigned flags, const void* h_in2, const char* who, HostFmt* f)
+{
+    const bool in16 = flags & SRT_HOST_IN_PCM16, in24 = flags & SRT_HOST_IN_PCM24, out16 = flags & SRT_HOST_OUT_PCM16, out24 = flags & SRT_HOST_OUT_PCM24;
+    if (in16 && in24) return fail(-1, "%s: SRT_HOST_IN_PCM16 and SRT_HOST_IN_PCM24 are two formats of one buffer: set one", who);
+    if (out16 && out24) return fail(-1, "%s: SRT_HOST_OUT_PCM16 and SRT_HOST_OUT_PCM24 are two formats of one buffer: set one", who);
+    if ((flags & SRT_HOST_OUT_DITHER) && !out16) return fail(-1, "%s: SRT_HOST_OUT_DITHER dithers the 16-bit output: it needs SRT_HOST_OUT_PCM16 (and is refused with 24-bit or float output)", who);
+    if ((in16 || in24) && h_in2) return fail(-1, in16 ? "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)" : "%s: SRT_HOST_IN_PCM24 takes one interleaved buffer (h_in2 must be NULL)", who);
+    f->in_bits = in16 ? 16 : in24 ? 24 : 32;
+    f->out_bits = out16 ? 16 : out24 ? 24 : 32;
+    f->dither = flags & SRT_HOST_OUT_DITHER;
+    return 0;
+}
+// a chunk's integer frames in d_inq -> planar floats; `count` frames of `pairs` pairs -> d_outq, pair p at p * stride frames, the clipped samples added to d_clip
+// (then its scratch follows it).  first_index: the position of the launch's sample 0 in its output plane, for the dither.  Without the new bits the launches
+// are the 16-bit ones under their timer names.
+static int host_unpack(srt_engine* e, const HostFmt& f, const void* d_q, size_t n, float* L, float* R)
+{
+    TimerScope ts(e, f.in_bits == 24 ? "pcm24_unpack" : "pcm16_unpack");
+    if (f.in_bits == 24 ? srt_launch_pcm24_unpack((const uint8_t*)d_q, n, L, R, e->stream) : srt_launch_pcm16_unpack((const int16_t*)d_q, n, L, R, e->stream))
+        return fail(-2, f.in_bits == 24 ? "pcm24 unpack launch failed" : "pcm16 unpack launch failed");
+    return 0;
+}
+static int host_pack(srt_engine* e, const HostFmt& f, const SepOpts& o, const float* planes, size_t stride, int pairs, size_t count, void* d_q, unsigned long long* d_clip, size_t first_index)
+{
+    unsigned long long* const scratch = d_clip ? d_clip + SRT_MAX_STEMS : nullptr;
+    TimerScope ts(e, f.out_bits == 24 ? "pcm24_pack" : f.dither ? "pcm16_pack_dither" : "pcm16_pack");
+    const int rc = f.out_bits == 24 ? srt_launch_pcm24_pack(planes, stride, pairs, count, (uint8_t*)d_q, stride, d_clip, scratch, e->stream)
+                 : f.dither ? srt_launch_pcm16_pack_dither(planes, stride, pairs, count, (int16_t*)d_q, stride, d_clip, scratch, o.dither_seed, 0, first_index, e->stream)
+                 : srt_launch_pcm16_pack(planes, stride, pairs, count, (int16_t*)d_q, stride, d_clip, scratch, e->stream);
+    return rc ? fail(-2, f.out_bits == 24 ? "pcm24 pack launch failed" : "pcm16 pack launch failed") : 0;
+}
+
 static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_t n, size_t frames, size_t rows, void* h_out, unsigned flags, int cli_stems,
                        SrtSeam seam = SrtSeam{0, nullptr, false}, unsigned long long* h_clipped = nullptr, int call_overlap = -1, const HostRate* rate = nullptr);
 
@@ -210,17 +253,19 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
 // host-resident spectrogram handles (main.c:455-495) - goes through the chunked pipeline of srtSeparateHostStream: max_tiles tiles
 // at a time, copies overlapped with compute, the residual chain evaluated per chunk (it is row-local) and the time-domain
 // subtraction applied after the 3072-sample chunk overlaps have been added on the device.
-// flags: SRT_HOST_* (srtSeparateCliHostIo).  A 16-bit side always takes the chunked pipeline, whose staging holds the conversion (one chunk when the file fits).
+// flags: SRT_HOST_* (srtSeparateCliHostIo).  An integer side always takes the chunked pipeline, whose staging holds the conversion (one chunk when the file fits).
 static int cli_host(srt_engine* e, const void* h_in, const void* h_in2, size_t n, int stems, void* h_out_, unsigned flags, unsigned long long* h_clipped)
 {
-    const bool pcm16 = flags & (SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16);
-    if (!e || !h_in || (!(flags & SRT_HOST_IN_PCM16) && !h_in2) || !h_out_) return fail(-1, "srtSeparateCliHost: null argument");
+    const bool pcm = flags & (SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16 | SRT_HOST_IN_PCM24 | SRT_HOST_OUT_PCM24);
+    HostFmt f;
+    if (const int rc = host_fmt(flags, h_in2, "srtSeparateCliHostIo", &f)) return rc;
+    if (!e || !h_in || (!f.pcm_in() && !h_in2) || !h_out_) return fail(-1, "srtSeparateCliHost: null argument");
     DeviceScope ds(e->device);
     int rc = cli_check(e, stems);
     if (rc) return rc;
     if (n < SRT_FFT) return fail(-1, "srtSeparateCli: need at least 4096 samples");
     const size_t rows = srtStftRows(n), len = srtIstftLength(rows);
-    if (pcm16 || (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles)
+    if (pcm || (rows + e->cfg.T - 1) / e->cfg.T > (size_t)e->cfg.max_tiles)
         return host_stream(e, h_in, h_in2, n, srtStftFrames(n), rows, h_out_, flags, stems, SrtSeam{0, nullptr, false}, h_clipped);
     const float *h_L = (const float*)h_in, *h_R = (const float*)h_in2;
     float* h_out = (float*)h_out_;
@@ -245,7 +290,6 @@ int srtSeparateCliHost(srt_engine* e, const float* h_L, const float* h_R, size_t
     return cli_host(e, h_L, h_R, n, stems, h_out, 0, nullptr);
 }
 
-static const unsigned SRT_HOST_FLAGS = SRT_HOST_PINNED | SRT_HOST_IN_PCM16 | SRT_HOST_OUT_PCM16;
 int srtSeparateCliHostIo(srt_engine* e, const void* h_in, const void* h_in2, size_t n, int stems, void* h_out, unsigned flags, unsigned long long* h_clipped)
 {
     if (flags & ~SRT_HOST_FLAGS) return fail(-1, "srtSeparateCliHostIo: unknown flag bits");
@@ -263,25 +307,29 @@ int srtSeparateCliHostIo(srt_engine* e, const void* h_in, const void* h_in2, siz
 // first samples - go to h_tail [planes][3072] instead of h_out; seam.head says a previous range will add its tail to this range's first
 // 3072 samples.  The CLI flows' time-domain subtraction is left out on exactly those seam samples (both contributions have to be added
 // first: the joiner does that, as the reference's main() does its subtraction on the host, main.c:794-798).
-// 16-bit PCM (flags).  SRT_HOST_IN_PCM16: h_in is int16 [n][2] (h_in2 unused); a chunk's frames go up as one copy into d_in16[b] and are unpacked
-// into d_in[b] on the compute stream (ev_cmp[b] releases both).  SRT_HOST_OUT_PCM16: h_out is int16 [planes / 2][total_len][2]; after the seam add (and the CLI
-// flows' subtraction) the samples this chunk downloads - each plane's [0, take) - are packed into d_out16[b], so every output sample is quantised and counted
-// once, and ev_cmp[b] is recorded after the pack.  h_clipped [stems]: the clipped samples of each stem (zero without the flag).
+// Integer PCM (flags).  SRT_HOST_IN_PCM16 / _PCM24: h_in is int16 [n][2] / uint8 [n][2][3] (h_in2 unused); a chunk's frames go up as one copy
+// into d_inq[b] and are unpacked into d_in[b] on the compute stream (ev_cmp[b] releases both).  SRT_HOST_OUT_PCM16 / _PCM24: h_out is int16 [planes / 2][total_len][2]
+// / uint8 [planes / 2][total_len][2][3]; after the seam add (and the CLI flows' subtraction) the samples this chunk downloads - each plane's [0, take) - are packed
+// into d_outq[b], so every output sample is quantised and counted once, and ev_cmp[b] is recorded after the pack.  SRT_HOST_OUT_DITHER: the 16-bit pack adds the
+// TPDF dither of (o.dither_seed, plane, position in the whole output plane), so the chunking does not show.  h_clipped [stems]: the clipped samples of each stem
+// (zero without an OUT flag).
 // call_overlap >= 0: srtSeparateHostStreamOverlap - the call's own overlap in place of the engine's, which is then neither read nor refused.  The
 // chunks are the pieces of host_ov_piece: a piece uploads and analyses stft_rows rows, of which it inverts, stitches and downloads the first own_rows
 // (separate_piece); after every piece but the last the mask rows the next piece's first O rows blend with are kept (srt_mask_seam_save_kernel).  At 0 the pieces are
 // the chunks and every launch is the one the engine's path issues.
-// rate != nullptr: srtSeparateHostStreamRate.  With rate->fin a piece uploads the source frames host_rate_piece names into d_rin[b] (16-bit: d_in16[b],
+// rate != nullptr: srtSeparateHostStreamRate.  With rate->fin a piece uploads the source frames host_rate_piece names into d_rin[b] (integer PCM: d_inq[b],
 // unpacked into d_rin[b]) and the spans kernel writes d_in[b] in front of the transform; with rate->fout the spans kernel converts every pair behind the seam add - span A
 // the rate carry, span B the piece's planes - into d_rout[b], which the pack and the download then take in d_out[b]'s place.  Without either the launches are the ones above.
 static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_t n, size_t frames, size_t rows, void* h_out_, unsigned flags, int cli_stems, SrtSeam seam,
                        unsigned long long* h_clipped, int call_overlap, const HostRate* rate)
 {
     const char* const who = rate ? "srtSeparateHostStreamRate" : call_overlap >= 0 ? "srtSeparateHostStreamOverlap" : "srtSeparateHostStream";
-    const bool in16 = flags & SRT_HOST_IN_PCM16, out16 = flags & SRT_HOST_OUT_PCM16;
-    if (!e || !h_in || (!in16 && !h_in2) || !h_out_) return fail(-1, "%s: null argument", who);
-    if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
-    if ((in16 || out16) && seam.out_stride) return fail(-1, "%s: the 16-bit PCM forms do not apply to a tile range of a multi-device stream (the seam join adds floats on the host)", who);
+    HostFmt f;
+    if (const int frc = host_fmt(flags, h_in2, who, &f)) return frc;
+    const bool inq = f.pcm_in(), outq = f.pcm_out();
+    const size_t ib = f.in_bytes(), ob = f.out_bytes();
+    if (!e || !h_in || (!inq && !h_in2) || !h_out_) return fail(-1, "%s: null argument", who);
+    if ((inq || outq) && seam.out_stride) return fail(-1, "%s: the 16-bit and 24-bit PCM forms and the dither do not apply to a tile range of a multi-device stream (the seam join adds floats on the host)", who);
     const float *h_L = (const float*)h_in, *h_R = (const float*)h_in2;
     float* h_out = (float*)h_out_;
     if (rows < 1 || frames > rows) return fail(-1, "%s: need 1 <= frames <= rows", who);
@@ -316,19 +364,19 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
         if (fout && c + 1 < nchunks && rp.fin1 - rp.fin0 < K) return fail(-1, "%s: a piece finalises fewer samples than the output converter's history", who);
     }
     if ((fin || fout) && (rc = ensure_rate_staging(e, fin ? 2 * rin_len : 0, fout ? (size_t)NP * rout_len : 0, (size_t)NP * K))) return rc;
-    if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? (fin && rin_len > in_cap ? rin_len : in_cap) : 0, out16 ? (size_t)S * (fout && rout_len > out_cap ? rout_len : out_cap) : 0))) return rc;
+    if ((inq || outq) && (rc = ensure_staging_pcm(e, inq ? ib * (fin && rin_len > in_cap ? rin_len : in_cap) : 0, outq ? ob * S * (fout && rout_len > out_cap ? rout_len : out_cap) : 0))) return rc;
     HostStaging& h = e->hs;
     if (h_clipped) memset(h_clipped, 0, (size_t)S * sizeof *h_clipped);
-    unsigned long long* d_clip = out16 && h_clipped ? h.d_clip : nullptr;
+    unsigned long long* d_clip = outq && h_clipped ? h.d_clip : nullptr;
     if (d_clip) HIPCHK(hipMemsetAsync(d_clip, 0, (size_t)S * sizeof *d_clip, e->stream));
     // Page-locked caller buffers let the copies run asynchronously.  SRT_HOST_PINNED: the caller guarantees they already are
     // (hipHostMalloc / hipHostRegister / torch pin_memory) and nothing is registered here; otherwise the three buffers are
     // registered for the duration of the call (if that fails the copies still work, staged by the runtime).
     bool pinL = false, pinR = false, pinO = false;
     if (!(flags & SRT_HOST_PINNED)) {
-        pinL = hipHostRegister((void*)h_in, n_host * sizeof(float), hipHostRegisterDefault) == hipSuccess;       // int16 [n][2] is n * 4 bytes too
-        pinR = !in16 && hipHostRegister((void*)h_R, n_host * sizeof(float), hipHostRegisterDefault) == hipSuccess;
-        pinO = !seam.out_stride && hipHostRegister((void*)h_out, (size_t)NP * out_len * (out16 ? sizeof(int16_t) : sizeof(float)), hipHostRegisterDefault) == hipSuccess;
+        pinL = hipHostRegister((void*)h_in, n_host * (inq ? ib : sizeof(float)), hipHostRegisterDefault) == hipSuccess;       // (int16 [n][2] is n * 4 bytes too)
+        pinR = !inq && hipHostRegister((void*)h_R, n_host * sizeof(float), hipHostRegisterDefault) == hipSuccess;
+        pinO = !seam.out_stride && hipHostRegister((void*)h_out, (size_t)S * out_len * ob, hipHostRegisterDefault) == hipSuccess;
         (void)hipGetLastError();
     }
     hipError_t er = hipSuccess;
@@ -345,12 +393,12 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
         // upload: the input buffer is free once the compute that read it two chunks ago has finished
         if (c >= 2) STEP(hipStreamWaitEvent(h.s_in, h.ev_cmp[b], 0));
         if (fin) {                                          // the source window, at the caller's rate
-            if (rp.src_len && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * rp.src0, rp.src_len * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
+            if (rp.src_len && inq) STEP(hipMemcpyAsync(h.d_inq[b], (const char*)h_in + ib * rp.src0, rp.src_len * ib, hipMemcpyHostToDevice, h.s_in));
             else if (rp.src_len) {
                 STEP(hipMemcpyAsync(h.d_rin[b], h_L + rp.src0, rp.src_len * sizeof(float), hipMemcpyHostToDevice, h.s_in));
                 STEP(hipMemcpyAsync(h.d_rin[b] + rin_len, h_R + rp.src0, rp.src_len * sizeof(float), hipMemcpyHostToDevice, h.s_in));
             }
-        } else if (ns && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * s0, ns * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
+        } else if (ns && inq) STEP(hipMemcpyAsync(h.d_inq[b], (const char*)h_in + ib * s0, ns * ib, hipMemcpyHostToDevice, h.s_in));
         else if (ns) {
             STEP(hipMemcpyAsync(h.d_in[b], h_L + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
             STEP(hipMemcpyAsync(h.d_in[b] + in_cap, h_R + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
@@ -360,12 +408,10 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
         STEP(hipStreamWaitEvent(e->stream, h.ev_in[b], 0));
         if (c >= 2) STEP(hipStreamWaitEvent(e->stream, h.ev_out[b], 0));
         if (er != hipSuccess) break;
-        if (in16 && fin && rp.src_len) {
-            TimerScope ts(e, "pcm16_unpack");
-            if (srt_launch_pcm16_unpack(h.d_in16[b], rp.src_len, h.d_rin[b], h.d_rin[b] + rin_len, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
-        } else if (in16 && ns && !fin) {
-            TimerScope ts(e, "pcm16_unpack");
-            if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
+        if (inq && fin && rp.src_len) {
+            if ((rc = host_unpack(e, f, h.d_inq[b], rp.src_len, h.d_rin[b], h.d_rin[b] + rin_len))) break;
+        } else if (inq && ns && !fin) {
+            if ((rc = host_unpack(e, f, h.d_inq[b], ns, h.d_in[b], h.d_in[b] + in_cap))) break;
         }
         if (fin && ns) {                                    // the piece's 44.1 kHz samples [s0, s0 + ns) from the source window: one span, one pair
             TimerScope ts(e, "rate_in");
@@ -400,21 +446,20 @@ static int host_stream(srt_engine* e, const void* h_in, const void* h_in2, size_
             if (c + 1 < nchunks) STEP(hipMemcpy2DAsync(h.d_rcarry, K * sizeof(float), h.d_out[b] + take - K, clen * sizeof(float), K * sizeof(float), NP, hipMemcpyDeviceToDevice, e->stream));
             if (er != hipSuccess) break;
         }
-        if (out16 && fout && nj) {
-            TimerScope ts(e, "pcm16_pack");
-            if (srt_launch_pcm16_pack(h.d_rout[b], rout_len, S, nj, h.d_out16[b], rout_len, d_clip, d_clip ? d_clip + SRT_MAX_STEMS : nullptr, e->stream)) { rc = fail(-2, "pcm16 pack launch failed"); break; }
-        } else if (out16 && !fout) {
-            TimerScope ts(e, "pcm16_pack");
-            if (srt_launch_pcm16_pack(h.d_out[b], clen, S, take, h.d_out16[b], clen, d_clip, d_clip ? d_clip + SRT_MAX_STEMS : nullptr, e->stream)) { rc = fail(-2, "pcm16 pack launch failed"); break; }
+        // (the dither's index is the sample's position in the whole output plane: the converted frames start at out0, the chunk's own at s0)
+        if (outq && fout && nj) {
+            if ((rc = host_pack(e, f, o, h.d_rout[b], rout_len, S, nj, h.d_outq[b], d_clip, rp.out0))) break;
+        } else if (outq && !fout) {
+            if ((rc = host_pack(e, f, o, h.d_out[b], clen, S, take, h.d_outq[b], d_clip, s0))) break;
         }
         STEP(hipEventRecord(h.ev_cmp[b], e->stream));
         // download: every plane's [0, crow*1024) (+ the final 3072 on the last chunk) lands at its place in h_out
         STEP(hipStreamWaitEvent(h.s_out, h.ev_cmp[b], 0));
         if (fout) {                                         // the converted planes: frames [out0, out1) of planes of out_len, one contiguous copy per plane (a pitched 2-D
                                                             // copy of this size slowed the next piece's first kernels and the copy itself: DESIGN.md 8.1)
-            for (int p = 0; nj && out16 && p < S; ++p) STEP(hipMemcpyAsync((int16_t*)h_out_ + 2 * ((size_t)p * out_len + rp.out0), h.d_out16[b] + 2 * (size_t)p * rout_len, nj * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, h.s_out));
-            for (int p = 0; nj && !out16 && p < NP; ++p) STEP(hipMemcpyAsync(h_out + (size_t)p * out_len + rp.out0, h.d_rout[b] + (size_t)p * rout_len, nj * sizeof(float), hipMemcpyDeviceToHost, h.s_out));
-        } else if (out16) STEP(hipMemcpy2DAsync((int16_t*)h_out_ + 2 * s0, total_len * 2 * sizeof(int16_t), h.d_out16[b], clen * 2 * sizeof(int16_t), take * 2 * sizeof(int16_t), S, hipMemcpyDeviceToHost, h.s_out));
+            for (int p = 0; nj && outq && p < S; ++p) STEP(hipMemcpyAsync((char*)h_out_ + ob * ((size_t)p * out_len + rp.out0), (const char*)h.d_outq[b] + ob * (size_t)p * rout_len, nj * ob, hipMemcpyDeviceToHost, h.s_out));
+            for (int p = 0; nj && !outq && p < NP; ++p) STEP(hipMemcpyAsync(h_out + (size_t)p * out_len + rp.out0, h.d_rout[b] + (size_t)p * rout_len, nj * sizeof(float), hipMemcpyDeviceToHost, h.s_out));
+        } else if (outq) STEP(hipMemcpy2DAsync((char*)h_out_ + ob * s0, total_len * ob, h.d_outq[b], clen * ob, take * ob, S, hipMemcpyDeviceToHost, h.s_out));
         else STEP(hipMemcpy2DAsync(h_out + s0, total_len * sizeof(float), h.d_out[b], clen * sizeof(float), take * sizeof(float), NP, hipMemcpyDeviceToHost, h.s_out));
         if (to_tail) STEP(hipMemcpy2DAsync(seam.h_tail, tail * sizeof(float), h.d_out[b] + crow * SRT_HOP, clen * sizeof(float), tail * sizeof(float), NP, hipMemcpyDeviceToHost, h.s_out));
         STEP(hipEventRecord(h.ev_out[b], h.s_out));
@@ -484,10 +529,10 @@ int srtSeparateHostStreamRate(srt_engine* e, const void* h_in, const void* h_in2
                               unsigned long long* h_clipped)
 {
     static const char* const who = "srtSeparateHostStreamRate";
-    const bool in16 = flags & SRT_HOST_IN_PCM16;
-    if (!e || !h_in || !h_out || (!in16 && !h_in2)) return fail(-1, "%s: null argument", who);
     if (flags & ~SRT_HOST_FLAGS) return fail(-1, "%s: unknown flag bits", who);
-    if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
+    HostFmt f;
+    if (const int rc = host_fmt(flags, h_in2, who, &f)) return rc;
+    if (!e || !h_in || !h_out || (!f.pcm_in() && !h_in2)) return fail(-1, "%s: null argument", who);
     HostRateDims d;
     if (const int rc = host_rate_dims(n, in_rate, out_rate, who, &d)) return rc;
     if (!overlap_ok(overlap_rows, e->cfg.T)) return fail(-1, "%s: overlap_rows must be 0 .. T / 2", who);
@@ -584,14 +629,17 @@ static int ensure_wstore(srt_engine* e, size_t bytes, bool ov)
 static int host_wiener(srt_engine* e, const void* h_in, const void* h_in2, size_t n, const srt_wiener_opts* opts, void* h_out_, unsigned flags, unsigned long long* h_clipped, bool ov)
 {
     const char* const who = ov ? "srtSeparateHostWienerOverlap" : "srtSeparateHostWiener";
-    const bool in16 = flags & SRT_HOST_IN_PCM16, out16 = flags & SRT_HOST_OUT_PCM16;
-    if (!e || !h_in || (!in16 && !h_in2) || !opts || !h_out_) return fail(-1, "%s: null argument", who);
     if (flags & ~SRT_HOST_FLAGS) return fail(-1, "%s: unknown flag bits", who);
-    if (in16 && h_in2) return fail(-1, "%s: SRT_HOST_IN_PCM16 takes one interleaved buffer (h_in2 must be NULL)", who);
+    HostFmt f;
+    if (const int frc = host_fmt(flags, h_in2, who, &f)) return frc;
+    const bool inq = f.pcm_in(), outq = f.pcm_out();
+    const size_t ib = f.in_bytes(), ob = f.out_bytes();
+    if (!e || !h_in || (!inq && !h_in2) || !opts || !h_out_) return fail(-1, "%s: null argument", who);
     DeviceScope ds(e->device);
     SepOpts o;
     int rc = host_wiener_check(e, opts, n, &o, ov);
     if (rc) return rc;
+    o.dither_seed = e->dither_seed;                     // the call's options come from `opts`; the seed is the engine's (srtSetDitherSeed)
     if (stream_capturing(e)) return fail(-1, "%s: not available inside a stream capture (the call is synchronous and allocates)", who);
     const size_t rows = srtStftRows(n), frames = srtStftFrames(n);
     const int S = e->cfg.n_stems, NO = o.n_out ? o.n_out : S, NP = NO * 2, iters = o.wiener, O = o.overlap;      // NO pairs staged, carried, packed and downloaded
@@ -602,17 +650,17 @@ static int host_wiener(srt_engine* e, const void* h_in, const void* h_in2, size_
     const size_t in_cap = span * SRT_HOP + tail, out_cap = srtIstftLength(span);
     if ((rc = host_wiener_ws(e, o, who))) return rc;
     if ((rc = ensure_staging(e, 2 * in_cap, (size_t)NP * out_cap, (size_t)NP * tail, 2))) return rc;
-    if ((in16 || out16) && (rc = ensure_staging16(e, in16 ? in_cap : 0, out16 ? (size_t)NO * out_cap : 0))) return rc;
+    if ((inq || outq) && (rc = ensure_staging_pcm(e, inq ? ib * in_cap : 0, outq ? ob * NO * out_cap : 0))) return rc;
     if ((rc = ensure_wstore(e, l.total, ov))) return rc;
     HostStaging& h = e->hs;
     if (h_clipped) memset(h_clipped, 0, (size_t)NO * sizeof *h_clipped);
-    unsigned long long* d_clip = out16 && h_clipped ? h.d_clip : nullptr;
+    unsigned long long* d_clip = outq && h_clipped ? h.d_clip : nullptr;
     if (d_clip) HIPCHK(hipMemsetAsync(d_clip, 0, (size_t)NO * sizeof *d_clip, e->stream));
     bool pinL = false, pinR = false, pinO = false;                  // as host_stream: register the caller's buffers for the call unless they are pinned already
     if (!(flags & SRT_HOST_PINNED)) {
-        pinL = hipHostRegister((void*)h_in, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;       // int16 [n][2] is n * 4 bytes too
-        pinR = !in16 && hipHostRegister((void*)h_in2, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;
-        pinO = hipHostRegister(h_out_, (size_t)NP * total_len * (out16 ? sizeof(int16_t) : sizeof(float)), hipHostRegisterDefault) == hipSuccess;
+        pinL = hipHostRegister((void*)h_in, n * (inq ? ib : sizeof(float)), hipHostRegisterDefault) == hipSuccess;       // (int16 [n][2] is n * 4 bytes too)
+        pinR = !inq && hipHostRegister((void*)h_in2, n * sizeof(float), hipHostRegisterDefault) == hipSuccess;
+        pinO = hipHostRegister(h_out_, (size_t)NO * total_len * ob, hipHostRegisterDefault) == hipSuccess;
         (void)hipGetLastError();
     }
     const float *h_L = (const float*)h_in, *h_R = (const float*)h_in2;
@@ -629,7 +677,7 @@ static int host_wiener(srt_engine* e, const void* h_in, const void* h_in2, size_
         const size_t ns = send > s0 ? send - s0 : 0;
         const size_t cfr = frames > pc.row0 ? (frames - pc.row0 < pc.stft_rows ? frames - pc.row0 : pc.stft_rows) : 0;
         if (c >= 2) STEP(hipStreamWaitEvent(h.s_in, h.ev_cmp[b], 0));      // the input buffer is free once the transform that read it two pieces ago has finished
-        if (ns && in16) STEP(hipMemcpyAsync(h.d_in16[b], (const int16_t*)h_in + 2 * s0, ns * 2 * sizeof(int16_t), hipMemcpyHostToDevice, h.s_in));
+        if (ns && inq) STEP(hipMemcpyAsync(h.d_inq[b], (const char*)h_in + ib * s0, ns * ib, hipMemcpyHostToDevice, h.s_in));
         else if (ns) {
             STEP(hipMemcpyAsync(h.d_in[b], h_L + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
             STEP(hipMemcpyAsync(h.d_in[b] + in_cap, h_R + s0, ns * sizeof(float), hipMemcpyHostToDevice, h.s_in));
@@ -637,10 +685,7 @@ static int host_wiener(srt_engine* e, const void* h_in, const void* h_in2, size_
         STEP(hipEventRecord(h.ev_in[b], h.s_in));
         STEP(hipStreamWaitEvent(e->stream, h.ev_in[b], 0));
         if (er != hipSuccess) break;
-        if (in16 && ns) {
-            TimerScope ts(e, "pcm16_unpack");
-            if (srt_launch_pcm16_unpack(h.d_in16[b], ns, h.d_in[b], h.d_in[b] + in_cap, e->stream)) { rc = fail(-2, "pcm16 unpack launch failed"); break; }
-        }
+        if (inq && ns && (rc = host_unpack(e, f, h.d_inq[b], ns, h.d_in[b], h.d_in[b] + in_cap))) break;
         if ((rc = host_wiener_analyse(e, sw, h.d_in[b], h.d_in[b] + in_cap, ns, cfr, pc, O))) break;
         STEP(hipEventRecord(h.ev_cmp[b], e->stream));                       // (the networks read the magnitudes, not the PCM, but the event is one per piece)
         if ((rc = host_wiener_stats(e, w, pc, 1, O))) break;
@@ -662,13 +707,10 @@ static int host_wiener(srt_engine* e, const void* h_in, const void* h_in2, size_
         if ((rc = host_wiener_render(e, w, o, pc, h.d_out[b]))) break;
         if (srt_launch_carry(h.d_out[b], clen, NP, pc.rows * SRT_HOP, h.d_carry, c == 0, last, e->stream)) { rc = fail(-2, "carry launch failed"); break; }
         const size_t take = last ? clen : pc.rows * SRT_HOP;
-        if (out16) {
-            TimerScope ts(e, "pcm16_pack");
-            if (srt_launch_pcm16_pack(h.d_out[b], clen, NO, take, h.d_out16[b], clen, d_clip, d_clip ? d_clip + SRT_MAX_STEMS : nullptr, e->stream)) { rc = fail(-2, "pcm16 pack launch failed"); break; }
-        }
+        if (outq && (rc = host_pack(e, f, o, h.d_out[b], clen, NO, take, h.d_outq[b], d_clip, s0))) break;
         STEP(hipEventRecord(h.ev_cmp[b], e->stream));
         STEP(hipStreamWaitEvent(h.s_out, h.ev_cmp[b], 0));
-        if (out16) STEP(hipMemcpy2DAsync((int16_t*)h_out_ + 2 * s0, total_len * 2 * sizeof(int16_t), h.d_out16[b], clen * 2 * sizeof(int16_t), take * 2 * sizeof(int16_t), NO, hipMemcpyDeviceToHost, h.s_out));
+        if (outq) STEP(hipMemcpy2DAsync((char*)h_out_ + ob * s0, total_len * ob, h.d_outq[b], clen * ob, take * ob, NO, hipMemcpyDeviceToHost, h.s_out));
         else STEP(hipMemcpy2DAsync((float*)h_out_ + s0, total_len * sizeof(float), h.d_out[b], clen * sizeof(float), take * sizeof(float), NP, hipMemcpyDeviceToHost, h.s_out));
         STEP(hipEventRecord(h.ev_out[b], h.s_out));
     }

@@ -281,6 +281,13 @@ int srt_launch_pcm16_unpack(const int16_t* in, size_t n, float* L, float* R, hip
 size_t srt_pcm16_pack_scratch(int pairs);
 int srt_launch_pcm16_pack(const float* planes, size_t plane_stride, int pairs, size_t count, int16_t* out, size_t out_stride,
                           unsigned long long* clipped, unsigned long long* scratch, hipStream_t s);
+// ... packed 24-bit: [n][2][3] bytes, x = q / 2^23; the pack writes pair p at out + p * out_stride * 6, q = clamp(rint(x * 2^23)); clipped and
+// scratch as above.  ... and the 16-bit pack with TPDF dither: q = clamp(rint(x * 32768 + d)), d of (seed, 2 (first_pair + p) + channel, first_index + i)
+int srt_launch_pcm24_unpack(const uint8_t* in, size_t n, float* L, float* R, hipStream_t s);
+int srt_launch_pcm24_pack(const float* planes, size_t plane_stride, int pairs, size_t count, uint8_t* out, size_t out_stride,
+                          unsigned long long* clipped, unsigned long long* scratch, hipStream_t s);
+int srt_launch_pcm16_pack_dither(const float* planes, size_t plane_stride, int pairs, size_t count, int16_t* out, size_t out_stride,
+                                 unsigned long long* clipped, unsigned long long* scratch, unsigned long long seed, int first_pair, unsigned long long first_index, hipStream_t s);
 // cross-stem ratio mask, in place on [nstems][count]: m_s <- (m_s^2 + eps/S) / (sum_j m_j^2 + eps)
 int srt_launch_ratio_mask(float* masks, int nstems, size_t count, hipStream_t s);
 
